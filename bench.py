@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the path-space hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+
+--dump-outputs DIR: right after the timed region (before any untimed iteration), rank 0 writes what the timed path
+computed in its last step as DIR/<name>.npy (float32 / float64, 64 MB at most): the losses of the timed steps, the
+net parameters Adam left, the gradient and Adam moments of that step, and the per-trajectory / reduced quantities the
+plan keeps (see dump_outputs).  Weights, X_0 and the on-device noise are seeded: equal arguments give equal inputs, so
+two builds can be compared output for output (e.g. DIR = bench_outputs/<build>, which git ignores).
 
 One "step" = one full training iteration of Solver.train (forward SDE rollout over N_t time
 steps, log-variance loss, analytic backward, Adam) on synthetic d-dimensional HJB data with
@@ -310,6 +316,42 @@ def timed_region(dist, dev, fn, steps, first):
     return elapsed
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, plan, extra):
+    """--dump-outputs: the arrays the last timed step left -- `extra` (the per-step losses etc.) and the plan's own buffers
+    (every native plan keeps the net as one flat fp32 vector; the gradient, Adam moments, per-trajectory terminal values D and
+    the reduced loss sums where the plan has them).  Written as float32 (float64 stays float64).  An array that would push the
+    total over DUMP_LIMIT_BYTES is replaced by a fixed sample of its flattened entries (seeded, sorted indices, saved as
+    <name>_sample_index.npy)."""
+    import numpy as np
+    arrays = dict(extra)
+    for name, attr in (("params", "flat"), ("grad", "grad"), ("adam_m", "m"), ("adam_v", "v"),
+                       ("terminal_D", "D"), ("loss_sums", "sums"), ("y0", "y0_param")):
+        t = getattr(plan, attr, None)
+        if torch.is_tensor(t) and (attr != "y0_param" or getattr(plan, "learn_y0", False)):
+            arrays[name] = t
+    host = {}
+    for name, t in arrays.items():                  # (the copies to the host wait for the launch stream)
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    used, written = 0, []
+    for name, a in sorted(host.items(), key=lambda kv: kv[1].nbytes):     # smallest first: only the largest get sampled
+        room = max(0, DUMP_LIMIT_BYTES - used)
+        if a.nbytes > room:
+            n = min(a.size, room // (a.itemsize + 8))   # the sample and its float64 index share the room
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, size=n, replace=False)).astype(np.float64)
+            np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx)
+            used += idx.nbytes
+            a = a.reshape(-1)[idx.astype(np.int64)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        used += a.nbytes
+        written.append("%s%s" % (name, list(a.shape)))
+    print("bench.py --dump-outputs %s: %s" % (out_dir, ", ".join(written)), file=sys.stderr)
+
+
 def check_c_abi_allreduce(psp, dist, rank, world, dev, rehearsal):
     """N > 1, outside the timed region: the C-ABI collective (psp_comm_* / psp_allreduce, include/psp.h) against
     torch.distributed's all-reduce on the same buffers.  Reported, never fatal: the timed path uses torch.distributed."""
@@ -609,7 +651,11 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] side measurement")
     ap.add_argument("--no-sustained", action="store_true", help="skip the >= 3 s steady-state leg")
     ap.add_argument("--sustain-s", type=float, default=3.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     spawn_ranks_if_needed(args)                          # N > 1 without a launcher: children do the work
 
     import path_space_pde_solver_amd as psp
@@ -656,10 +702,15 @@ def main():
     if getattr(plan, "n_chunks", 1) > 1:
         plan.pass1_events = []
     sharding.coll_events = [] if world > 1 else None
+
+    def dump():                                          # before any untimed iteration moves the weights on
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, plan, {"loss": losses[args.warmup:total]})
     if graph:
         # launch-bound iteration replayed as a hipGraph: `value` is timed on the replay; the per-kernel HIP events of the
         # roofline come from a few eager iterations of the same kernels AFTER the timed region
         elapsed = timed_region(dist, dev, lambda l: plan.iteration(l, losses), args.steps, args.warmup)
+        dump()
         plan.events = []
         for l in range(total, total + n_eager):
             plan.iteration(l, losses)
@@ -668,6 +719,7 @@ def main():
     else:
         plan.events = []                                 # (fwd_start, fwd_end, bwd_start, bwd_end) per launch pair
         elapsed = timed_region(dist, dev, lambda l: plan.iteration(l, losses), args.steps, args.warmup)
+        dump()
 
     n_ev = max(1, len(plan.events))
     fwd_ms = sum(e[0].elapsed_time(e[1]) for e in plan.events) / n_ev
@@ -977,6 +1029,9 @@ def main_general(args, psp, sharding):
         losses.append(loss)
 
     elapsed = timed_region(dist, dev, one, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plan, {"loss": torch.stack([torch.as_tensor(x) for x in losses]).float(),
+                                               "active_count": torch.stack([torch.as_tensor(c) for c in counts]).double()})
     coll = collective_summary(sharding, args.steps)
     sharding.coll_events = None
     active = float(torch.stack(counts).sum().item())
