@@ -44,7 +44,9 @@ extern "C" {
                          * 0.4.0: PSP_DOM_ANNULUS; psp_genl_config.activation / linear_layout, psp_genl_rollout_bwd replaces
                          *        psp_genl_adjoints (hand-written weight gradient), psp_genl_sizes re-laid out; the backward side of
                          *        the range guard; psp_hjb_sizes.fwd_coop_tiles (the former `reserved`); the on-device noise is
-                         *        Philox4x32-7 (psp_philox_normal_fill and every rollout kernel: 10 rounds before) */
+                         *        Philox4x32-7 (psp_philox_normal_fill and every rollout kernel: 10 rounds before);
+                         *        later in 0.4.0 (appended, no version bump): psp_dnet_config.ul2_* -- the u_L2 log of the
+                         *        DenseNet-control forward for reference controls that depend on x (PSP_UL2_LINEAR / PSP_UL2_GRID) */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
@@ -475,7 +477,28 @@ typedef struct psp_dnet_config {
     float* r2_out;        /* gradient pass the recomputation of the two hidden layers (both NULL: not stored)                */
     float* images_out;    /* optional (psp_dnet_sizes.image_bytes): X_n, relu(z1), relu(z2) and the xi image as register images
                            * for psp_dnet_rollout_bwd; when set they REPLACE the row-major stores (px, pxi, r1_out, r2_out) */
+    /* u_L2 log (solver.py:471-472, 491-494):  base.u_l2_out[k] = sum_n |-Z_n(X_n) - u*(X_{n+1}, t_n)|^2 dt  for three kinds of
+     * reference control u*.  The log is on when base.u_ref is set (kind PSP_UL2_TABLE) or ul2_kind != 0; base.u_l2_out is then
+     * required.  Every array is padded to base.d like the problem vectors.  (psp_hjb_config itself carries kind 0 only: the
+     * narrow and wide families have no way to receive the other kinds.) */
+    int32_t ul2_kind;     /* PSP_UL2_TABLE: base.u_ref = (N, d) table of u*(t_n), ul2_* unused;
+                           * PSP_UL2_LINEAR: u*(x, t_n) = M_n x, ul2_tables = (N, d, d) row-major M_n, staged into the table
+                           *   scratch once by psp_dnet_ul2_stage;
+                           * PSP_UL2_GRID: u*_i(x, t_n) = table_{ul2_group[i]}[ul2_row[n], cell(x_i)] with the reference's index
+                           *   arithmetic (problems.py:254-260): cell = floor((clamp(x, -xb, xhi) + xb) / dx) in fp32 with a true
+                           *   division, lowered by two for the globally last trajectory (k_offset + k == K_global - 1), a negative
+                           *   result counting from the end of the row (numpy indexing) */
+    int32_t ul2_ntables;  /* PSP_UL2_GRID: G tables, each (ul2_nrows, ul2_ncols), consecutive in ul2_tables */
+    int32_t ul2_nrows, ul2_ncols;
+    const float* ul2_tables;
+    const int32_t* ul2_group;  /* PSP_UL2_GRID: (d) table of every coordinate, in [0, G)                                 */
+    const int32_t* ul2_row;    /* PSP_UL2_GRID: (N) row of step n, ceil(t_n / dt_ref) formed on the host, in [0, nrows) */
+    float ul2_xb, ul2_dx; /* PSP_UL2_GRID: grid half-width and cell width (fp32 of the reference's values)              */
+    float ul2_xhi;        /* PSP_UL2_GRID: upper clamp, fp32(xb - 2 dx) with xb - 2 dx formed in double as the reference does */
+    int32_t ul2_reserved;
 } psp_dnet_config;
+
+enum { PSP_UL2_TABLE = 0, PSP_UL2_LINEAR = 1, PSP_UL2_GRID = 2 };
 
 typedef struct psp_dnet_sizes {
     int64_t table_bytes;       /* scratch for the A-operand tables the call writes (L2-resident)   */
@@ -497,6 +520,10 @@ int psp_dnet_terminal_reduce(const psp_dnet_config* cfg, const double* fwd_parti
  * time feature per step (importance-sampling grids, utilities.py:296-299), NULL -> n * dt.  Outputs as for
  * psp_hjb_rollout_fwd / psp_hjb_rollout_eval; psp_dnet_terminal_reduce reduces fwd_partial (this family's own
  * workgroup count) to the global (sum D, sum D^2). */
+/* u_L2 log, PSP_UL2_LINEAR: writes the gains cfg->ul2_tables into the table scratch `tables` in the layout the forward reads (behind
+ * the rollout's own tables, which the forward and adjoint calls rewrite without touching this part).  Once per table buffer and set
+ * of gains, before the first psp_dnet_rollout_fwd with ul2_kind = PSP_UL2_LINEAR; a no-op for the other kinds. */
+int psp_dnet_ul2_stage(const psp_dnet_config* cfg, float* tables, void* stream);
 int psp_dnet_rollout_fwd(const psp_dnet_config* cfg, const float* params, const float* x0, int32_t x0_stride,
                          const float* y0, const float* xi, uint64_t seed, uint32_t iter, const float* tfeat,
                          float* px, float* pxi, float* D_out, float* Fint_out, float* XN_out, float* Y_out,

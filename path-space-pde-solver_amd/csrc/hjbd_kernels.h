@@ -36,6 +36,15 @@ struct DnetArgs {
     int d_real, h_real;        // the net's real input / hidden widths (the instance is zero padded above them)
     int time_input;            // 1: input is [t, x] (time = column 0); 0: input is x
     int per_step;              // 1: N consecutive parameter sets, one per time step
+    // u_L2 log (solver.py:471-472, 491-494) of the LOGU forward: sum_n |-Z_n(X_n) - u*(X_{n+1}, t_n)|^2 dt into h.ul2.  h.uref is the
+    // reference data of the kind (non-null: the log is on): 0 the (N, D) table u*(t_n); 1 the (N, D, D) gains M_n (u* = M_n x); 2 the
+    // (G, ul2_nrows, ul2_ncols) grid tables (u*_i = table_{group[i]}[row[n], cell(x_i)], reference problems.py:254-260)
+    int ul2_kind;
+    const int* ul2_group;      // kind 2: (D) table of every coordinate
+    const int* ul2_row;        // kind 2: (N) table row of step n, ceil(t_n / dt_ref)
+    int ul2_ntables, ul2_nrows, ul2_ncols;
+    float ul2_xb, ul2_dx, ul2_xhi;   // kind 2: cell = floor((clamp(x, -xb, xhi) + xb) / dx), xhi = fp32(xb - 2 dx)
+    long long ul2_gofs;        // kind 1: float offset of the gain tables (N x DGeo::GAINF) in tbl, behind the rollout's tables
 };
 
 __device__ __forceinline__ f32x4 relu4d(f32x4 v) {
@@ -63,6 +72,9 @@ struct DGeo {
                          set_floats_x3 = xXall + MERGE * KS8 * NXB * 512;
     static constexpr int oA_x = 0, oB_x = oA_x + KS8 * DB * 512, oSets_x = oB_x + KS8 * DB * 512;
     static constexpr int IMGX = KS8 * 512;
+    // u_L2 log, kind 1: one gain matrix M_n as an fp32 A-operand table (gemm_img over the image of X_{n+1})
+    static constexpr int GAINF = KP * DB * 64;
+    static_assert(GAINF == D * D, "the host sizes the gain tables as N d^2 floats");
     // per-step bias vectors (time column folded in), T-layout order [block][q][r]
     static constexpr int v1 = 0, v2 = v1 + HB * 16, v3 = v2 + HB * 16, vec_floats = v3 + DB * 16;
     // region: [dt A][B][sets ...][vectors of step 0 .. N-1]
@@ -107,6 +119,19 @@ __global__ __launch_bounds__(256) void hjbd_tables_kernel(const DnetArgs a, int 
     const long long oW1 = 0, ob1 = (long long)di * hh, oW2 = ob1 + hh, ob2 = oW2 + (long long)(di + hh) * hh,
                     oW3 = ob2 + hh, ob3 = oW3 + (long long)(di + 2 * hh) * d;
     float* T = a.tbl;
+    if (adjoint == 4) {                                // u_L2 log, kind 1 (psp_dnet_ul2_stage): the gains M_n of every step as fp32
+        const float* __restrict__ M = h.uref;          // A-operand tables behind the rollout's tables -- once per table buffer (the
+        float* G = T + a.ul2_gofs;                     // forward and adjoint fills never write this region)
+        const long long total = (long long)h.N * W::GAINF;
+        for (long long idx = gtid; idx < total; idx += gs) {
+            const int n = (int)(idx / W::GAINF), e = (int)(idx % W::GAINF);
+            const int lane = e & 63, t = e >> 6;
+            const int mb = t % W::DB, ks = t / W::DB;
+            const int i = lane & 15, q = lane >> 4;
+            G[idx] = M[((long long)n * D + 16 * mb + 4 * (i & 3) + (i >> 2)) * D + 4 * ks + q];     // table_fill's layout
+        }
+        return;
+    }
     if (adjoint == 2) {                                // split-product forward tables (same sources as the fp32 forward set below)
         auto fill = [&](float* dstf, int MB, int NS, auto src) { table_fill_x3(dstf, MB, NS, gtid, gs, src); };
         if (h.drift_kind == DRIFT_DENSE) {
@@ -288,8 +313,16 @@ __global__ __launch_bounds__(256) void hjbd_tables_kernel(const DnetArgs a, int 
 // the tables of hjbd_tables_kernel(.., 2); the two images of a wave hold hi / lo packs
 // SPEC (round 4): dense drift, dense sigma, adaptive process, no running cost, Philox noise, not the relative-entropy loss as
 // compile-time constants -- the LLGC training launch of time_approx='outer' (hjb_kernels.h, hjb_fwd_kernel FAST_ = 2)
-template <int D, int H, bool X3 = false, bool SPEC = false>
+// LOGU: the u_L2 log, 1 + DnetArgs.ul2_kind (0: off).  One instance per kind, for the non-SPEC fp32 and split variants only: a
+// launch with the log off runs the code it ran before, and each kind carries only its own live state.  Kind 0 (u*(t_n)) is summed per
+// state block as Z_n is formed.  Kinds 1 / 2 compare with u*(X_{n+1}), which exists only after X += B v: at d <= 128 -Z_n waits in
+// this wave's X image (dead from the merged product to the next step), wider instances keep it in registers.  Kind 1 forms M_n X_{n+1}
+// over an fp32 image of X_{n+1} in the increment image, dead after X += B v.  Written once per trajectory at the end (like D: the range
+// guard's predicated fp32 rerun overwrites it)
+template <int D, int H, bool X3 = false, bool SPEC = false, int LOGU = 0>
 __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const DnetArgs da) {   // d <= 128: two workgroups per CU
+    static_assert(!(SPEC && LOGU) && LOGU >= 0 && LOGU <= 3, "the SPEC instance has no u_L2 log");
+    constexpr int ukind = LOGU - 1;
     PSP_COND_EXIT(da.h);
     using W = DGeo<D, H>;
     constexpr int DB = W::DB, HB = W::HB, KP = W::KP;
@@ -334,6 +367,7 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const
     const float* Vbase = T + oSets + (long long)(nsets_m1 + 1) * SETF;
 
     double sD = 0.0, sD2 = 0.0;
+    [[maybe_unused]] float ULsum = 0.f;
     {
         const f32x4* vecs0 = reinterpret_cast<const f32x4*>(lds) + q;
         const f32x4* vterm = vecs0 + W::vterm / 4;
@@ -469,6 +503,8 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const
             }
             // ---- control output four state blocks at a time: Z_g = W3x[g] x + W3h1[g] h1 + W3h2[g] h2 + b3
             float S = 0.f, Pz = 0.f;
+            [[maybe_unused]] float UL = 0.f;
+            [[maybe_unused]] f32x4 ZL[(LOGU >= 2 && !W::MERGE) ? DB : 1];     // -Z_n of kinds 1 / 2 (d > 128)
             auto z_group = [&](auto nbc, int g) __attribute__((always_inline)) {
                 constexpr int NB = decltype(nbc)::value;
                 f32x4 Zg[NB];
@@ -529,6 +565,21 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const
                         S = fmaf(Zg[m][r], Zg[m][r], S);
                         Pz = fmaf(Zg[m][r], xi[r], Pz);
                     }
+                    if constexpr (LOGU != 0) {
+                        if constexpr (ukind == 0) {    // |-Z_n - u*(t_n)|^2: u* does not depend on X_{n+1}
+                            const float* ur = a.uref + (size_t)n * D + 16 * b;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const float e = Zg[m][r] + ur[4 * r + q];
+                                UL = fmaf(e, e, UL);
+                            }
+                        } else if constexpr (W::MERGE) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) imgX[(4 * b + r) * 64 + lane] = -Zg[m][r];
+                        } else {
+                            ZL[b] = -Zg[m];
+                        }
+                    }
                     const f32x4 v = k_adaptive ? (sqdt * xi - dt * Zg[m]) : (sqdt * xi);
                     if (k_sigma == SIGMA_DENSE) {
                         if constexpr (X3) vg[m] = v;
@@ -564,6 +615,49 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const
             }
 #pragma unroll
             for (int b = 0; b < DB; ++b) X[b] = Xn[b];
+            if constexpr (LOGU != 0) {                 // kinds 1 / 2: |-Z_n - u*(X_{n+1}, t_n)|^2 (the log line follows the Euler step)
+                [[maybe_unused]] auto zneg = [&](int b, int r) __attribute__((always_inline)) {
+                    if constexpr (W::MERGE) return imgX[(4 * b + r) * 64 + lane];
+                    else return ZL[b][r];
+                };
+                if constexpr (ukind == 1) {            // u* = M_n X_{n+1}
+#pragma unroll
+                    for (int ks = 0; ks < KP; ++ks) imgV[ks * 64 + lane] = X[ks >> 2][ks & 3];
+                    f32x4 U[DB];
+#pragma unroll
+                    for (int b = 0; b < DB; ++b) U[b] = zero4x;
+                    gemm_img<DB, KP>(U, T + da.ul2_gofs + (long long)n * W::GAINF, imgV, lane);
+#pragma unroll
+                    for (int b = 0; b < DB; ++b)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float e = zneg(b, r) - U[b][r];
+                            UL = fmaf(e, e, UL);
+                        }
+                } else if constexpr (ukind == 2) {     // u*_i = table_{group[i]}[row[n], cell(x_i)] (problems.py:254-260)
+                    const long long rowofs = (long long)min(max(da.ul2_row[n], 0), da.ul2_nrows - 1) * da.ul2_ncols;
+                    const long long tstride = (long long)da.ul2_nrows * da.ul2_ncols;
+                    const bool last = (long long)a.k_offset + k == a.K_global - 1;    // the reference's i[-1] -= 2
+#pragma unroll
+                    for (int b = 0; b < DB; ++b)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int f = 16 * b + 4 * r + q;
+                            if (f < dr) {
+                                const float xc = fminf(fmaxf(X[b][r], -da.ul2_xb), da.ul2_xhi);
+                                int cell = (int)floorf((xc + da.ul2_xb) / da.ul2_dx);
+                                if (last) cell -= 2;
+                                if (cell < 0) cell += da.ul2_ncols;                         // numpy: a negative index counts from the end
+                                // (bounds: no effect on data the host builder describes -- ul2_reference)
+                                cell = min(max(cell, 0), da.ul2_ncols - 1);
+                                const int grp = min(max(da.ul2_group[f], 0), da.ul2_ntables - 1);
+                                const float e = zneg(b, r) - a.uref[grp * tstride + rowofs + cell];
+                                UL = fmaf(e, e, UL);
+                            }
+                        }
+                }
+                ULsum = fmaf(UL, dt, ULsum);
+            }
             // ---- running cost f(X_{n+1}) and Y update (solver.py:477-478)
             float fX = 0.f;
             if (k_run == RUN_DIAGQ) {
@@ -601,6 +695,10 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const
         const float Dk = Y - g;
         if (kvalid && q == 0) a.D[k] = Dk;
         if (a.Fint && kvalid && q == 0) a.Fint[k] = Fsum;
+        if constexpr (LOGU != 0) {
+            const float ULt = qsum(ULsum);
+            if (kvalid && q == 0) a.ul2[k] = ULt;
+        }
         if (a.Yout && kvalid && q == 0) a.Yout[k] = Y;
         if (a.XN && kvalid) {
 #pragma unroll
@@ -1207,6 +1305,7 @@ struct DnetInstance {
     hipError_t (*launch_fwd_x3)(const DnetArgs&, int grid, hipStream_t);
     hipError_t (*launch_adj_x3)(const DnetArgs&, int grid, hipStream_t);
     hipError_t (*launch_bwd_x3)(const DnetArgs&, int grid, hipStream_t);   // split-product weight-gradient outer products
+    hipError_t (*launch_ul2_stage)(const DnetArgs&, hipStream_t);          // u_L2 log, kind 1: the gain tables (hjbd_tables_kernel(.., 4))
 };
 
 template <int D, int H>
@@ -1234,11 +1333,30 @@ struct DnetLaunch {
         hipLaunchKernelGGL((hjbd_adj_kernel<D, H, true>), dim3(grid), dim3(256), bytes, s, a);
         return hipGetLastError();
     }
+    template <bool X3, int LOGU>
+    static hipError_t fwd_launch_k(const DnetArgs& a, int grid, int bytes, hipStream_t s) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_fwd_kernel<D, H, X3, false, LOGU>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((hjbd_fwd_kernel<D, H, X3, false, LOGU>), dim3(grid), dim3(256), bytes, s, a);
+        return hipGetLastError();
+    }
+    template <bool X3>
+    static hipError_t fwd_launch_log(const DnetArgs& a, int grid, int bytes, hipStream_t s) {      // u_L2 log on: its kind's instance
+        if (a.ul2_kind == 1) return fwd_launch_k<X3, 2>(a, grid, bytes, s);
+        if (a.ul2_kind == 2) return fwd_launch_k<X3, 3>(a, grid, bytes, s);
+        return fwd_launch_k<X3, 1>(a, grid, bytes, s);
+    }
+    static hipError_t ul2_stage(const DnetArgs& a, hipStream_t s) {
+        hipLaunchKernelGGL((hjbd_tables_kernel<D, H>), dim3(512), dim3(256), 0, s, a, 4);
+        return hipGetLastError();
+    }
     static hipError_t fwd(const DnetArgs& a, int grid, hipStream_t s) {
         hipLaunchKernelGGL((hjbd_tables_kernel<D, H>), dim3(512), dim3(256), 0, s, a, 0);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         const int bytes = W::lds_floats * 4;
+        if (a.h.uref != nullptr) return fwd_launch_log<false>(a, grid, bytes, s);            // u_L2 log on
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_fwd_kernel<D, H>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e != hipSuccess) return e;
@@ -1259,6 +1377,7 @@ struct DnetLaunch {
             hipLaunchKernelGGL((hjbd_fwd_kernel<D, H, true, true>), dim3(grid), dim3(256), bytes, s, a);
             return hipGetLastError();
         }
+        if (h.uref != nullptr) return fwd_launch_log<true>(a, grid, bytes, s);               // u_L2 log on
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_fwd_kernel<D, H, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e != hipSuccess) return e;
@@ -1312,7 +1431,8 @@ struct DnetLaunch {
         // (set / shared table sizes: the larger of the fp32 and the split layouts -- the caller allocates one region for both)
         return DnetInstance{D, H, W::lds_floats * 4, W::set_floats > W::set_floats_x3 ? W::set_floats : W::set_floats_x3, W::vec_floats,
                             W::oSets > W::oSets_x ? W::oSets : W::oSets_x, &fwd,
-                            W::PBI, W::PP, W::bwd_lds_floats * 4, kPasses, &bwd, &adj, W::lds_floats_x3 * 4, &fwd_x3, &adj_x3, &bwd_x3};
+                            W::PBI, W::PP, W::bwd_lds_floats * 4, kPasses, &bwd, &adj, W::lds_floats_x3 * 4, &fwd_x3, &adj_x3, &bwd_x3,
+                            &ul2_stage};
     }
 };
 

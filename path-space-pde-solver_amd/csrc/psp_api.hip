@@ -541,7 +541,8 @@ const char* psp_last_error(void) { return g_err; }
 
 // ---- DenseNet control (hjbd_kernels.h): time_approx='outer' and DenseNet(d+1 -> d) controls ---------------------
 namespace {
-struct DnetPlan { psp::DnetInstance inst; int ntile16, grid; long long table_floats, n_params; int slices, bwd_grid, bwd_ok; };
+struct DnetPlan { psp::DnetInstance inst; int ntile16, grid; long long table_floats, n_params; int slices, bwd_grid, bwd_ok; bool ul2;
+                  long long ul2_gofs; };
 int make_dnet_plan(const psp_dnet_config* c, DnetPlan* p) {
     if (!c) return fail(-1, "null config");
     const psp_hjb_config& b = c->base;
@@ -563,6 +564,25 @@ int make_dnet_plan(const psp_dnet_config* c, DnetPlan* p) {
     p->grid = (p->ntile16 + 3) / 4;
     p->table_floats = (long long)p->inst.shared_floats + (long long)(c->per_step ? b.N : 1) * p->inst.set_floats +
                       (long long)b.N * p->inst.vec_floats;
+    // u_L2 log (psp_dnet_config.ul2_*), validated before any launch
+    if (c->ul2_kind < PSP_UL2_TABLE || c->ul2_kind > PSP_UL2_GRID)
+        return fail(-1, "ul2_kind out of range (PSP_UL2_TABLE, PSP_UL2_LINEAR, PSP_UL2_GRID)");
+    p->ul2 = b.u_ref != nullptr || c->ul2_kind != PSP_UL2_TABLE;
+    if (c->ul2_kind != PSP_UL2_TABLE) {
+        if (b.u_ref) return fail(-1, "base.u_ref is the PSP_UL2_TABLE reference; ul2_kind 1 / 2 read ul2_tables");
+        if (!c->ul2_tables) return fail(-1, "ul2_kind 1 / 2 needs ul2_tables");
+    }
+    if (c->ul2_kind == PSP_UL2_GRID) {
+        if (!c->ul2_group) return fail(-1, "ul2_kind PSP_UL2_GRID needs ul2_group");
+        if (!c->ul2_row) return fail(-1, "ul2_kind PSP_UL2_GRID needs ul2_row");
+        if (c->ul2_ntables <= 0 || c->ul2_nrows <= 0 || c->ul2_ncols <= 0)
+            return fail(-1, "ul2_ntables / ul2_nrows / ul2_ncols must be positive");
+        if (!(c->ul2_dx > 0.f) || !(c->ul2_xb > 0.f)) return fail(-1, "ul2_xb / ul2_dx must be positive");
+    }
+    if (p->ul2 && !b.u_l2_out) return fail(-1, "the u_L2 log (base.u_ref or ul2_kind) needs base.u_l2_out");
+    // kind 1: the gains M_n as fp32 A-operand tables (N x d^2 floats, DGeo::GAINF) behind the rollout's tables
+    p->ul2_gofs = p->table_floats;
+    if (c->ul2_kind == PSP_UL2_LINEAR) p->table_floats += (long long)b.N * b.d * b.d;
     const long long di = c->d_real + (c->time_input ? 1 : 0), h = c->H_real, d = c->d_real;
     p->n_params = di * h + h + (di + h) * h + h + (di + 2 * h) * d + d;
     // backward work items = (step, slice): about two waves of workgroups over the chip, at least one round per item
@@ -673,6 +693,21 @@ extern "C" int psp_dnet_adjoint_sweep(const psp_dnet_config* cfg, const float* p
     return 0;
 }
 
+extern "C" int psp_dnet_ul2_stage(const psp_dnet_config* cfg, float* tables, void* stream) {
+    DnetPlan p;
+    int rc = make_dnet_plan(cfg, &p);
+    if (rc) return rc;
+    if (cfg->ul2_kind != PSP_UL2_LINEAR) return 0;
+    if (!tables) return fail(-1, "null buffer passed to psp_dnet_ul2_stage");
+    psp::DnetArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h.N = cfg->base.N; a.h.uref = cfg->ul2_tables;
+    a.tbl = tables; a.ul2_gofs = p.ul2_gofs;
+    hipError_t e = p.inst.launch_ul2_stage(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "hjbd_tables_kernel (gain tables) launch");
+    return 0;
+}
+
 extern "C" int psp_dnet_rollout_fwd(const psp_dnet_config* cfg, const float* params, const float* x0, int32_t x0_stride,
                                     const float* y0, const float* xi, uint64_t seed, uint32_t iter, const float* tfeat,
                                     float* px, float* pxi, float* D_out, float* Fint_out, float* XN_out, float* Y_out,
@@ -704,6 +739,13 @@ extern "C" int psp_dnet_rollout_fwd(const psp_dnet_config* cfg, const float* par
     if ((cfg->r1_out == nullptr) != (cfg->r2_out == nullptr)) return fail(-1, "r1_out and r2_out go together");
     a.pr1 = cfg->r1_out; a.pr2 = cfg->r2_out; a.pimg = cfg->images_out;
     a.d_real = cfg->d_real; a.h_real = cfg->H_real; a.time_input = cfg->time_input ? 1 : 0; a.per_step = cfg->per_step ? 1 : 0;
+    if (p.ul2) {                               // u_L2 log: h.uref = the kind's reference data (non-null selects the LOGU kernels)
+        h.uref = cfg->ul2_kind == PSP_UL2_TABLE ? b->u_ref : cfg->ul2_tables;
+        h.ul2 = b->u_l2_out;
+        a.ul2_kind = cfg->ul2_kind; a.ul2_group = cfg->ul2_group; a.ul2_row = cfg->ul2_row;
+        a.ul2_ntables = cfg->ul2_ntables; a.ul2_nrows = cfg->ul2_nrows; a.ul2_ncols = cfg->ul2_ncols;
+        a.ul2_xb = cfg->ul2_xb; a.ul2_dx = cfg->ul2_dx; a.ul2_xhi = cfg->ul2_xhi; a.ul2_gofs = p.ul2_gofs;
+    }
     const bool x3 = b->mlp_dtype == PSP_MLP_F16X3 && p.inst.launch_fwd_x3 && p.inst.lds_bytes_x3 <= kMaxLds;
     if (b->mlp_dtype == PSP_MLP_F16X3 && !x3) return fail(-3, "split-product forward images do not fit the 160 KiB LDS for this (d,H)");
     hipError_t e = x3 ? p.inst.launch_fwd_x3(a, p.grid, (hipStream_t)stream) : p.inst.launch_fwd(a, p.grid, (hipStream_t)stream);

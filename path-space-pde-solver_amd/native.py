@@ -20,6 +20,7 @@ SIGMA_IDENTITY, SIGMA_DENSE, SIGMA_SCALED_IDENTITY = 0, 1, 2
 RUNCOST_ZERO, RUNCOST_DIAG_QUAD = 0, 1
 TERM_LINEAR, TERM_DIAG_QUAD, TERM_SHIFTED_QUAD = 0, 1, 2
 LOSS_LOG_VARIANCE, LOSS_MOMENT, LOSS_WEIGHTS, LOSS_REL_ENTROPY = 0, 1, 2, 3
+UL2_TABLE, UL2_LINEAR, UL2_GRID = 0, 1, 2
 NOISE_SUPPLIED, NOISE_PHILOX = 0, 1
 GH_ZERO, GH_QUAD, GH_ALLEN_CAHN, GH_EXPBALL_LIN, GH_EXPBALL_SQ, GH_EXPBALL_SIN = 0, 1, 2, 3, 4, 5
 MLP_FP32, MLP_BF16_FWD, MLP_BF16, MLP_F16X3 = 0, 1, 2, 3
@@ -84,7 +85,11 @@ class GenConfig(C.Structure):
 
 class DnetConfig(C.Structure):
     _fields_ = [("base", HjbConfig), ("d_real", C.c_int32), ("H_real", C.c_int32), ("time_input", C.c_int32),
-                ("per_step", C.c_int32), ("r1_out", C.c_void_p), ("r2_out", C.c_void_p), ("images_out", C.c_void_p)]
+                ("per_step", C.c_int32), ("r1_out", C.c_void_p), ("r2_out", C.c_void_p), ("images_out", C.c_void_p),
+                # u_L2 log of reference controls that depend on x (include/psp.h: PSP_UL2_*)
+                ("ul2_kind", C.c_int32), ("ul2_ntables", C.c_int32), ("ul2_nrows", C.c_int32), ("ul2_ncols", C.c_int32),
+                ("ul2_tables", C.c_void_p), ("ul2_group", C.c_void_p), ("ul2_row", C.c_void_p),
+                ("ul2_xb", C.c_float), ("ul2_dx", C.c_float), ("ul2_xhi", C.c_float), ("ul2_reserved", C.c_int32)]
 
 
 class DnetSizes(C.Structure):
@@ -133,6 +138,7 @@ SIGNATURES = {
     "psp_dnet_terminal_reduce": (C.c_int, [C.POINTER(DnetConfig), _P, _P, _P]),
     "psp_dnet_rollout_bwd": (C.c_int, [C.POINTER(DnetConfig), _P, _P, _P, _P, _P]),
     "psp_dnet_adjoint_sweep": (C.c_int, [C.POINTER(DnetConfig), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psp_dnet_ul2_stage": (C.c_int, [C.POINTER(DnetConfig), _P, _P]),
     "psp_dnet_rollout_fwd": (C.c_int, [C.POINTER(DnetConfig), _P, _P, C.c_int32, _P, _P, C.c_uint64, C.c_uint32, _P,
                                        _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "psp_gen_instance_count": (C.c_int, []),

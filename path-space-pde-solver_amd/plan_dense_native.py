@@ -22,6 +22,9 @@ hand-written backward covers: the rollout leaves xi - sqrt(dt) Z (or Z) in the x
 psp_dnet_adjoint_sweep (csrc/hjbd_kernels.h: hjbd_adj_kernel) walks the adjoint recursion backwards in time with the
 Jacobian of the dense-concat net and overwrites the slot with dL/dZ_n / sqrt(dt), and the backward kernel runs with unit
 weights -- the scheme of plan_native.py / psp_hjb_adjoint_sweep.
+The u_L2 log (solver.py:471-472, 491-494; on by default whenever the problem has u_true) is accumulated per trajectory inside
+the forward kernel from a description of u* built once per plan by ul2_reference (below): a table of u*(t_n), the gains M_n of
+a u* linear in x, or the double wells' grid tables with the reference's index arithmetic.
 """
 import ctypes as C
 
@@ -32,13 +35,13 @@ try:
     from . import native_shapes as shapes
     from . import sharding
     from .function_space import DenseNet
-    from .plan_native import HjbNativePlan, PlanUnsupported, _overridden
+    from .plan_native import HjbNativePlan, PlanUnsupported, _overridden, _u_tables
 except ImportError:
     import native as nat
     import native_shapes as shapes
     import sharding
     from function_space import DenseNet
-    from plan_native import HjbNativePlan, PlanUnsupported, _overridden
+    from plan_native import HjbNativePlan, PlanUnsupported, _overridden, _u_tables
 
 _LOSSES = ('log-variance', 'moment', 'variance', 'cross_entropy', 'relative_entropy')
 
@@ -52,6 +55,87 @@ def _instance_for(d, H):
     return min(cands, key=lambda t: (t[0] * t[0] + 3 * t[0] * t[1], t[1])) if cands else None
 
 
+def ul2_kind(problem):
+    """Which description of the reference control u* the forward kernel can log u_L2 against (include/psp.h PSP_UL2_*): 2 the
+    grid tables of the double wells (problem.u_true_tables()), 0 a u* that does not depend on x, 1 a u* linear in x; None: none."""
+    if _u_tables(problem) is not None:
+        return nat.UL2_GRID
+    if getattr(problem, 'u_true_x_independent', False) is True:
+        return nat.UL2_TABLE
+    if getattr(problem, 'u_true_linear_in_x', False) is True:
+        return nat.UL2_LINEAR
+    return None
+
+
+def ul2_unsupported(problem, N, dt_np):
+    """None if the forward kernel can log u_L2 for this problem on the time grid (N steps of dt_np), else the precise reason."""
+    import numpy as np
+    kind = ul2_kind(problem)
+    if kind is None:
+        return ('u_l2_error_flag=True evaluates problem.u_true(X_n, t_n) on the host every step (reference solver.py:491-494); '
+                'the forward kernel logs u_L2 for a u_true that does not depend on x (u_true_x_independent), is linear in x '
+                '(u_true_linear_in_x) or is tabulated per coordinate (u_true_tables(), e.g. a double well after '
+                'compute_reference_solution) -- this problem has none of these; pass u_l2_error_flag=False for the native plan')
+    if kind != nat.UL2_GRID:
+        return None
+    tb = _u_tables(problem)
+    shapes = [np.shape(t) for t in tb['tables']]
+    if any(len(sh) != 2 or sh != shapes[0] for sh in shapes):
+        return ('the u_true_tables() of this problem have unequal shapes %s; the forward kernel reads tables of one '
+                '(rows, cells) shape' % shapes)
+    last = int(np.ceil((N - 1) * dt_np / tb['delta_t'])) if N > 0 else 0
+    if last >= shapes[0][0]:
+        return ('the u_true_tables() of this problem end at t = %g (%d rows of dt_ref = %g); the solver reads row %d at t = %g'
+                % ((shapes[0][0] - 1) * tb['delta_t'], shapes[0][0], tb['delta_t'], last, (N - 1) * dt_np))
+    return None
+
+
+def ul2_reference(problem, N, dt_np, d_pad, K_global, k_offset):
+    """Host-side description of u*(x, t_n), n < N, for the u_L2 log of the DenseNet-control forward kernel, padded to d_pad
+    (CPU tensors; None when the problem has no description the kernel reads -- see ul2_kind).  t_n = n * dt_np as the reference
+    forms it (solver.py:493).  Keys: 'kind', 'd', 'K_global', 'k_offset' and
+      kind 0: 'table' (N, d_pad) u*(t_n)                                     -- probed at x = 0 (plan_native.py recipe)
+      kind 1: 'gains' (N, d_pad, d_pad) M_n with u*(x, t_n) = M_n x          -- probed with the unit vectors
+      kind 2: 'tables' (G, nrows, ncols) fp32, 'group' (d_pad) int32, 'row' (N) int32 = ceil(t_n / dt_ref), 'xb', 'dx', 'xhi' =
+              fp32(xb - 2 dx) (formed in double, as the reference's clamp bound), 'nrows', 'ncols'.
+    The cell arithmetic of kind 2 (clamp, true fp32 division, the last global trajectory lowered by two, numpy wrap-around) is the
+    kernel's (csrc/hjbd_kernels.h); K_global / k_offset locate that trajectory.  Raises ValueError with ul2_unsupported's reason
+    for grid tables the kernel cannot read."""
+    import numpy as np
+    kind = ul2_kind(problem)
+    if kind is None:
+        return None
+    reason = ul2_unsupported(problem, N, dt_np)
+    if reason is not None:
+        raise ValueError(reason)
+    d = problem.d
+    out = dict(kind=kind, d=d, K_global=int(K_global), k_offset=int(k_offset))
+    if kind == nat.UL2_TABLE:
+        probe = torch.zeros(1, d)
+        rows = [torch.tensor(np.asarray(problem.u_true(probe, n * dt_np))).reshape(d, -1)[:, 0].float() for n in range(N)]
+        table = torch.zeros(N, d_pad)
+        table[:, :d] = torch.stack(rows)
+        out['table'] = table
+    elif kind == nat.UL2_LINEAR:
+        eye = torch.eye(d)
+        gains = torch.zeros(N, d_pad, d_pad)
+        for n in range(N):                                   # u_true returns (d, K): column j = M e_j
+            gains[n, :d, :d] = torch.tensor(np.asarray(problem.u_true(eye, n * dt_np))).reshape(d, d).float()
+        out['gains'] = gains
+    else:
+        tb = _u_tables(problem)
+        tabs = [np.asarray(t, dtype=np.float32) for t in tb['tables']]
+        nrows, ncols = tabs[0].shape
+        group = torch.zeros(d_pad, dtype=torch.int32)
+        group[:d] = torch.tensor(tb['group_of_dim'], dtype=torch.int32)
+        xb, dx = float(tb['xb']), float(tb['dx'])
+        out.update(tables=torch.from_numpy(np.stack(tabs)), group=group,
+                   row=torch.tensor([int(np.ceil(n * dt_np / tb['delta_t'])) for n in range(N)], dtype=torch.int32),
+                   xb=float(np.float32(xb)), dx=float(np.float32(dx)), xhi=float(np.float32(xb - 2 * dx)),
+                   nrows=int(nrows), ncols=int(ncols))
+    return out
+
+
 def dense_eligibility(solver):
     """None if the solver can run on this plan, else a human-readable reason."""
     if solver.device.type != 'cuda':
@@ -62,9 +146,13 @@ def dense_eligibility(solver):
         return 'loss_method %r is not native for a DenseNet control (%s are)' % (solver.loss_method, ', '.join(_LOSSES))
     if solver.loss_method == 'relative_entropy' and not solver.adaptive_forward_process:
         return 'relative_entropy with a non-adaptive forward process is not native for a DenseNet control'
-    if solver.burgers_drift or solver.u_l2_error_flag or solver.compute_gradient_variance > 0 or solver.log_gradient \
+    if solver.burgers_drift or solver.compute_gradient_variance > 0 or solver.log_gradient \
             or solver.metastability_logs is not None:
-        return 'per-step / per-iteration diagnostics (u_L2, gradient logs, metastability) are not native here'
+        return 'per-step / per-iteration diagnostics (gradient logs, metastability) are not native here'
+    if solver.u_l2_error_flag:
+        reason = ul2_unsupported(solver.problem, solver.N, solver.delta_t_np)
+        if reason is not None:
+            return reason
     nets = _nets(solver)
     outer = solver.time_approx == 'outer'
     if outer and len(nets) != solver.N:
@@ -145,6 +233,28 @@ class DenseNativePlan:
         cfg.d_real, cfg.H_real = s.d, self.H
         cfg.time_input, cfg.per_step = (0 if self.outer else 1), (1 if self.outer else 0)
         self.cfg = cfg
+        # u_L2 log (solver.py:491-494): the description of u* goes to the device once; the kernel writes one float per trajectory
+        self.ul2 = None
+        if s.u_l2_error_flag:
+            try:
+                ref = ul2_reference(s.problem, s.N, s.delta_t_np, self.d_pad, s.K, self.k_offset)
+            except ValueError as e:
+                raise PlanUnsupported(str(e))
+            self.ul2 = torch.zeros(self.K_local, dtype=torch.float32, device=dev)
+            b.u_l2_out = nat.ptr(self.ul2)
+            cfg.ul2_kind = ref['kind']
+            if ref['kind'] == nat.UL2_TABLE:          # (16 floats of slack: include/psp.h u_ref)
+                b.u_ref = nat.ptr(dev_f32(torch.cat([ref['table'].reshape(-1), torch.zeros(16)])))
+            elif ref['kind'] == nat.UL2_LINEAR:
+                cfg.ul2_tables = nat.ptr(dev_f32(ref['gains']))
+            else:
+                cfg.ul2_tables = nat.ptr(dev_f32(ref['tables']))
+                for key in ('group', 'row'):
+                    t = ref[key].to(device=dev).contiguous()
+                    self._keep.append(t)
+                    setattr(cfg, 'ul2_' + key, nat.ptr(t))
+                cfg.ul2_ntables, cfg.ul2_nrows, cfg.ul2_ncols = ref['tables'].shape[0], ref['nrows'], ref['ncols']
+                cfg.ul2_xb, cfg.ul2_dx, cfg.ul2_xhi = ref['xb'], ref['dx'], ref['xhi']
         sizes = nat.DnetSizes()
         # matrix products of the forward rollout: 'f16x3' = fp32-grade split products on the f16 matrix pipe (csrc/hjbd_kernels.h
         # hjbd_fwd_kernel<.., X3>; same parity bounds); 'auto' (the default) takes it where its images fit the LDS
@@ -166,6 +276,8 @@ class DenseNativePlan:
         assert sizes.n_params_per_set == self.Pset, (sizes.n_params_per_set, self.Pset)
         f32 = torch.float32
         self.tables = torch.empty(sizes.table_bytes // 4, dtype=f32, device=dev)
+        if self.ul2 is not None:            # u_L2 log, kind 1: the gain tables go into the table scratch once
+            nat.check(self.lib.psp_dnet_ul2_stage(C.byref(cfg), nat.ptr(self.tables), nat.stream_ptr(dev)), 'psp_dnet_ul2_stage')
         self.fwd_partial = torch.empty(sizes.fwd_partial_bytes // 8, dtype=torch.float64, device=dev)
         # gradient: the hand-written kernel (csrc/hjbd_kernels.h, hjbd_bwd_kernel) where the instance is covered, else the
         # library-GEMM formulation on row-major stores (PSP_DENSE_BWD=gemm forces the latter: cross-check / timing)
@@ -206,7 +318,6 @@ class DenseNativePlan:
         self.tn = (torch.arange(s.N, device=dev, dtype=f32) * b.dt)        # fp32 n * dt, as the kernel forms it
         self.step = 0
         self.events = None
-        self.ul2 = None
         self.learn_y0 = bool(s.learn_Y_0)
         if self.learn_y0:
             self.y0_param = s.y_0.Y_0
@@ -387,6 +498,10 @@ class DenseNativePlan:
             loss = sharding.loss_from_sums(self.sums, s.K, s.loss_method)
             w = None if self.relent else sharding.loss_weights(self.D, self.sums, s.K, s.loss_method)
         loss_out[l] = loss.to(torch.float32)
+        if self.ul2 is not None and ul2_out is not None:
+            m = (self.ul2.sum() / float(s.K)).reshape(1)           # mean over the GLOBAL K, no host sync
+            sharding.allreduce_sum_(m)
+            ul2_out[l:l + 1] = m
         if ev is not None:
             ev[2].record()
         if self.attached:
