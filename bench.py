@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the path-space hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run does only what its headline figure needs: set-up, W warm-up steps, the K timed steps, the dump (if asked) and
+the JSON line.  Its `roofline` is priced on the HIP events the timed steps record; a workload whose timed steps replay a
+hipGraph records none, and its plain line carries `roofline: null`.
+
+--full: also every measurement and check that takes a run of its own (`also_*`, `cpu_baseline`, `loss_rel_err_vs_cpu_ref`,
+`gpu_over_cpu`, `also_composite_torch_plan_same_gpu`, the eager iterations that time the kernels of a hipGraph workload,
+and with N > 1 `parity_vs_1rank` and the C-ABI all-reduce check).  All of them run after the timed region and the dump,
+except `parity_vs_1rank`, which runs before the warm-up.  --no-cpu-baseline, --no-secondary and --no-sustained drop single
+legs of a --full run.
 
 --dump-outputs DIR: right after the timed region (before any untimed iteration), rank 0 writes what the timed path
 computed in its last step as DIR/<name>.npy (float32 / float64, 64 MB at most): the losses of the timed steps, the
@@ -21,7 +31,7 @@ starts that same command as a child and relays its exit code; rank 0 prints the 
 Weak-scaling workloads keep the per-GPU trajectory count, strong-scaling ones (K_global in the
 workload) split a fixed global batch; `value` is always the whole-job aggregate.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  Extra objects (also_sustained, parity_vs_1rank and cpu_baseline with --full only):
   roofline     -- dominant kernel (the longer of the two rollout kernels), timed with HIP events recorded on the launch
                   stream inside the timed region.  Two terms, both from SURVEY.md 8(d)'s ALGORITHMIC work per
                   trajectory-timestep x the units one launch processes / the kernel's mean duration:
@@ -640,22 +650,29 @@ def load_traffic(workload, kernel):
     return ent
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="hjb_llgc_d100_K65536_N100_h64",
                     choices=sorted(WORKLOADS) + sorted(GENERAL_WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] side measurement")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the >= 3 s steady-state leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and self-checks (see the module docstring); off: the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle legs")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the side measurements on other configurations")
+    ap.add_argument("--no-sustained", action="store_true", help="--full: skip the >= 3 s steady-state leg")
     ap.add_argument("--sustain-s", type=float, default=3.0)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def main():
+    args = parse_args()
     spawn_ranks_if_needed(args)                          # N > 1 without a launcher: children do the work
 
     import path_space_pde_solver_amd as psp
@@ -691,9 +708,9 @@ def main():
         model.update_Phis()
     plan = model._choose_plan()
     assert model.plan_name == "native"
-    parity = parity_vs_one_rank(psp, sharding, dist, rank, world, dev, w, outer) if world > 1 else None
+    parity = parity_vs_one_rank(psp, sharding, dist, rank, world, dev, w, outer) if (world > 1 and args.full) else None
     N_t = model.N
-    n_eager = 6                                          # eager iterations after the timed region (graph workloads only)
+    n_eager = 6                                          # eager iterations after the timed region (graph workloads, --full)
     losses = torch.zeros(total + n_eager, dtype=torch.float32, device=dev)
     for l in range(args.warmup):
         plan.iteration(l, losses)
@@ -707,28 +724,30 @@ def main():
         if args.dump_outputs and rank == 0:
             dump_outputs(args.dump_outputs, plan, {"loss": losses[args.warmup:total]})
     if graph:
-        # launch-bound iteration replayed as a hipGraph: `value` is timed on the replay; the per-kernel HIP events of the
-        # roofline come from a few eager iterations of the same kernels AFTER the timed region
+        # launch-bound iteration replayed as a hipGraph: `value` is timed on the replay; with --full the per-kernel HIP events
+        # of the roofline come from a few eager iterations of the same kernels AFTER the timed region
         elapsed = timed_region(dist, dev, lambda l: plan.iteration(l, losses), args.steps, args.warmup)
         dump()
-        plan.events = []
-        for l in range(total, total + n_eager):
-            plan.iteration(l, losses)
-        torch.cuda.synchronize()
-        plan.events = plan.events[1:]
+        if args.full:
+            plan.events = []
+            for l in range(total, total + n_eager):
+                plan.iteration(l, losses)
+            torch.cuda.synchronize()
+            plan.events = plan.events[1:]
     else:
         plan.events = []                                 # (fwd_start, fwd_end, bwd_start, bwd_end) per launch pair
         elapsed = timed_region(dist, dev, lambda l: plan.iteration(l, losses), args.steps, args.warmup)
         dump()
 
-    n_ev = max(1, len(plan.events))
-    fwd_ms = sum(e[0].elapsed_time(e[1]) for e in plan.events) / n_ev
-    bwd_ms = sum(e[2].elapsed_time(e[3]) for e in plan.events) / n_ev
+    events = plan.events or []
+    n_ev = max(1, len(events))
+    fwd_ms = sum(e[0].elapsed_time(e[1]) for e in events) / n_ev
+    bwd_ms = sum(e[2].elapsed_time(e[3]) for e in events) / n_ev
     coll = collective_summary(sharding, args.steps)
     sharding.coll_events = None
     loss_vals = losses.cpu().tolist()[:total]
     if rank != 0:
-        finish_ranks(psp, dist, rank, world, dev, rehearsal)
+        finish_ranks(psp, dist, rank, world, dev, rehearsal, args.full)
         return
 
     dense = w["off_diag"] != 0.0
@@ -767,71 +786,73 @@ def main():
                 issued_x3 = (issued_x3[0], None)
         if quad:
             issued = (issued_mfma_quad_kernel(plan.d_pad, plan.H_pad, dense), 0, issued[2])
-    bwd_dominant = bwd_ms >= fwd_ms
-    dom, dom_ms, which = (bwd_name, bwd_ms, "bwd_kernel") if bwd_dominant else (fwd_name, fwd_ms, "fwd_kernel")
-    if issued is None:                                   # DenseNet control: algorithmic terms only
-        t = dom_ms * 1e-3
-        # (split-product forward: three f16 flops per algorithmic fp32 flop; its backward kernel runs fp32 MFMA)
-        mf = dict(achieved=fl2[which] * units_launch / t / 1e12,
-                  peak=(PEAK_BF16_MFMA_TFLOPS / 3.0) if (x3 and which == "fwd_kernel") else PEAK_FP32_MFMA_TFLOPS)
-        mf["frac"] = mf["achieved"] / mf["peak"]
-        mf["frac_issued"] = None
-        mf["frac_survey_m3"] = fl3[which] * units_launch / t / 1e12 / mf["peak"]
-    elif x3 and not (which == "bwd_kernel" and issued_x3[1] is None):
-        mf = x3_roofline(fl2, fl3, issued_x3, units_launch, tiles_steps, dom_ms, which)
-    else:
-        mf = mfma_roofline(fl2, fl3, issued, units_launch, tiles_steps, dom_ms, bf16_mlp, which)
-    # HBM term: SURVEY 8d's algorithmic bytes (state streamed once per step, 8d + 8) and this design's real ones (the path
-    # store: state stays on chip, the forward writes / the backward reads one block of register images per unit)
-    path_B_unit = float(plan.sizes.path_bytes) / max(1, units_launch) if hasattr(plan, "sizes") else None
-    if path_B_unit and getattr(plan, "regen_xi", False):
-        # store_path 4 (include/psp.h): the xi slot of a block is neither written nor read (the backward regenerates the
-        # increments from the Philox counters); the allocation keeps the slot, the traffic does not
-        path_B_unit -= 4.0 * 16 * ((plan.d_pad + 15) // 16)
     step_s = elapsed / args.steps
-    dom_s = dom_ms * 1e-3
-    alg_B_unit = 8 * w["d"] + 8
-    hbm = {"bytes_per_unit_alg": alg_B_unit, "achieved_GBps_alg": alg_B_unit * units_launch / dom_s / 1e9,
-           "bytes_per_unit_path_store": path_B_unit,
-           "achieved_GBps_path_store": (path_B_unit * units_launch / dom_s / 1e9) if path_B_unit else None,
-           "peak_GBps": PEAK_HBM_GBS, "achievable_GBps": 6300.0}
-    hbm["frac_alg_bytes"] = hbm["achieved_GBps_alg"] / PEAK_HBM_GBS
-    hbm["frac_path_store"] = (hbm["achieved_GBps_path_store"] or 0.0) / PEAK_HBM_GBS
-    hbm["frac"] = hbm["frac_alg_bytes"]
-    bound = "mfma" if mf["frac"] >= hbm["frac_alg_bytes"] else "hbm"
     value = K_global * N_t * args.steps / elapsed
-    whole_tf = fl2["total"] * K_local * N_t / step_s / 1e12
-    counters = load_counters(args.workload, dom)
-    roof = {"bound": bound, "kernel": dom,
-            "achieved": mf["achieved"] if bound == "mfma" else hbm["achieved_GBps_alg"],
-            "peak": mf["peak"] if bound == "mfma" else PEAK_HBM_GBS,
-            "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
-            "frac": max(mf["frac"], hbm["frac_alg_bytes"]),
-            "traffic": load_traffic(args.workload, dom),
-            "binder": binder_of(mf["frac"], hbm["frac_alg_bytes"], hbm["frac_path_store"], counters, tiles_steps),
-            "convention": ("SURVEY 8d algorithmic work per trajectory-timestep x units per launch / HIP-event kernel time / peak: "
-                           "bytes 8d+8 against 8 TB/s, minimal flops (m = 2 dense d x d products) against the peak of the pipe the "
-                           "kernel computes on (%s); frac = the larger of the two; hbm_term.frac_path_store prices the bytes the "
-                           "design really moves" % ("2500/3 TFLOP/s: split products, three f16 flops per fp32 flop" if x3 else
-                                                    ("bf16 / fp32 blend" if bf16_mlp else "157.3 TFLOP/s fp32 MFMA"))),
-            "mfma_term": mf, "hbm_term": hbm,
-            "alg_flops_per_traj_step": {k: fl2[k] for k in ("fwd_kernel", "bwd_kernel", "total")},
-            "alg_flops_per_traj_step_survey_m3": {k: fl3[k] for k in ("fwd_kernel", "bwd_kernel", "total")},
-            "issued_mfma_per_tile_step": ({"fwd": issued_x3[0], "bwd": issued_x3[1]} if (x3 and issued_x3) else
-                                          {"fwd_f32_16x16x4": issued[0], "fwd_bf16_16x16x32": issued[1],
-                                           "bwd_f32_16x16x4": issued[2]} if issued else None),
-            "units_per_launch": units_launch, "launches_per_step": n_chunks,
-            "fwd_kernel_ms": fwd_ms, "bwd_kernel_ms": bwd_ms,
-            "whole_step_tflops": whole_tf, "whole_step_frac_of_fp32_peak": whole_tf / PEAK_FP32_MFMA_TFLOPS}
-    # the other rollout kernel, same two terms (the iteration is the pair)
-    oth, oth_ms, oth_which = (fwd_name, fwd_ms, "fwd_kernel") if bwd_dominant else (bwd_name, bwd_ms, "bwd_kernel")
-    if oth_ms > 0:
-        oth_peak = mf["peak"] if not (x3 and oth_which == "bwd_kernel" and issued_x3 and issued_x3[1] is None) else PEAK_FP32_MFMA_TFLOPS
-        roof["other_kernel"] = {"kernel": oth, "ms": oth_ms,
-                                "frac_alg_bytes": alg_B_unit * units_launch / (oth_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                                "frac_path_store": ((path_B_unit or 0.0) * units_launch / (oth_ms * 1e-3) / 1e9) / PEAK_HBM_GBS,
-                                "frac_mfma": fl2[oth_which] * units_launch / (oth_ms * 1e-3) / 1e12 / oth_peak,
-                                "traffic": load_traffic(args.workload, oth)}
+    roof = None
+    if events:                                           # (none in a plain run of a hipGraph workload)
+        bwd_dominant = bwd_ms >= fwd_ms
+        dom, dom_ms, which = (bwd_name, bwd_ms, "bwd_kernel") if bwd_dominant else (fwd_name, fwd_ms, "fwd_kernel")
+        if issued is None:                                   # DenseNet control: algorithmic terms only
+            t = dom_ms * 1e-3
+            # (split-product forward: three f16 flops per algorithmic fp32 flop; its backward kernel runs fp32 MFMA)
+            mf = dict(achieved=fl2[which] * units_launch / t / 1e12,
+                      peak=(PEAK_BF16_MFMA_TFLOPS / 3.0) if (x3 and which == "fwd_kernel") else PEAK_FP32_MFMA_TFLOPS)
+            mf["frac"] = mf["achieved"] / mf["peak"]
+            mf["frac_issued"] = None
+            mf["frac_survey_m3"] = fl3[which] * units_launch / t / 1e12 / mf["peak"]
+        elif x3 and not (which == "bwd_kernel" and issued_x3[1] is None):
+            mf = x3_roofline(fl2, fl3, issued_x3, units_launch, tiles_steps, dom_ms, which)
+        else:
+            mf = mfma_roofline(fl2, fl3, issued, units_launch, tiles_steps, dom_ms, bf16_mlp, which)
+        # HBM term: SURVEY 8d's algorithmic bytes (state streamed once per step, 8d + 8) and this design's real ones (the path
+        # store: state stays on chip, the forward writes / the backward reads one block of register images per unit)
+        path_B_unit = float(plan.sizes.path_bytes) / max(1, units_launch) if hasattr(plan, "sizes") else None
+        if path_B_unit and getattr(plan, "regen_xi", False):
+            # store_path 4 (include/psp.h): the xi slot of a block is neither written nor read (the backward regenerates the
+            # increments from the Philox counters); the allocation keeps the slot, the traffic does not
+            path_B_unit -= 4.0 * 16 * ((plan.d_pad + 15) // 16)
+        dom_s = dom_ms * 1e-3
+        alg_B_unit = 8 * w["d"] + 8
+        hbm = {"bytes_per_unit_alg": alg_B_unit, "achieved_GBps_alg": alg_B_unit * units_launch / dom_s / 1e9,
+               "bytes_per_unit_path_store": path_B_unit,
+               "achieved_GBps_path_store": (path_B_unit * units_launch / dom_s / 1e9) if path_B_unit else None,
+               "peak_GBps": PEAK_HBM_GBS, "achievable_GBps": 6300.0}
+        hbm["frac_alg_bytes"] = hbm["achieved_GBps_alg"] / PEAK_HBM_GBS
+        hbm["frac_path_store"] = (hbm["achieved_GBps_path_store"] or 0.0) / PEAK_HBM_GBS
+        hbm["frac"] = hbm["frac_alg_bytes"]
+        bound = "mfma" if mf["frac"] >= hbm["frac_alg_bytes"] else "hbm"
+        whole_tf = fl2["total"] * K_local * N_t / step_s / 1e12
+        counters = load_counters(args.workload, dom)
+        roof = {"bound": bound, "kernel": dom,
+                "achieved": mf["achieved"] if bound == "mfma" else hbm["achieved_GBps_alg"],
+                "peak": mf["peak"] if bound == "mfma" else PEAK_HBM_GBS,
+                "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
+                "frac": max(mf["frac"], hbm["frac_alg_bytes"]),
+                "traffic": load_traffic(args.workload, dom),
+                "binder": binder_of(mf["frac"], hbm["frac_alg_bytes"], hbm["frac_path_store"], counters, tiles_steps),
+                "convention": ("SURVEY 8d algorithmic work per trajectory-timestep x units per launch / HIP-event kernel time / peak: "
+                               "bytes 8d+8 against 8 TB/s, minimal flops (m = 2 dense d x d products) against the peak of the pipe the "
+                               "kernel computes on (%s); frac = the larger of the two; hbm_term.frac_path_store prices the bytes the "
+                               "design really moves" % ("2500/3 TFLOP/s: split products, three f16 flops per fp32 flop" if x3 else
+                                                        ("bf16 / fp32 blend" if bf16_mlp else "157.3 TFLOP/s fp32 MFMA"))),
+                "mfma_term": mf, "hbm_term": hbm,
+                "alg_flops_per_traj_step": {k: fl2[k] for k in ("fwd_kernel", "bwd_kernel", "total")},
+                "alg_flops_per_traj_step_survey_m3": {k: fl3[k] for k in ("fwd_kernel", "bwd_kernel", "total")},
+                "issued_mfma_per_tile_step": ({"fwd": issued_x3[0], "bwd": issued_x3[1]} if (x3 and issued_x3) else
+                                              {"fwd_f32_16x16x4": issued[0], "fwd_bf16_16x16x32": issued[1],
+                                               "bwd_f32_16x16x4": issued[2]} if issued else None),
+                "units_per_launch": units_launch, "launches_per_step": n_chunks,
+                "fwd_kernel_ms": fwd_ms, "bwd_kernel_ms": bwd_ms,
+                "whole_step_tflops": whole_tf, "whole_step_frac_of_fp32_peak": whole_tf / PEAK_FP32_MFMA_TFLOPS}
+        # the other rollout kernel, same two terms (the iteration is the pair)
+        oth, oth_ms, oth_which = (fwd_name, fwd_ms, "fwd_kernel") if bwd_dominant else (bwd_name, bwd_ms, "bwd_kernel")
+        if oth_ms > 0:
+            oth_peak = mf["peak"] if not (x3 and oth_which == "bwd_kernel" and issued_x3 and issued_x3[1] is None) else PEAK_FP32_MFMA_TFLOPS
+            roof["other_kernel"] = {"kernel": oth, "ms": oth_ms,
+                                    "frac_alg_bytes": alg_B_unit * units_launch / (oth_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                                    "frac_path_store": ((path_B_unit or 0.0) * units_launch / (oth_ms * 1e-3) / 1e9) / PEAK_HBM_GBS,
+                                    "frac_mfma": fl2[oth_which] * units_launch / (oth_ms * 1e-3) / 1e12 / oth_peak,
+                                    "traffic": load_traffic(args.workload, oth)}
     out = {
         "metric": "trajectory-timesteps/sec (K*N/s), d=%d HJB log-variance training iteration" % w["d"],
         "value": value, "unit": "trajectory-timesteps/s", "n_gpus": world, "steps": args.steps,
@@ -886,7 +907,7 @@ def main():
     if getattr(plan, "range_flag", None) is not None:
         out["config"]["range_guard"] = ("on: device flag + predicated fp32-MFMA twins of the split kernels (include/psp.h range_flag); "
                                         "fallback iterations in this run: %d" % plan.range_fallbacks())
-    if world == 1 and not args.no_sustained and not graph:
+    if args.full and world == 1 and not args.no_sustained and not graph:
         # >= 3 s of back-to-back iterations (the timed region above is steps x ms_per_step, i.e. under 0.1 s by default)
         # (a continuation of the SAME training run: the iteration index keeps counting -- it is the Philox `iter` counter -- and the
         #  losses go to a log of their own; nothing of the timed region is replayed or overwritten)
@@ -903,32 +924,32 @@ def main():
             t_s = time.perf_counter() - t0
         out["also_sustained"] = {"value": K_global * N_t * n_s / t_s, "unit": "trajectory-timesteps/s", "ms_per_step": 1e3 * t_s / n_s,
                                  "steps": n_s, "seconds": t_s, "note": "same plan, iterations back to back after the timed region"}
-    if world == 1 and args.workload == "hjb_llgc_d100_K65536_N100_h64" and not args.no_secondary:
+    if args.full and world == 1 and args.workload == "hjb_llgc_d100_K65536_N100_h64" and not args.no_secondary:
         # BASELINE.json configs[1] (d=100, K=1024, N=50) measured in the same process, for readers who take
         # that as the quoted configuration (64 16-trajectory tiles: runs on the feature-split forward kernel)
         out["also_configs1_K1024_N50"] = secondary(psp, dev, WORKLOADS["hjb_llgc_d100_K1024_N50_h64"])
-    if world == 1 and x3 and not args.no_secondary:
+    if args.full and world == 1 and x3 and not args.no_secondary:
         # the same workload on the fp32-MFMA kernels (Solver(mlp_dtype='fp32')), same process, for comparison
         w32 = dict(w)
         w32["mlp"] = "fp32"
         out["also_fp32_mfma_kernels"] = secondary(psp, dev, w32, steps=args.steps, warmup=min(args.warmup, 3))
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(w)
         out["loss_rel_err_vs_cpu_ref"] = loss_rel_err_vs_cpu(psp, dev, w, getattr(plan, "matrix_mode", "fp32"))
         out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
     print(json.dumps(out))
     sys.stdout.flush()
-    finish_ranks(psp, dist, rank, world, dev, rehearsal)
+    finish_ranks(psp, dist, rank, world, dev, rehearsal, args.full)
 
 
-def finish_ranks(psp, dist, rank, world, dev, rehearsal):
-    """N > 1, AFTER rank 0 has printed the JSON line: cross-check of the C-ABI collective (psp_comm_* / psp_allreduce) against
+def finish_ranks(psp, dist, rank, world, dev, rehearsal, full):
+    """N > 1, AFTER rank 0 has printed the JSON line: with --full, cross-check of the C-ABI collective (psp_comm_* / psp_allreduce) against
     torch.distributed's all-reduce on every rank, reported as one line on rank 0's stderr.  A watchdog ends the process if the
     second RCCL communicator does not come up within a minute (exit status 3 and a line on stderr: a hung check must not
     read as success) -- the measurement is already out by then."""
     if dist is None:
         return
-    if not rehearsal and os.environ.get("PSP_BENCH_CABI_CHECK", "1") == "1":
+    if full and not rehearsal and os.environ.get("PSP_BENCH_CABI_CHECK", "1") == "1":
         import threading
         def bark():
             sys.stderr.write("bench.py: the C-ABI RCCL cross-check (second communicator) did not finish within 60 s on rank %d; "
@@ -1131,11 +1152,11 @@ def main_general(args, psp, sharding):
                 out["reference_published"]["note"] = ("units/s derived from this run's mean active steps per iteration and the midpoint of the "
                                                       "published seconds per iteration (the notebook logs no step counts)")
                 out["vs_baseline"] = mid / (elapsed / args.steps)
-            if world == 1 and not args.no_secondary:
+            if args.full and world == 1 and not args.no_secondary:
                 out["also_composite_torch_plan_same_gpu"] = general_composite_leg(psp, dev, w, arch)
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = general_cpu_baseline(w, arch)
-        if world == 1 and not args.no_sustained:
+        if args.full and world == 1 and not args.no_sustained:
             n_s, t_s, c_s = 0, 0.0, []
             plan.events = None
             torch.cuda.synchronize()

@@ -2,8 +2,8 @@
 
 A one-GPU box can only form a single-rank communicator (RCCL refuses two ranks on one device), so this covers the
 plumbing -- lazy librccl binding, id / init / in-place all-reduce on the caller's stream / destroy; the multi-rank path
-is exercised by `bench.py --gpus N` (its warm-up cross-checks psp_allreduce against torch.distributed's all-reduce and
-reports the outcome in the JSON line)."""
+is exercised by `bench.py --gpus N --full` (after the JSON line it cross-checks psp_allreduce against torch.distributed's
+all-reduce and reports the outcome on stderr)."""
 import ctypes as C
 
 import pytest

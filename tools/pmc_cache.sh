@@ -17,7 +17,7 @@ for C in "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum" "TCC_HIT_sum TCC_MI
     i=$((i + 1))
     rm -rf /tmp/pmcc_${W}_$i
     (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --pmc $C -d /tmp/pmcc_${W}_$i -o run --output-format csv -- \
-        python3 "$ROOT/bench.py" --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> "$OUT/${W}_cache_pass$i.err")
+        python3 "$ROOT/bench.py" --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> "$OUT/${W}_cache_pass$i.err")
     rc=$?
     [ $rc -ge 124 ] && { echo "pass $i killed ($rc)"; exit 1; }
     [ $rc -ne 0 ] && { echo "pass $i ($C) failed: $(tail -2 "$OUT/${W}_cache_pass$i.err")"; continue; }

@@ -12,7 +12,7 @@ for W in "$@"; do
   for C in FETCH_SIZE WRITE_SIZE SQ_INSTS_MFMA; do
     rm -rf /tmp/tr_${W}_$C
     (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --pmc $C -d /tmp/tr_${W}_$C -o run --output-format csv -- \
-        python3 "$ROOT/bench.py" --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> $OUT/${W}_$C.err) || { echo "$W $C failed"; tail -2 $OUT/${W}_$C.err; continue; }
+        python3 "$ROOT/bench.py" --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> $OUT/${W}_$C.err) || { echo "$W $C failed"; tail -2 $OUT/${W}_$C.err; continue; }
     F=$(find /tmp/tr_${W}_$C -name "*counter_collection.csv" | head -1)
     python3 - "$F" >> $OUT/$W.txt <<'PY'
 import csv, sys, collections

@@ -17,7 +17,7 @@ for C in "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ
     i=$((i + 1))
     rm -rf /tmp/pmc_${W}_$i
     (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --pmc $C -d /tmp/pmc_${W}_$i -o run --output-format csv -- \
-        python3 "$ROOT/bench.py" --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> "$OUT/${W}_pass$i.err") || { echo "pass $i ($C) failed"; tail -2 "$OUT/${W}_pass$i.err"; continue; }
+        python3 "$ROOT/bench.py" --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> "$OUT/${W}_pass$i.err") || { echo "pass $i ($C) failed"; tail -2 "$OUT/${W}_pass$i.err"; continue; }
     F=$(find /tmp/pmc_${W}_$i -name "*counter_collection.csv" | head -1)
     [ -z "$F" ] && { echo "pass $i: no csv"; continue; }
     python3 - "$F" >> "$OUT/${W}_summary.txt" <<'PY'

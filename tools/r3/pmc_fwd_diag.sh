@@ -14,7 +14,7 @@ for C in "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_I
     i=$((i + 1))
     rm -rf /tmp/pmcd_${W}_$i
     (cd /tmp && rocprofv3 --kernel-trace --pmc $C -d /tmp/pmcd_${W}_$i -o run --output-format csv -- \
-        python3 "$ROOT/bench.py" --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-sustained > /dev/null 2> "$OUT/${W}_pass$i.err") || { tail -5 "$OUT/${W}_pass$i.err"; exit 1; }
+        python3 "$ROOT/bench.py" --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-sustained > /dev/null 2> "$OUT/${W}_pass$i.err") || { tail -5 "$OUT/${W}_pass$i.err"; exit 1; }
     F=$(find /tmp/pmcd_${W}_$i -name "*counter_collection.csv" | head -1)
     python3 - "$F" >> "$OUT/${W}_diag.txt" <<'PY'
 import csv, sys, collections

@@ -7,7 +7,7 @@ VAR=$1; VALS=$2; shift 2
 for w in "$@"; do
   for rep in 1 2; do
     for v in $VALS; do
-      env $VAR=$v timeout -k 10 300 python bench.py --workload $w --no-cpu-baseline --no-secondary --no-sustained > $OUT/line.json 2>$OUT/err.txt || { tail -5 $OUT/err.txt; exit 1; }
+      env $VAR=$v timeout -k 10 300 python bench.py --full --workload $w --no-cpu-baseline --no-secondary --no-sustained > $OUT/line.json 2>$OUT/err.txt || { tail -5 $OUT/err.txt; exit 1; }
       python - "$w" "$VAR=$v" <<'PY' | tee -a $OUT/ab.txt
 import json, sys
 j = json.loads(open("gpurun_out/ab_env/line.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ LIBS=$1; shift
 for w in "$@"; do
   for rep in 1 2; do
     for L in $LIBS; do
-      PSP_LIB_PATH=$PWD/path-space-pde-solver_amd/csrc/$L timeout -k 10 300 python bench.py --workload $w --no-cpu-baseline --no-secondary --no-sustained > $OUT/line.json 2>$OUT/err.txt || { tail -5 $OUT/err.txt; exit 1; }
+      PSP_LIB_PATH=$PWD/path-space-pde-solver_amd/csrc/$L timeout -k 10 300 python bench.py --full --workload $w --no-cpu-baseline --no-secondary --no-sustained > $OUT/line.json 2>$OUT/err.txt || { tail -5 $OUT/err.txt; exit 1; }
       python - "$w" "$L" <<'PY' | tee -a $OUT/ab.txt
 import json, sys
 j = json.loads(open("gpurun_out/ab_multi/line.json").read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ B="--steps 30 --warmup 5 --no-sustained --no-cpu-baseline --no-secondary"
 for w in hjb_llgc_d100_K65536_N100_h64 hjb_llgc_d100_K1024_N50_h64 hjb_llgc_d100_K8192_N50_h64 hjb_llgc_d100_K65536_N50_outer_h30 diffusion_dw_d100_K65536_N100_h64; do
   for rep in 1 2; do
     for ns in 0 1; do
-      PSP_NO_SPEC=$ns timeout -k 10 150 python bench.py --workload $w $B > $OUT/${w}_nospec${ns}_$rep.json 2> $OUT/${w}_nospec${ns}_$rep.err
+      PSP_NO_SPEC=$ns timeout -k 10 150 python bench.py --full --workload $w $B > $OUT/${w}_nospec${ns}_$rep.json 2> $OUT/${w}_nospec${ns}_$rep.err
       python - $OUT/${w}_nospec${ns}_$rep.json "$w no_spec=$ns rep$rep" <<'PY'
 import json, sys
 try:

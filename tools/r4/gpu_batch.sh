@@ -19,10 +19,10 @@ except Exception as e:
 PY
 }
 for w in hjb_llgc_d100_K65536_N100_h64 hjb_llgc_d100_K65536_N50_outer_h30 diffusion_dw_d100_K65536_N100_h64 diffusion_dw_d100_K65536_N100_h64_bf16 hjb_llgc_d200_K32768_N100_h64 hjb_llgc_d500_K16384_N200_h64; do
-  timeout -k 10 150 python bench.py --workload $w $B > $OUT/$w.json 2> $OUT/$w.err
+  timeout -k 10 150 python bench.py --full --workload $w $B > $OUT/$w.json 2> $OUT/$w.err
   line $OUT/$w.json $w
 done
 for w in hjb_llgc_d200_K32768_N100_h64 hjb_llgc_d500_K16384_N200_h64; do
-  PSP_WIDE_SPEC=1 timeout -k 10 150 python bench.py --workload $w $B > $OUT/${w}_spec.json 2> $OUT/${w}_spec.err
+  PSP_WIDE_SPEC=1 timeout -k 10 150 python bench.py --full --workload $w $B > $OUT/${w}_spec.json 2> $OUT/${w}_spec.err
   line $OUT/${w}_spec.json "$w WIDE_SPEC"
 done

@@ -6,7 +6,7 @@ timeout -k 10 800 python -m pytest tests -q -m gpu > $OUT/pytest_gpu_all.log 2>&
 tail -4 $OUT/pytest_gpu_all.log
 B="--steps 20 --warmup 5 --no-sustained --no-cpu-baseline --no-secondary"
 for w in hjb_llgc_d100_K65536_N100_h64 hjb_llgc_d100_K1024_N50_h64 hjb_llgc_d100_K8192_N50_h64 hjb_llgc_d100_K65536_N100_h64_fp32mfma; do
-  timeout -k 10 150 python bench.py --workload $w $B > $OUT/$w.json 2> $OUT/$w.err
+  timeout -k 10 150 python bench.py --full --workload $w $B > $OUT/$w.json 2> $OUT/$w.err
   python - $OUT/$w.json $w <<'PY'
 import json, sys
 try:

@@ -24,12 +24,12 @@ for W in $WL; do
     EXTRA="--no-cpu-baseline --no-secondary"; [ "$W" = hjb_llgc_d100_K65536_N100_h64 ] && EXTRA=""
     [ "$W" = diffusion_allencahn_d100_K200_N25_a110 ] && EXTRA=""
     [ "$W" = elliptic_committor_d10_K200 ] && EXTRA=""
-    timeout -k 10 900 python3 bench.py --workload $W --steps $STEPS --warmup $WARM $EXTRA > "$OUT/${W}_bench.json" 2> "$OUT/${W}_bench.err" || { echo "bench $W failed"; tail -3 "$OUT/${W}_bench.err"; exit 1; }
+    timeout -k 10 900 python3 bench.py --full --workload $W --steps $STEPS --warmup $WARM $EXTRA > "$OUT/${W}_bench.json" 2> "$OUT/${W}_bench.err" || { echo "bench $W failed"; tail -3 "$OUT/${W}_bench.err"; exit 1; }
     echo "bench $W: $(python3 -c "import json,sys; j=json.loads(open('$OUT/${W}_bench.json').read().strip().splitlines()[-1]); print('%.4g units/s, %.3f ms/step, frac %.3f (issued %s)' % (j['value'], j['ms_per_step'], j['roofline']['frac'], j['roofline'].get('mfma_term',{}).get('frac_issued')))")"
     rm -rf /tmp/prof_$W
     PSTEPS=$STEPS; [ $PSTEPS -gt 40 ] && PSTEPS=40
     (cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$W -o run --output-format csv -- \
-        python3 "$ROOT/bench.py" --workload $W --steps $PSTEPS --warmup $WARM --no-cpu-baseline --no-secondary --no-sustained > /dev/null 2> "$OUT/${W}_prof.err") || { echo "profile $W failed"; tail -3 "$OUT/${W}_prof.err"; exit 1; }
+        python3 "$ROOT/bench.py" --full --workload $W --steps $PSTEPS --warmup $WARM --no-cpu-baseline --no-secondary --no-sustained > /dev/null 2> "$OUT/${W}_prof.err") || { echo "profile $W failed"; tail -3 "$OUT/${W}_prof.err"; exit 1; }
     F=$(find /tmp/prof_$W -name "*kernel_stats.csv" | head -1)
     [ -n "$F" ] && cp "$F" "$OUT/${W}_kernel_stats.csv" && echo "profile $W: $(head -3 "$OUT/${W}_kernel_stats.csv" | tail -2 | cut -c1-160)"
 done

@@ -5,7 +5,7 @@ set -o pipefail
 export TMPDIR=/tmp
 ROOT=$(pwd); W=$1; OUT=$ROOT/gpurun_out/trace; mkdir -p $OUT; rm -rf /tmp/tg_$W
 (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace -d /tmp/tg_$W -o run --output-format csv -- \
-    python3 "$ROOT/bench.py" --workload $W --steps 6 --warmup 2 --no-cpu-baseline --no-secondary > /dev/null 2> $OUT/$W.err) || { tail -3 $OUT/$W.err; exit 1; }
+    python3 "$ROOT/bench.py" --full --workload $W --steps 6 --warmup 2 --no-cpu-baseline --no-secondary > /dev/null 2> $OUT/$W.err) || { tail -3 $OUT/$W.err; exit 1; }
 F=$(find /tmp/tg_$W -name "*kernel_trace.csv" | head -1)
 python3 - "$F" <<'PY' | tee $OUT/$W.txt
 import csv, sys
