@@ -94,11 +94,7 @@ struct GGeo {
     static constexpr int NIB = cdiv(HB, WH);               // column blocks per wave
     static constexpr int NRX = cdiv(DBI, WD), NRH = cdiv(HB, WD);   // x-row / h-row blocks per wave
     static constexpr int gW2hr = 0, gEx = gW2hr + HB * KSH * 64;
-    // exchange tiles (1 KiB) per wave: [gz2 | gz2' | gz1 | gz1'].  d=100, H=64: 16 KiB table + 64 KiB
-    // exchange = exactly 80 KiB -> two workgroups per CU (the w3 vectors are read from global instead)
-    static constexpr int EXT = 4 * HB;
-    static constexpr int gEnd = gEx + 4 * EXT * 256;
-    static int bwd_lds_floats() { return gEnd; }
+    static constexpr int EXT = 4 * HB;                     // exchange tiles (1 KiB) per sample block: [gz2 | gz2' | gz1 | gz1']
 };
 
 // dispatch of one product: fp32 16x16x4 chain (gemm_T) or the bf16 16x16x32 one
@@ -155,10 +151,6 @@ __device__ __forceinline__ float bf_hi(float packed) { return __uint_as_float(__
 template <bool P16>
 __device__ __forceinline__ f32x4 image_get_T(const float* base, int o32, int o16, int m) {
     f32x4 v;
-#if defined(PSP_GEN_ABLATE) && (PSP_GEN_ABLATE & 2)
-    v[0] = v[1] = v[2] = v[3] = 1.f;                        // diagnostic build: producers skip their path-store loads
-    return v;
-#endif
     if constexpr (P16) {
         const float u0 = base[o16 + (2 * m) * 64], u1 = base[o16 + (2 * m + 1) * 64];
         v[0] = bf_lo(u0); v[2] = bf_hi(u0); v[1] = bf_lo(u1); v[3] = bf_hi(u1);
@@ -592,330 +584,7 @@ __global__ __launch_bounds__(512) void gen_fwd_kernel(const GenArgs a_) {
 //              gz1' = gh1' d1 ;  gz1 = gh1 d1 + gh1' phi''(z1) z1'
 //   gradients: dW2 = [x0,h1]^T gz2 + [x0',h1']^T gz2' ; dW1 = x0^T gz1 + x0'^T gz1' ;
 //              dW3 = a [x0,h1,h2] + [x0',h1',h2'] ; db2 = gz2 ; db1 = gz1 ; db3 = a
-// Workgroup = 4 waves, rounds of 4 sample blocks, weight-gradient tiles split over the waves as in
-// hjb_bwd_kernel; the A operands (x0, x0', h1, h1') come straight from the stored images in
-// feature-on-lane form, the B operands (adjoints) through per-wave LDS exchange tiles.
-// =======================================================================================
-template <int D, int H>
-__global__ __launch_bounds__(256, 2) void gen_bwd_kernel(const GenArgs a) {
-    PSP_COND_EXIT(a);
-    using G = GGeo<D, H>;
-    constexpr int DI = G::DI, DBI = G::DBI, HB = G::HB, KSH = G::KSH;
-    constexpr int WH = G::WH, WD = G::WD, NIB = G::NIB, NRX = G::NRX, NRH = G::NRH;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 15, q = lane >> 4;
-    const int wh = (WH == 1) ? 0 : wave % WH, wd = (WD == 1) ? 0 : wave / WH;
-    const int lofsF = image_lane_offset_F(lane);
-    const int qq = lane >> 4, col = lane & 15;
-    const float* __restrict__ P = a.params;
-
-    stage_aop(lds + G::gW2hr, HB, KSH, tid, nthr, [&](int row, int c2) {
-        return (row < H && c2 < H) ? P[G::oW2 + (DI + row) * H + c2] : 0.f; });
-    __syncthreads();
-    // w3 (h1 / h2 parts) in T layout, straight from the parameter vector (32 L1-resident loads per round)
-    auto w3_T = [&](int base, int m, int o0) {          // o0 = opaque zero: keeps the loads inside the round loop
-        f32x4 v;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { const int f = 16 * m + 4 * r + q; v[r] = f < H ? P[base + o0 + (f < H ? f : 0)] : 0.f; }
-        return v;
-    };
-    float* exch = lds + G::gEx;
-    float* my_ex = exch + wave * (G::EXT * 256);
-
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    // weight-gradient accumulators of this wave (rows x columns): dW2 x-rows, dW2 h-rows, dW1
-    f32x4 acc2x[NRX][NIB], acc2h[NRH][NIB], acc1[NRX][NIB];
-    float bs2[NIB], bs1[NIB], g3x[NRX], g3h1[NRH];
-    f32x4 g3h2T[HB];                                    // dW3 (h2 part) in T layout, reduced over lanes at the end
-    float g3b = 0.f;
-#pragma unroll
-    for (int s = 0; s < NRX; ++s) { g3x[s] = 0.f;
-#pragma unroll
-        for (int t = 0; t < NIB; ++t) { acc2x[s][t] = zero4; acc1[s][t] = zero4; } }
-#pragma unroll
-    for (int s = 0; s < NRH; ++s) { g3h1[s] = 0.f;
-#pragma unroll
-        for (int t = 0; t < NIB; ++t) acc2h[s][t] = zero4; }
-#pragma unroll
-    for (int t = 0; t < NIB; ++t) { bs2[t] = 0.f; bs1[t] = 0.f; }
-#pragma unroll
-    for (int m = 0; m < HB; ++m) g3h2T[m] = zero4;
-
-    int cbc[NIB], rxc[NRX], rhc[NRH];
-#pragma unroll
-    for (int t = 0; t < NIB; ++t) cbc[t] = ((wh + WH * t) < HB ? (wh + WH * t) : HB - 1) * 256;
-#pragma unroll
-    for (int s = 0; s < NRX; ++s) rxc[s] = ((wd + WD * s) < DBI ? (wd + WD * s) : DBI - 1) * 256;
-#pragma unroll
-    for (int s = 0; s < NRH; ++s) rhc[s] = ((wd + WD * s) < HB ? (wd + WD * s) : HB - 1) * 256;
-
-    const int Kpad = a.ntile16 * 16;
-    const long long nblk = (long long)(a.N + 1) * a.ntile16;
-    const long long nround = (nblk + 3) / 4;
-    for (long long round = blockIdx.x; round < nround; round += gridDim.x) {
-        const long long rb = round * 4;
-        // L2 touch-prefetch (one dword per 128-B line): wave w pulls block w's X / U / d1 / z1^ images
-        // (read in P2/P3 by every wave) and its own block of the NEXT round (d1, d2, z1^, z2^ for P1).
-        float touch[6];
-        {
-            const long long xb0 = rb + wave;
-            const float* xt = a.path + (size_t)(xb0 < nblk ? xb0 : nblk - 1) * (size_t)G::PB;
-            constexpr int NA = G::pD2;                       // X, U, d1 images are contiguous: [0, pD2)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { const int o = lane * 32 + i * 2048; touch[i] = xt[o < NA ? o : 0]; }
-            touch[4] = xt[G::pZ1 + ((lane * 32 < 4 * HB * 64) ? lane * 32 : 0)];
-            const long long nb0 = (round + gridDim.x) * 4 + wave;
-            const float* nt = a.path + (size_t)(nb0 < nblk ? nb0 : nblk - 1) * (size_t)G::PB + G::pD1;
-            touch[5] = nt[(lane * 32 < 16 * HB * 64) ? lane * 32 : 0];
-        }
-        // ------------------------------------------------------------------ P1: adjoints of the own block
-        {
-            f32x4 gz1[HB], gz1t[HB];
-            const long long blk0 = rb + wave;
-            const bool bvalid = blk0 < nblk;
-            const long long blk = bvalid ? blk0 : nblk - 1;
-            const int n = (int)(blk / a.ntile16), t16 = (int)(blk % a.ntile16);
-            const int k = t16 * 16 + j;
-            const bool kvalid = bvalid && k < a.K_local;
-            const float* pb = a.path + (size_t)blk * (size_t)G::PB + lane;
-            const bool fin = (n == a.N);
-            // wY / wV / ahat are zero-padded to 16*ntile16 entries: plain loads, no branch around them
-            const size_t wofs = a.per_sample ? (size_t)n * Kpad : 0;            // per-sample mode: wY is (N+1, Kpad), ahat IS the coefficient
-            const float wy = a.wY[wofs + k], wv = a.per_sample ? 0.f : a.wV[k], ah = a.ahat[(size_t)n * Kpad + k];
-            const float wsv = (bvalid && !fin) ? wy : 0.f;                             // weight of the tangent part
-            const float av = bvalid ? (a.per_sample ? ah : (fin ? wv : wy * ah)) : 0.f;
-            const int o0 = opaque_i(0);
-            f32x4 gz2[HB], gz2t[HB];
-            {
-                f32x4 d2[HB], z2t[HB];
-#pragma unroll
-                for (int m = 0; m < HB; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        d2[m][r] = pb[G::pD2 + (4 * m + r) * 64];
-                        z2t[m][r] = wsv * pb[G::pZ2 + (4 * m + r) * 64];
-                    }
-#pragma unroll
-                for (int m = 0; m < HB; ++m) {
-                    const f32x4 w3h2 = w3_T(G::oW3 + DI + H, m, o0);
-                    gz2t[m] = w3h2 * d2[m];
-                    gz2[m] = av * gz2t[m] + w3h2 * step2(d2[m]) * z2t[m];
-                    // dW3 (h2 part): a h2 + h2'   with h2 = (d2/2)^2, h2' = d2 z2'
-                    g3h2T[m] += av * (0.25f * d2[m] * d2[m]) + d2[m] * z2t[m];
-                }
-            }
-            g3b += (q == 0) ? av : 0.f;
-#pragma unroll
-            for (int m = 0; m < HB; ++m) { gz1t[m] = w3_T(G::oW3 + DI, m, o0); gz1[m] = av * gz1t[m]; }
-            gemm_T<HB, KSH, HB>(gz1t, lds + G::gW2hr, gz2t, lane);      // gh1' = w3h1 + W2h gz2'
-            gemm_T<HB, KSH, HB>(gz1, lds + G::gW2hr, gz2, lane);        // gh1  = a w3h1 + W2h gz2
-            {   // d1 / z1^ are L2-resident (touch-prefetched one round ahead): fetch them only now
-                f32x4 d1[HB], z1t[HB];
-#pragma unroll
-                for (int m = 0; m < HB; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        d1[m][r] = pb[G::pD1 + (4 * m + r) * 64];
-                        z1t[m][r] = wsv * pb[G::pZ1 + (4 * m + r) * 64];
-                    }
-#pragma unroll
-                for (int m = 0; m < HB; ++m) {
-                    gz1[m] = gz1[m] * d1[m] + gz1t[m] * step2(d1[m]) * z1t[m];
-                    gz1t[m] = gz1t[m] * d1[m];
-                }
-            }
-            if (!kvalid) {
-#pragma unroll
-                for (int m = 0; m < HB; ++m) { gz2[m] = zero4; gz2t[m] = zero4; gz1[m] = zero4; gz1t[m] = zero4; }
-            }
-#pragma unroll
-            for (int m = 0; m < HB; ++m) {
-                tile_put(my_ex + m * 256, gz2[m], lane);
-                tile_put(my_ex + (HB + m) * 256, gz2t[m], lane);
-                tile_put(my_ex + (2 * HB + m) * 256, gz1[m], lane);
-                tile_put(my_ex + (3 * HB + m) * 256, gz1t[m], lane);
-            }
-        }
-        __syncthreads();
-        // ------------------------------------------------------------------ P2: all weight gradients
-        // One loop over the 4 sample blocks feeds dW2 (x- and h-rows) and dW1 from a single load of the
-        // X / U images per block.  Two-stage operand pipeline: while the x-row MFMAs of block sb issue,
-        // its h-row images (d1, z1^) are in flight; while the h-row MFMAs issue, X / U of block sb+1 are.
-        {
-            auto blk_of = [&](int sb) {                            // provably wave-uniform 32-bit block index
-                const long long c0 = rb + sb;
-                return (size_t)__builtin_amdgcn_readfirstlane((int)(c0 < nblk ? c0 : nblk - 1));
-            };
-            f32x4 xbuf[NRX], ubuf[NRX], dbuf[NRH], zbuf[NRH];
-            {
-                const float* sp = a.path + (size_t)blk_of(0) * (size_t)G::PB;
-#pragma unroll
-                for (int s2 = 0; s2 < NRX; ++s2) {
-                    xbuf[s2] = image_get_F(sp + G::pX + rxc[s2], lofsF);
-                    ubuf[s2] = image_get_F(sp + G::pU + rxc[s2], lofsF);
-                }
-            }
-#pragma unroll 1
-            for (int sb = 0; sb < 4; ++sb) {
-                const bool sval = (rb + sb) < nblk;
-                const int cb = (int)blk_of(sb);
-                const int n = cb / a.ntile16, t16 = cb % a.ntile16;
-                const float* sp = a.path + (size_t)cb * (size_t)G::PB;
-                const float* ex = exch + sb * (G::EXT * 256);
-                // stage A loads: h-row images of this block
-#pragma unroll
-                for (int s2 = 0; s2 < NRH; ++s2) {
-                    dbuf[s2] = image_get_F(sp + G::pD1 + rhc[s2], lofsF);
-                    zbuf[s2] = image_get_F(sp + G::pZ1 + rhc[s2], lofsF);
-                }
-                // per-sample weights of the 4 samples this lane sees in F layout (samples 4q'..4q'+3)
-                const bool fin = (n == a.N);
-                const int k4 = t16 * 16 + 4 * qq;
-                const f32x4 wy4 = *reinterpret_cast<const f32x4*>(a.wY + (a.per_sample ? (size_t)n * Kpad : 0) + k4);
-                const f32x4 wv4 = a.per_sample ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(a.wV + k4);
-                const f32x4 ah4 = *reinterpret_cast<const f32x4*>(a.ahat + (size_t)n * Kpad + k4);
-                const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-                const f32x4 w4 = (sval && !fin) ? wy4 : z4;
-                const f32x4 a4 = sval ? (a.per_sample ? ah4 : (fin ? wv4 : wy4 * ah4)) : z4;
-                f32x4 bz2[NIB], bz2t[NIB], bz1[NIB], bz1t[NIB];
-#pragma unroll
-                for (int t = 0; t < NIB; ++t) {
-                    bz2[t] = tile_get(ex + cbc[t], lane);
-                    bz2t[t] = tile_get(ex + HB * 256 + cbc[t], lane);
-                    bz1[t] = tile_get(ex + 2 * HB * 256 + cbc[t], lane);
-                    bz1t[t] = tile_get(ex + 3 * HB * 256 + cbc[t], lane);
-                    bs2[t] += hsum4(bz2[t]);
-                    bs1[t] += hsum4(bz1[t]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int s2 = 0; s2 < NRX; ++s2) {                          // x-rows: A = x0, x0' = w U
-                    const f32x4 x0 = xbuf[s2];
-                    const f32x4 xt = w4 * ubuf[s2];
-                    g3x[s2] += hsum4(a4 * x0 + xt);
-#pragma unroll
-                    for (int t = 0; t < NIB; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            acc2x[s2][t] = mfma16(x0[r], bz2[t][r], acc2x[s2][t]);
-                            acc1[s2][t] = mfma16(x0[r], bz1[t][r], acc1[s2][t]);
-                            acc2x[s2][t] = mfma16(xt[r], bz2t[t][r], acc2x[s2][t]);
-                            acc1[s2][t] = mfma16(xt[r], bz1t[t][r], acc1[s2][t]);
-                        }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                {   // stage B loads: x-row images of the next block (xbuf / ubuf are free now)
-                    const float* spn = a.path + (size_t)blk_of(sb < 3 ? sb + 1 : sb) * (size_t)G::PB;
-#pragma unroll
-                    for (int s2 = 0; s2 < NRX; ++s2) {
-                        xbuf[s2] = image_get_F(spn + G::pX + rxc[s2], lofsF);
-                        ubuf[s2] = image_get_F(spn + G::pU + rxc[s2], lofsF);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int s2 = 0; s2 < NRH; ++s2) {                          // h-rows: A = h1 = (d1/2)^2, h1' = d1 w z1^
-                    const f32x4 d1 = dbuf[s2];
-                    const f32x4 h1 = 0.25f * d1 * d1;
-                    const f32x4 ht = d1 * (w4 * zbuf[s2]);
-                    g3h1[s2] += hsum4(a4 * h1 + ht);
-#pragma unroll
-                    for (int t = 0; t < NIB; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            acc2h[s2][t] = mfma16(h1[r], bz2[t][r], acc2h[s2][t]);
-                            acc2h[s2][t] = mfma16(ht[r], bz2t[t][r], acc2h[s2][t]);
-                        }
-                }
-            }
-        }
-        asm volatile("" :: "v"(touch[0]), "v"(touch[1]), "v"(touch[2]), "v"(touch[3]), "v"(touch[4]), "v"(touch[5]));
-        __syncthreads();
-    }
-
-    // ---- write-out: tile (rb, cb): lane (col, qq), reg rr <-> dW[16 rb + 4 qq + rr][16 cb + col]   (weights are (in, out))
-    float* gp = a.grad_partial + (size_t)blockIdx.x * G::P;
-#pragma unroll
-    for (int s = 0; s < NRX; ++s)
-#pragma unroll
-        for (int t = 0; t < NIB; ++t) {
-            const int rbk = wd + WD * s, cbk = wh + WH * t;
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int i = 16 * rbk + 4 * qq + rr, jo = 16 * cbk + col;
-                if (rbk < DBI && cbk < HB && i < DI && jo < H) {
-                    gp[G::oW2 + i * H + jo] = acc2x[s][t][rr];
-                    gp[G::oW1 + i * H + jo] = acc1[s][t][rr];
-                }
-            }
-        }
-#pragma unroll
-    for (int s = 0; s < NRH; ++s)
-#pragma unroll
-        for (int t = 0; t < NIB; ++t) {
-            const int rbk = wd + WD * s, cbk = wh + WH * t;
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int i = 16 * rbk + 4 * qq + rr, jo = 16 * cbk + col;
-                if (rbk < HB && cbk < HB && i < H && jo < H) gp[G::oW2 + (DI + i) * H + jo] = acc2h[s][t][rr];
-            }
-        }
-    // biases: lane = output feature in F layout; sum over q', lanes q' == 0 of the wd == 0 waves write
-#pragma unroll
-    for (int t = 0; t < NIB; ++t) {
-        const float v2 = qsum(bs2[t]), v1 = qsum(bs1[t]);
-        const int f = 16 * (wh + WH * t) + col;
-        if (wd == 0 && qq == 0 && (wh + WH * t) < HB && f < H) { gp[G::ob2 + f] = v2; gp[G::ob1 + f] = v1; }
-    }
-    // dW3: x and h1 parts live on lane = feature (F layout) in the wh == 0 waves; h2 part and b3 in T layout
-#pragma unroll
-    for (int s = 0; s < NRX; ++s) {
-        const float v = qsum(g3x[s]);
-        const int f = 16 * (wd + WD * s) + col;
-        if (wh == 0 && qq == 0 && (wd + WD * s) < DBI && f < DI) gp[G::oW3 + f] = v;
-    }
-#pragma unroll
-    for (int s = 0; s < NRH; ++s) {
-        const float v = qsum(g3h1[s]);
-        const int f = 16 * (wd + WD * s) + col;
-        if (wh == 0 && qq == 0 && (wd + WD * s) < HB && f < H) gp[G::oW3 + DI + f] = v;
-    }
-    // T-layout partial sums: reduce over the 16 trajectory lanes, then over the 4 waves through LDS
-    __syncthreads();
-    float* red = lds;                                   // [4 waves][HB*16 + 1]
-#pragma unroll
-    for (int m = 0; m < HB; ++m)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float v = g3h2T[m][r];
-            v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-            if (j == 0) red[wave * (HB * 16 + 1) + 16 * m + 4 * r + q] = v;
-        }
-    {
-        float v = g3b;
-        v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-        if (lane == 0) red[wave * (HB * 16 + 1) + HB * 16] = v;
-    }
-    __syncthreads();
-    for (int f = tid; f < HB * 16 + 1; f += nthr) {
-        const float v = (red[f] + red[(HB * 16 + 1) + f]) + (red[2 * (HB * 16 + 1) + f] + red[3 * (HB * 16 + 1) + f]);
-        if (f < H) gp[G::oW3 + DI + H + f] = v;
-        else if (f == HB * 16) gp[G::ob3] = v;
-    }
-}
-
-
-#ifndef PSP_GEN_X3_RING
-#define PSP_GEN_X3_RING 2         // depth of the split-product consumers' row-operand ring (3 spills 32 dwords under the 256-register cap)
-#endif
-#ifndef PSP_GEN_BF16_RING
-#define PSP_GEN_BF16_RING 4       // depth of the bf16 consumers' row-operand ring (A/B: -DPSP_GEN_BF16_RING=3 is round 1's)
-#endif
-// =======================================================================================
-// Backward kernel, role-specialised variant (same scheme as hjb_bwd2_kernel).
-// One 8-wave workgroup per CU, rounds of 4 sample blocks, one barrier per round, double-buffered LDS exchange.
+// Role-specialised as hjb_bwd2_kernel: one 8-wave workgroup per CU, rounds of 4 sample blocks, one barrier per round, double-buffered LDS exchange.
 //   producers (waves 0-3): the adjoint panels gz2, gz2', gz1, gz1' of their own block (two register-chained
 //       64-MFMA products + the element-wise adjoint algebra) -> exchange buffer of the NEXT round; the T-layout parts
 //       of dW3 (h2 rows) and db3 as running register sums;
@@ -1187,12 +856,7 @@ __global__ __launch_bounds__(512) void gen_bwd2_kernel(const GenArgs a) {
         } else {
             addr = sgpr_block_addr(a.path, (unsigned long long)blk, (unsigned)PBx, (unsigned)ofs);
         }
-#if defined(PSP_GEN_ABLATE) && (PSP_GEN_ABLATE & 1)
-        f32x4 v = {1.f, 1.f, 1.f, 1.f};                     // diagnostic build: consumers skip their path-store loads
-        (void)addr;
-#else
         f32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) f32x4*>((gptr_t)addr + lofsU);
-#endif
         if constexpr (BF16) {                              // four samples of this lane's feature: its half of each dword -> fp32
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -1233,7 +897,7 @@ __global__ __launch_bounds__(512) void gen_bwd2_kernel(const GenArgs a) {
             w4 = (sval && !fin) ? wy4 : zero4;
             a4 = sval ? (fin ? wv4 : wy4 * ah4) : zero4;
         };
-        constexpr int RB = PSP_GEN_X3_RING;
+        constexpr int RB = 2;                                   // ring depth (3 spills 32 dwords under the 256-register cap)
         constexpr int NROWP = cdiv(NROW, RB) * RB;
         f32x4 ra0[RB], rb0[RB], ra1[RB], rb1[RB];
         auto unit_blk = [&](int u, int which) __attribute__((always_inline)) {
@@ -1372,7 +1036,7 @@ __global__ __launch_bounds__(512) void gen_bwd2_kernel(const GenArgs a) {
         // (vmcnt retires in order), so the first item of every pair waited a full memory latency -- without the consumers'
         // loads the kernel ran 1.89 instead of 3.56 ms.  Slots stay compile-time: items are counted modulo NROWP, the item
         // count padded to a multiple of the ring depth (the padding item loads and multiplies nothing).
-        constexpr int RB = PSP_GEN_BF16_RING;
+        constexpr int RB = 4;                                   // ring depth (3 was round 1's)
         constexpr int NROWP = cdiv(NROW, RB) * RB;
         f32x4 ra0[RB], rb0[RB], ra1[RB], rb1[RB];
         // block ids of pair unit u (two per round): round blockIdx.x + (u / 2) gridDim.x, blocks 2 (u % 2), 2 (u % 2) + 1
@@ -1598,9 +1262,7 @@ struct GenInstance {
     int d, H, n_params, path_floats_per_block;
     int path_dwords_per_block16;     // bf16-pair path block (mlp_dtype == PSP_MLP_BF16)
     int (*fwd_lds_bytes)();
-    int (*bwd_lds_bytes)();
     hipError_t (*launch_fwd)(const GenArgs&, int grid, int block, hipStream_t);
-    hipError_t (*launch_bwd)(const GenArgs&, int grid, int block, hipStream_t);
     int (*bwd2_lds_bytes)();
     hipError_t (*launch_bwd2)(const GenArgs&, int grid, hipStream_t);   // role-specialised variant, 512 threads
     hipError_t (*launch_fwd_bf16)(const GenArgs&, int grid, int block, hipStream_t);   // value-net products on bf16 MFMA
@@ -1614,7 +1276,6 @@ template <int D, int H>
 struct GenLaunch {
     using G = GGeo<D, H>;
     static int fwd_lds() { return G::fwd_lds_floats() * 4; }
-    static int bwd_lds() { return G::bwd_lds_floats() * 4; }
     static int bwd2_lds() { return (G::gEx + 2 * 4 * G::EXT * 256) * 4; }
     static hipError_t bwd2(const GenArgs& a, int grid, hipStream_t s) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gen_bwd2_kernel<D, H>),
@@ -1687,21 +1348,8 @@ struct GenLaunch {
         if (sk == (DRIFT_ZERO | (GH_ALLEN_CAHN << 4))) return fwd_spec<false, true, DRIFT_ZERO | (GH_ALLEN_CAHN << 4)>(a, grid, block, s);
         return a.noise_mode == NOISE_PHILOX ? fwd_x3_as<true>(a, grid, block, s) : fwd_x3_as<false>(a, grid, block, s);
     }
-#ifdef PSP_LEGACY_BWD
-    // gen_bwd_kernel: superseded by gen_bwd2_kernel; diagnostic builds only (-DPSP_LEGACY_BWD + PSP_BWD_VARIANT=1)
-    static hipError_t bwd(const GenArgs& a, int grid, int block, hipStream_t s) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gen_bwd_kernel<D, H>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds());
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((gen_bwd_kernel<D, H>), dim3(grid), dim3(block), bwd_lds(), s, a);
-        return hipGetLastError();
-    }
-    static constexpr auto legacy_bwd = &bwd;
-#else
-    static constexpr hipError_t (*legacy_bwd)(const GenArgs&, int, int, hipStream_t) = nullptr;
-#endif
     static GenInstance instance() {
-        return GenInstance{D, H, G::P, G::PB, G::PB16, &fwd_lds, &bwd_lds, &fwd, legacy_bwd, &bwd2_lds, &bwd2, &fwd_bf16, &bwd2_bf16,
+        return GenInstance{D, H, G::P, G::PB, G::PB16, &fwd_lds, &fwd, &bwd2_lds, &bwd2, &fwd_bf16, &bwd2_bf16,
                            &fwd_x3_lds, &fwd_x3, &bwd2_x3};
     }
 };

@@ -72,7 +72,8 @@ struct GenlArgs {
     int n_tiles;                    // weight-gradient tiles: sum_i off[i + 1] * HB[i]
     int tcum[GENL_MAXL + 1];        // tiles of the layers below i
     long long P;
-    long long table_floats;         // size of the table region (TLDS instances copy it into LDS)
+    long long table_floats;         // size of the table region -- no kernel reads it, but dropping it moves the fields below and
+                                    // with them the backward kernels' register allocation
     int time_first;                 // 1: the net's input is [t, x] (Solver's value-function ansatz, solver.py:338) -- the kernels keep the
                                     // time in their LAST input row; only the parameter index map differs
     float time_scale;               // the net sees time_scale * t (value-function ansatz: the step index n = t / dt, solver.py:336, 439)
@@ -298,25 +299,19 @@ __host__ __device__ inline int genl_fwd_lds_bytes(int TB) { return 2 * TB * 1024
 // (NW = 4: two workgroups per CU at 256 registers a wave -- the step chain of a tile is bound by the L2 latency of its table
 //  operands and by its barriers, not by the matrix pipe, so two tiles in flight per CU are worth more than eight waves on one
 //  once the batch fills the chip; NW = 8 for small batches, where the latency of ONE tile is what counts)
-// TLDS (one-wave instances of small nets): the whole table region is copied into LDS behind the images at kernel start -- the step
-// chain of a small net is a sequence of ~20 tiny products, each of which otherwise opens with the full L2 latency of its first
-// operands (`Committor function.ipynb`'s net: 29 KB of tables, 15 us per step from L2)
-template <int NW, bool TLDS = false>
+// (Tried and dropped: the whole table region copied into LDS by the one-wave instances of small nets.  On the committor notebook's
+//  net -- 29 KB of tables -- it shortened the step chain of a K = 200 batch by 6 % (12.1 -> 11.3 ms: the chain is bound by its
+//  instruction count, not by the L2 latency of the tables) and cost a batch that fills the chip 75 % (72.7 -> 127 ms at K = 65536:
+//  three workgroups per CU instead of twelve, and every workgroup copies the tables).)
+template <int NW>
 __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(const GenlArgs ga_) {
     PSP_COND_EXIT(ga_.g);
-    static_assert(!TLDS || NW == 1, "LDS-resident tables: one-wave instances only");
     const KArgs ga = &ga_;
     const KGen a = &ga->g;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* A = lds;
     float* G = A + ga->TB * 256;
     const float* __restrict__ T = ga->tables;
-    if constexpr (TLDS) {
-        float* Tl = lds + 2 * ga->TB * 256;
-        for (long long i = threadIdx.x; i < ga->table_floats / 4; i += 64 * NW)
-            reinterpret_cast<f32x4*>(Tl)[i] = reinterpret_cast<const f32x4*>(ga->tables)[i];
-        T = Tl;
-    }
     const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const bool w0 = wave == 0;                                       // every wave carries the tile's state; wave 0 writes the outputs
@@ -552,10 +547,9 @@ __host__ __device__ inline int genl_bwd_lds_bytes(int TB, int DB0, int NW) {
 // net has 18) keeps 12 registers less per array and requests its table operands two k-step groups ahead instead of four: 37
 // instead of 97 spilled dwords -- the weight-tile accumulators that lived in scratch no longer do -- and the backward of that net
 // goes 3.98 -> 3.29 ms at K = 16 384 (same-box A/B).
-template <int NW, bool TLDS = false, int MS = GenlGeo<NW>::MAXSLOT>
+template <int NW, int MS = GenlGeo<NW>::MAXSLOT>
 __global__ __launch_bounds__(64 * NW) void genl_bwd_kernel(const GenlArgs ga_) {
     PSP_COND_EXIT(ga_.g);
-    static_assert(!TLDS || NW == 1, "LDS-resident tables: one-wave instances only");
     const KArgs ga = &ga_;
     const KGen a = &ga->g;
     const float* __restrict__ T = ga->tables;
@@ -568,12 +562,6 @@ __global__ __launch_bounds__(64 * NW) void genl_bwd_kernel(const GenlArgs ga_) {
     float* AB = Ad + TB * 256;        // abar of hidden block hb at AB + 256 hb; zbar_i in place once layer i has been swept
     float* ABd = AB + (HBS + 1) * 256;    // abar' / zbar_i'
     int* tdesc = reinterpret_cast<int*>(ABd + (HBS + 1) * 256);
-    if constexpr (TLDS) {                                            // tables behind the tile descriptors (genl_fwd_kernel)
-        float* Tl = reinterpret_cast<float*>(tdesc + NW * GenlGeo<NW>::MAXT);
-        for (long long i = threadIdx.x; i < ga->table_floats / 4; i += 64 * NW)
-            reinterpret_cast<f32x4*>(Tl)[i] = reinterpret_cast<const f32x4*>(ga->tables)[i];
-        T = Tl;
-    }
     const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int Kpad = a->ntile16 * 16;
@@ -741,16 +729,16 @@ __global__ __launch_bounds__(64 * NW) void genl_bwd_kernel(const GenlArgs ga_) {
 }
 
 // host side: launches (the dynamic LDS size exceeds the 64 KiB default)
-template <int NW, bool TLDS = false> inline hipError_t genl_launch_fwd(const GenlArgs& a, int ntile16, int lds_bytes, hipStream_t st) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW, TLDS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+template <int NW> inline hipError_t genl_launch_fwd(const GenlArgs& a, int ntile16, int lds_bytes, hipStream_t st) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((genl_fwd_kernel<NW, TLDS>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
+    hipLaunchKernelGGL((genl_fwd_kernel<NW>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
     return hipGetLastError();
 }
-template <int NW, bool TLDS = false, int MS = GenlGeo<NW>::MAXSLOT> inline hipError_t genl_launch_bwd(const GenlArgs& a, int grid, int groups, int lds_bytes, hipStream_t st) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_bwd_kernel<NW, TLDS, MS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+template <int NW, int MS = GenlGeo<NW>::MAXSLOT> inline hipError_t genl_launch_bwd(const GenlArgs& a, int grid, int groups, int lds_bytes, hipStream_t st) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_bwd_kernel<NW, MS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((genl_bwd_kernel<NW, TLDS, MS>), dim3(grid, groups), dim3(64 * NW), lds_bytes, st, a);
+    hipLaunchKernelGGL((genl_bwd_kernel<NW, MS>), dim3(grid, groups), dim3(64 * NW), lds_bytes, st, a);
     return hipGetLastError();
 }
 

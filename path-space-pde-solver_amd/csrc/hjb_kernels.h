@@ -162,12 +162,8 @@ __device__ __forceinline__ const T* opaque(const T* p) {   // same pointer + opa
 }
 
 // Path-store writes are a pure stream (read back by the next kernel, never by this one): non-temporal stores keep them from
-// displacing operand tables and the other kernels' lines in L2 (measured: d = 200 forward 7.5 -> 6.9 ms).  -DPSP_PATH_STORE_PLAIN restores ordinary stores (A/B).
-#if defined(PSP_PATH_STORE_PLAIN) && PSP_PATH_STORE_PLAIN
-#define PSP_PATH_STORE(ptr, val) (*(ptr) = (val))
-#else
+// displacing operand tables and the other kernels' lines in L2 (measured: d = 200 forward 7.5 -> 6.9 ms).
 #define PSP_PATH_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#endif
 
 // ---------------------------------------------------------------------------------------
 // Philox4x32-R (Salmon et al. 2011), counter = (global trajectory, step, call index, iteration)
@@ -248,11 +244,7 @@ __device__ __forceinline__ void regen_xi(f32x4 (&xin)[DB], uint32_t kglob, uint3
                                          uint32_t seed_lo, uint32_t seed_hi) {
 #pragma unroll
     for (int b = 0; b < DB; ++b) {
-#ifdef PSP_ABL_REGEN
-        xin[b] = f32x4{1e-3f * (float)(kglob & 255u), 0.5f, -0.25f * (float)(n & 7u), 0.125f * (float)b};   // timing ablation only
-#else
         xin[b] = philox_block(kglob, n, (uint32_t)(4 * b + q), iter, seed_lo, seed_hi);
-#endif
         if (16 * b + 16 > D) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) if (16 * b + 4 * r + q >= D) xin[b][r] = 0.f;
@@ -761,11 +753,6 @@ struct Geo {
     static constexpr int NIB = cdiv(HB, WH);     // H-blocks per wave along the WH axis
     static constexpr int NOBD = cdiv(DB, WD);    // d-blocks per wave along the WD axis
     static constexpr int NOBH = cdiv(HB, WD);    // H-blocks per wave along the WD axis (dW2 rows)
-    // backward LDS carve (floats): transposed weight tables, b3, [W3], per-wave exchange tiles
-    static constexpr int gW2T = 0, gW3T = gW2T + HB * KSH * 64, gVec = gW3T + HB * KSD * 64;
-    static constexpr int gb3 = gVec, gEx = gb3 + DB * 16;
-    static constexpr int EXT = (DB > 2 * HB ? DB : 2 * HB);   // exchange tiles (1 KiB) per wave
-    static int bwd_lds_floats(int) { return gEx + 4 * EXT * 256; }
     // role-specialised backward (hjb_bwd2_kernel): per sample block the exchange area holds the G panel as
     // an exact k-step image (KSD x 64 floats) followed by the dz2 and dz1 panels; two buffers of 4 blocks
     static constexpr int EXB = KSD * 64 + 4 * HB * 64;
@@ -1191,19 +1178,7 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
 // With detach_forward=True the state path carries no gradient (solver.py:468-472), so
 //   dL/dZ_n[k,:] = w_k ((Z_n + c) dt + xi_{n+1} sqrt(dt)),  (Z + c = 0 when adaptive)
 // and the parameter gradient is one batched MLP backward over all (n, k) samples, using the
-// X_n, h1, h2 panels the forward kernel stored (register-image layout).
-//
-// Workgroup = 4 waves, 2 workgroups per CU (<= 256 VGPRs, <= 80 KiB LDS), persistent over
-// "rounds" of 4 sample blocks (16 samples each):
-//   P1  each wave, own block: G = w xi sqrt(dt) (same Philox counters as the forward),
-//       dz2 = (W3^T G)(1-h2^2), dz1 = (W2^T dz2)(1-h1^2)      [T layout, register-chained MFMA]
-//       -> G panel to this wave's LDS exchange tiles
-//   P2  weight gradient of layer 3 over all 4 blocks: every wave owns a fixed subset of the
-//       dW3 tiles; A operand = G in feature-on-lane form (ds_read_b128 of the exchange tile),
-//       B operand = h2 read DIRECTLY in feature-on-lane form from the path store (16 B/lane)
-//   P3  same for layers 2 and 1 (A = dz2 / dz1 from the exchange tiles, B = h1 / X_n from HBM/L2)
-// Weight-gradient tiles are disjoint between waves (72 accumulator registers per wave instead
-// of 288 for a per-wave copy), so there is no cross-wave reduction; workgroups are summed by
+// X_n, h1, h2 panels the forward kernel stored (register-image layout); workgroups are summed by
 // reduce_grad_kernel in a fixed order.
 // =======================================================================================
 __device__ __forceinline__ void tile_put(float* tile, f32x4 v, int lane) {
@@ -1222,17 +1197,6 @@ __device__ __forceinline__ int image_lane_offset_F(int lane) {
 __device__ __forceinline__ f32x4 image_get_F(const float* block, int lofs) {
     return *reinterpret_cast<const f32x4*>(block + lofs);
 }
-#ifndef PSP_ABLATE
-#define PSP_ABLATE 0      // diagnostic builds: 1 no Philox, 2 idle consumers, 4 idle producers, 8 consumers skip HBM, 16 producers skip HBM
-#endif
-#ifndef PSP_PRODUCER_PRIO
-#define PSP_PRODUCER_PRIO 3
-#endif
-#if defined(PSP_NO_SGB) && PSP_NO_SGB
-#define PSP_SGB(mask, n)
-#else
-#define PSP_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
-#endif
 // accumulate-in-place MFMA (vDst tied to SrcC): keeps a persistent accumulator in ONE register quad across a
 // long unrolled stream (the builtin lets the allocator rename it, which costs copies and spills there).
 // Only for accumulators that no VALU / store reads until well after the stream (no hazard tracking in asm).
@@ -1240,332 +1204,6 @@ __device__ __forceinline__ void mfma16_inplace(f32x4& c, float a, float b) {
     asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
 }
 __device__ __forceinline__ float hsum4(f32x4 v) { return (v[0] + v[1]) + (v[2] + v[3]); }
-
-template <int D, int H>
-__global__ __launch_bounds__(256, 2) void hjb_bwd_kernel(const HjbArgs a) {
-    PSP_COND_EXIT(a);
-    using G = Geo<D, H>;
-    constexpr int DB = G::DB, HB = G::HB, KSD = G::KSD, KSH = G::KSH;
-    constexpr int WH = G::WH, WD = G::WD, NIB = G::NIB, NOBD = G::NOBD, NOBH = G::NOBH;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 15, q = lane >> 4;
-    // wave grid coordinates; compile-time zero along a 1-wide axis so tile validity folds statically
-    const int wh = (WH == 1) ? 0 : wave % WH, wd = (WD == 1) ? 0 : wave / WH;
-    const int lofsF = image_lane_offset_F(lane);
-    const float* __restrict__ P = a.params;
-
-    // transposed tables for the data-gradient GEMMs: da1 = W2^T dz2, da2 = W3^T G
-    stage_aop(lds + G::gW2T, HB, KSH, tid, nthr, [&](int row, int col) {
-        return (row < H && col < H) ? P[G::oW2 + col * H + row] : 0.f; });
-    stage_aop(lds + G::gW3T, HB, KSD, tid, nthr, [&](int row, int col) {
-        return (row < H && col < D) ? P[G::oW3 + col * H + row] : 0.f; });
-    stage_vec(lds + G::gb3, DB, tid, nthr, [&](int f) { return f < D ? P[G::ob3 + f] : 0.f; });
-    __syncthreads();
-
-    const f32x4* vb3_0 = reinterpret_cast<const f32x4*>(lds + G::gb3) + q;
-    float* exch = lds + G::gEx;                       // [4 waves][EXT tiles][256]
-    float* my_ex = exch + wave * (G::EXT * 256);
-
-    // accumulators: this wave's tiles only
-    f32x4 acc3[NOBD][NIB], acc2[NOBH][NIB], acc1[NIB][NOBD];
-    float bs3[NOBD], bs2[NOBH], bs1[NIB], bt1[NIB];
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < NOBD; ++s) { bs3[s] = 0.f;
-#pragma unroll
-        for (int t = 0; t < NIB; ++t) { acc3[s][t] = zero4; acc1[t][s] = zero4; } }
-#pragma unroll
-    for (int s = 0; s < NOBH; ++s) { bs2[s] = 0.f;
-#pragma unroll
-        for (int t = 0; t < NIB; ++t) acc2[s][t] = zero4; }
-#pragma unroll
-    for (int t = 0; t < NIB; ++t) { bs1[t] = 0.f; bt1[t] = 0.f; }
-
-    const double invK = 1.0 / (double)a.K_global;
-    const float meanD = (a.loss_kind == LOSS_LOGVAR) ? (float)(a.sums[0] * invK) : 0.f;
-    const float coef = (float)(2.0 * invK);
-    const float dt = a.dt, sqdt = a.sqdt;
-
-    const long long nblk = (long long)a.N * a.ntile16;
-    const long long nround = (nblk + 3) / 4;
-#ifdef PSP_STAMPS
-    unsigned long long stamps[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    for (long long round = blockIdx.x; round < nround; round += gridDim.x) {
-        PSP_STAMP(ts0);
-        // L2 touch-prefetch (one dword per 128-B line, value unused): this round's X_n panels are
-        // first read in P3 and the NEXT round's h1/h2 panels in its P1 -- both would otherwise be
-        // ~2 us HBM first-touch misses that a one-block register prefetch cannot cover.
-        float touch0, touch1;
-        {
-            const long long xb0 = round * 4 + wave;                         // wave w touches block w's X_n
-            const float* xt = a.path + (size_t)(xb0 < nblk ? xb0 : nblk - 1) * (size_t)G::PB + G::pX;
-            touch0 = xt[(lane * 32 < 4 * DB * 64) ? lane * 32 : 0];
-            const long long nb0 = (round + gridDim.x) * 4 + wave;           // own block of the next round
-            const float* ht = a.path + (size_t)(nb0 < nblk ? nb0 : nblk - 1) * (size_t)G::PB + G::pH1;
-            touch1 = ht[(lane * 32 < 8 * HB * 64) ? lane * 32 : 0];
-        }
-        // ------------------------------------------------------------------ P1: own block
-        {
-            const long long blk0 = round * 4 + wave;
-            const bool bvalid = blk0 < nblk;
-            const long long blk = bvalid ? blk0 : nblk - 1;
-            const int n = (int)(blk / a.ntile16), t16 = (int)(blk % a.ntile16);
-            const int k = t16 * 16 + j;
-            const bool kvalid = bvalid && k < a.K_local;
-            const float* pb = a.path + (size_t)blk * (size_t)G::PB + lane;
-            // LOSS_WEIGHTS: the caller supplies w_k = dLoss/dY_k directly in the D argument
-            const float dk = a.D[kvalid ? k : 0];
-            const float wk = kvalid ? (a.loss_kind == LOSS_WEIGHTS ? dk : coef * (dk - meanD)) : 0.f;
-            f32x4 Gt[DB];
-#pragma unroll
-            for (int m = 0; m < DB; ++m) Gt[m] = zero4;
-#pragma unroll
-            for (int b = 0; b < DB; ++b) {
-                f32x4 xi;                                        // xi_{n+1} image stored by the forward kernel
-#pragma unroll
-                for (int r = 0; r < 4; ++r) xi[r] = pb[G::pXi + (4 * b + r) * 64];
-                Gt[b] = (wk * sqdt) * xi;      // the image is xi (+ sqrt(dt) Z when the forward process is not adaptive)
-            }
-            // h2 / h1 are fetched right before the GEMM whose epilogue consumes them: the GEMM
-            // (100 / 64 MFMAs) covers the load latency and the panels are not live during Philox
-            f32x4 dz2[HB], dz1[HB];
-            {
-                f32x4 h2[HB];
-#pragma unroll
-                for (int m = 0; m < HB; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h2[m][r] = pb[G::pH2 + (4 * m + r) * 64];
-#pragma unroll
-                for (int m = 0; m < HB; ++m) dz2[m] = zero4;
-                gemm_T<HB, KSD, DB>(dz2, lds + G::gW3T, Gt, lane);
-#pragma unroll
-                for (int m = 0; m < HB; ++m) dz2[m] = dz2[m] * (1.0f - h2[m] * h2[m]);
-            }
-            // G panel -> exchange tiles [0, DB) (done here so Gt dies before the next GEMM)
-#pragma unroll
-            for (int b = 0; b < DB; ++b) tile_put(my_ex + b * 256, Gt[b], lane);
-            {
-                f32x4 h1[HB];
-#pragma unroll
-                for (int m = 0; m < HB; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h1[m][r] = pb[G::pH1 + (4 * m + r) * 64];
-#pragma unroll
-                for (int m = 0; m < HB; ++m) dz1[m] = zero4;
-                gemm_T<HB, KSH, HB>(dz1, lds + G::gW2T, dz2, lane);
-#pragma unroll
-                for (int m = 0; m < HB; ++m) dz1[m] = dz1[m] * (1.0f - h1[m] * h1[m]);
-            }
-
-            PSP_STAMP(ts1);
-            __syncthreads();
-            PSP_STAMP(ts2);
-            PSP_ACC(0, ts1, ts0);   // P1 compute
-            PSP_ACC(1, ts2, ts1);   // barrier A
-            // -------------------------------------------------------------- P2: dW3, db3
-            // (tile indices are clamped, never branched on: out-of-range tiles accumulate into
-            //  registers that are not written back).  Rolled loop, operands of block sb+1 are
-            //  requested before the MFMAs of block sb.
-            {
-                int ibc[NIB], obc[NOBD];
-#pragma unroll
-                for (int t = 0; t < NIB; ++t) ibc[t] = ((wh + WH * t) < HB ? (wh + WH * t) : HB - 1) * 256;
-#pragma unroll
-                for (int s2 = 0; s2 < NOBD; ++s2) obc[s2] = ((wd + WD * s2) < DB ? (wd + WD * s2) : DB - 1) * 256;
-                const long long rb = round * 4;
-                f32x4 bnext[NIB], anext[NOBD];
-                {
-                    const float* sp = a.path + (size_t)(rb < nblk ? rb : nblk - 1) * (size_t)G::PB + G::pH2;
-#pragma unroll
-                    for (int t = 0; t < NIB; ++t) bnext[t] = image_get_F(sp + ibc[t], lofsF);
-#pragma unroll
-                    for (int s2 = 0; s2 < NOBD; ++s2) anext[s2] = tile_get(exch + obc[s2], lane);
-                }
-#pragma unroll 1
-                for (int sb = 0; sb < 4; ++sb) {
-                    f32x4 bv[NIB], av[NOBD];
-#pragma unroll
-                    for (int t = 0; t < NIB; ++t) bv[t] = bnext[t];
-#pragma unroll
-                    for (int s2 = 0; s2 < NOBD; ++s2) av[s2] = anext[s2];
-                    {   // operands of block sb+1: h2 panel from L2/HBM, G tiles from LDS
-                        const int sn = sb < 3 ? sb + 1 : sb;
-                        const long long nb = rb + sn;
-                        const float* sp = a.path + (size_t)(nb < nblk ? nb : nblk - 1) * (size_t)G::PB + G::pH2;
-                        const float* exn = exch + sn * (G::EXT * 256);
-#pragma unroll
-                        for (int t = 0; t < NIB; ++t) bnext[t] = image_get_F(sp + ibc[t], lofsF);
-#pragma unroll
-                        for (int s2 = 0; s2 < NOBD; ++s2) anext[s2] = tile_get(exn + obc[s2], lane);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);   // the prefetch is issued before the work below
-#pragma unroll
-                    for (int s2 = 0; s2 < NOBD; ++s2) bs3[s2] += hsum4(av[s2]);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-#pragma unroll
-                        for (int s2 = 0; s2 < NOBD; ++s2)
-#pragma unroll
-                            for (int t = 0; t < NIB; ++t) acc3[s2][t] = mfma16(av[s2][r], bv[t][r], acc3[s2][t]);
-                }
-            }
-            PSP_STAMP(ts3);
-            __syncthreads();                             // everyone is done with the G tiles
-#pragma unroll
-            for (int m = 0; m < HB; ++m) {
-                tile_put(my_ex + m * 256, dz2[m], lane);
-                tile_put(my_ex + (HB + m) * 256, dz1[m], lane);
-            }
-            __syncthreads();
-            PSP_STAMP(ts4);
-            PSP_ACC(2, ts3, ts2);   // P2 compute
-            PSP_ACC(3, ts4, ts3);   // barriers B + C + dz exchange
-        }
-        PSP_STAMP(ts5);
-        // ------------------------------------------------------------------ P3: dW2, db2, dW1, db1, dW1[:,0]
-        {
-            int ibc[NIB], xbc[NOBD], o2c[NOBH], o1c[NIB];
-#pragma unroll
-            for (int t = 0; t < NIB; ++t) {
-                const int hb = (wh + WH * t) < HB ? (wh + WH * t) : HB - 1;
-                ibc[t] = hb * 256;
-                o1c[t] = (HB + hb) * 256;
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < NOBD; ++s2) xbc[s2] = ((wd + WD * s2) < DB ? (wd + WD * s2) : DB - 1) * 256;
-#pragma unroll
-            for (int s2 = 0; s2 < NOBH; ++s2) o2c[s2] = ((wd + WD * s2) < HB ? (wd + WD * s2) : HB - 1) * 256;
-            const long long rb = round * 4;
-            f32x4 hnext[NIB], xnext[NOBD], a2next[NOBH], a1next[NIB];
-            {
-                const float* sp = a.path + (size_t)(rb < nblk ? rb : nblk - 1) * (size_t)G::PB;
-#pragma unroll
-                for (int t = 0; t < NIB; ++t) hnext[t] = image_get_F(sp + G::pH1 + ibc[t], lofsF);
-#pragma unroll
-                for (int s2 = 0; s2 < NOBD; ++s2) xnext[s2] = image_get_F(sp + G::pX + xbc[s2], lofsF);
-#pragma unroll
-                for (int s2 = 0; s2 < NOBH; ++s2) a2next[s2] = tile_get(exch + o2c[s2], lane);
-#pragma unroll
-                for (int t = 0; t < NIB; ++t) a1next[t] = tile_get(exch + o1c[t], lane);
-            }
-#pragma unroll 1
-            for (int sb = 0; sb < 4; ++sb) {
-                const long long cb = (rb + sb) < nblk ? (rb + sb) : nblk - 1;
-                const float tn = (float)((int)(cb / a.ntile16)) * dt;
-                f32x4 hv[NIB], xv[NOBD], a2[NOBH], a1[NIB];
-#pragma unroll
-                for (int t = 0; t < NIB; ++t) { hv[t] = hnext[t]; a1[t] = a1next[t]; }
-#pragma unroll
-                for (int s2 = 0; s2 < NOBD; ++s2) xv[s2] = xnext[s2];
-#pragma unroll
-                for (int s2 = 0; s2 < NOBH; ++s2) a2[s2] = a2next[s2];
-                {   // operands of block sb+1: h1 / X_n panels (L2 after the touch-prefetch), dz tiles from LDS
-                    const int sn = sb < 3 ? sb + 1 : sb;
-                    const long long nb = rb + sn;
-                    const float* sp = a.path + (size_t)(nb < nblk ? nb : nblk - 1) * (size_t)G::PB;
-                    const float* exn = exch + sn * (G::EXT * 256);
-#pragma unroll
-                    for (int t = 0; t < NIB; ++t) hnext[t] = image_get_F(sp + G::pH1 + ibc[t], lofsF);
-#pragma unroll
-                    for (int s2 = 0; s2 < NOBD; ++s2) xnext[s2] = image_get_F(sp + G::pX + xbc[s2], lofsF);
-#pragma unroll
-                    for (int s2 = 0; s2 < NOBH; ++s2) a2next[s2] = tile_get(exn + o2c[s2], lane);
-#pragma unroll
-                    for (int t = 0; t < NIB; ++t) a1next[t] = tile_get(exn + o1c[t], lane);
-                }
-                __builtin_amdgcn_sched_barrier(0);       // the prefetch is issued before the work below
-                // layer 2: rows = dz2 blocks (WD axis), cols = h1 blocks (WH axis)
-#pragma unroll
-                for (int s2 = 0; s2 < NOBH; ++s2) bs2[s2] += hsum4(a2[s2]);
-                // layer 1: rows = dz1 blocks (WH axis), cols = X_n blocks (WD axis)
-#pragma unroll
-                for (int t = 0; t < NIB; ++t) {
-                    const float sv = hsum4(a1[t]);
-                    bs1[t] += sv;
-                    bt1[t] = fmaf(tn, sv, bt1[t]);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                    for (int s2 = 0; s2 < NOBH; ++s2)
-#pragma unroll
-                        for (int t = 0; t < NIB; ++t) acc2[s2][t] = mfma16(a2[s2][r], hv[t][r], acc2[s2][t]);
-#pragma unroll
-                    for (int s2 = 0; s2 < NOBD; ++s2)
-#pragma unroll
-                        for (int t = 0; t < NIB; ++t) acc1[t][s2] = mfma16(a1[t][r], xv[s2][r], acc1[t][s2]);
-                }
-            }
-        }
-        asm volatile("" :: "v"(touch0), "v"(touch1));    // keep the touch loads alive until here
-        PSP_STAMP(ts6);
-        __syncthreads();                                 // exchange tiles are rewritten next round
-        PSP_STAMP(ts7);
-        PSP_ACC(4, ts6, ts5);       // P3 compute
-        PSP_ACC(5, ts7, ts6);       // barrier D
-        PSP_ACC(6, ts7, ts0);       // whole round
-    }
-#ifdef PSP_STAMPS
-    if (a.dbg && lane == 0) {
-        stamps[7] = (unsigned long long)((nround - blockIdx.x + gridDim.x - 1) / gridDim.x);
-        for (int i = 0; i < 8; ++i) a.dbg[((size_t)blockIdx.x * 4 + wave) * 8 + i] = stamps[i];
-    }
-#endif
-
-    // ---- write this wave's tiles into the workgroup's partial gradient (torch flat layout).
-    // D tile (ob, ib): lane (col = l&15, qq = l>>4), reg rr  <->  dW[16 ob + 4 qq + rr][16 ib + col]
-    float* gp = a.grad_partial + (size_t)blockIdx.x * G::P;
-    const int col = lane & 15, qq = lane >> 4;
-#pragma unroll
-    for (int s = 0; s < NOBD; ++s)
-#pragma unroll
-        for (int t = 0; t < NIB; ++t) {
-            const int ob = wd + WD * s, ib = wh + WH * t;
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int o3 = 16 * ob + 4 * qq + rr, i3 = 16 * ib + col;       // dW3[o in d][i in H]
-                if (ob < DB && ib < HB && o3 < D && i3 < H) gp[G::oW3 + o3 * H + i3] = acc3[s][t][rr];
-                const int o1 = 16 * ib + 4 * qq + rr, i1 = 16 * ob + col;       // dW1[o in H][i in d] (acc1[t][s])
-                if (ob < DB && ib < HB && o1 < H && i1 < D) gp[G::oW1 + o1 * (D + 1) + 1 + i1] = acc1[t][s][rr];
-            }
-        }
-#pragma unroll
-    for (int s = 0; s < NOBH; ++s)
-#pragma unroll
-        for (int t = 0; t < NIB; ++t) {
-            const int ob = wd + WD * s, ib = wh + WH * t;
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int o2 = 16 * ob + 4 * qq + rr, i2 = 16 * ib + col;
-                if (ob < HB && ib < HB && o2 < H && i2 < H) gp[G::oW2 + o2 * H + i2] = acc2[s][t][rr];
-            }
-        }
-    // bias sums live on lane i = feature (q' partial sums): reduce over q', lanes q' == 0 write
-#pragma unroll
-    for (int s = 0; s < NOBD; ++s) {
-        const float v = qsum(bs3[s]);
-        const int f = 16 * (wd + WD * s) + col;
-        if (wh == 0 && qq == 0 && (wd + WD * s) < DB && f < D) gp[G::ob3 + f] = v;
-    }
-#pragma unroll
-    for (int s = 0; s < NOBH; ++s) {
-        const float v = qsum(bs2[s]);
-        const int f = 16 * (wd + WD * s) + col;
-        if (wh == 0 && qq == 0 && (wd + WD * s) < HB && f < H) gp[G::ob2 + f] = v;
-    }
-#pragma unroll
-    for (int t = 0; t < NIB; ++t) {
-        const float v1 = qsum(bs1[t]), vt = qsum(bt1[t]);
-        const int f = 16 * (wh + WH * t) + col;
-        if (wd == 0 && qq == 0 && (wh + WH * t) < HB && f < H) {
-            gp[G::ob1 + f] = v1;
-            gp[G::oW1 + f * (D + 1)] = vt;
-        }
-    }
-}
 
 // =======================================================================================
 // Backward kernel, role-specialised variant (adaptive forward process only).
@@ -1650,7 +1288,7 @@ __global__ __launch_bounds__(512) void hjb_bwd2_kernel(const HjbArgs a) {
         }
         for (int it = 0; it <= R; ++it) {
             PSP_STAMP(tp0);
-            if (it < R && !(PSP_ABLATE & 4)) {
+            if (it < R) {
                 // ---------------------------------------------------------- produce round r into bufs[it & 1]
                 const long long blk0 = own_block(it);
                 const bool bvalid = blk0 >= 0;
@@ -1658,7 +1296,7 @@ __global__ __launch_bounds__(512) void hjb_bwd2_kernel(const HjbArgs a) {
                 const int t16 = (int)(blk % a.ntile16);
                 const int k = t16 * 16 + j;
                 const bool kvalid = bvalid && k < a.K_local;
-                const float* pb = a.path + (size_t)((PSP_ABLATE & 16) ? 0 : blk) * (size_t)G::PB + lane;
+                const float* pb = a.path + (size_t)blk * (size_t)G::PB + lane;
                 float* ex = bufs + ((it & 1) * 4 + sub) * EXB + lane;
                 // LOSS_WEIGHTS: the caller supplies w_k = dLoss/dY_k directly in the D argument
                 const float dk = dkn;
@@ -1782,7 +1420,7 @@ __global__ __launch_bounds__(512) void hjb_bwd2_kernel(const HjbArgs a) {
     const int nblk_i = (int)nblk;                     // N * ntile16 < 2^31 is checked by the host
     auto blk_at = [&](long long c0) __attribute__((always_inline)) {
         const int c = (c0 < (long long)nblk_i) ? (int)c0 : nblk_i - 1;
-        return __builtin_amdgcn_readfirstlane((PSP_ABLATE & 8) ? 0 : c);
+        return __builtin_amdgcn_readfirstlane(c);
     };
     // wave-uniform tile base pointers are forced into SGPRs so every load is "SGPR base + lane offset"
     typedef const __attribute__((address_space(1))) float* gptr_t;
@@ -1873,30 +1511,28 @@ __global__ __launch_bounds__(512) void hjb_bwd2_kernel(const HjbArgs a) {
         }
     };
 
-    if (!(PSP_ABLATE & 2)) load_first(blk_at((long long)blockIdx.x * 4));   // first block's operands, while the producers start
+    load_first(blk_at((long long)blockIdx.x * 4));   // first block's operands, while the producers start
     __syncthreads();                                      // pairs with producer iteration 0
 #ifdef PSP_STAMPS
     unsigned long long stamps[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     for (int it = 1; it <= R; ++it) {
         PSP_STAMP(tc0);
-        if (!(PSP_ABLATE & 2)) {
-            // -------------------------------------------------------------- consume round r from bufs[(it-1) & 1]
-            const int rb = (blockIdx.x + (it - 1) * gridDim.x) * 4;
-            const float* exch = bufs + ((it - 1) & 1) * 4 * EXB;
-            const int b0 = blk_at(rb), b1 = blk_at(rb + 1), b2 = blk_at(rb + 2), b3 = blk_at(rb + 3);
-            const int bn = blk_at((long long)rb + 4LL * gridDim.x);       // first block of this workgroup's next round
-            load_lds_first(exch);
-            __builtin_amdgcn_sched_barrier(0);
-            phase_l3(0, b0, b1, exch);
-            phase_l21(0, b1, exch + EXB);
-            phase_l3(1, b1, b2, exch + EXB);
-            phase_l21(1, b2, exch + 2 * EXB);
-            phase_l3(0, b2, b3, exch + 2 * EXB);
-            phase_l21(0, b3, exch + 3 * EXB);
-            phase_l3(1, b3, bn, exch + 3 * EXB);
-            phase_l21(1, bn, nullptr);
-        }
+        // -------------------------------------------------------------- consume round r from bufs[(it-1) & 1]
+        const int rb = (blockIdx.x + (it - 1) * gridDim.x) * 4;
+        const float* exch = bufs + ((it - 1) & 1) * 4 * EXB;
+        const int b0 = blk_at(rb), b1 = blk_at(rb + 1), b2 = blk_at(rb + 2), b3 = blk_at(rb + 3);
+        const int bn = blk_at((long long)rb + 4LL * gridDim.x);       // first block of this workgroup's next round
+        load_lds_first(exch);
+        __builtin_amdgcn_sched_barrier(0);
+        phase_l3(0, b0, b1, exch);
+        phase_l21(0, b1, exch + EXB);
+        phase_l3(1, b1, b2, exch + EXB);
+        phase_l21(1, b2, exch + 2 * EXB);
+        phase_l3(0, b2, b3, exch + 2 * EXB);
+        phase_l21(0, b3, exch + 3 * EXB);
+        phase_l3(1, b3, bn, exch + 3 * EXB);
+        phase_l21(1, bn, nullptr);
         PSP_STAMP(tc1);
         __syncthreads();                                  // swap the exchange buffers (pairs with the producer loop)
         PSP_STAMP(tc2);
@@ -1912,7 +1548,7 @@ __global__ __launch_bounds__(512) void hjb_bwd2_kernel(const HjbArgs a) {
 #endif
 
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // matrix-pipe results settle before VALU / stores read them
-    // ---- consumers write their tiles into the workgroup's partial gradient (same mapping as hjb_bwd_kernel)
+    // ---- consumers write their tiles into the workgroup's partial gradient
     float* gp = a.grad_partial + (size_t)blockIdx.x * G::P;
     const int col = lane & 15, qq = lane >> 4;
 #pragma unroll
@@ -1967,9 +1603,7 @@ __global__ __launch_bounds__(512) void hjb_bwd2_kernel(const HjbArgs a) {
 struct HjbInstance {
     int d, H, n_params;
     int (*fwd_lds_bytes)(int drift_kind, int sigma_kind);
-    int (*bwd_lds_bytes)(int adaptive);
     hipError_t (*launch_fwd)(const HjbArgs&, int grid, int block, hipStream_t);
-    hipError_t (*launch_bwd)(const HjbArgs&, int grid, int block, hipStream_t);
     int path_floats_per_tile_step;   // Geo::PB
     int (*bwd2_lds_bytes)();
     hipError_t (*launch_bwd2)(const HjbArgs&, int grid, hipStream_t);   // role-specialised variant, 512 threads
@@ -1996,7 +1630,6 @@ template <int D, int H>
 struct HjbLaunch {
     using G = Geo<D, H>;
     static int fwd_lds(int dk, int sk) { return G::fwd_lds_floats(dk, sk) * 4; }
-    static int bwd_lds(int ad) { return G::bwd_lds_floats(ad) * 4; }
     static int fwd_x3_lds(int dk, int sk) { return G::fwd_x3_lds_floats(dk, sk) * 4; }
     template <int MODE, int FAST>
     static hipError_t fwd_as(const HjbArgs& a, int grid, int block, hipStream_t s) {
@@ -2022,22 +1655,6 @@ struct HjbLaunch {
                           (a.store_path == 4 || a.store_path == 1) && a.loss_kind != LOSS_RELENT;
         return spec ? fwd_as<2, 2>(a, grid, block, s) : fast(a) ? fwd_as<2, 1>(a, grid, block, s) : fwd_as<2, 0>(a, grid, block, s);
     }
-#ifdef PSP_LEGACY_BWD
-    // hjb_bwd_kernel (the second backward version: two 4-wave workgroups per CU, every wave runs all phases) is superseded by
-    // hjb_bwd2_kernel for every shipped instance; it is only instantiated in diagnostic builds (-DPSP_LEGACY_BWD, selected at
-    // run time with PSP_BWD_VARIANT=1) for A/B timing
-    static hipError_t bwd(const HjbArgs& a, int grid, int block, hipStream_t s) {
-        const int bytes = bwd_lds(a.adaptive);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjb_bwd_kernel<D, H>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjb_bwd_kernel<D, H>), dim3(grid), dim3(block), bytes, s, a);
-        return hipGetLastError();
-    }
-    static constexpr auto legacy_bwd = &bwd;
-#else
-    static constexpr hipError_t (*legacy_bwd)(const HjbArgs&, int, int, hipStream_t) = nullptr;
-#endif
     static int bwd2_lds() { return G::bwd2_lds_floats() * 4; }
     static hipError_t bwd2(const HjbArgs& a, int grid, hipStream_t s) {
         const int bytes = bwd2_lds();
@@ -2048,7 +1665,7 @@ struct HjbLaunch {
         return hipGetLastError();
     }
     static HjbInstance instance() {
-        return HjbInstance{D, H, G::P, &fwd_lds, &bwd_lds, &fwd, legacy_bwd, G::PB, &bwd2_lds, &bwd2};
+        return HjbInstance{D, H, G::P, &fwd_lds, &fwd, G::PB, &bwd2_lds, &bwd2};
     }
 };
 

@@ -312,9 +312,6 @@ __global__ __launch_bounds__(512, 2) void hjbc_fwd_kernel(const HjbArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) if (16 * b + 4 * r + q >= D) v[r] = 0.f;
             }
-#if defined(PSP_XI_PIN) && PSP_XI_PIN
-            asm volatile("" : "+v"(v));            // (A/B switch)
-#endif
             // (NOT pinned with an empty asm: the compiler sinks part of this arithmetic towards its use in P4; pinning it here keeps 16 - 64
             //  more registers live across three phases and measured slower -- four tiles 11.9 -> 12.3 ms, two tiles unchanged: the
             //  "shadow" of the hidden layer's product is not free, the vector issue port is as busy there as in P4)

@@ -342,23 +342,9 @@ __device__ __forceinline__ void gemm_img_x3(f32x4 (&acc)[MB], const float* __res
 #pragma unroll
             for (int m = 0; m < CH; m += 2) {                           // fresh SGPR base every 4 KiB (two output blocks)
                 if (c * CH + m < gn) {
-#if defined(PSP_ABL_WIDE) && (PSP_ABL_WIDE & 1)      // timing ablation: every S-step re-reads step 0's operands (L1 hits, same instruction stream)
-                    gptr8_t tp = sgpr_ptr8(tbl + ((size_t)(S & 0) * LD + g0 + c * CH + m) * 512);
-#elif defined(PSP_ABL_WIDE) && (PSP_ABL_WIDE & 2)    // ... every chunk re-reads ONE 4 KiB pair of blocks
-                    gptr8_t tp = sgpr_ptr8(tbl + ((size_t)(S & 0) * LD + ((g0 + c * CH + m) & 0)) * 512);
-#else
                     gptr8_t tp = sgpr_ptr8(tbl + ((size_t)S * LD + g0 + c * CH + m) * 512);
-#endif
-#if defined(PSP_ABL_WIDE) && (PSP_ABL_WIDE & 4)      // timing ablation: half the operand bytes (lo := hi, no second load)
-                    ah[st][m] = tp[ul]; al[st][m] = ah[st][m];
-                    if (m + 1 < CH && c * CH + m + 1 < gn) { ah[st][m + 1] = tp[128 + ul]; al[st][m + 1] = ah[st][m + 1]; }
-#elif defined(PSP_ABL_WIDE) && (PSP_ABL_WIDE & 8)    // ... no operand loads inside the loop at all
-                    if (S == 0 && c == 0) { ah[st][m] = tp[ul]; al[st][m] = tp[64 + ul]; if (m + 1 < CH) { ah[st][m + 1] = tp[128 + ul]; al[st][m + 1] = tp[192 + ul]; } }
-                    else { asm volatile("" : "+v"(ah[st][m]), "+v"(al[st][m])); if (m + 1 < CH) asm volatile("" : "+v"(ah[st][m + 1]), "+v"(al[st][m + 1])); }
-#else
                     ah[st][m] = tp[ul]; al[st][m] = tp[64 + ul];
                     if (m + 1 < CH && c * CH + m + 1 < gn) { ah[st][m + 1] = tp[128 + ul]; al[st][m + 1] = tp[192 + ul]; }
-#endif
                 }
             }
         };
@@ -535,18 +521,10 @@ __device__ __forceinline__ void gemm_regs_x3(f32x4 (&acc)[MB], const float* __re
     for (int mb = 0; mb < MB; ++mb) acc[mb] = acc[mb] + kSplitInv * corr[mb];
 }
 
-// The four waves of a workgroup stream the SAME operand tables in the same order, each for its own tile.  A workgroup
-// barrier in front of every long product keeps them within a few k-steps of one another, so that a table line one wave
-// misses in the CU's vector L1 is a hit (or a merged in-flight miss) for the other three: the L2 -> L1 stream, which bounds
-// these kernels, is then shared instead of fetched per wave.  Every wave runs every step (surplus waves of the last
-// workgroup run along on the last tile), so the barriers are uniform.  -DPSP_WIDE_NOSYNC restores free-running waves (A/B).
-// Measured (round 2, d = 200 and d = 500): no gain (6.94 vs 6.9 ms, 38.9 vs 37 ms) -- the kernels are not bound by a per-wave
-// L2 -> L1 stream after all; the barriers stay available as -DPSP_WIDE_SYNC_ON for A/B runs.
-#if defined(PSP_WIDE_SYNC_ON) && PSP_WIDE_SYNC_ON
-#define PSP_WIDE_SYNC() __syncthreads()
-#else
-#define PSP_WIDE_SYNC()
-#endif
+// The four waves of a workgroup stream the SAME operand tables in the same order, each for its own tile, and run free.  A
+// workgroup barrier in front of every long product, to keep them within a few k-steps of one another and share the L2 -> L1
+// stream, measured no gain (round 2, d = 200 and d = 500: 6.94 vs 6.9 ms, 38.9 vs 37 ms) -- the kernels are not bound by a
+// per-wave L2 -> L1 stream after all.
 
 // =======================================================================================
 // Wide forward kernel: one wave = one 16-trajectory tile for all N steps (same per-step algebra, same
@@ -672,14 +650,12 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void hjbw_fwd_kernel(const
             f32x4 h1[HB];
 #pragma unroll
             for (int m = 0; m < HB; ++m) h1[m] = vb1[m * 4] + tn * vw1t[m * 4];
-            PSP_WIDE_SYNC();
             if constexpr (X3 && kShare) gemm_img_x3s<HB, W::KS8>(h1, T + W::xW1, img, lds + W::fStage, lane, wave);
             else if constexpr (X3) gemm_img_x3<HB, W::KS8>(h1, T + W::xW1, img, lane);
             else gemm_img<HB, KP>(h1, T + W::tW1, img, lane);
             PSP_STAMP(ws2);
             // ---- X_{n+1} = X + b(X) dt + sigma v (solver.py:471-472): the drift part now, while the image still holds X_n
             if (k_drift == DRIFT_DENSE) {
-                PSP_WIDE_SYNC();
                 if constexpr (X3 && kShare) gemm_img_x3s<DB, W::KS8>(X, T + W::xA, img, lds + W::fStage, lane, wave);
                 else if constexpr (X3) gemm_img_x3<DB, W::KS8>(X, T + W::xA, img, lane);
                 else gemm_img<DB, KP>(X, T + W::tA, img, lane);                  // X += (dt A) X_n
@@ -793,7 +769,6 @@ __global__ __launch_bounds__(256, (D <= 256 ? 2 : 1)) void hjbw_fwd_kernel(const
             if constexpr (LOGU) ULsum = fmaf(UL, dt, ULsum);
             PSP_STAMP(ws5);
             if (k_sigma == SIGMA_DENSE) {
-                PSP_WIDE_SYNC();
                 if constexpr (X3 && kShare) gemm_img_x3s<DB, W::KS8>(X, T + W::xB, img, lds + W::fStage, lane, wave);
                 else if constexpr (X3) gemm_img_x3<DB, W::KS8>(X, T + W::xB, img, lane);
                 else gemm_img<DB, KP>(X, T + W::tB, img, lane); // X += B v
@@ -1751,13 +1726,10 @@ __global__ __launch_bounds__(256, 1) void hjbw_bwd_x3_kernel(const HjbArgs a) {
 #pragma unroll
             for (int m = 0; m < HB; ++m) { dz2[m] = zero4; dzc[m] = zero4; }
             const float* xip = pb + G::pXi;
-#ifndef PSP_WBX_NX
-#define PSP_WBX_NX 7
-#endif
             // two rings: the xi dwords of an S-step are requested NX - 1 steps ahead (global memory), its table operands one step
             // ahead (LDS; the KG <= 1 leading S-steps that did not fit are read from global memory in the prologue, where their
             // latency hides behind the first xi requests)
-            constexpr int NX = PSP_WBX_NX, TS = 2, KG = KS8 - KSL;
+            constexpr int NX = 7, TS = 2, KG = KS8 - KSL;
             static_assert(KG <= 1, "at most the first S-step of the table outside the LDS");
             float xb[NX][8];
             f16x8 ah[TS][HB], al[TS][HB];
@@ -1999,7 +1971,6 @@ struct HjbwLaunch {
     using G = Geo<D, H>;
     using W = GeoW<D, H>;
     static int fwd_lds(int, int) { return W::fwd_lds_floats * 4; }
-    static int bwd_lds(int) { return W::bwd_lds_floats * 4; }
     static int bwd2_lds() {
         return ((D <= 256) && (GeoB2<D, H>::lds_floats * 4 <= 160 * 1024) && (G::HB == 4)) ? GeoB2<D, H>::lds_floats * 4 : W::bwd_lds_floats * 4;
     }
@@ -2053,7 +2024,6 @@ struct HjbwLaunch {
         hipLaunchKernelGGL((hjbw_fwd_kernel<D, H, false, false, true>), dim3(grid), dim3(block), bytes, s, a);
         return hipGetLastError();
     }
-    static hipError_t bwd(const HjbArgs&, int, int, hipStream_t) { return hipErrorNotSupported; }
     // d <= 256: the role-specialised kernel (8 waves, W3^T staged in LDS from the parameters: no table pass), if its LDS fits
     static constexpr bool kRoles = (D <= 256) && (GeoB2<D, H>::lds_floats * 4 <= 160 * 1024) && (G::HB == 4);
     static hipError_t bwd2(const HjbArgs& a, int grid, hipStream_t s) {
@@ -2113,7 +2083,7 @@ struct HjbwLaunch {
         return hipGetLastError();
     }
     static HjbInstance instance() {
-        HjbInstance r{D, H, G::P, &fwd_lds, &bwd_lds, &fwd, &bwd, G::PB, &bwd2_lds, &bwd2};
+        HjbInstance r{D, H, G::P, &fwd_lds, &fwd, G::PB, &bwd2_lds, &bwd2};
         r.launch_adj = &adj;
         r.launch_adj_x3 = &adj_x3;
         r.launch_bwd2_x3 = &bwd2_x3;

@@ -16,11 +16,6 @@
 #pragma once
 #include "hjbw_kernels.h"
 
-#ifndef PSP_ABL_WX
-#define PSP_ABL_WX 0   // measurement only (tools/r4): 1 = consumers without their MFMAs (operands stay live); 4 = producers without
-                       // their xi reads (what fetching xi once could save at most: d = 200 1.85 -> 1.71 ms)
-#endif
-
 namespace psp {
 
 template <int D, int H>
@@ -31,11 +26,8 @@ struct GeoBX {
     static constexpr int tbl2F = SplitGeo<KSH, HB>::floats(HB);         // split W2^T table (producers)
     static constexpr int oZ1 = 4 * HB * 64, oWts = 2 * 4 * HB * 64, EXQ = oWts + 64;   // per block: dz2 and dz1 k-step images, 16 weights
     static constexpr int bufs = tblF + tbl2F, oScan = bufs + 2 * 4 * EXQ, lds_floats = oScan + 16;
-#ifdef PSP_WX_RD
-    static constexpr int RD = PSP_WX_RD;                                // (measurement builds)
-#else
     static constexpr int RD = DB <= 13 ? 10 : 8;                        // ring depth in item PAIRS (two f32x4 each): what the consumer's
-#endif                                                                  // 4 (2 DB + HB) accumulator registers leave room for without spills
+                                                                        // 4 (2 DB + HB) accumulator registers leave room for without spills
     static constexpr int NIP = 2 * DB + 2;                              // items of a pair: h2, h1, DB xi tiles, DB X tiles
     static constexpr int NIR = ((2 * NIP + RD - 1) / RD) * RD;          // items of a round, padded to a multiple of RD
     static constexpr int RS = 16 * DB + 3 * 16 * HB;                    // per-producer bias-sum slots: G | dz2 | dz1 | t dz1
@@ -167,10 +159,11 @@ __global__ __launch_bounds__(512) void hjbw_bwd2x_kernel(const HjbArgs a) {
                     const float* pn = a.path + (size_t)nblk1 * (size_t)G::PB + lane;
                     const int k1 = (int)(nblk1 % a.ntile16) * 16 + j;
                     dkn = a.D[k1 < a.K_local ? k1 : 0];
+                    // (an ablation build without these xi reads, the most fetching xi once could save: d = 200 1.85 -> 1.71 ms)
 #pragma unroll
                     for (int b = 0; b < DB; ++b)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) xin[b][r] = (PSP_ABL_WX & 4) ? 0.25f * (float)(b + r) : pn[G::pXi + (4 * b + r) * 64];
+                        for (int r = 0; r < 4; ++r) xin[b][r] = pn[G::pXi + (4 * b + r) * 64];
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 f32x4 h1[HB], dz1[HB];
@@ -256,9 +249,6 @@ __global__ __launch_bounds__(512) void hjbw_bwd2x_kernel(const HjbArgs a) {
     };
     auto pack = [&](const f32x4& u0, const f32x4& u1, f16x8& hi, f16x8& lo) __attribute__((always_inline)) { split8u(u0, u1, hi, lo); };
     auto mma3 = [&](f32x4& acc, const f16x8& Ah, const f16x8& Al, const f16x8& Bh, const f16x8& Bl) __attribute__((always_inline)) {
-#if (PSP_ABL_WX & 1)
-        acc[0] += (float)Ah[0] + (float)Al[1] + (float)Bh[2] + (float)Bl[3]; return;   // ablation: operands stay live, no MFMA
-#endif
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bh, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bl, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, Bh, acc, 0, 0, 0);

@@ -77,7 +77,7 @@ def loss_from_sums(sums, K_global, loss_method):
 def loss_weights(D_local, sums, K_global, loss_method):
     """w_k = dLoss/dD_k for this rank's trajectories, from GLOBAL sums:
     log-variance (2/K)(D_k - mean D), moment (2/K) D_k.  The HIP backward kernel applies the
-    same formula (csrc/hjb_kernels.h, hjb_bwd_kernel)."""
+    same formula (csrc/hjb_kernels.h, hjb_bwd2_kernel)."""
     K = float(K_global)
     if loss_method == 'log-variance':
         return (2.0 / K) * (D_local - (sums[0] / K).to(D_local.dtype))

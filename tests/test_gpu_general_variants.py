@@ -2,8 +2,8 @@
   * MANY rounds per persistent workgroup (the golden cases are one round each, which cannot see cross-round pipeline bugs):
     K = 32768 / 20000 trajectories, N = 20, against the CPU oracle's autograd on the reference's noise stream;
   * the bf16 MFMA modes (BASELINE.json configs[2]) against the fp32 kernels and the goldens, with their own tolerance.
-(The two-workgroups-per-CU backward gen_bwd_kernel that this file used to cross-check is no longer part of the shipped
-library: -DPSP_LEGACY_BWD diagnostic builds only.)"""
+(The two-workgroups-per-CU backward gen_bwd_kernel that this file used to cross-check has been removed from the
+sources.)"""
 import json
 import os
 import subprocess

@@ -6,7 +6,6 @@ The fp32 MFMA peak quoted in MI355X_MICROARCH.md assumes 2.4 GHz; this shows the
 sustains under each kernel, i.e. how much of the distance to that peak is clock rather than schedule.
 
     python tools/clock_probe.py [--seconds 4] [--mode fwd|bwd|both]
-    PSP_BWD_VARIANT=1 python tools/clock_probe.py --mode bwd      # the two-workgroups-per-CU backward
 """
 import argparse
 import ctypes as C
@@ -107,7 +106,7 @@ def main():
         ms = e0.elapsed_time(e1) / n
         sc = [s for s, _ in samples[1:] if s]
         pw = [p for _, p in samples[1:] if p]
-        print(json.dumps({'mode': name, 'variant': os.environ.get('PSP_BWD_VARIANT', 'default'), 'launches': n,
+        print(json.dumps({'mode': name, 'launches': n,
                           'ms_per_launch': ms, 'sclk_mhz_mean': sum(sc) / len(sc) if sc else None,
                           'sclk_mhz_min_max': [min(sc), max(sc)] if sc else None,
                           'power_w_mean': sum(pw) / len(pw) if pw else None, 'n_samples': len(samples)}))

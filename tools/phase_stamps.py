@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic: per-phase cycle breakdown of hjb_bwd_kernel from in-kernel s_memtime stamps.
+"""Diagnostic: per-phase cycle breakdown of hjb_fwd_kernel and hjb_bwd2_kernel from in-kernel s_memtime stamps.
 
 Needs the diagnostic library (built with -DPSP_STAMPS):
     python tools/phase_stamps.py            # builds csrc/libpsp_hip_stamps.so if missing, then runs
@@ -50,31 +50,20 @@ print("forward: workgroups %d, cycles per time step (mean over waves): %.0f; MFM
 for i, n in enumerate(fn):
     v = f[:, :, i] / steps
     print("  %-40s mean %8.0f  (%5.1f%%)" % (n, v.mean(), 100 * v.mean() / ftot))
-if os.environ.get("PSP_BWD_VARIANT", "") != "1":
-    # role-specialised backward: 8 waves per workgroup, waves 0-3 producers, 4-7 consumers
-    s = allb[fwg * 64:fwg * 64 + nwg * 64].reshape(nwg, 8, 8)
-    pr, co = s[:, :4, :], s[:, 4:, :]
-    R = pr[:, :, 7].clamp(min=1)
-    print("backward (role-specialised): workgroups %d, rounds per workgroup %.1f" % (nwg, R.mean()))
-    x3 = model._native_plan.matrix_mode == 'f16x3' if hasattr(model, '_native_plan') and model._native_plan is not None else plan.matrix_mode == 'f16x3'
-    prod = ([("h2 loads issued, weights -> G", 0), ("G split + image write", 1), ("W3^T G, tanh', h1 loads, next xi", 2),
-             ("whole produce phase", 3), ("barrier wait", 4), ("whole round", 6)] if x3 else
-            [("xi -> G, issue h2 / next-xi loads", 0), ("G store, GEMM W3^T G, tanh'", 1), ("dz2 store", 3), ("barrier wait", 4), ("whole round", 6)])
-    for nm, i in prod:
-        v = pr[:, :, i] / R
-        print("  producer  %-40s mean %8.0f   min %8.0f  max %8.0f" % (nm, v.mean(), v.min(), v.max()))
-    Rc = co[:, :, 7].clamp(min=1)
-    for nm, i in ([("both pairs", 0), ("first pair", 1), ("barrier wait", 4), ("whole round", 6)] if x3 else
-                  [("eight phases (352 MFMA)", 0), ("barrier wait", 4), ("whole round", 6)]):
-        v = co[:, :, i] / Rc
-        print("  consumer  %-40s mean %8.0f   min %8.0f  max %8.0f" % (nm, v.mean(), v.min(), v.max()))
-    sys.exit(0)
-s = allb[fwg * 64:].reshape(nwg, 4, 8)
-rounds = s[:, :, 7]
-names = ["P1 compute", "barrier A", "P2 compute", "barriers B+C + dz exchange", "P3 compute", "barrier D", "whole round"]
-tot = (s[:, :, 6] / rounds).mean()
-print("workgroups %d, rounds per workgroup %.1f, cycles per round (mean over waves): %.0f" % (nwg, rounds.mean(), tot))
-for i, n in enumerate(names):
-    v = (s[:, :, i] / rounds)
-    print("  %-28s mean %8.0f  (%5.1f%%)   min %8.0f  max %8.0f" % (n, v.mean(), 100 * v.mean() / tot, v.min(), v.max()))
-print("MFMA floor per round per wave (452 MFMA x 32 cyc): %d; x2 waves/SIMD: %d" % (452 * 32, 452 * 64))
+# role-specialised backward: 8 waves per workgroup, waves 0-3 producers, 4-7 consumers
+s = allb[fwg * 64:fwg * 64 + nwg * 64].reshape(nwg, 8, 8)
+pr, co = s[:, :4, :], s[:, 4:, :]
+R = pr[:, :, 7].clamp(min=1)
+print("backward (role-specialised): workgroups %d, rounds per workgroup %.1f" % (nwg, R.mean()))
+x3 = model._native_plan.matrix_mode == 'f16x3' if hasattr(model, '_native_plan') and model._native_plan is not None else plan.matrix_mode == 'f16x3'
+prod = ([("h2 loads issued, weights -> G", 0), ("G split + image write", 1), ("W3^T G, tanh', h1 loads, next xi", 2),
+         ("whole produce phase", 3), ("barrier wait", 4), ("whole round", 6)] if x3 else
+        [("xi -> G, issue h2 / next-xi loads", 0), ("G store, GEMM W3^T G, tanh'", 1), ("dz2 store", 3), ("barrier wait", 4), ("whole round", 6)])
+for nm, i in prod:
+    v = pr[:, :, i] / R
+    print("  producer  %-40s mean %8.0f   min %8.0f  max %8.0f" % (nm, v.mean(), v.min(), v.max()))
+Rc = co[:, :, 7].clamp(min=1)
+for nm, i in ([("both pairs", 0), ("first pair", 1), ("barrier wait", 4), ("whole round", 6)] if x3 else
+              [("eight phases (352 MFMA)", 0), ("barrier wait", 4), ("whole round", 6)]):
+    v = co[:, :, i] / Rc
+    print("  consumer  %-40s mean %8.0f   min %8.0f  max %8.0f" % (nm, v.mean(), v.min(), v.max()))
