@@ -311,7 +311,8 @@ class TanhMLP(torch.nn.Module):
 class DenseNetOracle(torch.nn.Module):
     """function_space.py:116-140: dense-concat net, relu(.)**2, weights randn*0.1, zero bias.  ``activation='tanh2'`` is the
     variant `Committor function.ipynb` (cell 1, DenseNet_tanh_2) defines for itself and swaps into model.V: the same
-    constructor, tanh(.)**2 in the forward."""
+    constructor, tanh(.)**2 in the forward.  ``activation='tanh'``: the same constructor with tanh, the dense-concat layout the
+    package's DenseNet(activation='tanh') keeps (unlike DenseNet_tanh, whose weights are nn.Linear layers)."""
 
     def __init__(self, d_in, d_out, lr, arch=(30, 30), seed=42, activation="relu2"):
         super().__init__()
@@ -336,6 +337,8 @@ class DenseNetOracle(torch.nn.Module):
                 x = lin
             elif self.activation == "tanh2":
                 x = torch.cat([x, torch.tanh(lin) ** 2], dim=1)      # Committor function.ipynb cell 1
+            elif self.activation == "tanh":
+                x = torch.cat([x, torch.tanh(lin)], dim=1)           # the package's DenseNet(activation='tanh')
             else:
                 x = torch.cat([x, torch.nn.functional.relu(lin) ** 2], dim=1)
         return x
@@ -365,15 +368,16 @@ class DenseNetTanhOracle(torch.nn.Module):
 
 def value_net(d_in, lr, seed, net=None, arch=None):
     """The value net of a golden case: ``net`` = dict(kind, arch, seed) ('densenet' / absent kind: DenseNet; 'user_tanh2': the
-    committor notebook's own class; 'densenet_tanh': DenseNet_tanh), or just ``arch`` for a DenseNet with the solver's seed."""
+    committor notebook's own class; 'densenet_tanh': DenseNet_tanh; 'densenet_concat_tanh': DenseNet with tanh), or just
+    ``arch`` for a DenseNet with the solver's seed."""
     if net is None:
         kw = {} if arch is None else dict(arch=arch)
         return DenseNetOracle(d_in, 1, lr, seed=seed, **kw)
     kind = net.get("kind", "densenet")
     if kind == "densenet_tanh":
         return DenseNetTanhOracle(d_in, 1, lr, arch=net["arch"], seed=net["seed"])
-    return DenseNetOracle(d_in, 1, lr, arch=net["arch"], seed=net["seed"],
-                          activation="tanh2" if kind == "user_tanh2" else "relu2")
+    act = {"user_tanh2": "tanh2", "densenet_concat_tanh": "tanh"}.get(kind, "relu2")
+    return DenseNetOracle(d_in, 1, lr, arch=net["arch"], seed=net["seed"], activation=act)
 
 
 class ScalarY0(torch.nn.Module):

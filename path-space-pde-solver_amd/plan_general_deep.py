@@ -106,6 +106,17 @@ def value_net_spec(V, d_in):
     return "V's forward is none of the dense-concat formulas the kernels implement (relu^2, tanh^2, tanh)"
 
 
+def neumann_points(img_last, nexec, n_last, XN, tN):
+    """Where the BSDE loss's Neumann residual takes grad_x V (solver.py:1182-1183): [x, t] of every trajectory at the start of
+    the last loop step n_last the reference executed.  A tile that left the time loop before that step (nexec[tile] <= n_last)
+    never wrote slot n_last of the path store; its trajectories have all stopped, and a stopped trajectory keeps its state, so
+    its point is the frozen (X_N, t_N).  img_last: (K, d + 1) decoded slot n_last; nexec: (ceil(K / 16),) loop steps per tile;
+    XN: (K, d); tN: (K,).  Returns (K, d + 1); the unread slots never enter the result, not even as a NaN."""
+    K = img_last.shape[0]
+    left = (nexec.to(torch.int64) <= n_last).repeat_interleave(16)[:K].unsqueeze(1)
+    return torch.where(left, torch.cat([XN, tN.reshape(-1, 1)], 1), img_last)
+
+
 def deep_eligibility(solver):
     """None if the value net is one the genl kernels take, else a reason."""
     d_in = solver.d + (0 if solver.elliptic else 1)
@@ -206,6 +217,12 @@ class GeneralDeepPlan(GeneralNativePlan):
         """Loop steps every tile of this rank executed (int32 view of the tail of `ahat`, include/psp.h)."""
         nt = (self.K_local + 15) // 16
         return self.ahat[(self.s.N + 1) * nt * 16:(self.s.N + 1) * nt * 16 + nt].view(torch.int32)
+
+    def _last_step_points(self, n_last):
+        """As GeneralNativePlan's, but the genl forward leaves the time loop per tile: tiles that stopped early give X_N, t_N."""
+        d_in = self.dims[0]
+        img = super()._last_step_points(n_last)[:, :d_in]
+        return neumann_points(img, self._tile_steps(), n_last, self.XN, self.tN)
 
     def _loop_steps(self, t0):
         """The kernels count the executed steps of every tile themselves: the loop of the reference runs as long as the

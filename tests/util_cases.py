@@ -66,7 +66,8 @@ def flat_params(module):
 
 def general_oracle_run(case, L=None, trace=False):
     """Oracle run of a GeneralSolver / EllipticSolver golden case (families 'general', 'general_bounded', 'elliptic'): every
-    solver switch of the case and its value net (kind 'densenet' | 'user_tanh2' | 'densenet_tanh').  Returns (problem, out)."""
+    solver switch of the case and its value net (kind 'densenet' | 'user_tanh2' | 'densenet_tanh' |
+    'densenet_concat_tanh').  Returns (problem, out)."""
     import numpy as np
     kw = dict(case["problem"]["kwargs"])
     kw.update(case["problem"].get("attrs", {}))          # attributes set on the instance -> oracle keywords
@@ -93,5 +94,7 @@ def make_pkg_value_net(net, d_in, lr, device):
     kind = net.get("kind", "densenet")
     if kind == "densenet_tanh":
         return psp.DenseNet_tanh(d_in=d_in, d_out=1, lr=lr, arch=net["arch"], seed=net["seed"]).to(device)
+    if kind == "densenet_concat_tanh":
+        return psp.DenseNet(d_in=d_in, d_out=1, lr=lr, arch=net["arch"], seed=net["seed"], activation="tanh").to(device)
     cls = psp.DenseNet_tanh_2 if kind == "user_tanh2" else psp.DenseNet
     return cls(d_in=d_in, d_out=1, lr=lr, arch=net["arch"], seed=net["seed"]).to(device)
