@@ -46,7 +46,9 @@ extern "C" {
                          *        the range guard; psp_hjb_sizes.fwd_coop_tiles (the former `reserved`); the on-device noise is
                          *        Philox4x32-7 (psp_philox_normal_fill and every rollout kernel: 10 rounds before);
                          *        later in 0.4.0 (appended, no version bump): psp_dnet_config.ul2_* -- the u_L2 log of the
-                         *        DenseNet-control forward for reference controls that depend on x (PSP_UL2_LINEAR / PSP_UL2_GRID) */
+                         *        DenseNet-control forward for reference controls that depend on x (PSP_UL2_LINEAR / PSP_UL2_GRID);
+                         *        psp_is_config / psp_is_rollout / psp_is_query / psp_abi_struct_sizes3 -- the reference-control and
+                         *        uncontrolled importance-sampling rollout (PSP_ISC_*) */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
@@ -551,6 +553,61 @@ int psp_dnet_adjoint_sweep(const psp_dnet_config* cfg, const float* params, floa
  * step, cuts the real rows / columns out and -- with time_input -- forms the time rows as sum_n t_n * (bias gradient of step n). */
 int psp_dnet_rollout_bwd(const psp_dnet_config* cfg, const float* params, const float* images, const float* w,
                          float* partial, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Importance-sampling evaluation under the problem's REFERENCE control u* or under no control (utilities.do_importance_sampling_me,
+ * reference utilities.py:287-359, with control='true' and simulate_naive=True; csrc/hjbe_kernels.h).  Forward only, one lane per
+ * trajectory, no net.  Per step n (t_n = n dt), from X_0 = x0:
+ *     u      = u*(X_n, t_n)            (kind PSP_ISC_NONE: u = 0, the naive estimator)
+ *     X_n+1  = X_n + (b(X_n) + sigma u) dt + sigma xi_n+1 sqrt(dt)
+ *     logw  += -f(X_n+1) dt - u.xi_n+1 sqrt(dt) - |u|^2 dt / 2
+ * and at the end logw -= g(X_N).  fp32, every sum sequential in n; the elementwise drift and sigma kinds round the update op by op
+ * as the reference's torch ops do (no fma contraction).  Coefficient kinds and pointers as in psp_hjb_config (d-sized, unpadded).
+ * The u* fields mirror psp_dnet_config.ul2_*; the kinds:
+ *   PSP_ISC_TABLE : u_ref = (N, d) table of u*(t_n), independent of x (LLGC)
+ *   PSP_ISC_LINEAR: u_ref = (N, d, d) row-major gains M_n, u* = M_n x (LQGC)
+ *   PSP_ISC_GRID  : u_ref = (u_ntables, u_nrows, u_ncols) tables, u*_i = table_{u_group[i]}[u_row[n], cell(x_i)] with the index
+ *                   arithmetic of psp_dnet_config.ul2_kind = PSP_UL2_GRID (the last GLOBAL trajectory, k_offset + k = K_global - 1,
+ *                   lowered by two); u_row must hold rows < u_nrows for every step (the kernel clamps)
+ * ------------------------------------------------------------------------------------------------ */
+enum { PSP_ISC_NONE = 0, PSP_ISC_TABLE = 1, PSP_ISC_LINEAR = 2, PSP_ISC_GRID = 3 };
+
+typedef struct psp_is_config {
+    int32_t d;            /* state dimension, 1 <= d <= 64 (the compiled buckets 1, 4, 16, 32, 64)                          */
+    int32_t K_local;      /* trajectories of this call                                                                        */
+    int32_t N;            /* time steps, ceil(T / delta_t) (utilities.py:299)                                                 */
+    int32_t control_kind; /* PSP_ISC_*                                                                                        */
+    int64_t K_global;     /* trajectories over all calls (the GRID kind's last trajectory)                                    */
+    int64_t k_offset;     /* global index of local trajectory 0 (Philox counter, last trajectory)                             */
+    float dt, sqrt_dt;    /* fp32 step and fp32(sqrt(delta_t))                                                                */
+    int32_t drift_kind, sigma_kind, runcost_kind, term_kind;
+    int32_t noise_mode;   /* PSP_NOISE_SUPPLIED: xi (N+1, K_local, d), slice n+1 drives step n; PSP_NOISE_PHILOX: the counters of
+                           * psp_hjb_rollout_eval (the same (seed, iter) draws the same increments)                            */
+    int32_t dwell_form;   /* PSP_DRIFT_DOUBLE_WELL rounding: 0 = -(4 kappa_i) (x (x^2 - 1)) (DoubleWell_multidim),
+                           * 1 = -((4 kappa) x) (x^2 - 1) (DoubleWell)                                                        */
+    float sigma_scale;    /* PSP_SIGMA_SCALED_IDENTITY                                                                        */
+    int32_t reserved;
+    const float* x0;      /* (d) initial state                                                                                */
+    const float* drift;
+    const float* sigma;
+    const float* runcost;
+    const float* term;
+    const float* u_ref;   /* the kind's u* data (above); NULL for PSP_ISC_NONE                                                */
+    const int32_t* u_group; /* PSP_ISC_GRID: (d) table of every coordinate, in [0, u_ntables)                                 */
+    const int32_t* u_row;   /* PSP_ISC_GRID: (N) table row of step n, ceil(t_n / dt_ref) formed on the host                   */
+    int32_t u_ntables, u_nrows, u_ncols;
+    float u_xb, u_dx, u_xhi; /* PSP_ISC_GRID: as psp_dnet_config.ul2_xb / ul2_dx / ul2_xhi                                    */
+} psp_is_config;
+
+/* logw_out: (K_local) per-trajectory log-weight -int f dt - g(X_N) - int u.dW - 0.5 int |u|^2 dt (the last two terms are zero for
+ * PSP_ISC_NONE); XN_out: optional (K_local, d) final states.  -1 invalid argument, -2 d outside the native range, -3 u* tables that
+ * do not fit the LDS. */
+int psp_is_rollout(const psp_is_config* cfg, const float* xi, uint64_t seed, uint32_t iter, float* logw_out, float* XN_out,
+                   void* stream);
+/* Every check psp_is_rollout makes of the config, without a launch (no GPU needed); *lds_bytes = the workgroup's LDS. */
+int psp_is_query(const psp_is_config* cfg, int32_t* lds_bytes);
+/* sizeof(psp_is_config) (added in 0.4.0). */
+int psp_abi_struct_sizes3(int32_t out[1]);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, trajectories sharded in contiguous blocks, parameters replicated.

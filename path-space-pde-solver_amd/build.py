@@ -90,10 +90,15 @@ def _build(force, jobs, verbose, only):
     # box: d = 100 forward -1.8 %, diffusion iteration -3 %, others unchanged; wide d = 500 backward +30 % from spills -- it keeps
     # the round-3 form).
     NOSLP, CLASSIC = ["-fno-slp-vectorize"], ["-DPSP_SPLIT_CLASSIC=1"]
-    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, ghdr, whdr, dhdr, os.path.join(CSRC, "genl_kernels.h"), inc, idef, gdef, wdef, ddef])]
+    ugrid = os.path.join(CSRC, "ugrid.h")
+    ehdr = os.path.join(CSRC, "hjbe_kernels.h")
+    einst_src = os.path.join(CSRC, "hjbe_instance.hip")
+    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, ghdr, whdr, dhdr, ehdr, ugrid, os.path.join(CSRC, "genl_kernels.h"), inc, idef, gdef, wdef, ddef])]
+    # the reference-control / uncontrolled evaluation rollout (psp_is_rollout): every d bucket and control kind in one unit
+    tasks.append((einst_src, os.path.join(OBJ, "hjbe_inst.o"), NOSLP, [einst_src, ehdr, ugrid, hdr]))
     for d, H in instances("dense_instances.def"):
         tasks.append((dinst_src, os.path.join(OBJ, "dnet_inst_%d_%d.o" % (d, H)),
-                      ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [dinst_src, dhdr, whdr, hdr]))
+                      ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [dinst_src, dhdr, ugrid, whdr, hdr]))
     for d, H in instances():
         tasks.append((inst_src, os.path.join(OBJ, "inst_%d_%d.o" % (d, H)),
                       ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [inst_src, hdr, os.path.join(CSRC, "hjbs_kernels.h"), os.path.join(CSRC, "hjba_kernels.h"),

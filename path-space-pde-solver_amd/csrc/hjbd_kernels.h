@@ -18,6 +18,7 @@
 // (plan_dense_native.py), not by a hand-written kernel.
 #pragma once
 #include "hjbw_kernels.h"
+#include "ugrid.h"
 
 namespace psp {
 
@@ -644,12 +645,7 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const
                         for (int r = 0; r < 4; ++r) {
                             const int f = 16 * b + 4 * r + q;
                             if (f < dr) {
-                                const float xc = fminf(fmaxf(X[b][r], -da.ul2_xb), da.ul2_xhi);
-                                int cell = (int)floorf((xc + da.ul2_xb) / da.ul2_dx);
-                                if (last) cell -= 2;
-                                if (cell < 0) cell += da.ul2_ncols;                         // numpy: a negative index counts from the end
-                                // (bounds: no effect on data the host builder describes -- ul2_reference)
-                                cell = min(max(cell, 0), da.ul2_ncols - 1);
+                                const int cell = ugrid_cell(X[b][r], da.ul2_xb, da.ul2_xhi, da.ul2_dx, last, da.ul2_ncols);
                                 const int grp = min(max(da.ul2_group[f], 0), da.ul2_ntables - 1);
                                 const float e = zneg(b, r) - a.uref[grp * tstride + rowofs + cell];
                                 UL = fmaf(e, e, UL);

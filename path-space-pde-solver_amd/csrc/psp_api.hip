@@ -14,6 +14,7 @@
 #include "hjbw_kernels.h"
 #include "hjbd_kernels.h"
 #include "genl_kernels.h"
+#include "hjbe_kernels.h"
 
 #define X(D_, H_) PSP_DECLARE_DNET_INSTANCE(D_, H_)
 #include "dense_instances.def"
@@ -522,6 +523,85 @@ int psp_abi_struct_sizes2(int32_t out[2]) {
     return 0;
 }
 const char* psp_last_error(void) { return g_err; }
+
+int psp_abi_struct_sizes3(int32_t out[1]) {
+    if (!out) return fail(-1, "null output");
+    out[0] = (int32_t)sizeof(psp_is_config);
+    return 0;
+}
+
+// ---- importance sampling under the reference control u* / no control (hjbe_kernels.h) -----------------------------------------
+namespace {
+// every check of a psp_is_config, the LDS budget included (psp_is_query and psp_is_rollout share it)
+int is_validate(const psp_is_config* c, int* lds_bytes) {
+    if (!c) return fail(-1, "null config");
+    if (c->K_local <= 0 || c->N <= 0 || c->d <= 0) return fail(-1, "non-positive d / K / N");
+    if (c->d > psp::kIsMaxD) {
+        snprintf(g_err, sizeof(g_err), "psp_is_rollout: d = %d is outside the native range d <= %d", c->d, psp::kIsMaxD);
+        return -2;
+    }
+    if (c->control_kind < PSP_ISC_NONE || c->control_kind > PSP_ISC_GRID)
+        return fail(-1, "control_kind out of range (PSP_ISC_NONE, PSP_ISC_TABLE, PSP_ISC_LINEAR, PSP_ISC_GRID)");
+    if (c->drift_kind < 0 || c->drift_kind > 3 || c->sigma_kind < 0 || c->sigma_kind > 2 || c->runcost_kind < 0 ||
+        c->runcost_kind > 1 || c->term_kind < 0 || c->term_kind > 2 || c->noise_mode < 0 || c->noise_mode > 1)
+        return fail(-1, "config enum out of range");
+    if (c->k_offset < 0 || c->K_global < (int64_t)c->K_local + c->k_offset) return fail(-1, "K_global must cover k_offset + K_local");
+    if (!c->x0) return fail(-1, "null x0 in psp_is_config");
+    if (c->drift_kind != PSP_DRIFT_ZERO && !c->drift) return fail(-1, "drift parameters missing");
+    if (c->sigma_kind == PSP_SIGMA_DENSE && !c->sigma) return fail(-1, "sigma matrix missing");
+    if (c->runcost_kind == PSP_RUNCOST_DIAG_QUAD && !c->runcost) return fail(-1, "running-cost vector missing");
+    if (!c->term) return fail(-1, "terminal-cost vector missing");
+    if (c->control_kind != PSP_ISC_NONE && !c->u_ref) return fail(-1, "control kinds TABLE / LINEAR / GRID need u_ref");
+    long long ucells = 0;
+    if (c->control_kind == PSP_ISC_GRID) {
+        if (!c->u_group || !c->u_row) return fail(-1, "control kind PSP_ISC_GRID needs u_group and u_row");
+        if (c->u_ntables <= 0 || c->u_nrows <= 0 || c->u_ncols <= 0) return fail(-1, "u_ntables / u_nrows / u_ncols must be positive");
+        if (!(c->u_dx > 0.f) || !(c->u_xb > 0.f)) return fail(-1, "u_xb / u_dx must be positive");
+        ucells = (long long)c->u_ntables * c->u_ncols;
+    }
+    const char* too_big = "psp_is_rollout: the coefficient tables and the u* data of one step do not fit the 160 KiB LDS";
+    if (ucells > kMaxLds / 4) return fail(-3, too_big);
+    const psp::IsLds L = psp::is_lds_layout(psp::is_bucket(c->d), c->control_kind, c->drift_kind == PSP_DRIFT_DENSE,
+                                            c->sigma_kind == PSP_SIGMA_DENSE, c->u_ntables, c->u_ncols);
+    if ((long long)L.total * 4 > kMaxLds) return fail(-3, too_big);
+    const long long total = L.total;
+    *lds_bytes = (int)(total * 4);
+    return 0;
+}
+}  // namespace
+
+int psp_is_query(const psp_is_config* c, int32_t* lds_bytes) {
+    int bytes = 0;
+    const int rc = is_validate(c, &bytes);
+    if (rc) return rc;
+    if (lds_bytes) *lds_bytes = bytes;
+    return 0;
+}
+
+int psp_is_rollout(const psp_is_config* c, const float* xi, uint64_t seed, uint32_t iter, float* logw_out, float* XN_out,
+                   void* stream) {
+    int lds_bytes = 0;
+    const int rc = is_validate(c, &lds_bytes);
+    if (rc) return rc;
+    if (!logw_out) return fail(-1, "null logw_out passed to psp_is_rollout");
+    if (c->noise_mode == PSP_NOISE_SUPPLIED && !xi) return fail(-1, "supplied-noise mode needs xi");
+    if ((long long)c->N * c->K_local * c->d >= (1LL << 40)) return fail(-1, "N * K_local * d too large");
+    psp::IsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x0 = c->x0; a.xi = xi; a.drift = c->drift; a.sigma = c->sigma; a.runcost = c->runcost; a.term = c->term;
+    a.uref = c->u_ref; a.ugroup = c->u_group; a.urow = c->u_row; a.logw = logw_out; a.XN = XN_out;
+    a.k_offset = c->k_offset; a.K_global = c->K_global;
+    a.d = c->d; a.K_local = c->K_local; a.N = c->N; a.ctrl = c->control_kind;
+    a.drift_kind = c->drift_kind; a.sigma_kind = c->sigma_kind; a.runcost_kind = c->runcost_kind; a.term_kind = c->term_kind;
+    a.noise_mode = c->noise_mode; a.dwell_form = c->dwell_form ? 1 : 0;
+    a.u_ntables = c->u_ntables; a.u_nrows = c->u_nrows; a.u_ncols = c->u_ncols;
+    a.dt = c->dt; a.sqdt = c->sqrt_dt; a.sigma_scale = c->sigma_scale; a.u_xb = c->u_xb; a.u_dx = c->u_dx; a.u_xhi = c->u_xhi;
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.iter = iter;
+    const long long grid = ((long long)c->K_local + psp::kIsThreads - 1) / psp::kIsThreads;
+    hipError_t e = psp::is_rollout_launch(a, (int)grid, lds_bytes, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "hjbe_rollout_kernel launch");
+    return 0;
+}
 
 // ---- DenseNet control (hjbd_kernels.h): time_approx='outer' and DenseNet(d+1 -> d) controls ---------------------
 namespace {

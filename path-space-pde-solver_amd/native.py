@@ -21,6 +21,8 @@ RUNCOST_ZERO, RUNCOST_DIAG_QUAD = 0, 1
 TERM_LINEAR, TERM_DIAG_QUAD, TERM_SHIFTED_QUAD = 0, 1, 2
 LOSS_LOG_VARIANCE, LOSS_MOMENT, LOSS_WEIGHTS, LOSS_REL_ENTROPY = 0, 1, 2, 3
 UL2_TABLE, UL2_LINEAR, UL2_GRID = 0, 1, 2
+ISC_NONE, ISC_TABLE, ISC_LINEAR, ISC_GRID = 0, 1, 2, 3
+IS_MAX_D = 64                     # native range of psp_is_rollout (include/psp.h)
 NOISE_SUPPLIED, NOISE_PHILOX = 0, 1
 GH_ZERO, GH_QUAD, GH_ALLEN_CAHN, GH_EXPBALL_LIN, GH_EXPBALL_SQ, GH_EXPBALL_SIN = 0, 1, 2, 3, 4, 5
 MLP_FP32, MLP_BF16_FWD, MLP_BF16, MLP_F16X3 = 0, 1, 2, 3
@@ -92,6 +94,17 @@ class DnetConfig(C.Structure):
                 ("ul2_xb", C.c_float), ("ul2_dx", C.c_float), ("ul2_xhi", C.c_float), ("ul2_reserved", C.c_int32)]
 
 
+class IsConfig(C.Structure):
+    _fields_ = [("d", C.c_int32), ("K_local", C.c_int32), ("N", C.c_int32), ("control_kind", C.c_int32),
+                ("K_global", C.c_int64), ("k_offset", C.c_int64), ("dt", C.c_float), ("sqrt_dt", C.c_float),
+                ("drift_kind", C.c_int32), ("sigma_kind", C.c_int32), ("runcost_kind", C.c_int32), ("term_kind", C.c_int32),
+                ("noise_mode", C.c_int32), ("dwell_form", C.c_int32), ("sigma_scale", C.c_float), ("reserved", C.c_int32),
+                ("x0", C.c_void_p), ("drift", C.c_void_p), ("sigma", C.c_void_p), ("runcost", C.c_void_p), ("term", C.c_void_p),
+                ("u_ref", C.c_void_p), ("u_group", C.c_void_p), ("u_row", C.c_void_p),
+                ("u_ntables", C.c_int32), ("u_nrows", C.c_int32), ("u_ncols", C.c_int32),
+                ("u_xb", C.c_float), ("u_dx", C.c_float), ("u_xhi", C.c_float)]
+
+
 class DnetSizes(C.Structure):
     _fields_ = [("table_bytes", C.c_int64), ("fwd_partial_bytes", C.c_int64), ("n_params_per_set", C.c_int64),
                 ("fwd_workgroups", C.c_int32), ("reserved", C.c_int32),
@@ -125,6 +138,9 @@ SIGNATURES = {
     "psp_abi_struct_sizes": (C.c_int, [C.POINTER(C.c_int32 * 6)]),
     "psp_abi_struct_sizes2": (C.c_int, [C.POINTER(C.c_int32 * 2)]),
     "psp_last_error": (C.c_char_p, []),
+    "psp_abi_struct_sizes3": (C.c_int, [C.POINTER(C.c_int32 * 1)]),
+    "psp_is_rollout": (C.c_int, [C.POINTER(IsConfig), _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
+    "psp_is_query": (C.c_int, [C.POINTER(IsConfig), C.POINTER(C.c_int32)]),
     "psp_genl_query": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlSizes)]),
     "psp_genl_rollout_fwd": (C.c_int, [C.POINTER(GenlConfig), _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P]),
@@ -208,6 +224,11 @@ def load():
     if list(sizes2) != mine2:
         raise NativeLibraryError("%s was built for other struct layouts (library %s, binding %s): rebuild it"
                                  % (LIB_PATH, list(sizes2), mine2))
+    sizes3 = (C.c_int32 * 1)()
+    lib.psp_abi_struct_sizes3(C.byref(sizes3))
+    if list(sizes3) != [C.sizeof(IsConfig)]:
+        raise NativeLibraryError("%s was built for other struct layouts (library %s, binding %s): rebuild it"
+                                 % (LIB_PATH, list(sizes3), [C.sizeof(IsConfig)]))
     _lib = lib
     return lib
 

@@ -60,7 +60,7 @@ def _stats(logw):
     return mean_IS, variance_IS, float(np.sqrt(variance_IS) / mean_IS)
 
 
-def _is_native(problem, model, K, delta_t):
+def _is_native(problem, model, K, delta_t, logw_only=False):
     dev = model.device
     lib = nat.load()
     N = int(np.ceil(problem.T / delta_t))
@@ -97,12 +97,13 @@ def _is_native(problem, model, K, delta_t):
     cfg.term = nat.ptr(dev_f32(pad.vec(spec['term'][1])))
     flat = torch.cat([p.detach().reshape(-1) for p in model.z_n.flat_layout()]).to(dev).contiguous()
     flat = pad.scatter_params(flat, pad.new_padded_params() if not pad.identity else None)
-    xi = None
+    xi = xi_dev = None
     if not philox:                                   # the reference's draws: N x randn(K, d) (utilities.py:310)
         xi_cpu = torch.zeros(N + 1, K, model.d)
         for n in range(N):
             xi_cpu[n + 1] = torch.randn(K, model.d)
-        xi = pad.last_dim(xi_cpu.to(dev))
+        xi_dev = xi_cpu.to(dev)
+        xi = pad.last_dim(xi_dev)
     tfeat = _time_feature_table(model, N, delta_t).to(dev)
     x0 = dev_f32(pad.vec(torch.as_tensor(problem.X_0, dtype=torch.float32).to(dev)))
     D = torch.empty(K, dtype=torch.float32, device=dev)
@@ -113,6 +114,8 @@ def _is_native(problem, model, K, delta_t):
                                        (int(model.seed) + 7919) & 0xFFFFFFFFFFFFFFFF, model._is_calls,
                                        nat.ptr(tfeat), nat.ptr(D), nat.ptr(Fint), None, nat.ptr(part),
                                        nat.stream_ptr(dev)), 'psp_hjb_rollout_eval')
+    if logw_only:                                    # (log-weights, the unpadded device noise for the uncontrolled rollout)
+        return D - 2.0 * Fint, xi_dev
     return _stats(D - 2.0 * Fint)
 
 
@@ -132,7 +135,7 @@ def _dense_reason(problem, model):
         model.IS_variance_K, model.u_l2_error_flag, model.loss_method, model.detach_forward = saved
 
 
-def _is_dense_native(problem, model, K, delta_t):
+def _is_dense_native(problem, model, K, delta_t, logw_only=False):
     """The controlled forward sweep of utilities.py:296-330 on the DenseNet-control rollout kernel.  The reference
     evaluates Z_n(X, n delta_t) through solver.py:360-362: step index ceil(t / model.delta_t) -> the time feature
     (inner) or the per-step net (outer); here that index selects the time-feature entry or the parameter set."""
@@ -182,12 +185,13 @@ def _is_dense_native(problem, model, K, delta_t):
         flat = sets[0].contiguous()
     sizes = nat.DnetSizes()
     nat.check(lib.psp_dnet_query(C.byref(cfg), C.byref(sizes)), 'psp_dnet_query')
-    xi = None
+    xi = xi_dev = None
     if not philox:                                   # the reference's draws: N x randn(K, d) (utilities.py:310)
         xi_cpu = torch.zeros(N + 1, K, model.d)
         for n in range(N):
             xi_cpu[n + 1] = torch.randn(K, model.d)
-        xi = pad.last_dim(xi_cpu.to(dev))
+        xi_dev = xi_cpu.to(dev)
+        xi = pad.last_dim(xi_dev)
     tfeat = tfeat.to(dev)
     x0 = dev_f32(pad.vec(torch.as_tensor(problem.X_0, dtype=torch.float32).to(dev)))
     D = torch.empty(K, dtype=torch.float32, device=dev)
@@ -199,6 +203,8 @@ def _is_dense_native(problem, model, K, delta_t):
                                        (int(model.seed) + 7919) & 0xFFFFFFFFFFFFFFFF, model._is_calls, nat.ptr(tfeat),
                                        None, None, nat.ptr(D), nat.ptr(Fint), None, None, nat.ptr(part),
                                        nat.ptr(tables), nat.stream_ptr(dev)), 'psp_dnet_rollout_fwd')
+    if logw_only:
+        return D - 2.0 * Fint, xi_dev
     return _stats(D - 2.0 * Fint)
 
 
@@ -224,11 +230,13 @@ def _is_composite(problem, model, K, delta_t):
 
 def do_importance_sampling_me(problem, model, K, control='approx', simulate_naive=False, verbose=False,
                               delta_t=0.01, on_cpu=False, cross_statistics=None):
-    """Returns (mean_IS, variance_IS, rel_error_IS) -- reference utilities.py:287-359 for control='approx'.
-    ``simulate_naive``, ``control='true'`` with a reference solution, ``on_cpu`` and ``cross_statistics``
-    are not built."""
-    if simulate_naive or on_cpu or cross_statistics is not None or (control != 'approx' and model.u_l2_error_flag):
-        raise NotImplementedError('only the controlled estimator with the learned control is built')
+    """Reference utilities.py:287-359.  Returns (mean_IS, variance_IS, rel_error_IS), preceded by the naive estimator's three
+    numbers when ``simulate_naive``.  ``control='true'`` (with model.u_l2_error_flag) evaluates IS under problem.u_true;
+    ``cross_statistics`` adds the counts of final states above it to the verbose lines.  ``on_cpu`` is not built."""
+    if on_cpu:
+        raise NotImplementedError('on_cpu is not built')
+    if simulate_naive or cross_statistics is not None or (control != 'approx' and model.u_l2_error_flag):
+        return _is_estimators(problem, model, K, control, simulate_naive, verbose, delta_t, cross_statistics)
     reason = _native_reason(problem, model, control, simulate_naive)
     if reason is None:
         out = _is_native(problem, model, K, delta_t)
@@ -241,6 +249,234 @@ def do_importance_sampling_me(problem, model, K, control='approx', simulate_naiv
     if verbose:
         print('IS mean: %.4e, IS variance: %.4e, IS RE %.4e' % out)
     return out
+
+
+
+
+# ---- simulate_naive / control='true' / cross_statistics (reference utilities.py:296-337) ----------------------------------------
+def _true_control_reason(problem, model, N, delta_t):
+    """None if psp_is_rollout can evaluate the problem's u* (include/psp.h PSP_ISC_*), else the reason."""
+    try:
+        from .plan_dense_native import ul2_kind, ul2_unsupported
+    except ImportError:
+        from plan_dense_native import ul2_kind, ul2_unsupported
+    if ul2_kind(problem) is None:
+        return 'the problem has no description of u_true the kernel reads (ul2_kind is None)'
+    why = ul2_unsupported(problem, N, delta_t)
+    if why is not None:
+        return why
+    return None                                      # (the LDS budget is psp_is_query's to judge: _is_estimators)
+
+
+def _coeff_reason(problem, model):
+    try:
+        from .problems import coefficients_overridden
+    except ImportError:
+        from problems import coefficients_overridden
+    if getattr(model, 'backend', 'auto') == 'torch':
+        return "backend='torch' requested"
+    if not hasattr(problem, 'native_spec') or problem.native_spec() is None:
+        return 'the problem has no catalogue description of its coefficients (native_spec)'
+    over = coefficients_overridden(problem)
+    if over is not None:
+        return 'problem.%s is not the catalogue implementation' % over
+    if problem.d > nat.IS_MAX_D:
+        return 'd = %d is outside the native range d <= %d of psp_is_rollout' % (problem.d, nat.IS_MAX_D)
+    if model.device.type != 'cuda':
+        return 'the model is not on a GPU'
+    return None
+
+
+def _ref_noise(N, K, d, dev):
+    """The reference's draws: N x randn(K, d) from the CPU generator (utilities.py:310), slice n + 1 drives step n."""
+    xi = torch.zeros(N + 1, K, d)
+    for n in range(N):
+        xi[n + 1] = torch.randn(K, d)
+    return xi.to(dev)
+
+
+def _is_config(problem, model, K, delta_t, kind, philox):
+    """(psp_is_config, the device tensors it points to) for one psp_is_rollout call on the model's device."""
+    try:
+        from .plan_dense_native import ul2_reference
+        from .problems import DoubleWell
+    except ImportError:
+        from plan_dense_native import ul2_reference
+        from problems import DoubleWell
+    dev = model.device
+    d = problem.d
+    N = int(np.ceil(problem.T / delta_t))
+    spec = problem.native_spec()
+    keep = []
+
+    def dev_t(t, dtype=torch.float32):
+        t = torch.as_tensor(t).detach().to(device=dev, dtype=dtype).contiguous()
+        keep.append(t)
+        return t
+
+    cfg = nat.IsConfig()
+    cfg.d, cfg.K_local, cfg.N, cfg.control_kind = d, K, N, kind
+    cfg.K_global, cfg.k_offset = K, 0
+    cfg.dt = float(torch.tensor(delta_t, dtype=torch.float32).item())
+    cfg.sqrt_dt = float(torch.tensor(np.sqrt(delta_t), dtype=torch.float32).item())
+    cfg.drift_kind, cfg.sigma_kind, cfg.sigma_scale = spec['drift'][0], spec['sigma'][0], float(spec['sigma'][2])
+    cfg.runcost_kind, cfg.term_kind = spec['runcost'][0], spec['term'][0]
+    cfg.dwell_form = 1 if isinstance(problem, DoubleWell) else 0        # the two roundings of -grad V (problems.py)
+    cfg.noise_mode = nat.NOISE_PHILOX if philox else nat.NOISE_SUPPLIED
+    cfg.x0 = nat.ptr(dev_t(torch.as_tensor(problem.X_0, dtype=torch.float32).reshape(-1)))
+    cfg.drift = nat.ptr(dev_t(spec['drift'][1])) if spec['drift'][1] is not None else None
+    cfg.sigma = nat.ptr(dev_t(spec['sigma'][1])) if spec['sigma'][1] is not None else None
+    cfg.runcost = nat.ptr(dev_t(spec['runcost'][1])) if spec['runcost'][1] is not None else None
+    cfg.term = nat.ptr(dev_t(spec['term'][1]))
+    if kind != nat.ISC_NONE:
+        ref = ul2_reference(problem, N, delta_t, d, K, 0)
+        if kind == nat.ISC_TABLE:
+            cfg.u_ref = nat.ptr(dev_t(ref['table']))
+        elif kind == nat.ISC_LINEAR:
+            cfg.u_ref = nat.ptr(dev_t(ref['gains']))
+        else:
+            cfg.u_ref = nat.ptr(dev_t(ref['tables']))
+            cfg.u_group = nat.ptr(dev_t(ref['group'], torch.int32))
+            cfg.u_row = nat.ptr(dev_t(ref['row'], torch.int32))
+            cfg.u_ntables, (cfg.u_nrows, cfg.u_ncols) = ref['tables'].shape[0], ref['tables'].shape[1:]
+            cfg.u_xb, cfg.u_dx, cfg.u_xhi = ref['xb'], ref['dx'], ref['xhi']
+    return cfg, keep
+
+
+def _is_query(cfg):
+    """None if psp_is_rollout accepts the config (the LDS budget included), else its reason."""
+    lib = nat.load()
+    if lib.psp_is_query(C.byref(cfg), None) != 0:
+        return nat.last_error()
+    return None
+
+
+def _is_rollout(problem, model, K, cfg, xi, iter_, want_XN):
+    """One psp_is_rollout call: (log-weights (K), X_N (K, d) or None) on the model's device."""
+    dev = model.device
+    lib = nat.load()
+    d = problem.d
+    logw = torch.empty(K, dtype=torch.float32, device=dev)
+    XN = torch.empty(K, d, dtype=torch.float32, device=dev) if want_XN else None
+    nat.check(lib.psp_is_rollout(C.byref(cfg), nat.ptr(xi), (int(model.seed) + 7919) & 0xFFFFFFFFFFFFFFFF, iter_, nat.ptr(logw),
+                                 nat.ptr(XN), nat.stream_ptr(dev)), 'psp_is_rollout')
+    return logw, XN
+
+
+_KIND_OF_UL2 = {nat.UL2_TABLE: nat.ISC_TABLE, nat.UL2_LINEAR: nat.ISC_LINEAR, nat.UL2_GRID: nat.ISC_GRID}
+
+
+def _is_composite_full(problem, model, K, control, simulate_naive, delta_t):
+    """utilities.py:296-337 restated: the naive and the controlled path on one noise stream, u* on the host for control='true'.
+    Returns (naive weights or None, IS weights, X naive or None, X_u)."""
+    device = model.device
+    sq_delta_t = np.sqrt(delta_t)
+    N = int(np.ceil(problem.T / delta_t))
+    X = problem.X_0.repeat(K, 1).to(device) if simulate_naive else None
+    X_u = problem.X_0.repeat(K, 1).to(device)
+    ito_int = torch.zeros(K).to(device)
+    riemann_int = torch.zeros(K).to(device)
+    f_int = torch.zeros(K).to(model.device)
+    f_int_u = torch.zeros(K).to(model.device)
+    for n in range(N):
+        xi = torch.randn(K, problem.d).to(device)
+        if simulate_naive:
+            X = (X + problem.b(X) * delta_t + torch.mm(problem.sigma(X), xi.t()).t() * sq_delta_t)
+            f_int += model.f(X, n * delta_t) * delta_t
+        if control == 'approx' or model.u_l2_error_flag is False:
+            with torch.no_grad():
+                ut = -model.Z_n(X_u, n * delta_t)
+        elif control == 'true':
+            ut = torch.tensor(problem.u_true(X_u.cpu(), n * delta_t)).t().float().to(device)
+        X_u = (X_u + (problem.b(X_u) + torch.mm(problem.sigma(X_u), ut.t()).t()) * delta_t
+               + torch.mm(problem.sigma(X_u), xi.t()).t() * sq_delta_t)
+        ito_int += torch.sum(ut * xi, 1) * sq_delta_t
+        riemann_int += torch.sum(ut ** 2, 1) * delta_t
+        f_int_u += model.f(X_u, n * delta_t) * delta_t
+    girsanov = torch.exp(- ito_int - 0.5 * riemann_int)
+    w_naive = torch.exp(- f_int - problem.g(X)) if simulate_naive else None
+    return w_naive, torch.exp(- f_int_u - problem.g(X_u)) * girsanov, X, X_u
+
+
+def _weight_stats(w):
+    mean = torch.mean(w).item()
+    var = torch.var(w).item()
+    return mean, var, np.sqrt(var) / mean
+
+
+def _learned_kernel(problem, model, control):
+    """The evaluation kernel of today's path for a learned control (_is_native / _is_dense_native), or a reason."""
+    reason = _native_reason(problem, model, control, False)
+    if reason is None:
+        return _is_native
+    if _dense_reason(problem, model) is None:
+        return _is_dense_native
+    return reason
+
+
+def _full_reason(problem, model, K, control, simulate_naive, delta_t, cross):
+    """None if _is_estimators runs natively (psp_is_rollout, next to today's evaluation kernel for a learned control), else the
+    reason."""
+    why = _coeff_reason(problem, model)
+    if why is not None:
+        return why
+    if control != 'approx' and model.u_l2_error_flag:
+        return _true_control_reason(problem, model, int(np.ceil(problem.T / delta_t)), delta_t)
+    if cross is not None:
+        return 'cross_statistics with the learned control needs the final states of the controlled evaluation rollout'
+    kernel = _learned_kernel(problem, model, control)
+    return kernel if isinstance(kernel, str) else None
+
+
+def _is_estimators(problem, model, K, control, simulate_naive, verbose, delta_t, cross):
+    """simulate_naive / control='true' / cross_statistics: fully native or fully composite (utilities.py:296-359)."""
+    try:
+        from .plan_dense_native import ul2_kind
+    except ImportError:
+        from plan_dense_native import ul2_kind
+    reason = _full_reason(problem, model, K, control, simulate_naive, delta_t, cross)
+    true_control = control != 'approx' and model.u_l2_error_flag
+    philox = getattr(model, 'noise', 'reference') == 'philox'
+    cfgs = {}
+    if reason is None:                                   # the library's own checks (LDS budget of the u* data) before any draw
+        kinds = ([nat.ISC_NONE] if simulate_naive else []) + ([_KIND_OF_UL2[ul2_kind(problem)]] if true_control else [])
+        for kind in kinds:
+            cfgs[kind] = _is_config(problem, model, K, delta_t, kind, philox)
+            reason = reason or _is_query(cfgs[kind][0])
+    X = X_u = None
+    if reason is None:
+        N = int(np.ceil(problem.T / delta_t))
+        want = cross is not None
+        if true_control:                                               # u* on the device, naive and IS on one noise stream
+            xi = None if philox else _ref_noise(N, K, problem.d, model.device)
+            model._is_calls = getattr(model, '_is_calls', 0) + 1
+            if simulate_naive:
+                lw_naive, X = _is_rollout(problem, model, K, cfgs[nat.ISC_NONE][0], xi, model._is_calls, want)
+            kind = _KIND_OF_UL2[ul2_kind(problem)]
+            lw, X_u = _is_rollout(problem, model, K, cfgs[kind][0], xi, model._is_calls, want)
+        else:                                                          # learned control: IS on today's kernel, unchanged
+            lw, xi = _learned_kernel(problem, model, control)(problem, model, K, delta_t, logw_only=True)   # counts the call
+            lw_naive, _ = _is_rollout(problem, model, K, cfgs[nat.ISC_NONE][0], xi, model._is_calls, False)   # same noise
+        w_naive = torch.exp(lw_naive) if simulate_naive else None
+        w_is = torch.exp(lw)
+    else:
+        if getattr(model, 'backend', 'auto') == 'native':
+            raise NotImplementedError('native IS evaluation unavailable: ' + reason)
+        w_naive, w_is, X, X_u = _is_composite_full(problem, model, K, control, simulate_naive, delta_t)
+    naive = _weight_stats(w_naive) if simulate_naive else None
+    out = _weight_stats(w_is)
+    if verbose is True:
+        string = ''
+        if simulate_naive:
+            string += 'naive mean: %.4e, naive variance: %.4e, naive RE %.4e' % naive
+            if cross is not None:
+                string += ', crossed: %d/%d' % (torch.sum(X > torch.as_tensor(cross).to(X.device)), X.shape[0])
+            string += '\n'
+        string += 'IS mean: %.4e, IS variance: %.4e, IS RE %.4e' % out
+        if cross is not None:
+            string += ', crossed: %d/%d' % (torch.sum(X_u > torch.as_tensor(cross).to(X_u.device)), X_u.shape[0])
+        print(string)
+    return (naive + out) if simulate_naive else out
 
 
 def compute_test_error(model, problem, K, device=None, modus='elliptic'):
