@@ -48,7 +48,9 @@ extern "C" {
                          *        later in 0.4.0 (appended, no version bump): psp_dnet_config.ul2_* -- the u_L2 log of the
                          *        DenseNet-control forward for reference controls that depend on x (PSP_UL2_LINEAR / PSP_UL2_GRID);
                          *        psp_is_config / psp_is_rollout / psp_is_query / psp_abi_struct_sizes3 -- the reference-control and
-                         *        uncontrolled importance-sampling rollout (PSP_ISC_*) */
+                         *        uncontrolled importance-sampling rollout (PSP_ISC_*);
+                         *        psp_genl_config.sigma_kind / sigma -- a dense constant diffusion matrix in the run-time-shaped
+                         *        value-net kernels (PSP_GENL_SIGMA_*), and PSP_GH_EXPBALL_SIN_FULL */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
@@ -315,9 +317,10 @@ int psp_hjb_control_eval(int32_t d, int32_t H, const float* params, const float*
 /* nonlinearity h(t,x,y,z): problems.py:1755 (0), :519 (-|z|^2/2), :1204 (y - y^3), and the exponential-on-the-ball
  * family  h = -2 al y (2 al |x|^2 + d) - e y + nl,  nl = 0 (LIN: problems.py:985, :1130 with e = 1),
  * E - y^2 (SQ: :1022), sin(E - y^2) (SIN: :1058, :1166 with e = 1 and the time term), E = exp(2 al |x|^2 + 2 tau t_n);
- * h_par = {al, d, e, tau} */
+ * h_par = {al, d, e, tau}.  SIN_FULL (:1094, the full-Hessian problem; psp_genl_* only): SIN with (sum_i x_i)^2 = sum_ij x_i x_j
+ * in place of |x|^2 in the linear term, |x|^2 kept in E */
 enum { PSP_GH_ZERO = 0, PSP_GH_QUAD = 1, PSP_GH_ALLEN_CAHN = 2, PSP_GH_EXPBALL_LIN = 3, PSP_GH_EXPBALL_SQ = 4,
-       PSP_GH_EXPBALL_SIN = 5 };
+       PSP_GH_EXPBALL_SIN = 5, PSP_GH_EXPBALL_SIN_FULL = 6 };
 /* exit test of a bounded domain: a trajectory stays active while (solver.py:1119-1129; EllipticSolver :758-767)
  *   SPHERE        |X_n| < dom_a               (the state BEFORE the move, as the reference tests it)
  *   BOX           dom_a <= X_proposal <= dom_b in every coordinate
@@ -406,6 +409,11 @@ int psp_gen_rollout_bwd(const psp_gen_config* cfg, const float* params, const fl
  * step is the one of psp_gen_rollout_fwd (same noise counters, exit tests, h kinds, outputs); a tile whose trajectories have
  * all stopped leaves the time loop early (solver.py:1093-1097 / :742-744) and the backward pass skips what it did not execute.
  */
+/* diffusion matrix of psp_genl_config: s I from base.sigma_scale (what a zero-initialised struct means), or a dense constant
+ * B (problems.py:1072: sqrt(2 / d) ones(d, d)).  Dense: per step Z = B^T grad_x V, X += (b dt + B (xi sqrt(dt) + c dt)) alive,
+ * and the stored tangent direction is B u^ -- two d x d fp32-MFMA products per step (three with PSP_GH_QUAD) from tables of B
+ * and B^T built next to the weight tables; psp_genl_rollout_bwd is the same kernel for both kinds. */
+enum { PSP_GENL_SIGMA_SCALED = 0, PSP_GENL_SIGMA_DENSE = 1 };
 enum { PSP_ACT_RELU2 = 0,   /* h = relu(z)^2   (function_space.py:138)                       */
        PSP_ACT_TANH2 = 1,   /* h = tanh(z)^2   (Committor function.ipynb, DenseNet_tanh_2)    */
        PSP_ACT_TANH = 2 };  /* h = tanh(z)     (function_space.py:157)                        */
@@ -421,12 +429,16 @@ typedef struct psp_genl_config {
                                * index map changes, the kernels keep the time in their last input row                          */
     float time_scale;         /* the net sees time_scale * t (0 = 1): Solver's value-function ansatz feeds the STEP INDEX
                                * n = t / dt as the time (solver.py:336, 439)                                                    */
+    /* appended in 0.4.0 (the fields above keep their offsets) */
+    int32_t sigma_kind;       /* PSP_GENL_SIGMA_SCALED (0): sigma = base.sigma_scale I; PSP_GENL_SIGMA_DENSE: sigma = B           */
+    int32_t reserved;
+    const float* sigma;       /* DENSE: B, DEVICE, d*d row-major fp32 (read by every psp_genl_rollout_fwd call); else NULL       */
 } psp_genl_config;
 /* base.v_steps_out / y_steps_out / per_sample_weights of the embedded psp_gen_config are honoured by psp_genl_rollout_fwd /
  * psp_genl_rollout_bwd exactly as by the psp_gen_* entry points (Solver(approx_method='value_function'), plan_value_native.py) */
 
 typedef struct psp_genl_sizes {
-    int64_t table_bytes;      /* scratch for the operand tables (rebuilt by every forward call)                                 */
+    int64_t table_bytes;      /* scratch for the operand tables (rebuilt by every forward call; a dense sigma adds those of B, B^T) */
     int64_t path_bytes;       /* (N + 1) x ceil(K/16) blocks of x and s u^ images                                               */
     int64_t ahat_bytes;       /* (N + 1) x 16 ceil(K/16) floats, then ceil(K/16) int32: the step count of every tile            */
     int64_t n_params;         /* registration order W_1, b_1, .., W_out, b_out                                                  */
@@ -438,7 +450,8 @@ typedef struct psp_genl_sizes {
     int32_t reserved;
 } psp_genl_sizes;
 
-/* <0: shape outside the limits above, or the activation images exceed 160 KiB. */
+/* <0: shape outside the limits above, the activation images (with a dense sigma: plus its three product images where they
+ * do not fit the dead part of the gradient image) exceed 160 KiB, or PSP_GENL_SIGMA_DENSE without a matrix. */
 int psp_genl_query(const psp_genl_config* cfg, psp_genl_sizes* out);
 /* Forward rollout; arguments as psp_gen_rollout_fwd plus the table scratch.  `ahat` is required (it carries the tiles' step
  * counts behind the coefficients). */

@@ -31,6 +31,18 @@
 //       zbar_i' = abar_h' phi1(r_i),   zbar_i = abar_h phi1(r_i) + abar_h' phi2(r_i) z_i',
 //       abar_{i-1} = abar_a + W_i zbar_i,  abar_{i-1}' = abar_a' + W_i zbar_i';
 //   dW_i = a_{i-1} zbar_i^T + a_{i-1}' zbar_i'^T, db_i = zbar_i, dw = a a_L + w a_L', db = a.
+// Dense constant sigma(x) = B (genl_fwd_kernel<NW, true>; `Nonlinear toy problem - elliptic with full Hessian.ipynb`:
+// B = sqrt(2 / d) ones(d, d)).  With g = grad_x V the step (solver.py:725-774 / :1100-1149) is
+//   Z = B^T g,   w = xi sqrt(dt) + c dt  (c = -Z detached, or 0),   X += (b(X) dt + B w) alive,
+//   Y += ((-h + Z . c) dt + Z . xi sqrt(dt)) act,   u = w (+ dt Z for h = -|z|^2 / 2),   U = act B u.
+// Every parameter dependence of Y_N goes through V: through  Z . (xi sqrt(dt) + c dt) = grad V . B w  (c detached) and, for the
+// quadratic h, through |Z|^2 / 2 = |B^T grad V|^2 / 2, whose derivative is (B Z) . d(grad V).  So dY_N / dtheta is the sum over the
+// active steps of  a^ dV/dtheta + d/dtheta (grad V . U)  with the stored direction U = act B u -- the backward kernel consumes
+// (x, t), U and a^ and nothing else: it is the one of sigma = s I, where U = act s u is the special case B = s I.
+// The two products per step (three with the quadratic h: B w and B u share the table operands) have the shape of the layer
+// products -- A operand = a k-quad-major table of B^T resp. B built by genl_tables_kernel next to the weight tables, B operand =
+// a T-layout LDS image -- and run through genl_gemm1 / genl_gemm1x2; their output blocks are dealt over the tile's waves
+// (block ob -> wave ob mod NW, as in the reverse sweep) and exchanged through the images.
 #pragma once
 #include "gen_kernels.h"
 
@@ -40,6 +52,9 @@ constexpr int GENL_MAXL = 4;        // hidden layers
 constexpr int GENL_MAXDB = 7;       // input blocks (d + 1 <= 112)
 constexpr int GENL_MAXHB = 8;       // hidden blocks per layer (H <= 128)
 enum { GACT_RELU2 = 0, GACT_TANH2 = 1, GACT_TANH = 2 };
+// h of ExponentialOnBallNonlinearSinHessian (problems.py:1094): GH_EXPBALL_SIN with (sum_i x_i)^2 = sum_ij x_i x_j in the linear
+// term, |x|^2 kept in the exponent.  Served by the dense-sigma instances of the forward kernel only.
+constexpr int GH_EXPBALL_SIN_FULL = 6;
 
 // per-NW register-array bounds: hidden blocks per wave (HBsum <= 32; NW = 1 only for HBsum <= 8), concatenation blocks per wave
 // (TB <= 39; NW = 1 only for TB <= 16)
@@ -77,6 +92,10 @@ struct GenlArgs {
     int time_first;                 // 1: the net's input is [t, x] (Solver's value-function ansatz, solver.py:338) -- the kernels keep the
                                     // time in their LAST input row; only the parameter index map differs
     float time_scale;               // the net sees time_scale * t (value-function ansatz: the step index n = t / dt, solver.py:336, 439)
+    // dense constant sigma (appended: every field above keeps its offset)
+    int dense;                      // 1: genl_fwd_kernel<NW, true> runs; the tables of B and B^T are built
+    const float* sigmaB;            // B (d x d row-major); NULL with dense = 1: B = g.sigma_scale I
+    long long tSB, tSBT;            // float offsets of the A-operand tables of B (for B w, B u) and of B^T (for B^T grad V)
 };
 
 // padded feature index -> real index inside the concatenation a (or -1: padding)
@@ -142,6 +161,25 @@ __global__ __launch_bounds__(256) void genl_tables_kernel(const GenlArgs a) {
             const int r = (int)(idx & 3), q = (int)((idx >> 2) & 3), b = (int)(idx >> 4);
             const int f = 16 * b + 4 * r + q;
             T[a.vB[i] + idx] = f < Hi ? P[a.ob[i] + f] : 0.f;
+        }
+    }
+    if (a.dense) {
+        // sigma = B as A-operand tables in the forward layout above, DB0 x DB0 blocks: tSB holds M = B (out = B in), tSBT holds
+        // M = B^T (Z = B^T grad_x V, solver.py:729 / :1104); rows and columns >= d are zero, so the time input, the padding and
+        // dV/dt never enter.  (The value-function ansatz of Solver takes Z = sigma grad Y, solver.py:330: the other table.)
+        const int DBs = a.DB0, KSs = 4 * DBs, d = a.d;
+        for (long long idx = gtid; idx < (long long)DBs * KSs * 64; idx += gn) {
+            const int lane = (int)((idx >> 2) & 63);
+            const long long t = idx >> 8;                           // (mb, ks / 4)
+            const int ks = 4 * (int)(t % (KSs / 4)) + (int)(idx & 3), mb = (int)(t / (KSs / 4));
+            const int ii = lane & 15, q = lane >> 4;
+            const int row = 16 * mb + 4 * (ii & 3) + (ii >> 2), col = 4 * ks + q;
+            const bool in = row < d && col < d;
+            float m = 0.f, mt = 0.f;
+            if (in && a.sigmaB) { m = a.sigmaB[(size_t)row * d + col]; mt = a.sigmaB[(size_t)col * d + row]; }
+            else if (in && row == col) m = mt = a.g.sigma_scale;
+            T[a.tSB + idx] = m;
+            T[a.tSBT + idx] = mt;
         }
     }
     for (long long idx = gtid; idx < (long long)a.TB * 16; idx += gn) {       // output layer over the padded concatenation
@@ -295,6 +333,9 @@ __device__ __forceinline__ void genl_input_gradient(KArgs a, const float* __rest
 
 // LDS: A, G (TB blocks each), 1 KiB per block
 __host__ __device__ inline int genl_fwd_lds_bytes(int TB) { return 2 * TB * 1024; }
+// dense sigma: three more images of DB0 blocks (Z then B u; w; u) behind the input blocks of G.  The hidden blocks of G hold dead
+// scratch once the input gradient is formed; where they are fewer than 3 DB0 the carve grows past G
+__host__ __device__ inline int genl_fwd_lds_bytes_dense(int TB, int DB0) { return (2 * TB > TB + 4 * DB0 ? 2 * TB : TB + 4 * DB0) * 1024; }
 
 // (NW = 4: two workgroups per CU at 256 registers a wave -- the step chain of a tile is bound by the L2 latency of its table
 //  operands and by its barriers, not by the matrix pipe, so two tiles in flight per CU are worth more than eight waves on one
@@ -303,7 +344,9 @@ __host__ __device__ inline int genl_fwd_lds_bytes(int TB) { return 2 * TB * 1024
 //  net -- 29 KB of tables -- it shortened the step chain of a K = 200 batch by 6 % (12.1 -> 11.3 ms: the chain is bound by its
 //  instruction count, not by the L2 latency of the tables) and cost a batch that fills the chip 75 % (72.7 -> 127 ms at K = 65536:
 //  three workgroups per CU instead of twelve, and every workgroup copies the tables).)
-template <int NW>
+// DENSE: sigma = B through the tables tSB / tSBT (header comment); a template parameter, so that the instances of sigma = s I
+// stay the code they were
+template <int NW, bool DENSE = false>
 __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(const GenlArgs ga_) {
     PSP_COND_EXIT(ga_.g);
     const KArgs ga = &ga_;
@@ -311,6 +354,9 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* A = lds;
     float* G = A + ga->TB * 256;
+    float* Zi = G + ga->DB0 * 256;                                   // DENSE: Z = B^T grad_x V, later B u
+    float* Wi = Zi + ga->DB0 * 256;                                  //        w = xi sqrt(dt) + c dt
+    float* Ui = Wi + ga->DB0 * 256;                                  //        u = w + dt Z (quadratic h only)
     const float* __restrict__ T = ga->tables;
     const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -393,6 +439,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             return xi;
         };
         auto z_block = [&](int b) __attribute__((always_inline)) {       // Z = sigma^T grad_x V, sigma = s I (solver.py:1104)
+            if constexpr (DENSE) return img_get(Zi, b, lane);        // (rows >= d of the B^T table are zero)
             const f32x4 gx = img_get(G, b, lane);
             f32x4 Z;
 #pragma unroll
@@ -410,16 +457,60 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             f32x4 drift = 0.f * Z;
             if (a->drift_kind == DRIFT_DWELL) drift = -(4.0f * drift_vec(b) * (X[b] * (X[b] * X[b] - 1.0f)));
             else if (a->drift_kind == DRIFT_DIAG) drift = drift_vec(b) * X[b];
+            if constexpr (DENSE) return (drift * dt + img_get(G, b, lane)) * alivef;      // B w: formed once per step, below
             return (drift * dt + sig * cdt + (sig * sqdt) * xi) * alivef;
         };
-        float rr = 0.f;
+        float S = 0.f, Pz = 0.f;
+        const float* BU = G;                                         // DENSE: the image that holds B u
+        if constexpr (DENSE) {
+            const int KSd = 4 * DB0;
+            const bool quad = a->h_kind == GH_QUAD;
+            for (int ob = wave; ob < DB0; ob += NW) {                // Z = B^T grad_x V
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                genl_gemm1<8>(acc, T + ga->tSBT + (size_t)ob * KSd * 64, KSd, G, lane);
+                img_put(Zi, ob, acc, lane);
+            }
+            tile_sync<NW>();
+#pragma unroll
+            for (int b = 0; b < GENL_MAXDB; ++b)
+                if (b < DB0) {
+                    const f32x4 xi = noise_block(b);
+                    const f32x4 Z = img_get(Zi, b, lane);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { S = fmaf(Z[r], Z[r], S); Pz = fmaf(Z[r], xi[r], Pz); }
+                    const f32x4 cdt = a->adaptive ? (-dt) * Z : 0.f * Z;
+                    const f32x4 w = sqdt * xi + cdt;
+                    if (w0) {
+                        img_put(Wi, b, w, lane);
+                        if (quad) img_put(Ui, b, w + dt * Z, lane);
+                    }
+                }
+            tile_sync<NW>();                                         // (every wave has read Z: its image may take B u)
+            for (int ob = wave; ob < DB0; ob += NW) {                // B w (the move; the boxes test it) and B u (the stored tangent)
+                f32x4 acw = {0.f, 0.f, 0.f, 0.f}, acu = {0.f, 0.f, 0.f, 0.f};
+                if (quad) {
+                    genl_gemm1x2<4>(acw, acu, T + ga->tSB + (size_t)ob * KSd * 64, KSd, Wi, Ui, lane);
+                    img_put(Zi, ob, acu, lane);
+                } else {
+                    genl_gemm1<8>(acw, T + ga->tSB + (size_t)ob * KSd * 64, KSd, Wi, lane);
+                }
+                img_put(G, ob, acw, lane);
+            }
+            tile_sync<NW>();
+            if (quad) BU = Zi;
+        }
+        float rr = 0.f, sx = 0.f;
         if (a->domain_kind == DOM_SPHERE || a->domain_kind == DOM_ANNULUS || a->h_kind >= GH_EXPBALL_LIN) {
 #pragma unroll
             for (int b = 0; b < GENL_MAXDB; ++b)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (b < DB0 && (16 * b + 4 * r + qv) < D) rr = fmaf(X[b][r], X[b][r], rr);
+                    if (b < DB0 && (16 * b + 4 * r + qv) < D) {
+                        rr = fmaf(X[b][r], X[b][r], rr);
+                        if constexpr (DENSE) sx += X[b][r];
+                    }
             rr = qsum(rr);
+            if constexpr (DENSE) sx = qsum(sx);
         }
         bool inside = true;
         if (a->domain_kind == DOM_SPHERE) {
@@ -432,8 +523,9 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
 #pragma unroll
             for (int b = 0; b < GENL_MAXDB; ++b)
                 if (b < DB0) {
-                    const f32x4 xi = noise_block(b);
-                    const f32x4 Xp = X[b] + move_block(b, z_block(b), xi);
+                    f32x4 xi = {0.f, 0.f, 0.f, 0.f}, Zb = xi;
+                    if constexpr (!DENSE) { xi = noise_block(b); Zb = z_block(b); }
+                    const f32x4 Xp = X[b] + move_block(b, Zb, xi);
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if ((16 * b + 4 * r + qv) < D) {
@@ -448,20 +540,25 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
         const bool in_time = inside && (t + dt) <= Tend;             // new_selection (:1119-1131), fp32
         const bool act = in_time && !stopped;
         const float actf = act ? 1.f : 0.f;
-        float S = 0.f, Pz = 0.f;
         float* pblk = a->path + ((size_t)n * a->ntile16 + t16) * PBL + lane;
 #pragma unroll
         for (int b = 0; b < GENL_MAXDB; ++b)
             if (b < DB0) {
-                const f32x4 xi = noise_block(b);
-                const f32x4 Z = z_block(b);
+                f32x4 U, step;
+                if constexpr (DENSE) {
+                    U = actf * img_get(BU, b, lane);                 // act B u
+                    step = move_block(b, U, U);                      // (reads B w from its image)
+                } else {
+                    const f32x4 xi = noise_block(b);
+                    const f32x4 Z = z_block(b);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { S = fmaf(Z[r], Z[r], S); Pz = fmaf(Z[r], xi[r], Pz); }
-                const f32x4 cdt = a->adaptive ? (-dt) * Z : 0.f * Z;
-                f32x4 u = sqdt * xi + cdt;                           // u^ = act ((-h_z + c) dt + xi sqrt(dt)), -h_z = Z for h = -|z|^2 / 2
-                if (a->h_kind == GH_QUAD) u += dt * Z;
-                const f32x4 U = (actf * sig) * u;
-                const f32x4 step = move_block(b, Z, xi);
+                    for (int r = 0; r < 4; ++r) { S = fmaf(Z[r], Z[r], S); Pz = fmaf(Z[r], xi[r], Pz); }
+                    const f32x4 cdt = a->adaptive ? (-dt) * Z : 0.f * Z;
+                    f32x4 u = sqdt * xi + cdt;                       // u^ = act ((-h_z + c) dt + xi sqrt(dt)), -h_z = Z for h = -|z|^2 / 2
+                    if (a->h_kind == GH_QUAD) u += dt * Z;
+                    U = (actf * sig) * u;
+                    step = move_block(b, Z, xi);
+                }
                 if (a->store_path && w0) {                            // the sample point is the state BEFORE the move
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -481,7 +578,9 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
         else if (a->h_kind == GH_ALLEN_CAHN) { minus_h = -(Vnow - Vnow * Vnow * Vnow); hy = 1.0f - 3.0f * Vnow * Vnow; }
         else if (a->h_kind >= GH_EXPBALL_LIN) {
             const float al = a->h_par[0];
-            const float lin = 2.0f * al * (2.0f * al * rr + a->h_par[1]) + a->h_par[2];
+            float rl = rr;                                           // |x|^2, or (sum x)^2 for the full-Hessian problem
+            if constexpr (DENSE) { if (a->h_kind == GH_EXPBALL_SIN_FULL) rl = sx * sx; }
+            const float lin = 2.0f * al * (2.0f * al * rl + a->h_par[1]) + a->h_par[2];
             float nl = 0.f, nly = 0.f;
             if (a->h_kind != GH_EXPBALL_LIN) {
                 const float arg = expf(2.0f * al * rr + 2.0f * a->h_par[3] * ((float)n * dt)) - Vnow * Vnow;
@@ -729,10 +828,10 @@ __global__ __launch_bounds__(64 * NW) void genl_bwd_kernel(const GenlArgs ga_) {
 }
 
 // host side: launches (the dynamic LDS size exceeds the 64 KiB default)
-template <int NW> inline hipError_t genl_launch_fwd(const GenlArgs& a, int ntile16, int lds_bytes, hipStream_t st) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+template <int NW, bool DENSE = false> inline hipError_t genl_launch_fwd(const GenlArgs& a, int ntile16, int lds_bytes, hipStream_t st) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW, DENSE>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((genl_fwd_kernel<NW>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
+    hipLaunchKernelGGL((genl_fwd_kernel<NW, DENSE>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
     return hipGetLastError();
 }
 template <int NW, int MS = GenlGeo<NW>::MAXSLOT> inline hipError_t genl_launch_bwd(const GenlArgs& a, int grid, int groups, int lds_bytes, hipStream_t st) {

@@ -1232,8 +1232,10 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p) {
     const int D0 = b.d + (c->has_time ? 1 : 0);
     if (D0 > 16 * psp::GENL_MAXDB) return fail(-2, "value net: input width above 112");
     if ((b.drift_kind != PSP_DRIFT_ZERO && b.drift_kind != PSP_DRIFT_DOUBLE_WELL && b.drift_kind != PSP_DRIFT_DIAG) || b.h_kind < 0 ||
-        b.h_kind > PSP_GH_EXPBALL_SIN || b.noise_mode < 0 || b.noise_mode > 1 || b.domain_kind < 0 || b.domain_kind > PSP_DOM_ANNULUS)
+        b.h_kind > PSP_GH_EXPBALL_SIN_FULL || b.noise_mode < 0 || b.noise_mode > 1 || b.domain_kind < 0 || b.domain_kind > PSP_DOM_ANNULUS ||
+        c->sigma_kind < PSP_GENL_SIGMA_SCALED || c->sigma_kind > PSP_GENL_SIGMA_DENSE)
         return fail(-1, "config enum out of range");
+    if (c->sigma_kind == PSP_GENL_SIGMA_DENSE && !c->sigma) return fail(-1, "sigma matrix missing");
     if (c->activation < 0 || c->activation > PSP_ACT_TANH) return fail(-1, "value net: unknown activation");
     if (b.domain_kind == PSP_DOM_SPHERE && !(b.dom_a > 0.f)) return fail(-1, "sphere radius must be positive");
     if (b.domain_kind == PSP_DOM_BOX && !(b.dom_a < b.dom_b)) return fail(-1, "box bounds must satisfy X_l < X_r");
@@ -1270,6 +1272,15 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p) {
     tiles += blocks;                                                            // the output layer as a layer of one unit
     a.n_tiles = tiles;
     a.vW = tofs; tofs += (long long)blocks * 16;
+    // a dense sigma -- or the h of the full-Hessian problem, whose (sum x)^2 only the dense-sigma instances of the forward kernel
+    // form (with a scaled identity the tables kernel writes s I) -- adds the tables of B and B^T
+    a.dense = (c->sigma_kind == PSP_GENL_SIGMA_DENSE || b.h_kind == PSP_GH_EXPBALL_SIN_FULL) ? 1 : 0;
+    a.sigmaB = c->sigma_kind == PSP_GENL_SIGMA_DENSE ? c->sigma : nullptr;
+    if (a.dense) {
+        tofs = (tofs + 3) & ~3LL;                                                // (16-byte table loads)
+        a.tSB = tofs; tofs += (long long)a.DB0 * 4 * a.DB0 * 64;
+        a.tSBT = tofs; tofs += (long long)a.DB0 * 4 * a.DB0 * 64;
+    }
     p->table_floats = tofs; p->n_params = pofs;
     p->ntile16 = (b.K_local + 15) / 16;
     // waves per tile: one (no barriers, many tiles per CU) for small nets -- always for the smallest, for the others once the
@@ -1284,7 +1295,7 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p) {
     if (nw == 8 && p->ntile16 >= 2 * cus) p->nw_fwd = 4;                        // two tiles per CU in flight (genl_kernels.h)
     if (force && force[0] == '4' && nw == 8) p->nw_fwd = 4;
     if (force && force[0] == '8') p->nw_fwd = 8;
-    p->fwd_lds = psp::genl_fwd_lds_bytes(a.TB); p->bwd_lds = psp::genl_bwd_lds_bytes(a.TB, a.DB0, p->nw_bwd);
+    p->fwd_lds = a.dense ? psp::genl_fwd_lds_bytes_dense(a.TB, a.DB0) : psp::genl_fwd_lds_bytes(a.TB); p->bwd_lds = psp::genl_bwd_lds_bytes(a.TB, a.DB0, p->nw_bwd);
     a.table_floats = tofs;
     if (p->fwd_lds > kMaxLds || p->bwd_lds > kMaxLds)
         return fail(-3, "value net: the activation images exceed the 160 KiB LDS (sum of the padded widths too large)");
@@ -1356,6 +1367,10 @@ int psp_genl_rollout_fwd(const psp_genl_config* cfg, const float* params, const 
     hipLaunchKernelGGL(psp::genl_tables_kernel, dim3(128), dim3(256), 0, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "genl_tables_kernel launch");
+    if (p.a.dense)
+        e = p.nw_fwd == 1 ? psp::genl_launch_fwd<1, true>(p.a, p.ntile16, p.fwd_lds, st)
+            : p.nw_fwd == 4 ? psp::genl_launch_fwd<4, true>(p.a, p.ntile16, p.fwd_lds, st) : psp::genl_launch_fwd<8, true>(p.a, p.ntile16, p.fwd_lds, st);
+    else
     e = p.nw_fwd == 1 ? psp::genl_launch_fwd<1>(p.a, p.ntile16, p.fwd_lds, st)
         : p.nw_fwd == 4 ? psp::genl_launch_fwd<4>(p.a, p.ntile16, p.fwd_lds, st) : psp::genl_launch_fwd<8>(p.a, p.ntile16, p.fwd_lds, st);
     if (e != hipSuccess) return fail_hip(e, "genl_fwd_kernel launch");

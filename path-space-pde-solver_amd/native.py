@@ -24,7 +24,8 @@ UL2_TABLE, UL2_LINEAR, UL2_GRID = 0, 1, 2
 ISC_NONE, ISC_TABLE, ISC_LINEAR, ISC_GRID = 0, 1, 2, 3
 IS_MAX_D = 64                     # native range of psp_is_rollout (include/psp.h)
 NOISE_SUPPLIED, NOISE_PHILOX = 0, 1
-GH_ZERO, GH_QUAD, GH_ALLEN_CAHN, GH_EXPBALL_LIN, GH_EXPBALL_SQ, GH_EXPBALL_SIN = 0, 1, 2, 3, 4, 5
+GH_ZERO, GH_QUAD, GH_ALLEN_CAHN, GH_EXPBALL_LIN, GH_EXPBALL_SQ, GH_EXPBALL_SIN, GH_EXPBALL_SIN_FULL = 0, 1, 2, 3, 4, 5, 6
+GENL_SIGMA_SCALED, GENL_SIGMA_DENSE = 0, 1      # psp_genl_config.sigma_kind
 MLP_FP32, MLP_BF16_FWD, MLP_BF16, MLP_F16X3 = 0, 1, 2, 3
 DT_F32, DT_F64 = 0, 1
 COMM_ID_BYTES = 128
@@ -122,7 +123,9 @@ class GenSizes(C.Structure):
 
 class GenlConfig(C.Structure):
     _fields_ = [("base", GenConfig), ("has_time", C.c_int32), ("n_hidden", C.c_int32), ("widths", C.c_int32 * 4),
-                ("activation", C.c_int32), ("linear_layout", C.c_int32), ("time_first", C.c_int32), ("time_scale", C.c_float)]
+                ("activation", C.c_int32), ("linear_layout", C.c_int32), ("time_first", C.c_int32), ("time_scale", C.c_float),
+                # appended: a dense constant diffusion matrix (0: base.sigma_scale * I; 1: `sigma`, device, d*d row-major)
+                ("sigma_kind", C.c_int32), ("reserved", C.c_int32), ("sigma", C.c_void_p)]
 
 
 class GenlSizes(C.Structure):

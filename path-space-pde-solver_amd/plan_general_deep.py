@@ -25,12 +25,12 @@ try:
     from . import native as nat
     from . import sharding
     from .function_space import DenseNet, DenseNet_tanh
-    from .plan_general_native import GeneralNativePlan, set_domain
+    from .plan_general_native import GeneralNativePlan, set_domain, set_sigma
 except ImportError:
     import native as nat
     import sharding
     from function_space import DenseNet, DenseNet_tanh
-    from plan_general_native import GeneralNativePlan, set_domain
+    from plan_general_native import GeneralNativePlan, set_domain, set_sigma
 
 _ACT = {'relu2': nat.ACT_RELU2, 'tanh2': nat.ACT_TANH2, 'tanh': nat.ACT_TANH}
 
@@ -171,7 +171,7 @@ class GeneralDeepPlan(GeneralNativePlan):
         cfg.d_real = s.d
         for i, v in enumerate(spec.get('h_par', ())):
             cfg.h_par[i] = float(v)
-        cfg.sigma_scale = float(spec['sigma_scale'])
+        set_sigma(gcfg, spec, self.dev, self._keep)
         cfg.drift_kind, cfg.h_kind = spec['drift'][0], spec['h']
         cfg.adaptive = 1 if s.adaptive_forward_process else 0
         cfg.noise_mode = nat.NOISE_PHILOX if s.noise == 'philox' else nat.NOISE_SUPPLIED

@@ -66,6 +66,8 @@ def native_eligibility(solver, deep=False):
     over = coefficients_overridden(solver.problem)
     if over is not None:
         return 'problem.%s is not the catalogue implementation general_native_spec() describes' % over
+    if not deep and spec_fn().get('sigma') is not None:
+        return 'a dense sigma runs on the run-time-shaped kernels (csrc/genl_kernels.h), whatever the net'
     if not nat.is_built():
         raise nat.NativeLibraryError('libpsp_hip.so is not built; run __graft_entry__.build()')
     if not deep and not shapes.gen_candidates(solver.d, dims[1]):
@@ -85,6 +87,25 @@ def set_domain(cfg, pb, elliptic):
             (nat.DOM_BOX_UPPER_ALL if elliptic else nat.DOM_BOX_UPPER_ANY)
     elif pb.boundary == 'square-corner':                          # solver.py:759-760: any(X_proposal <= X_r)
         cfg.domain_kind, cfg.dom_a, cfg.dom_b = nat.DOM_BOX_UPPER_ANY, float(pb.X_l), float(pb.X_r)
+
+
+def set_sigma(gcfg, spec, device, keep):
+    """psp_genl_config.sigma_kind / sigma / base.sigma_scale from a problem's ``general_native_spec()``: a spec that carries a
+    ``'sigma'`` matrix (d x d, constant) goes dense -- B is uploaded row-major in fp32 and kept alive in ``keep`` --, any other
+    names its scaled identity by ``'sigma_scale'``."""
+    B = spec.get('sigma')
+    if B is None:
+        gcfg.sigma_kind, gcfg.sigma = nat.GENL_SIGMA_SCALED, None
+        gcfg.base.sigma_scale = float(spec['sigma_scale'])
+        return
+    d = int(gcfg.base.d)
+    B = torch.as_tensor(B)
+    if tuple(B.shape) != (d, d):
+        raise ValueError('general_native_spec(): sigma must be a (%d, %d) matrix, got %s' % (d, d, tuple(B.shape)))
+    t = B.detach().to(device=device, dtype=torch.float32).contiguous()
+    keep.append(t)
+    gcfg.sigma_kind, gcfg.sigma = nat.GENL_SIGMA_DENSE, nat.ptr(t)
+    gcfg.base.sigma_scale = 0.0
 
 
 class GeneralNativePlan:

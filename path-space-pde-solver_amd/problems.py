@@ -530,13 +530,18 @@ class HeatEquation:
 class _ExpBall:
     """v(x[,t]) = exp(alpha |x|^2 [+ t]) on the unit ball, b = 0, sigma = sqrt(2) I (reference problems.py:962-1172).
     ``_nl`` selects the nonlinearity of h: 'none' | 'sq' | 'sin'; ``_parabolic`` adds the time argument, the extra -y
-    and the 2t in the exponent (ExponentialOnSphereNonlinearParabolic, :1166)."""
-    _nl, _parabolic = 'none', False
+    and the 2t in the exponent (ExponentialOnSphereNonlinearParabolic, :1166); ``_full`` makes the diffusion matrix the
+    dense sqrt(2 / d) ones(d, d) -- a full second-order operator -- and with it the linear part of h carries
+    (sum_i x_i)^2 = sum_ij x_i x_j where the others carry |x|^2 (ExponentialOnBallNonlinearSinHessian, :1067-1100)."""
+    _nl, _parabolic, _full = 'none', False, False
 
     def _setup(self, name, d, alpha, boundary_type, device):
         self.device = _resolve(device)
         self.name, self.d, self.alpha = name, d, alpha
-        self.B = (torch.sqrt(torch.tensor(2.0)) * torch.eye(d)).to(self.device)
+        if self._full:
+            self.B = (torch.sqrt(torch.tensor(2.0) / d) * torch.ones(d, d)).to(self.device)
+        else:
+            self.B = (torch.sqrt(torch.tensor(2.0)) * torch.eye(d)).to(self.device)
         self.X_0 = torch.zeros(d).to(self.device)
         self.Y_0 = torch.zeros(1).to(self.device)
         self.boundary, self.boundary_distance = 'sphere', 1.0
@@ -555,7 +560,7 @@ class _ExpBall:
         al, d = self.alpha, self.d
         if self._nl == 'none':
             return -al * y * (al * 4 * self._r2(x) + 2 * d)
-        lin = -2 * al * y * (al * 2 * self._r2(x) + d)
+        lin = -2 * al * y * (al * 2 * (torch.sum(x, 1) ** 2 if self._full else self._r2(x)) + d)
         if self._parabolic:
             return lin - y + torch.sin(torch.exp(2 * al * self._r2(x) + 2 * t) - y ** 2)
         e = torch.exp(2 * al * self._r2(x))
@@ -567,6 +572,9 @@ class _ExpBall:
     def general_native_spec(self):
         kind = {'none': _nat.GH_EXPBALL_LIN, 'sq': _nat.GH_EXPBALL_SQ, 'sin': _nat.GH_EXPBALL_SIN}[self._nl]
         par = 1.0 if self._parabolic else 0.0
+        if self._full:                                   # a dense constant sigma: the matrix itself (plan_general_native.set_sigma)
+            return {'drift': (_nat.DRIFT_ZERO, None), 'sigma': self.B, 'h': _nat.GH_EXPBALL_SIN_FULL,
+                    'h_par': (float(self.alpha), float(self.d), par, par)}
         return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': float(self.B[0, 0]), 'h': kind,
                 'h_par': (float(self.alpha), float(self.d), par, par)}
 
@@ -605,6 +613,15 @@ class ExponentialOnBallNonlinear(_ExpBallElliptic):
 class ExponentialOnBallNonlinearSin(_ExpBallElliptic):
     """h carries sin(exp(2 alpha |x|^2) - y^2) (reference problems.py:1031-1065)."""
     _nl = 'sin'
+
+    def __init__(self, name='Exponential on ball nonlinear', d=2, alpha=1.0, boundary_type='Dirichlet', device=None):
+        self._setup(name, d, alpha, boundary_type, device)
+
+
+class ExponentialOnBallNonlinearSinHessian(_ExpBallElliptic):
+    """The elliptic problem with a full Hessian (reference problems.py:1067-1100): sigma = sqrt(2 / d) ones(d, d), so the
+    operator is sum_ij d_i d_j v, and h carries sum_ij x_i x_j in its linear part; same solution exp(alpha |x|^2)."""
+    _nl, _full = 'sin', True
 
     def __init__(self, name='Exponential on ball nonlinear', d=2, alpha=1.0, boundary_type='Dirichlet', device=None):
         self._setup(name, d, alpha, boundary_type, device)
@@ -679,13 +696,17 @@ class QuadraticOnBox:
     """NOT a reference class: b = 0, sigma = scale I, h = -|z|^2/2 (or 0) with data |x|^2 on the box [X_l, X_r]^d.
     It exercises the 'square' exit tests of the solvers (reference solver.py:1125-1129, :762-767) with coefficients
     the kernels have; ``parabolic`` selects the GeneralSolver (h(t,x,y,z), f(x), g(x,t)) or the EllipticSolver
-    (h(x,y,z), g(x)) calling convention."""
+    (h(x,y,z), g(x)) calling convention.  ``B`` (optional, d x d) replaces scale I by a dense constant diffusion matrix."""
 
     def __init__(self, name='Quadratic on box', d=2, T=0.5, X_l=-1.0, X_r=1.0, one_boundary=False, scale=1.0,
-                 parabolic=True, quad_h=True, device=None):
+                 parabolic=True, quad_h=True, device=None, B=None):
         self.device = _resolve(device)
         self.name, self.d, self.T = name, d, T
-        self.B = (scale * torch.eye(d)).to(self.device)
+        self.dense_B = B is not None
+        if self.dense_B:
+            self.B = torch.as_tensor(B, dtype=torch.float32).reshape(d, d).clone().to(self.device)
+        else:
+            self.B = (scale * torch.eye(d)).to(self.device)
         self.boundary, self.boundary_type = 'square', 'Dirichlet'
         self.X_l, self.X_r, self.one_boundary = X_l, X_r, one_boundary
         self.parabolic, self.quad_h = parabolic, quad_h
@@ -710,5 +731,7 @@ class QuadraticOnBox:
         return torch.sum(x ** 2, 1)
 
     def general_native_spec(self):
-        return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': float(self.B[0, 0]),
-                'h': _nat.GH_QUAD if self.quad_h else _nat.GH_ZERO}
+        h = _nat.GH_QUAD if self.quad_h else _nat.GH_ZERO
+        if self.dense_B:
+            return {'drift': (_nat.DRIFT_ZERO, None), 'sigma': self.B, 'h': h}
+        return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': float(self.B[0, 0]), 'h': h}
