@@ -50,7 +50,9 @@ extern "C" {
                          *        psp_is_config / psp_is_rollout / psp_is_query / psp_abi_struct_sizes3 -- the reference-control and
                          *        uncontrolled importance-sampling rollout (PSP_ISC_*);
                          *        psp_genl_config.sigma_kind / sigma -- a dense constant diffusion matrix in the run-time-shaped
-                         *        value-net kernels (PSP_GENL_SIGMA_*), and PSP_GH_EXPBALL_SIN_FULL */
+                         *        value-net kernels (PSP_GENL_SIGMA_*), and PSP_GH_EXPBALL_SIN_FULL;
+                         *        psp_hjb_basis_params / psp_hjb_basis_grad -- the per-iteration transforms of a rollout in the
+                         *        sigma basis */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
@@ -621,6 +623,26 @@ int psp_is_rollout(const psp_is_config* cfg, const float* xi, uint64_t seed, uin
 int psp_is_query(const psp_is_config* cfg, int32_t* lds_bytes);
 /* sizeof(psp_is_config) (added in 0.4.0). */
 int psp_abi_struct_sizes3(int32_t out[1]);
+
+/* ------------------------------------------------------------------------------------------------
+ * Rollout in the sigma basis (appended in 0.4.0, no version bump).  For a constant invertible sigma = B a caller may hand the
+ * rollout entry points the equivalent problem in X~ = B^-1 X -- drift B^-1 A B, PSP_SIGMA_IDENTITY, terminal vector B^T alpha,
+ * x0 = B^-1 x0 -- which needs ONE d x d product per step instead of two.  Z, Y, D, h1, h2 and the noise are unchanged; the net
+ * sees W1x X = (W1x B) X~.  Two launches per iteration keep parameters and gradient in the original basis (a few workgroups
+ * each, fp32 fmaf chains in a fixed order, capturable, no host sync); d, H are the kernel instance's (padded) shape, B is (d, d)
+ * row-major, W1 is the first H (d + 1) entries of the flat layout with the time input in column 0 of every row:
+ *   psp_hjb_basis_params : params_out = params with W1[:, 1:] <- W1[:, 1:] B; every other of the n_params entries is copied
+ *                          (params_out == params: in place)
+ *   psp_hjb_basis_grad   : grad's W1[:, 1:] block <- (that block) B^T, in place, after psp_hjb_rollout_bwd and before the
+ *                          gradient all-reduce / psp_adam_step
+ * Between the two, every buffer of the iteration is in the sigma basis: the path store holds X~, and psp_hjb_rollout_bwd leaves
+ * dW~1x, not dW1x.  A caller that takes these buffers from the Python plan (HjbNativePlan: cfg, path store, grad_k) and drives
+ * psp_hjb_rollout_bwd itself must check plan.state_basis and apply psp_hjb_basis_grad when it reads 'sigma'.
+ * -1 invalid argument, -3 B does not fit 64 KiB of LDS (d <= 112 does).
+ * ------------------------------------------------------------------------------------------------ */
+int psp_hjb_basis_params(const float* params, float* params_out, const float* B, int32_t d, int32_t H, int64_t n_params,
+                         void* stream);
+int psp_hjb_basis_grad(float* grad, const float* B, int32_t d, int32_t H, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, trajectories sharded in contiguous blocks, parameters replicated.

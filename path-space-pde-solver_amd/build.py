@@ -93,7 +93,7 @@ def _build(force, jobs, verbose, only):
     ugrid = os.path.join(CSRC, "ugrid.h")
     ehdr = os.path.join(CSRC, "hjbe_kernels.h")
     einst_src = os.path.join(CSRC, "hjbe_instance.hip")
-    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, ghdr, whdr, dhdr, ehdr, ugrid, os.path.join(CSRC, "genl_kernels.h"), inc, idef, gdef, wdef, ddef])]
+    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, os.path.join(CSRC, "hjb_basis_kernels.h"), ghdr, whdr, dhdr, ehdr, ugrid, os.path.join(CSRC, "genl_kernels.h"), inc, idef, gdef, wdef, ddef])]
     # the reference-control / uncontrolled evaluation rollout (psp_is_rollout): every d bucket and control kind in one unit
     tasks.append((einst_src, os.path.join(OBJ, "hjbe_inst.o"), NOSLP, [einst_src, ehdr, ugrid, hdr]))
     for d, H in instances("dense_instances.def"):

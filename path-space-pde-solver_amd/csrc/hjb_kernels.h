@@ -775,12 +775,16 @@ struct Geo {
 // no running cost, store_path 1 or 4, not the relative-entropy loss: the LLGC configuration of every BASELINE config.  The time loop of
 // the general instance tests those wave-uniform switches at run time: ~100 scalar branches per step, each one a basic-block
 // boundary that the scheduler cannot move the path stores, the Philox slices or the operand prefetches across.
+// FAST_ = 3: the FAST_ = 2 instance for IDENTITY sigma -- the problem a plan hands over when it rolls the state out in the sigma
+// basis (X~ = B^-1 X, plan_native.py: drift B^-1 A B, sigma I): the state panel is still split once for W1 x~ and (dt M) x~, the
+// Philox slices stay in the W2 / W3 products, X~_{n+1} = Tn + v is element-wise; no B table is staged, no product of the v panel.
 template <int D, int H, int MODE = 0, int FAST_ = 0>
 __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
     PSP_COND_EXIT(a);
-    constexpr bool FAST = FAST_ != 0, SPEC = FAST_ == 2;
-    // the problem switches: kernel arguments in the general instances, constants in the specialised one
-    const int k_drift = SPEC ? (int)DRIFT_DENSE : a.drift_kind, k_sigma = SPEC ? (int)SIGMA_DENSE : a.sigma_kind;
+    constexpr bool FAST = FAST_ != 0, SPEC = FAST_ >= 2;
+    // the problem switches: kernel arguments in the general instances, constants in the specialised ones
+    const int k_drift = SPEC ? (int)DRIFT_DENSE : a.drift_kind;
+    const int k_sigma = FAST_ == 3 ? (int)SIGMA_IDENT : SPEC ? (int)SIGMA_DENSE : a.sigma_kind;
     const int k_run = SPEC ? (int)RUN_ZERO : a.runcost_kind, k_loss = SPEC ? (int)LOSS_LOGVAR : a.loss_kind;
     const int k_store = a.store_path;                             // (SPEC: 1 or 4 -- the xi image is kept or regenerated; ONE instance for both,
                                                                   //  so that the two modes stay bit-identical: tests/test_gpu_path_noise.py)
@@ -1650,10 +1654,13 @@ struct HjbLaunch {
     }
     // every product fp32-grade on the f16 matrix pipe (gemm_Tx)
     static hipError_t fwd_x3(const HjbArgs& a, int grid, int block, hipStream_t s) {
-        // (the specialised instance: dense drift and sigma, adaptive, no running cost, store_path 1 / 4 -- hjb_fwd_kernel, FAST_ = 2)
-        const bool spec = spec_enabled() && fast(a) && a.drift_kind == DRIFT_DENSE && a.sigma_kind == SIGMA_DENSE && a.adaptive && a.runcost_kind == RUN_ZERO &&
+        // (the specialised instances: dense drift, dense (FAST_ = 2) or identity (FAST_ = 3) sigma, adaptive, no running cost,
+        //  store_path 1 / 4 -- hjb_fwd_kernel)
+        const bool spec = spec_enabled() && fast(a) && a.drift_kind == DRIFT_DENSE && a.adaptive && a.runcost_kind == RUN_ZERO &&
                           (a.store_path == 4 || a.store_path == 1) && a.loss_kind != LOSS_RELENT;
-        return spec ? fwd_as<2, 2>(a, grid, block, s) : fast(a) ? fwd_as<2, 1>(a, grid, block, s) : fwd_as<2, 0>(a, grid, block, s);
+        if (spec && a.sigma_kind == SIGMA_DENSE) return fwd_as<2, 2>(a, grid, block, s);
+        if (spec && a.sigma_kind == SIGMA_IDENT) return fwd_as<2, 3>(a, grid, block, s);
+        return fast(a) ? fwd_as<2, 1>(a, grid, block, s) : fwd_as<2, 0>(a, grid, block, s);
     }
     static int bwd2_lds() { return G::bwd2_lds_floats() * 4; }
     static hipError_t bwd2(const HjbArgs& a, int grid, hipStream_t s) {

@@ -10,6 +10,7 @@
 
 #include "../../include/psp.h"
 #include "hjb_kernels.h"
+#include "hjb_basis_kernels.h"
 #include "gen_kernels.h"
 #include "hjbw_kernels.h"
 #include "hjbd_kernels.h"
@@ -1499,6 +1500,30 @@ int psp_adam_step(float* params, const float* grad, float* exp_avg, float* exp_a
                        grad, exp_avg, exp_avg_sq, (long long)n, lr, beta1, beta2, eps, step_size, bc2_sqrt);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "adam_kernel launch");
+    return 0;
+}
+
+// sigma-basis plans (include/psp.h): W~1x = W1x B into the kernel-layout parameters, dW1x = dW~1x B^T on the reduced gradient
+static int basis_check(const void* a, const void* b, const float* B, int32_t d, int32_t H, const char* who) {
+    if (!a || !b || !B) { snprintf(g_err, sizeof(g_err), "null buffer passed to %s", who); return -1; }
+    if (d <= 0 || H <= 0) { snprintf(g_err, sizeof(g_err), "%s needs d > 0 and H > 0", who); return -1; }
+    if (psp::basis_lds_bytes(d) > 64 * 1024) { snprintf(g_err, sizeof(g_err), "%s: B does not fit 64 KiB of LDS (narrow kernel family only, d <= 112)", who); return -3; }
+    return 0;
+}
+int psp_hjb_basis_params(const float* params, float* params_out, const float* B, int32_t d, int32_t H, int64_t n_params,
+                         void* stream) {
+    int rc = basis_check(params, params_out, B, d, H, "psp_hjb_basis_params");
+    if (rc) return rc;
+    if (n_params < (int64_t)H * (d + 1)) return fail(-1, "psp_hjb_basis_params: n_params is smaller than W1");
+    hipError_t e = psp::launch_basis_w1<false>(params, params_out, B, d, H, (long long)n_params, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "hjb_basis_w1_kernel launch");
+    return 0;
+}
+int psp_hjb_basis_grad(float* grad, const float* B, int32_t d, int32_t H, void* stream) {
+    int rc = basis_check(grad, grad, B, d, H, "psp_hjb_basis_grad");
+    if (rc) return rc;
+    hipError_t e = psp::launch_basis_w1<true>(grad, grad, B, d, H, (long long)H * (d + 1), (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "hjb_basis_w1_kernel launch");
     return 0;
 }
 

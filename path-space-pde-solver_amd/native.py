@@ -172,6 +172,8 @@ SIGNATURES = {
     "psp_hjb_terminal_reduce": (C.c_int, [C.POINTER(HjbConfig), _P, _P, _P]),
     "psp_hjb_rollout_bwd": (C.c_int, [C.POINTER(HjbConfig), _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "psp_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "psp_hjb_basis_params": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, _P]),
+    "psp_hjb_basis_grad": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "psp_philox_normal_fill": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint32, _P]),
     "psp_hjb_control_eval": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P]),
     "psp_debug_set_stamp_buffer": (C.c_int, [_P, C.c_int64]),

@@ -22,6 +22,7 @@ w_k = (2/K)(D_k - mean D) need the GLOBAL mean, a chunked iteration is either
 The reference keeps the whole autograd graph instead (SURVEY.md 7 "Activation memory").
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -52,6 +53,95 @@ def _overridden(problem):
 
 class PlanUnsupported(Exception):
     """The (problem, net, loss, flags) combination is outside the native catalogue."""
+
+
+# ---- state basis (DESIGN.md section 3) -------------------------------------------------------------------------------------
+# With a constant invertible sigma = B the rollout may carry X~ = B^-1 X:  X~_{n+1} = X~_n + dt (B^-1 A B) X~_n + v_n  -- ONE
+# d x d product per step instead of two (A X and B v).  The kernels are handed the equivalent problem (drift M = B^-1 A B,
+# sigma = I, terminal vector B^T alpha, x0 = B^-1 x0); Z, Y, D, h1, h2 and the noise are unchanged; the net sees
+# W1x X = (W1x B) X~ (psp_hjb_basis_params before the forward) and the backward's dW~1x goes back through
+# dW1x = dW~1x B^T (psp_hjb_basis_grad before the all-reduce and Adam).
+# plan.cfg, plan.path and plan.grad_k are then in the sigma basis (the store holds X~, the backward leaves dW~1x): code that
+# drives psp_hjb_rollout_bwd on a plan's buffers itself must read plan.state_basis; plan.grad and the parameters stay in x.
+STATE_BASIS_MAX_COND = 4.0       # fp32 rollouts of the two forms are indistinguishable against fp64 up to cond_2(B) = 4.2 and
+                                 # 4x apart at 41 (DESIGN.md section 3, table)
+STATE_BASIS_MAX_D = 112          # the narrow kernel family
+
+
+def sigma_basis_problem(A, B, alpha, x0):
+    """M = B^-1 A B, alpha' = B^T alpha, x~0 = B^-1 x0 in fp64 (numpy arrays in, numpy float64 out)."""
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    alpha, x0 = np.asarray(alpha, dtype=np.float64).reshape(-1), np.asarray(x0, dtype=np.float64).reshape(-1)
+    return np.linalg.solve(B, A @ B), B.T @ alpha, np.linalg.solve(B, x0)
+
+
+def state_basis_decision(solver, spec=None):
+    """('sigma' | 'x', reason) for the solver's HJB plan -- host arithmetic only, no GPU.  Solver(state_basis='x' | 'sigma' |
+    'auto'); PSP_STATE_BASIS=0 in the environment forces 'x' (same-build A/B runs; read once, when the plan is built).
+    'sigma' on an ineligible configuration raises ValueError (whatever the backend)."""
+    want = getattr(solver, 'state_basis', 'auto')
+    if want not in ('auto', 'x', 'sigma'):
+        raise ValueError("state_basis must be 'auto', 'x' or 'sigma'")
+    if os.environ.get('PSP_STATE_BASIS', '') == '0':
+        return 'x', 'PSP_STATE_BASIS=0'
+    if want == 'x':
+        return 'x', "state_basis='x' requested"
+    why = _sigma_basis_obstacle(solver, spec)
+    if why is None and want == 'auto':
+        why = _sigma_basis_auto_obstacle(solver)
+    if why is not None:
+        if want == 'sigma':
+            # (a ValueError, not PlanUnsupported: backend='auto' must not answer an explicit request with the composite plan)
+            raise ValueError("state_basis='sigma' is not available: " + why)
+        return 'x', why
+    return 'sigma', 'dense drift and sigma, linear terminal cost, fixed X_0, cond_2(B) <= %g' % STATE_BASIS_MAX_COND
+
+
+STATE_BASIS_MAX_X0_SPREAD = 100.0
+
+
+def _sigma_basis_auto_obstacle(solver):
+    """'auto' only.  An fp32 X~ resolves X = B X~ to eps ||B|| max |X~| in EVERY component, so a start vector whose largest
+    component is orders of magnitude above the others costs the small ones their digits (measured: one component at 7e4 next to
+    O(1) ones, d = 100: gradient error 1.8e-4 of max |grad| against 9e-8 in the x basis); cond_2(B) does not see that."""
+    x0 = np.abs(solver.X_0.detach().double().cpu().numpy().reshape(-1))
+    if x0.size and float(x0.max()) > STATE_BASIS_MAX_X0_SPREAD * max(1.0, float(np.median(x0))):
+        return 'max |X_0| = %.3g is more than %g x the typical component' % (float(x0.max()), STATE_BASIS_MAX_X0_SPREAD)
+    return None
+
+
+def _sigma_basis_obstacle(solver, spec=None):
+    if spec is None:
+        fn = getattr(solver.problem, 'native_spec', None)
+        spec = fn() if fn is not None else None
+    if spec is None:
+        return 'problem has no native_spec()'
+    if getattr(solver, 'approx_method', 'control') != 'control' or getattr(solver, 'time_approx', 'inner') != 'inner':
+        return "only the time-input control net (time_approx='inner') rolls out in the sigma basis"
+    if spec['drift'][0] != nat.DRIFT_DENSE or spec['sigma'][0] != nat.SIGMA_DENSE:
+        return 'drift and sigma are not both dense matrices'
+    if solver.adaptive_forward_process and not solver.detach_forward:
+        return 'attached forward process: the adjoint sweep differentiates through the state path in the x basis'
+    if spec['runcost'][0] != nat.RUNCOST_ZERO:
+        return 'the running cost reads X in the x basis'
+    if spec['term'][0] != nat.TERM_LINEAR:
+        return 'the terminal cost is not linear in X'
+    if solver.random_X_0:
+        return 'random_X_0 draws a per-trajectory X_0 in the x basis'
+    if solver.u_l2_error_flag and getattr(solver.problem, 'u_true_x_independent', False) is not True:
+        return 'the u_L2 log of an x-dependent reference control reads X from the path store'
+    if getattr(solver, 'mlp_dtype', 'auto') == 'bf16':
+        return "mlp_dtype='bf16' keeps its own tolerance in the x basis"
+    if solver.d > STATE_BASIS_MAX_D or os.environ.get('PSP_FORCE_WIDE', '') == '1':
+        return 'the wide kernel family (d > %d) is built around the two products' % STATE_BASIS_MAX_D
+    B = spec['sigma'][1].detach().double().cpu().numpy()
+    sv = np.linalg.svd(B, compute_uv=False)
+    if not (sv[-1] > 0.0) or not np.isfinite(sv).all():
+        return 'sigma is singular'
+    cond = float(sv[0] / sv[-1])
+    if cond > STATE_BASIS_MAX_COND:
+        return 'cond_2(sigma) = %.3g exceeds %g' % (cond, STATE_BASIS_MAX_COND)
+    return None
 
 
 def native_eligibility(solver):
@@ -152,7 +242,17 @@ class HjbNativePlan:
         cfg.dt = float(solver.delta_t.item())
         cfg.sqrt_dt = float(solver.sq_delta_t.item())
         cfg.drift_kind = spec['drift'][0]
-        cfg.sigma_kind = spec['sigma'][0]
+        # the state basis of every launch of this plan (module comment above): under 'sigma' the kernels get identity sigma
+        self.state_basis, self.state_basis_reason = state_basis_decision(solver, spec)
+        if (self.state_basis == 'sigma' and getattr(solver, 'state_basis', 'auto') == 'auto' and torch.device(dev).type == 'cuda'
+                and (-(-K // self.world) + 15) // 16 <= 2 * torch.cuda.get_device_properties(dev).multi_processor_count):
+            # (from the even share K / world, not this rank's K_local: every rank of a job picks the same basis)
+            # 'auto' follows the size rule of the split-product mode and of store_path 4 below: at most two tiles per CU the
+            # iteration is launch-bound and pays for the two transform launches (and for the fused backward + Adam launch of the
+            # hipGraph replay, which the gradient transform splits).  Conservative: at d = 100, K = 8192 an explicit 'sigma' still
+            # measures 4 % faster.  state_basis='sigma' overrides.
+            self.state_basis, self.state_basis_reason = 'x', 'launch-bound size (at most two 16-trajectory tiles per CU)'
+        cfg.sigma_kind = nat.SIGMA_IDENTITY if self.state_basis == 'sigma' else spec['sigma'][0]
         cfg.sigma_scale = float(spec['sigma'][2])
         cfg.runcost_kind = spec['runcost'][0]
         cfg.term_kind = spec['term'][0]
@@ -176,6 +276,12 @@ class HjbNativePlan:
         chosen, why = shapes.choose(cfg, solver.d, self.H)
         if chosen is None:
             raise PlanUnsupported(why)
+        if self.state_basis == 'sigma' and chosen[2] != 1:          # (only the narrow family has the one-product forward)
+            self.state_basis, self.state_basis_reason = 'x', 'the configuration runs on the wide kernel family'
+            cfg.sigma_kind = spec['sigma'][0]
+            chosen, why = shapes.choose(cfg, solver.d, self.H)
+            if chosen is None:
+                raise PlanUnsupported(why)
         self.d_pad, self.H_pad, self.family, sizes = chosen
         if want == 'auto' and torch.device(dev).type == 'cuda':
             cus = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -213,17 +319,33 @@ class HjbNativePlan:
                 cfg.store_path = 1
         self.pad = shapes.ParamPad(solver.d, self.H, self.d_pad, self.H_pad, dev)
         pad = self.pad
-        cfg.drift = nat.ptr(dev_f32(pad.drift_or_sigma(spec['drift'][1]))) if spec['drift'][1] is not None else None
-        cfg.sigma = nat.ptr(dev_f32(pad.drift_or_sigma(spec['sigma'][1]))) if spec['sigma'][1] is not None else None
+        x0_plan = solver.X_0.detach().to(dev)
+        if self.state_basis == 'sigma':
+            # the transformed problem, once per plan in fp64 on the host, rounded to fp32: M = B^-1 A B, alpha' = B^T alpha,
+            # x~0 = B^-1 x0.  EVERY launch of the plan (forward, backward, the range guard's fp32 twins, chunks, ranks, the small-K
+            # forwards) takes its problem from this one config.
+            M, al, x0t = sigma_basis_problem(spec['drift'][1].detach().double().cpu().numpy(), spec['sigma'][1].detach().double().cpu().numpy(),
+                                             spec['term'][1].detach().double().cpu().numpy(), solver.X_0.detach().double().cpu().numpy())
+            self.basis_B = dev_f32(pad.mat(spec['sigma'][1]))                   # for the two per-iteration transforms
+            cfg.drift = nat.ptr(dev_f32(pad.mat(torch.from_numpy(M).to(torch.float32))))
+            cfg.sigma = None
+            cfg.term = nat.ptr(dev_f32(pad.vec(torch.from_numpy(al).to(torch.float32))))
+            x0_plan = torch.from_numpy(x0t).to(torch.float32).to(dev)
+        else:
+            self.basis_B = None
+            cfg.drift = nat.ptr(dev_f32(pad.drift_or_sigma(spec['drift'][1]))) if spec['drift'][1] is not None else None
+            cfg.sigma = nat.ptr(dev_f32(pad.drift_or_sigma(spec['sigma'][1]))) if spec['sigma'][1] is not None else None
+            cfg.term = nat.ptr(dev_f32(pad.vec(spec['term'][1])))
         cfg.runcost = nat.ptr(dev_f32(pad.vec(spec['runcost'][1]))) if spec['runcost'][1] is not None else None
-        cfg.term = nat.ptr(dev_f32(pad.vec(spec['term'][1])))
+        solver.state_basis_plan = (self.state_basis, self.state_basis_reason)
         self.cfg = cfg
         assert sizes.n_params == pad.Pp, (sizes.n_params, pad.Pp)
         self._setup_chunks(solver, cfg, sizes)
         solver.path_plan = dict(n_chunks=self.n_chunks, chunk_mode=self.chunk_mode, chunk_K=self.chunk_K)   # what the budget chose
         sizes = self.sizes
         # kernel-side (padded) parameter and gradient vectors; identical to the real ones when nothing is padded
-        self.flat_k = self.flat if pad.identity else pad.new_padded_params()
+        # (sigma basis: always a buffer of its own -- it holds W1x B where self.flat, the nn.Parameter views, holds W1x)
+        self.flat_k = self.flat if (pad.identity and self.state_basis != 'sigma') else pad.new_padded_params()
         self.grad_k = None
         self.path = torch.empty(sizes.path_bytes // 4, dtype=torch.float32, device=dev)
         self.fwd_partial = torch.empty(max(1, self.n_chunks) * (sizes.fwd_partial_bytes // 8), dtype=torch.float64, device=dev)
@@ -236,7 +358,7 @@ class HjbNativePlan:
         self.grad_k = self.grad if pad.identity else torch.empty(pad.Pp, dtype=torch.float32, device=dev)
         self.m = torch.zeros(self.P, dtype=torch.float32, device=dev)
         self.v = torch.zeros(self.P, dtype=torch.float32, device=dev)
-        self.x0_vec = dev_f32(pad.vec(solver.X_0.detach().to(dev)))
+        self.x0_vec = dev_f32(pad.vec(x0_plan))
         self.ul2 = None
         self.ul2_gain = None
         self.ul2_tab = None
@@ -316,6 +438,22 @@ class HjbNativePlan:
 
     def _stream(self):
         return nat.stream_ptr(self.dev)
+
+    def _kernel_params(self, st):
+        """The kernel-layout parameter vector of this iteration: self.flat itself, its zero-padded scatter, or -- sigma basis -- one
+        launch that copies it into self.flat_k with W1x B in place of W1x (psp_hjb_basis_params; capturable, no host sync)."""
+        if self.state_basis != 'sigma':
+            return self.pad.scatter_params(self.flat, self.flat_k)
+        src = self.pad.scatter_params(self.flat, self.flat_k)          # identity padding: self.flat; else scattered into flat_k
+        nat.check(self.lib.psp_hjb_basis_params(nat.ptr(src), nat.ptr(self.flat_k), nat.ptr(self.basis_B), self.d_pad, self.H_pad,
+                                                self.pad.Pp, st), 'psp_hjb_basis_params')
+        return self.flat_k
+
+    def _grad_to_x_basis(self, st):
+        """sigma basis: dW1x = dW~1x B^T on the kernel-layout gradient (linear: before the all-reduce is as good as after)."""
+        if self.state_basis == 'sigma':
+            nat.check(self.lib.psp_hjb_basis_grad(nat.ptr(self.grad_k), nat.ptr(self.basis_B), self.d_pad, self.H_pad, st),
+                      'psp_hjb_basis_grad')
 
     # ---- K-chunking (module docstring) -------------------------------------------------------------------------------
     DEFAULT_PATH_BUDGET = 180 * 2 ** 30         # five eighths of the 288 GB of HBM3E when the device cannot be asked
@@ -417,7 +555,7 @@ class HjbNativePlan:
             g.manual_seed(int(s.seed) * 1000003 + l)
             x0 = self.pad.last_dim(torch.randn(s.K, s.d, generator=g, device=self.dev)[
                 self.k_offset:self.k_offset + self.K_local].contiguous())
-        flat_k = self.pad.scatter_params(self.flat, self.flat_k)
+        flat_k = self._kernel_params(st)
         y0_ptr = nat.ptr(self.y0_param) if self.learn_y0 else None
         K = float(s.K)
 
@@ -576,7 +714,7 @@ class HjbNativePlan:
         s, lib, cfg = self.s, self.lib, self._gcfg
         st = self._stream()
         state = nat.ptr(self._gstate)
-        flat_k = self.pad.scatter_params(self.flat, self.flat_k)
+        flat_k = self._kernel_params(st)
         y0_ptr = nat.ptr(self.y0_param) if self.learn_y0 else None
         seed = int(s.seed) & 0xFFFFFFFFFFFFFFFF
         nat.check(lib.psp_hjb_rollout_fwd(C.byref(cfg), nat.ptr(flat_k), nat.ptr(self.x0_vec), 0, y0_ptr, None, seed, 0,
@@ -599,8 +737,9 @@ class HjbNativePlan:
         elif self.relent:                                # detached relative entropy: weight sqrt(dt) / K on the Z image
             d_or_w, bcfg = self.w_bwd, self._gcfg_w
         lr, b1, b2, eps = self._graph_hyper
-        if self.pad.identity and not self.learn_y0:
-            # backward + (gradient reduction, Adam, state advance) as two launches
+        if self.pad.identity and not self.learn_y0 and self.state_basis != 'sigma':
+            # backward + (gradient reduction, Adam, state advance) as two launches (sigma basis: the gradient transform stands
+            # between the reduction and Adam -- the separate launches below)
             nat.check(lib.psp_hjb_rollout_bwd_step(C.byref(bcfg), nat.ptr(self.flat), nat.ptr(self.path), nat.ptr(d_or_w),
                                                    nat.ptr(self.sums), nat.ptr(self.grad_partial), nat.ptr(self.grad),
                                                    nat.ptr(self.m), nat.ptr(self.v), state, nat.ptr(self._gticket),
@@ -609,6 +748,7 @@ class HjbNativePlan:
         nat.check(lib.psp_hjb_rollout_bwd(C.byref(bcfg), nat.ptr(flat_k), None, seed, 0, nat.ptr(self.path),
                                           nat.ptr(d_or_w), nat.ptr(self.sums), nat.ptr(self.grad_partial),
                                           nat.ptr(self.grad_k), st), 'psp_hjb_rollout_bwd')
+        self._grad_to_x_basis(st)
         self.pad.gather_grad(self.grad_k, self.grad)
         nat.check(lib.psp_adam_step_dev(nat.ptr(self.flat), nat.ptr(self.grad), nat.ptr(self.m), nat.ptr(self.v), self.P,
                                         state, lr, b1, b2, eps, st), 'psp_adam_step_dev')
@@ -701,6 +841,7 @@ class HjbNativePlan:
     def _finish_step(self, st, w_generic):
         """Gather the real gradient entries, all-reduce, Adam on the net and on the learnable Y_0."""
         s, lib = self.s, self.lib
+        self._grad_to_x_basis(st)
         self.pad.gather_grad(self.grad_k, self.grad)    # real entries of the (possibly padded) gradient
         sharding.allreduce_sum_(self.grad)              # collective 2: p floats
         self.step += 1
@@ -770,7 +911,7 @@ class HjbNativePlan:
                 self.k_offset:self.k_offset + self.K_local].contiguous())
         x0_t = x0 if x0 is not None else self.x0_vec
         x0_stride = self.d_pad if x0 is not None else 0
-        flat_k = self.pad.scatter_params(self.flat, self.flat_k)
+        flat_k = self._kernel_params(st)
         y0_ptr = nat.ptr(self.y0_param) if self.learn_y0 else None
         ev = None
         if self.events is not None:      # events go on torch's current stream = the launch stream
@@ -877,9 +1018,11 @@ class HjbNativePlan:
             xi, x0 = self._reference_noise()
         x0_t = x0 if x0 is not None else self.x0_vec
         XN = torch.empty(self.K_local, self.d_pad, dtype=torch.float32, device=self.dev) if want_XN else None
-        flat_k = self.pad.scatter_params(self.flat, self.flat_k)
+        flat_k = self._kernel_params(self._stream())
         nat.check(lib.psp_hjb_rollout_fwd(C.byref(cfg), nat.ptr(flat_k), nat.ptr(x0_t), self.d_pad if x0 is not None else 0,
                                           nat.ptr(self.y0_param) if self.learn_y0 else None, nat.ptr(xi),
                                           int(s.seed), l, None, nat.ptr(self.D), nat.ptr(XN), None,
                                           nat.ptr(self.fwd_partial), self._stream()), 'psp_hjb_rollout_fwd')
+        if XN is not None and self.state_basis == 'sigma':
+            XN = XN @ self.basis_B.t()                   # the kernel left X~_N; X_N = B X~_N (an evaluation helper, not the hot path)
         return self.D, (XN[:, :s.d] if XN is not None else None)

@@ -66,7 +66,7 @@ class Solver:
                  log_gradient=False, burgers_drift=False, verbose=True,
                  device=None, backend='auto', noise='reference', widths=(30, 30), mlp_dtype='auto',
                  path_budget_bytes=None, path_chunks=None, chunk_mode='auto', use_graph='auto', range_guard=True,
-                 path_noise='auto'):
+                 path_noise='auto', state_basis='auto'):
         self.problem, self.name = problem, name
         self.date = date.today().strftime('%Y-%m-%d')
         self.d, self.T = problem.d, problem.T
@@ -97,6 +97,13 @@ class Solver:
         if path_noise not in ('auto', 'store'):
             raise ValueError("path_noise must be 'auto' or 'store'")
         self.path_noise = path_noise
+        # native plan: 'auto' rolls the state out as B^-1 X (one d x d product per step instead of two) where that is exact and
+        # well conditioned -- dense drift and sigma, linear terminal cost, fixed X_0, detached, d <= 112, cond_2(B) <= 4
+        # (plan_native.py: state_basis_decision); 'x' never, 'sigma' raises where 'auto' would decline.  Parameters, gradients
+        # and every logged quantity stay in the original basis.
+        if state_basis not in ('auto', 'x', 'sigma'):
+            raise ValueError("state_basis must be 'auto', 'x' or 'sigma'")
+        self.state_basis = state_basis
         # native plan: HBM budget of the path store kept for the backward pass (None: a third of the HBM); a larger store is
         # processed in K-chunks (plan_native.py).  path_chunks forces a chunk count; chunk_mode 'auto' | 'two_gradient' | 'recompute'
         self.path_budget_bytes, self.path_chunks, self.chunk_mode = path_budget_bytes, path_chunks, chunk_mode
@@ -282,7 +289,7 @@ class Solver:
         nets = nets + tuple(id(v) for v in getattr(self, 'y_n', []))
         return (nets, self.noise, self.K, self.N, float(self.delta_t_np), self.loss_method, self.approx_method,
                 self.time_approx, bool(self.learn_Y_0), bool(self.adaptive_forward_process), bool(self.detach_forward),
-                bool(self.random_X_0), bool(self.u_l2_error_flag), self.mlp_dtype, getattr(self, 'range_guard', True), getattr(self, 'path_noise', 'auto'), self.path_budget_bytes, self.path_chunks,
+                bool(self.random_X_0), bool(self.u_l2_error_flag), self.mlp_dtype, getattr(self, 'range_guard', True), getattr(self, 'path_noise', 'auto'), getattr(self, 'state_basis', 'auto'), os.environ.get('PSP_STATE_BASIS', ''), self.path_budget_bytes, self.path_chunks,
                 self.chunk_mode, id(self.problem), id(self.y_0) if hasattr(self, 'y_0') else None)
 
     def _choose_plan(self):
@@ -330,6 +337,7 @@ class Solver:
                 plan = HjbNativePlan(self, noise=self.noise)     # owns the flat parameters and Adam moments
                 plan.key = self._plan_key()
                 self._native_plan = plan
+            self.plan_reason = 'state basis %s: %s' % (plan.state_basis, plan.state_basis_reason)
             return plan
         dense_reason = dense_eligibility(self)  # DenseNet controls: time_approx='outer', DenseNet swapped into z_n
         if dense_reason is None:
