@@ -17,6 +17,8 @@
  *                 detach_forward False and relative_entropy through psp_dnet_adjoint_sweep
  *   GeneralSolver.train / EllipticSolver.train (solver.py:1001-1206, :628-826)
  *     psp_gen_*   diffusion / BSDE loss on unbounded, sphere and box domains, V = DenseNet(d+1 -> 1) / DenseNet(d -> 1)
+ *     psp_genl_*  the same for dense-concat value nets of one to four hidden layers; psp_genl_test_error: the K_test_log
+ *                 diagnostic (utilities.py:440-472) sampled, evaluated and reduced on the device
  *   shared: psp_adam_step (per-net Adam, function_space.py:185), psp_allreduce + psp_comm_* (trajectory sharding over
  *   the GPUs of a node), diagnostics.
  *
@@ -52,7 +54,9 @@ extern "C" {
                          *        psp_genl_config.sigma_kind / sigma -- a dense constant diffusion matrix in the run-time-shaped
                          *        value-net kernels (PSP_GENL_SIGMA_*), and PSP_GH_EXPBALL_SIN_FULL;
                          *        psp_hjb_basis_params / psp_hjb_basis_grad -- the per-iteration transforms of a rollout in the
-                         *        sigma basis */
+                         *        sigma basis;
+                         *        psp_genl_eval_config / psp_genl_eval_query / psp_genl_test_error / psp_abi_struct_sizes4 -- the
+                         *        K_test_log diagnostic sampled, evaluated and reduced on the device (PSP_TSAMPLE_*, PSP_VTRUE_*) */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
@@ -643,6 +647,68 @@ int psp_abi_struct_sizes3(int32_t out[1]);
 int psp_hjb_basis_params(const float* params, float* params_out, const float* B, int32_t d, int32_t H, int64_t n_params,
                          void* stream);
 int psp_hjb_basis_grad(float* grad, const float* B, int32_t d, int32_t H, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The K_test_log diagnostic on the device (appended in 0.4.0, no version bump; csrc/genl_eval_kernels.h): the Monte-Carlo error
+ * of a value net against the problem's closed-form solution on K_points fresh points of the domain (utilities.compute_test_error,
+ * reference utilities.py:440-472; solver.py:1193-1197 / :821-825) -- points drawn, V and v_true evaluated and the statistics
+ * reduced by two kernels, no host sync, nothing allocated, capturable.  The net is any dense-concat net psp_genl_* takes.
+ * Points (PSP_TSAMPLE_*): supplied by the caller, or drawn from Philox4x32-7 on a stream no training kernel uses:
+ *     key = (seed & 0xffffffff, (seed >> 32) ^ 0x54455354), counter = (k_offset + k, c1, c2, iter)
+ *     c1 = 0, c2 = 4 b + q : features 16 b + 4 r + q, r = 0..3 -- N(0, 1) by two Box-Muller pairs (BALL, ANNULUS) or the 24-bit
+ *                            uniforms ((r >> 8) + 1/2) 2^-24 (BOX)
+ *     c1 = 1, c2 = 0       : output 0 = radial uniform u, output 1 = time uniform u_t; t = u_t T (nets with a time input)
+ *     BALL    x = bound_b g / |g| u^(1/d)                                   ('sphere', 'unbounded')
+ *     ANNULUS the ball of radius bound_b; points with |x| <= bound_a are rejected and not counted  ('two_spheres')
+ *     BOX     x = (bound_b - bound_a) u + bound_a                           ('square', 'unbounded_square')
+ * v_true (PSP_VTRUE_*), fp32, from r2 = |x|^2 and t:
+ *     EXP        exp(p0 r2 + p1 t)                                          (exponential on the ball; parabolic: p1 = 1)
+ *     QUAD       r2 + p0 (p1 - t)                                           (HeatEquation p0 = 2 d, p1 = T; QuadraticOnBox p0 = 0)
+ *     COMMITTOR  (a^2 - r^(2-d) a^d) / (a^2 - c^(2-d) a^d), p0 = a, p1 = c, p2 = d
+ * log_out[4 slot .. 4 slot + 3] = sum e^2, sum |e|, sum |e| / v_true, count over the kept points, e = v_true - V, in fp64
+ * (per-workgroup partials summed in a fixed order: equal arguments give bit-identical output).
+ * ------------------------------------------------------------------------------------------------ */
+enum { PSP_TSAMPLE_SUPPLIED = 0, PSP_TSAMPLE_BALL = 1, PSP_TSAMPLE_ANNULUS = 2, PSP_TSAMPLE_BOX = 3 };
+enum { PSP_VTRUE_EXP = 0, PSP_VTRUE_QUAD = 1, PSP_VTRUE_COMMITTOR = 2 };
+
+typedef struct psp_genl_eval_config {
+    int32_t d;                /* state dimension                                                                                 */
+    int32_t has_time, n_hidden, widths[4], activation, linear_layout, time_first;   /* the net: as in psp_genl_config            */
+    float time_scale;
+    int32_t K_points;         /* test points of this call                                                                        */
+    int32_t sample_kind;      /* PSP_TSAMPLE_*                                                                                   */
+    int64_t k_offset;         /* global index of point 0 (Philox counter); k_offset + K_points <= 2^32                           */
+    float bound_a, bound_b;   /* BALL: (unused, R); ANNULUS: (r1, r2); BOX: (l, r)                                               */
+    float T;                  /* sampled points of a net with a time input: t ~ U(0, T)                                          */
+    int32_t vtrue_kind;       /* PSP_VTRUE_*                                                                                     */
+    float vtrue_par[4];
+    int32_t log_slots;        /* rows of log_out; a slot outside [0, log_slots) is dropped by the kernel, never written          */
+    int32_t reserved;
+} psp_genl_eval_config;
+
+typedef struct psp_genl_eval_sizes {
+    int64_t table_bytes;      /* scratch for the operand tables (rebuilt by every call)                                          */
+    int64_t partial_bytes;    /* 4 doubles per workgroup                                                                         */
+    int64_t n_params;         /* registration order W_1, b_1, .., W_out, b_out                                                   */
+    int32_t workgroups;       /* ceil(K_points / 16): one 16-point tile each                                                     */
+    int32_t waves_per_tile;   /* 1 or 8: one wave for the nets psp_genl_query gives one wave at K_local = K_points, else 8
+                               * (never the rollout's 4-wave refinement for large batches)                                       */
+    int32_t lds_bytes;        /* the activation image alone                                                                      */
+    int32_t reserved;
+} psp_genl_eval_sizes;
+
+/* Every check psp_genl_test_error makes of the config, and the sizes, without a launch (no GPU needed).  -1 invalid argument,
+ * -2 net outside the limits of psp_genl_query, -3 LDS. */
+int psp_genl_eval_query(const psp_genl_eval_config* cfg, psp_genl_eval_sizes* out);
+/* Rebuilds the operand tables from `params`, then launches the evaluation and the reduction.  x (K_points, d) / t (K_points):
+ * the points of PSP_TSAMPLE_SUPPLIED (t with a time input), NULL otherwise.  slot_dev: optional DEVICE uint32 read by the
+ * reduction kernel as the slot (a psp_iter_state.iter pointer is the intended use); NULL: `slot`.  Optional per-point dumps
+ * (NULL: not written): x_out (K_points, d), t_out, v_out, vtrue_out (K_points) fp32, keep_out (K_points) int32. */
+int psp_genl_test_error(const psp_genl_eval_config* cfg, const float* params, const float* x, const float* t, uint64_t seed,
+                        uint32_t iter, float* tables, double* partial, double* log_out, int32_t slot, const uint32_t* slot_dev,
+                        float* x_out, float* t_out, float* v_out, float* vtrue_out, int32_t* keep_out, void* stream);
+/* sizeof(psp_genl_eval_config), sizeof(psp_genl_eval_sizes). */
+int psp_abi_struct_sizes4(int32_t out[2]);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, trajectories sharded in contiguous blocks, parameters replicated.

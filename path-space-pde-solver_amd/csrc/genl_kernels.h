@@ -125,6 +125,9 @@ __device__ __forceinline__ int genl_w_index(AP a, int i, int rf, int u) {
 }
 
 // A-operand tables + staged vectors from the flat parameters (registration order W_1, b_1, .., W_out, b_out)
+// (an ordinary kernel: defined in the one translation unit that launches it, psp_api.hip; a unit that includes this header for
+//  its device helpers alone defines PSP_GENL_DEVICE_HELPERS_ONLY)
+#ifndef PSP_GENL_DEVICE_HELPERS_ONLY
 __global__ __launch_bounds__(256) void genl_tables_kernel(const GenlArgs a) {
     PSP_COND_EXIT(a.g);
     const float* __restrict__ P = a.g.params;
@@ -188,6 +191,7 @@ __global__ __launch_bounds__(256) void genl_tables_kernel(const GenlArgs a) {
         T[a.vW + idx] = rf >= 0 ? genl_feature_scale(&a, 16 * b + 4 * r + q) * P[a.oW[a.L] + rf] : 0.f;
     }
 }
+#endif
 
 typedef const GenlArgs* KArgs;
 typedef const GenArgs* KGen;

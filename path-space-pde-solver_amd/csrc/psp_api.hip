@@ -15,6 +15,7 @@
 #include "hjbw_kernels.h"
 #include "hjbd_kernels.h"
 #include "genl_kernels.h"
+#include "genl_eval_kernels.h"
 #include "hjbe_kernels.h"
 
 #define X(D_, H_) PSP_DECLARE_DNET_INSTANCE(D_, H_)
@@ -1401,6 +1402,100 @@ int psp_genl_rollout_bwd(const psp_genl_config* cfg, const float* params, const 
     hipLaunchKernelGGL(reduce_grad_kernel, dim3((P + 31) / 32), dim3(256), 0, st, grad_partial, p.bwd_grid, P, grad_out);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "reduce_grad_kernel launch");
+    return 0;
+}
+
+// ---- the K_test_log diagnostic on the device (genl_eval_kernels.h) ----------------------------------------------------------
+namespace {
+struct EvalPlan { GenlPlan p; int grid, nw, lds; };
+// every check of a psp_genl_eval_config (psp_genl_eval_query and psp_genl_test_error share it); the net goes through
+// make_genl_plan as a one-step rollout of K_points trajectories, which also applies its waves-per-tile rule to K_points.
+// (Its LDS test of the rollout kernels cannot fire here: the shape limits -- 7 input and 4 x 8 hidden blocks, TB <= 39 -- keep
+//  the rollout's largest request, (4 TB - 2 DB0 + 2) KiB <= 144 KiB, below the 160 KiB, so every net that passes the shape checks
+//  is served; the evaluation itself asks for TB KiB.)
+int make_eval_plan(const psp_genl_eval_config* c, EvalPlan* e) {
+    if (!c) return fail(-1, "null config");
+    if (c->K_points <= 0) return fail(-1, "K_points must be positive");
+    if (c->k_offset < 0 || c->k_offset + (int64_t)c->K_points > (1LL << 32)) return fail(-1, "k_offset + K_points must stay within 2^32");
+    if (c->sample_kind < PSP_TSAMPLE_SUPPLIED || c->sample_kind > PSP_TSAMPLE_BOX)
+        return fail(-1, "sample_kind out of range (PSP_TSAMPLE_SUPPLIED, _BALL, _ANNULUS, _BOX)");
+    if (c->vtrue_kind < PSP_VTRUE_EXP || c->vtrue_kind > PSP_VTRUE_COMMITTOR)
+        return fail(-1, "vtrue_kind out of range (PSP_VTRUE_EXP, _QUAD, _COMMITTOR)");
+    if (c->sample_kind == PSP_TSAMPLE_BALL && !(c->bound_b > 0.f)) return fail(-1, "ball radius must be positive");
+    if (c->sample_kind == PSP_TSAMPLE_ANNULUS && !(c->bound_a >= 0.f && c->bound_a < c->bound_b))
+        return fail(-1, "annulus radii must satisfy 0 <= r_1 < r_2");
+    if (c->sample_kind == PSP_TSAMPLE_BOX && !(c->bound_a < c->bound_b)) return fail(-1, "box bounds must satisfy X_l < X_r");
+    if (c->vtrue_kind == PSP_VTRUE_COMMITTOR && !(c->vtrue_par[0] > 0.f)) return fail(-1, "committor: inner radius must be positive");
+    if (c->log_slots <= 0) return fail(-1, "log_slots must be positive");
+    psp_genl_config g;
+    memset(&g, 0, sizeof(g));
+    g.base.d = c->d; g.base.K_local = c->K_points; g.base.N = 1;
+    g.has_time = c->has_time; g.n_hidden = c->n_hidden;
+    for (int i = 0; i < 4; ++i) g.widths[i] = c->widths[i];
+    g.activation = c->activation; g.linear_layout = c->linear_layout; g.time_first = c->time_first; g.time_scale = c->time_scale;
+    const int rc = make_genl_plan(&g, &e->p);
+    if (rc) return rc;
+    e->grid = e->p.ntile16;
+    e->nw = e->p.nw_bwd;                                              // 1 or 8 (nw_fwd may read 4: a refinement of the rollout only)
+    e->lds = psp::genl_eval_lds_bytes(e->p.a.TB);
+    return 0;
+}
+}  // namespace
+
+int psp_abi_struct_sizes4(int32_t out[2]) {
+    if (!out) return fail(-1, "null output");
+    out[0] = (int32_t)sizeof(psp_genl_eval_config); out[1] = (int32_t)sizeof(psp_genl_eval_sizes);
+    return 0;
+}
+
+int psp_genl_eval_query(const psp_genl_eval_config* cfg, psp_genl_eval_sizes* out) {
+    EvalPlan e;
+    const int rc = make_eval_plan(cfg, &e);
+    if (rc) return rc;
+    if (!out) return fail(-1, "null output");
+    memset(out, 0, sizeof(*out));
+    out->table_bytes = e.p.table_floats * 4;
+    out->partial_bytes = (int64_t)e.grid * psp::kEvalStats * 8;
+    out->n_params = e.p.n_params;
+    out->workgroups = e.grid;
+    out->waves_per_tile = e.nw;
+    out->lds_bytes = e.lds;
+    return 0;
+}
+
+int psp_genl_test_error(const psp_genl_eval_config* cfg, const float* params, const float* x, const float* t, uint64_t seed,
+                        uint32_t iter, float* tables, double* partial, double* log_out, int32_t slot, const uint32_t* slot_dev,
+                        float* x_out, float* t_out, float* v_out, float* vtrue_out, int32_t* keep_out, void* stream) {
+    EvalPlan e;
+    const int rc = make_eval_plan(cfg, &e);
+    if (rc) return rc;
+    if (!params || !tables || !partial || !log_out) return fail(-1, "null buffer passed to psp_genl_test_error");
+    const bool supplied = cfg->sample_kind == PSP_TSAMPLE_SUPPLIED;
+    if (supplied && (!x || (cfg->has_time && !t))) return fail(-1, "PSP_TSAMPLE_SUPPLIED needs x (and t with a time input)");
+    if (!supplied && (x || t)) return fail(-1, "x / t are the points of PSP_TSAMPLE_SUPPLIED only");
+    if (!slot_dev && (slot < 0 || slot >= cfg->log_slots)) return fail(-1, "slot outside [0, log_slots)");
+    psp::GenlEvalArgs ea;
+    memset(&ea, 0, sizeof(ea));
+    ea.n = e.p.a;
+    ea.n.tables = tables; ea.n.tables_w = tables;
+    ea.n.g.params = params;
+    ea.x = x; ea.t = t; ea.k_offset = cfg->k_offset; ea.K = cfg->K_points;
+    ea.sample_kind = cfg->sample_kind; ea.lo = cfg->bound_a; ea.hi = cfg->bound_b; ea.T = cfg->T;
+    ea.vtrue_kind = cfg->vtrue_kind;
+    for (int i = 0; i < 4; ++i) ea.vp[i] = cfg->vtrue_par[i];
+    if (cfg->vtrue_kind == PSP_VTRUE_COMMITTOR) {
+        const double a = cfg->vtrue_par[0], c = cfg->vtrue_par[1], dd = cfg->vtrue_par[2];
+        ea.vden = (float)(a * a - pow(c, 2.0 - dd) * pow(a, dd));
+    }
+    ea.key0 = (uint32_t)seed; ea.key1 = (uint32_t)(seed >> 32) ^ psp::kTestKeyXor; ea.iter = iter;
+    ea.partial = partial; ea.log_out = log_out; ea.slot_dev = slot_dev; ea.slot = slot; ea.log_slots = cfg->log_slots;
+    ea.x_out = x_out; ea.t_out = t_out; ea.v_out = v_out; ea.vtrue_out = vtrue_out; ea.keep_out = keep_out;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(psp::genl_tables_kernel, dim3(128), dim3(256), 0, st, ea.n);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail_hip(err, "genl_tables_kernel launch");
+    err = psp::genl_eval_launch(ea, e.nw, e.grid, e.lds, st);
+    if (err != hipSuccess) return fail_hip(err, "genl_eval_kernel launch");
     return 0;
 }
 

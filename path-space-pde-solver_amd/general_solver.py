@@ -107,8 +107,14 @@ class GeneralSolver:
                  verbose=True, approx_method='Y', sample_center=False, loss_method='diffusion',
                  loss_with_stopped=False, K_test_log=None, PINN_log_variance=False, log_loss_parts=False,
                  boundary_loss=True, full_hessian=False, uniform_square=False, solve_linear_L2_projection=False,
-                 device=None, backend='auto', noise='reference', mlp_dtype='auto', range_guard=True):
+                 device=None, backend='auto', noise='reference', mlp_dtype='auto', range_guard=True, test_log='reference'):
         self.problem, self.name = problem, name
+        # K_test_log: 'reference' = the reference's host code after every iteration (CPU generator, one device-to-host sync);
+        # 'device' = sampled, evaluated and reduced by the native plans' own kernels into a device log that is read back once
+        # when train() returns (device_test_log.py)
+        if test_log not in ('reference', 'device'):
+            raise ValueError("test_log must be 'reference' or 'device'")
+        self.test_log = test_log
         # split-product kernels ('auto' / 'f16x3'): redo an iteration on the fp32-MFMA kernels when an operand left the f16 range
         # (include/psp.h: psp_gen_config.range_flag); self.range_fallback_iterations counts them after train()
         self.range_guard, self.range_fallback_iterations = bool(range_guard), 0
@@ -238,17 +244,31 @@ class GeneralSolver:
     def train(self):
         torch.manual_seed(self.seed)
         self._check_scope()
+        self._check_test_log()
         plan = self._choose_plan()
         if plan is not None:
             return plan.train()
         self._train_composite()
+
+    def _check_test_log(self):
+        """An explicit test_log='device' that cannot be served is an error, never a silent fall-back to the host log."""
+        if getattr(self, 'test_log', 'reference') != 'device' or self.K_test_log is None:
+            return
+        try:
+            from .device_test_log import eval_reason
+        except ImportError:
+            from device_test_log import eval_reason
+        why = eval_reason(self.problem)
+        if why is not None:
+            raise ValueError("test_log='device' unavailable: " + why)
 
     def _plan_key(self):
         """What a native plan sizes its buffers / fixes its kernel configuration from (the value net is compared by identity:
         `model.V = DenseNet(...)` after a first train() must rebuild the plan, Allen-Cahn.ipynb:72)."""
         return (id(self.V), self.K, self.N, self.K_boundary, float(self.delta_t_np), self.loss_method, tuple(self.alpha),
                 bool(self.adaptive_forward_process), bool(self.detach_forward), getattr(self, 'noise', None),
-                getattr(self, 'mlp_dtype', None), bool(getattr(self, 'range_guard', True)), bool(getattr(self, 'uniform_square', False)), id(self.problem))
+                getattr(self, 'mlp_dtype', None), bool(getattr(self, 'range_guard', True)), bool(getattr(self, 'uniform_square', False)), id(self.problem),
+                getattr(self, 'test_log', 'reference'), self.K_test_log)
 
     def _choose_plan(self):
         if self.backend == 'torch':
@@ -408,7 +428,8 @@ class EllipticSolver(GeneralSolver):
                  approx_method='Y', sample_center=False, loss_method='diffusion', loss_with_stopped=False,
                  K_test_log=None, PINN_log_variance=False, log_loss_parts=False, boundary_loss=True,
                  boundary_type='Dirichlet', variance_moment_split=False, full_hessian=False, uniform_square=False,
-                 device=None, backend='auto', noise='reference', mlp_dtype='auto', v_l2_error_flag=True, range_guard=True):
+                 device=None, backend='auto', noise='reference', mlp_dtype='auto', v_l2_error_flag=True, range_guard=True,
+                 test_log='reference'):
         self.v_l2_error_flag = v_l2_error_flag   # False: skip the V_L2 diagnostic of solver.py:738 on the native plan (timed runs)
         super().__init__(problem, name, seed=seed, delta_t=delta_t, N=N, lr=lr, L=L, K=K, K_boundary=K_boundary,
                          alpha=alpha, adaptive_forward_process=adaptive_forward_process, detach_forward=detach_forward,
@@ -416,7 +437,7 @@ class EllipticSolver(GeneralSolver):
                          loss_method=loss_method, loss_with_stopped=loss_with_stopped, K_test_log=K_test_log,
                          PINN_log_variance=PINN_log_variance, log_loss_parts=log_loss_parts, boundary_loss=boundary_loss,
                          full_hessian=full_hessian, uniform_square=uniform_square, device=device, backend=backend,
-                         noise=noise, mlp_dtype=mlp_dtype, range_guard=range_guard)
+                         noise=noise, mlp_dtype=mlp_dtype, range_guard=range_guard, test_log=test_log)
         self.approx_method = approx_method
         self.boundary_type = boundary_type
         self.variance_moment_split = variance_moment_split
@@ -446,6 +467,7 @@ class EllipticSolver(GeneralSolver):
         torch.manual_seed(self.seed)
         np.random.seed(self.seed)                                 # solver.py:631
         self._check_scope()
+        self._check_test_log()
         plan = self._choose_plan()
         if plan is not None:
             return plan.train()

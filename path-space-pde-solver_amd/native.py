@@ -31,6 +31,8 @@ DT_F32, DT_F64 = 0, 1
 COMM_ID_BYTES = 128
 DOM_NONE, DOM_SPHERE, DOM_BOX, DOM_BOX_UPPER_ALL, DOM_BOX_UPPER_ANY, DOM_ANNULUS = 0, 1, 2, 3, 4, 5
 ACT_RELU2, ACT_TANH2, ACT_TANH = 0, 1, 2
+TSAMPLE_SUPPLIED, TSAMPLE_BALL, TSAMPLE_ANNULUS, TSAMPLE_BOX = 0, 1, 2, 3     # psp_genl_eval_config.sample_kind
+VTRUE_EXP, VTRUE_QUAD, VTRUE_COMMITTOR = 0, 1, 2                              # psp_genl_eval_config.vtrue_kind
 
 
 class NativeLibraryError(RuntimeError):
@@ -135,6 +137,19 @@ class GenlSizes(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class GenlEvalConfig(C.Structure):
+    _fields_ = [("d", C.c_int32), ("has_time", C.c_int32), ("n_hidden", C.c_int32), ("widths", C.c_int32 * 4),
+                ("activation", C.c_int32), ("linear_layout", C.c_int32), ("time_first", C.c_int32), ("time_scale", C.c_float),
+                ("K_points", C.c_int32), ("sample_kind", C.c_int32), ("k_offset", C.c_int64),
+                ("bound_a", C.c_float), ("bound_b", C.c_float), ("T", C.c_float), ("vtrue_kind", C.c_int32),
+                ("vtrue_par", C.c_float * 4), ("log_slots", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GenlEvalSizes(C.Structure):
+    _fields_ = [("table_bytes", C.c_int64), ("partial_bytes", C.c_int64), ("n_params", C.c_int64),
+                ("workgroups", C.c_int32), ("waves_per_tile", C.c_int32), ("lds_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
 _P = C.c_void_p
 SIGNATURES = {
     "psp_version": (C.c_int, []),
@@ -144,6 +159,10 @@ SIGNATURES = {
     "psp_abi_struct_sizes3": (C.c_int, [C.POINTER(C.c_int32 * 1)]),
     "psp_is_rollout": (C.c_int, [C.POINTER(IsConfig), _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
     "psp_is_query": (C.c_int, [C.POINTER(IsConfig), C.POINTER(C.c_int32)]),
+    "psp_abi_struct_sizes4": (C.c_int, [C.POINTER(C.c_int32 * 2)]),
+    "psp_genl_eval_query": (C.c_int, [C.POINTER(GenlEvalConfig), C.POINTER(GenlEvalSizes)]),
+    "psp_genl_test_error": (C.c_int, [C.POINTER(GenlEvalConfig), _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, C.c_int32, _P,
+                                      _P, _P, _P, _P, _P, _P]),
     "psp_genl_query": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlSizes)]),
     "psp_genl_rollout_fwd": (C.c_int, [C.POINTER(GenlConfig), _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P]),
@@ -234,6 +253,12 @@ def load():
     if list(sizes3) != [C.sizeof(IsConfig)]:
         raise NativeLibraryError("%s was built for other struct layouts (library %s, binding %s): rebuild it"
                                  % (LIB_PATH, list(sizes3), [C.sizeof(IsConfig)]))
+    sizes4 = (C.c_int32 * 2)()
+    lib.psp_abi_struct_sizes4(C.byref(sizes4))
+    mine4 = [C.sizeof(GenlEvalConfig), C.sizeof(GenlEvalSizes)]
+    if list(sizes4) != mine4:
+        raise NativeLibraryError("%s was built for other struct layouts (library %s, binding %s): rebuild it"
+                                 % (LIB_PATH, list(sizes4), mine4))
     _lib = lib
     return lib
 

@@ -210,6 +210,27 @@ class GeneralNativePlan:
         self._extra_grad = None
         self.events = None   # bench.py: HIP-event pairs around the two rollout kernels
         self._batch_views()
+        self.test_log = self._device_test_log()
+
+    def _device_test_log(self):
+        """test_log='device': the K_test_log diagnostic on this plan's stream (device_test_log.py); every rank evaluates all
+        K_test_log points with its replicated parameters -- no collective, identical logs.  None: the host log."""
+        s = self.s
+        if getattr(s, 'test_log', 'reference') != 'device' or s.K_test_log is None:
+            return None
+        try:
+            from . import device_test_log as dtl
+            from .plan_general_deep import value_net_spec
+        except ImportError:
+            import device_test_log as dtl
+            from plan_general_deep import value_net_spec
+        why = dtl.eval_reason(s.problem)
+        net = getattr(self, 'net_spec', None) or value_net_spec(s.V, s.d + (0 if self.elliptic else 1))
+        if why is None and isinstance(net, str):
+            why = net
+        if why is not None:
+            raise ValueError("test_log='device' unavailable: " + why)
+        return dtl.DeviceTestLog(net, s.problem, s.K_test_log, 'elliptic' if self.elliptic else 'parabolic', self.dev, max(1, s.L))
 
     def _batch_views(self):
         """Output views for this iteration's batch (K_local <= K_cap)."""
@@ -474,7 +495,9 @@ class GeneralNativePlan:
                                     self.P, self.step, lr, b1, b2, eps, st), 'psp_adam_step')
         kc = self.kcount.clone()
         sharding.allreduce_sum_(kc)
-        if s.K_test_log is not None:                             # solver.py:1193-1197 / :821-825: after the update, CPU generator
+        if s.K_test_log is not None and self.test_log is not None:     # on the device: the updated parameters, no host sync
+            self.test_log.enqueue(self.flat, s.seed, l, l, st)
+        elif s.K_test_log is not None:                           # solver.py:1193-1197 / :821-825: after the update, CPU generator
             s._log_test_error('elliptic' if ell else 'parabolic')
         return loss, kc
 
@@ -571,6 +594,29 @@ class GeneralNativePlan:
         return tot[0] / float(s.K)
 
     def train(self):
+        s = self.s
+        if self.test_log is None:
+            return self._train_loop()
+        self.test_log.begin(max(1, s.L))
+        try:
+            self._train_loop()
+        except BaseException:                                        # the log of the iterations that ran; the loop's error survives
+            try:
+                self._read_test_log()
+            except Exception:
+                pass
+            raise
+        self._read_test_log()
+
+    def _read_test_log(self):
+        """The one read-back of the device test log."""
+        s = self.s
+        l2, mae, mre = self.test_log.read()
+        s.V_test_L2 += l2
+        s.V_test_abs += mae
+        s.V_test_rel_abs += mre
+
+    def _train_loop(self):
         import time
         s = self.s
         losses, counts, vl2, Ks = [], [], [], []

@@ -523,6 +523,10 @@ class HeatEquation:
     def v_true(self, x, t):
         return torch.sum(x ** 2, 1) + 2 * (self.T - t) * self.d
 
+    def native_vtrue_spec(self):
+        """v_true as a closed form of the device test log (include/psp.h PSP_VTRUE_QUAD: |x|^2 + p0 (p1 - t))."""
+        return {'kind': _nat.VTRUE_QUAD, 'par': (2.0 * self.d, float(self.T), 0.0, 0.0)}
+
 
 # ---------------------------------------------------------------------------------------------
 # bounded domains (SURVEY 8f rank 3): the exponential-on-the-ball family and a box problem
@@ -577,6 +581,10 @@ class _ExpBall:
                     'h_par': (float(self.alpha), float(self.d), par, par)}
         return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': float(self.B[0, 0]), 'h': kind,
                 'h_par': (float(self.alpha), float(self.d), par, par)}
+
+    def native_vtrue_spec(self):
+        """v_true = exp(alpha |x|^2 [+ t]) as a closed form of the device test log (include/psp.h PSP_VTRUE_EXP)."""
+        return {'kind': _nat.VTRUE_EXP, 'par': (float(self.alpha), 1.0 if self._parabolic else 0.0, 0.0, 0.0)}
 
 
 class _ExpBallElliptic(_ExpBall):
@@ -688,6 +696,10 @@ class Committor:
         r = torch.sqrt(torch.sum(x ** 2, 1))
         return (self.a ** 2 - r ** (2 - self.d) * self.a ** self.d) / (self.a ** 2 - self.c ** (2 - self.d) * self.a ** self.d)
 
+    def native_vtrue_spec(self):
+        """v_true as a closed form of the device test log (include/psp.h PSP_VTRUE_COMMITTOR: a, c, d)."""
+        return {'kind': _nat.VTRUE_COMMITTOR, 'par': (float(self.a), float(self.c), float(self.d), 0.0)}
+
     def general_native_spec(self):
         return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': 1.0, 'h': _nat.GH_ZERO}
 
@@ -729,6 +741,10 @@ class QuadraticOnBox:
 
     def v_true(self, x, t=None):
         return torch.sum(x ** 2, 1)
+
+    def native_vtrue_spec(self):
+        """v_true = |x|^2 as a closed form of the device test log (include/psp.h PSP_VTRUE_QUAD with p0 = 0)."""
+        return {'kind': _nat.VTRUE_QUAD, 'par': (0.0, 0.0, 0.0, 0.0)}
 
     def general_native_spec(self):
         h = _nat.GH_QUAD if self.quad_h else _nat.GH_ZERO

@@ -504,3 +504,50 @@ def compute_test_error(model, problem, K, device=None, modus='elliptic'):
             v_est = model.V(X).squeeze().cpu().numpy()
     diff = v_true - v_est
     return float(np.mean(diff ** 2)), float(np.mean(np.abs(diff))), float(np.mean(np.abs(diff) / v_true))
+
+
+def compute_test_error_native(model, problem, K, modus='elliptic', seed=None, iteration=0, return_points=False):
+    """``compute_test_error`` on the device (psp_genl_test_error, csrc/genl_eval_kernels.h): the K points are drawn from the
+    sampler's own Philox stream (seed, iteration), V and the problem's closed-form v_true are evaluated and the statistics
+    reduced by two kernels.  Serves every value net ``plan_general_deep.value_net_spec`` accepts -- the two-layer and the deep
+    plan's nets alike.  Returns (L2 error, mean absolute error, mean relative error) like compute_test_error; with
+    ``return_points`` a fourth entry, a dict of the per-point device tensors x (K, d), t, v, v_true (K) and keep (K, bool: False
+    for the points 'two_spheres' rejects).  ``seed`` defaults to ``model.seed``.
+    NotImplementedError with the reason when the net, the domain or the problem is not covered."""
+    try:
+        from . import device_test_log as dtl
+        from .plan_general_deep import value_net_spec
+    except ImportError:
+        import device_test_log as dtl
+        from plan_general_deep import value_net_spec
+    if modus not in ('elliptic', 'parabolic'):
+        raise ValueError("modus must be 'elliptic' or 'parabolic'")
+    why = dtl.eval_reason(problem)
+    if why is not None:
+        raise NotImplementedError('native test error unavailable: ' + why)
+    d = problem.d
+    net = value_net_spec(model.V, d + (1 if modus == 'parabolic' else 0))
+    if isinstance(net, str):
+        raise NotImplementedError('native test error unavailable: ' + net)
+    if len(net['dims']) - 2 > 4:
+        raise NotImplementedError('native test error unavailable: V has %d hidden layers (the native value-net kernels take 1 to 4)'
+                                  % (len(net['dims']) - 2))
+    sizes, why = dtl.eval_query(dtl.eval_config(net, problem, K, modus))
+    if sizes is None:
+        raise NotImplementedError('native test error unavailable: ' + why)
+    dev = net['params'][0].device
+    if dev.type != 'cuda':
+        raise NotImplementedError('native test error unavailable: the value net lives on %s (the HIP kernels need a GPU)' % dev)
+    log = dtl.DeviceTestLog(net, problem, K, modus, dev)
+    flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in net['params']]).contiguous()
+    dumps = None
+    if return_points:
+        f32 = dict(dtype=torch.float32, device=dev)
+        dumps = {'x': torch.zeros(K, d, **f32), 't': torch.zeros(K, **f32), 'v': torch.zeros(K, **f32),
+                 'v_true': torch.zeros(K, **f32), 'keep': torch.zeros(K, dtype=torch.int32, device=dev)}
+    log.enqueue(flat, model.seed if seed is None else seed, iteration, 0, nat.stream_ptr(dev), dumps)
+    l2, mae, mre = (v[0] for v in log.read())
+    if return_points:
+        dumps['keep'] = dumps['keep'].bool()
+        return l2, mae, mre, dumps
+    return l2, mae, mre
