@@ -56,7 +56,10 @@ extern "C" {
                          *        psp_hjb_basis_params / psp_hjb_basis_grad -- the per-iteration transforms of a rollout in the
                          *        sigma basis;
                          *        psp_genl_eval_config / psp_genl_eval_query / psp_genl_test_error / psp_abi_struct_sizes4 -- the
-                         *        K_test_log diagnostic sampled, evaluated and reduced on the device (PSP_TSAMPLE_*, PSP_VTRUE_*) */
+                         *        K_test_log diagnostic sampled, evaluated and reduced on the device (PSP_TSAMPLE_*, PSP_VTRUE_*);
+                         *        psp_genl_coeffs / psp_genl_query_lq / psp_genl_rollout_fwd_lq -- Z = sigma grad V, a dense drift matrix
+                         *        and the diagonal running cost in the run-time-shaped value-net kernels (Solver's value-function
+                         *        ansatz on LLGC / LQGC); the struct carries its own size instead of joining psp_abi_struct_sizes* */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
@@ -471,6 +474,40 @@ int psp_genl_rollout_fwd(const psp_genl_config* cfg, const float* params, const 
  * `tables` must hold the tables of the SAME parameters (psp_genl_rollout_fwd leaves them there). */
 int psp_genl_rollout_bwd(const psp_genl_config* cfg, const float* params, const float* tables, const float* path,
                          const float* ahat, const float* wY, const float* wV, float* grad_partial, float* grad_out, void* stream);
+
+/* Linear-quadratic coefficients of the forward rollout (appended in 0.4.0, no version bump): what
+ * Solver(approx_method='value_function') needs on LLGC with off-diagonal entries and on LQGC (reference problems.py:14-65,
+ * 118-175; solver.py:334-339, 471-478).  They travel beside psp_genl_config, which keeps its layout.  With g = grad_x V(X_n, t_n):
+ *   Z  = B^T g (PSP_GENL_Z_SIGMA_T: GeneralSolver / EllipticSolver, solver.py:729 / :1104) or B g (PSP_GENL_Z_SIGMA: the ansatz of
+ *        Solver, solver.py:338);  B = cfg->sigma, or base.sigma_scale I;
+ *   w  = xi sqrt(dt) + c dt,  c = -Z (base.adaptive) or 0;   X += (b(X) dt + B w) alive,  b(X) = A X with `drift_matrix`
+ *        (one more d x d product per step from a table of dt A; the boxes' exit test sees the whole proposal), else base.drift_kind;
+ *   Y += ((-h + Z . c) dt + Z . xi sqrt(dt)) act;  DIAG_QUAD: -h = |Z|^2 / 2 + sum_i runcost[i] x_i^2 at the state AFTER the move
+ *        (solver.py:477: h sees the updated X), PSP_GH_QUAD only;
+ *   stored tangent U = act B u (Z_SIGMA_T) or act B^T u (Z_SIGMA), u = w (+ dt Z with PSP_GH_QUAD): Z . w = g . B^T w and
+ *        d(|Z|^2 / 2) = (B^T Z) . dg, so psp_genl_rollout_bwd consumes (x, t), U and a^ unchanged -- call it with the same cfg.
+ * The running cost does not depend on the parameters while the state path is detached: a^ is what it is without it.
+ * Any coefficient that is set runs the dense-sigma path (s I then goes through the tables of B).  A NULL or all-zero struct --
+ * and one that asks for nothing: Z_SIGMA_T, RUNCOST_ZERO, no matrix -- means psp_genl_query / psp_genl_rollout_fwd exactly: the
+ * same plan, kernel instance and bits. */
+enum { PSP_GENL_Z_SIGMA_T = 0, PSP_GENL_Z_SIGMA = 1 };
+typedef struct psp_genl_coeffs {
+    int32_t struct_bytes;        /* sizeof(psp_genl_coeffs): checked by the library (this struct is not in psp_abi_struct_sizes*) */
+    int32_t z_kind;              /* PSP_GENL_Z_*                                                                                 */
+    int32_t runcost_kind;        /* PSP_RUNCOST_ZERO | PSP_RUNCOST_DIAG_QUAD                                                     */
+    int32_t reserved;
+    const float* drift_matrix;   /* A, DEVICE, d*d row-major fp32: b(x) = A x (base.drift_kind must be PSP_DRIFT_ZERO); NULL:
+                                  * base.drift_kind as in psp_genl_rollout_fwd                                                    */
+    const float* runcost;        /* DIAG_QUAD: p, DEVICE, d floats; else NULL                                                    */
+} psp_genl_coeffs;
+/* psp_genl_query with the coefficients: table_bytes grows by the table of dt A (and by those of B, B^T where the config alone
+ * would not build them).  <0 as psp_genl_query, or: wrong struct_bytes, an enum out of range, DIAG_QUAD without a vector or with
+ * another h than PSP_GH_QUAD, a drift matrix together with a non-zero base.drift_kind.  No GPU needed. */
+int psp_genl_query_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, psp_genl_sizes* out);
+/* psp_genl_rollout_fwd with the coefficients (every other argument as there; `tables`: psp_genl_query_lq's table_bytes). */
+int psp_genl_rollout_fwd_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const float* params, const float* x0,
+                            const float* t0, const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path,
+                            float* ahat, float* VN, float* YN, float* XN, float* tN, unsigned long long* kcount, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Solver.train with a DenseNet control (function_space.py:116-140: dense-concat layers, relu^2, weights (in, out)):

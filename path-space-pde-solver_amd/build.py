@@ -100,6 +100,9 @@ def _build(force, jobs, verbose, only):
     vinst_src = os.path.join(CSRC, "genl_eval_instance.hip")
     tasks.append((vinst_src, os.path.join(OBJ, "genl_eval_inst.o"), NOSLP,
                   [vinst_src, os.path.join(CSRC, "genl_eval_kernels.h"), os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr]))
+    # the linear-quadratic instances of the run-time-shaped forward kernel (psp_genl_rollout_fwd_lq): three waves-per-tile variants
+    lqinst_src = os.path.join(CSRC, "genl_lq_instance.hip")
+    tasks.append((lqinst_src, os.path.join(OBJ, "genl_lq_inst.o"), NOSLP, [lqinst_src, os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr]))
     for d, H in instances("dense_instances.def"):
         tasks.append((dinst_src, os.path.join(OBJ, "dnet_inst_%d_%d.o" % (d, H)),
                       ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [dinst_src, dhdr, ugrid, whdr, hdr]))

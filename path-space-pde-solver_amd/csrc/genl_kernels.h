@@ -43,6 +43,16 @@
 // products -- A operand = a k-quad-major table of B^T resp. B built by genl_tables_kernel next to the weight tables, B operand =
 // a T-layout LDS image -- and run through genl_gemm1 / genl_gemm1x2; their output blocks are dealt over the tile's waves
 // (block ob -> wave ob mod NW, as in the reverse sweep) and exchanged through the images.
+// Linear-quadratic coefficients (genl_fwd_kernel<NW, true, true>; Solver's value-function ansatz on LLGC / LQGC, reference
+// solver.py:334-339, 471-478, problems.py:14-65, 118-175): the ansatz takes Z = B grad_x V -- the OTHER orientation --, the drift
+// is b(x) = A x with a dense A, and h carries the running cost f(x) = sum_i p_i x_i^2 at the state AFTER the move:
+//   Z = B g (table tSB),   w = xi sqrt(dt) + c dt,   X += ((dt A) X + B w) alive,
+//   Y += ((|Z|^2 / 2 + f(X_{n+1}) + Z . c) dt + Z . xi sqrt(dt)) act,   u = w (+ dt Z),   U = act B^T u.
+// Z . w = g . B^T w and d(|Z|^2 / 2) = (B^T Z) . dg, so dY_N / dtheta is again the sum of  a^ dV/dtheta + d/dtheta (g . U): the same
+// backward kernel.  f does not depend on theta while the state path is detached, so a^ is untouched.  (dt A) X is one more product
+// of the same shape -- A operand: a table of dt A built next to tSB (rows and columns >= d zero: the time row never enters),
+// B operand: the X image in A -- accumulated into the accumulator of B w, so the boxes' proposal test sees it and no image is added.
+// B w and B^T u read different tables: three sigma products and the drift product per step.
 #pragma once
 #include "gen_kernels.h"
 
@@ -96,6 +106,13 @@ struct GenlArgs {
     int dense;                      // 1: genl_fwd_kernel<NW, true> runs; the tables of B and B^T are built
     const float* sigmaB;            // B (d x d row-major); NULL with dense = 1: B = g.sigma_scale I
     long long tSB, tSBT;            // float offsets of the A-operand tables of B (for B w, B u) and of B^T (for B^T grad V)
+    // linear-quadratic coefficients (appended; lq = 1: genl_fwd_kernel<NW, true, true> runs)
+    int lq;
+    int z_sigma;                    // 1: Z = B grad_x V and U = act B^T u (Solver's value-function ansatz) instead of Z = B^T grad_x V, U = act B u
+    int runcost_kind;               // 1: f(x) = sum_i runcost[i] x_i^2 enters h at the state after the move (h_kind = GH_QUAD only)
+    const float* driftA;            // A (d x d row-major): b(x) = A x; NULL: g.drift_kind
+    const float* runcost;           // p (d)
+    long long tA;                   // float offset of the A-operand table of dt A
 };
 
 // padded feature index -> real index inside the concatenation a (or -1: padding)
@@ -183,6 +200,7 @@ __global__ __launch_bounds__(256) void genl_tables_kernel(const GenlArgs a) {
             else if (in && row == col) m = mt = a.g.sigma_scale;
             T[a.tSB + idx] = m;
             T[a.tSBT + idx] = mt;
+            if (a.driftA) T[a.tA + idx] = in ? a.g.dt * a.driftA[(size_t)row * d + col] : 0.f;     // (dt A) X: same layout as B
         }
     }
     for (long long idx = gtid; idx < (long long)a.TB * 16; idx += gn) {       // output layer over the padded concatenation
@@ -349,9 +367,11 @@ __host__ __device__ inline int genl_fwd_lds_bytes_dense(int TB, int DB0) { retur
 //  instruction count, not by the L2 latency of the tables) and cost a batch that fills the chip 75 % (72.7 -> 127 ms at K = 65536:
 //  three workgroups per CU instead of twelve, and every workgroup copies the tables).)
 // DENSE: sigma = B through the tables tSB / tSBT (header comment); a template parameter, so that the instances of sigma = s I
-// stay the code they were
-template <int NW, bool DENSE = false>
+// stay the code they were.  LQ (with DENSE only): the linear-quadratic coefficients of the header comment, as uniform run-time
+// branches inside instances of their own -- for the same reason
+template <int NW, bool DENSE = false, bool LQ = false>
 __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(const GenlArgs ga_) {
+    static_assert(DENSE || !LQ, "the linear-quadratic coefficients run on the dense-sigma path");
     PSP_COND_EXIT(ga_.g);
     const KArgs ga = &ga_;
     const KGen a = &ga->g;
@@ -469,9 +489,11 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
         if constexpr (DENSE) {
             const int KSd = 4 * DB0;
             const bool quad = a->h_kind == GH_QUAD;
+            bool zs = false;                                         // LQ: Z = B grad_x V, and the stored tangent is B^T u
+            if constexpr (LQ) zs = ga->z_sigma != 0;
             for (int ob = wave; ob < DB0; ob += NW) {                // Z = B^T grad_x V
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                genl_gemm1<8>(acc, T + ga->tSBT + (size_t)ob * KSd * 64, KSd, G, lane);
+                genl_gemm1<8>(acc, T + (zs ? ga->tSB : ga->tSBT) + (size_t)ob * KSd * 64, KSd, G, lane);
                 img_put(Zi, ob, acc, lane);
             }
             tile_sync<NW>();
@@ -492,16 +514,23 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             tile_sync<NW>();                                         // (every wave has read Z: its image may take B u)
             for (int ob = wave; ob < DB0; ob += NW) {                // B w (the move; the boxes test it) and B u (the stored tangent)
                 f32x4 acw = {0.f, 0.f, 0.f, 0.f}, acu = {0.f, 0.f, 0.f, 0.f};
-                if (quad) {
+                if (zs) {                                            // B w and B^T u: two tables, nothing shared
+                    genl_gemm1<8>(acw, T + ga->tSB + (size_t)ob * KSd * 64, KSd, Wi, lane);
+                    genl_gemm1<8>(acu, T + ga->tSBT + (size_t)ob * KSd * 64, KSd, quad ? Ui : Wi, lane);
+                    img_put(Zi, ob, acu, lane);
+                } else if (quad) {
                     genl_gemm1x2<4>(acw, acu, T + ga->tSB + (size_t)ob * KSd * 64, KSd, Wi, Ui, lane);
                     img_put(Zi, ob, acu, lane);
                 } else {
                     genl_gemm1<8>(acw, T + ga->tSB + (size_t)ob * KSd * 64, KSd, Wi, lane);
                 }
+                if constexpr (LQ) {                                  // + (dt A) X: the X image of this step; columns >= d of the table are zero
+                    if (ga->driftA) genl_gemm1<8>(acw, T + ga->tA + (size_t)ob * KSd * 64, KSd, A, lane);
+                }
                 img_put(G, ob, acw, lane);
             }
             tile_sync<NW>();
-            if (quad) BU = Zi;
+            if (quad || zs) BU = Zi;
         }
         float rr = 0.f, sx = 0.f;
         if (a->domain_kind == DOM_SPHERE || a->domain_kind == DOM_ANNULUS || a->h_kind >= GH_EXPBALL_LIN) {
@@ -593,6 +622,19 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             }
             minus_h = Vnow * lin - nl;
             hy = nly - lin;
+        }
+        if constexpr (LQ) {
+            if (ga->runcost_kind != 0) {                             // + f(X_{n+1}): Solver's h sees the state AFTER the move (solver.py:477)
+                float fx = 0.f;
+#pragma unroll
+                for (int b = 0; b < GENL_MAXDB; ++b)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int f = 16 * b + 4 * r + qv;
+                        if (b < DB0 && f < D) fx = fmaf(ga->runcost[f] * X[b][r], X[b][r], fx);
+                    }
+                minus_h += qsum(fx);
+            }
         }
         const float zc = a->adaptive ? -S : 0.f;
         Y = Y + ((minus_h + zc) * dt + Pz * sqdt) * actf;
@@ -832,12 +874,15 @@ __global__ __launch_bounds__(64 * NW) void genl_bwd_kernel(const GenlArgs ga_) {
 }
 
 // host side: launches (the dynamic LDS size exceeds the 64 KiB default)
-template <int NW, bool DENSE = false> inline hipError_t genl_launch_fwd(const GenlArgs& a, int ntile16, int lds_bytes, hipStream_t st) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW, DENSE>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+template <int NW, bool DENSE = false, bool LQ = false> inline hipError_t genl_launch_fwd(const GenlArgs& a, int ntile16, int lds_bytes, hipStream_t st) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW, DENSE, LQ>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((genl_fwd_kernel<NW, DENSE>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
+    hipLaunchKernelGGL((genl_fwd_kernel<NW, DENSE, LQ>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
     return hipGetLastError();
 }
+// the linear-quadratic instances <NW, true, true> are compiled in a unit of their own (genl_lq_instance.hip), so that the unit
+// of the other instances holds the kernels it held; nw = 1, 4 or 8
+hipError_t genl_lq_launch_fwd(const GenlArgs& a, int nw, int ntile16, int lds_bytes, hipStream_t st);
 template <int NW, int MS = GenlGeo<NW>::MAXSLOT> inline hipError_t genl_launch_bwd(const GenlArgs& a, int grid, int groups, int lds_bytes, hipStream_t st) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_bwd_kernel<NW, MS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;

@@ -1225,8 +1225,26 @@ int psp_gen_rollout_bwd(const psp_gen_config* cfg, const float* params, const fl
 namespace {
 struct GenlPlan { psp::GenlArgs a; int ntile16; long long table_floats; long long n_params; int fwd_lds, bwd_lds, nw_fwd, nw_bwd,
                   bwd_grid, bwd_groups; };
-int make_genl_plan(const psp_genl_config* c, GenlPlan* p) {
+// q: the linear-quadratic coefficients of psp_genl_query_lq / psp_genl_rollout_fwd_lq (NULL or all zero: none -- the plan, the
+// table layout and the kernel instance of psp_genl_rollout_fwd)
+int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs* q = nullptr) {
     if (!c) return fail(-1, "null config");
+    if (q) {
+        static const psp_genl_coeffs zero = {};
+        if (memcmp(q, &zero, sizeof(zero)) == 0) q = nullptr;
+    }
+    if (q) {
+        if (q->struct_bytes != (int32_t)sizeof(psp_genl_coeffs)) return fail(-1, "psp_genl_coeffs.struct_bytes is not sizeof(psp_genl_coeffs)");
+        if (q->z_kind < PSP_GENL_Z_SIGMA_T || q->z_kind > PSP_GENL_Z_SIGMA || q->runcost_kind < PSP_RUNCOST_ZERO ||
+            q->runcost_kind > PSP_RUNCOST_DIAG_QUAD)
+            return fail(-1, "coefficient enum out of range");
+        if (q->runcost_kind == PSP_RUNCOST_DIAG_QUAD && !q->runcost) return fail(-1, "running-cost vector missing");
+        if (q->runcost_kind != PSP_RUNCOST_ZERO && c->base.h_kind != PSP_GH_QUAD)
+            return fail(-1, "a running cost is defined for h = -|z|^2 / 2 - f(x) only (PSP_GH_QUAD)");
+        if (q->drift_matrix && c->base.drift_kind != PSP_DRIFT_ZERO)
+            return fail(-1, "a drift matrix excludes base.drift_kind (give A alone, or the diagonal kind alone)");
+        if (q->z_kind == PSP_GENL_Z_SIGMA_T && q->runcost_kind == PSP_RUNCOST_ZERO && !q->drift_matrix) q = nullptr;   // nothing asked
+    }
     const psp_gen_config& b = c->base;
     if (b.d <= 0 || b.K_local <= 0 || b.N <= 0) return fail(-1, "non-positive d/K/N");
     const int L = c->n_hidden;
@@ -1278,10 +1296,17 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p) {
     // form (with a scaled identity the tables kernel writes s I) -- adds the tables of B and B^T
     a.dense = (c->sigma_kind == PSP_GENL_SIGMA_DENSE || b.h_kind == PSP_GH_EXPBALL_SIN_FULL) ? 1 : 0;
     a.sigmaB = c->sigma_kind == PSP_GENL_SIGMA_DENSE ? c->sigma : nullptr;
+    if (q) {                                                                     // (they run on the dense path: s I through the tables)
+        a.dense = 1; a.lq = 1;
+        a.z_sigma = q->z_kind == PSP_GENL_Z_SIGMA ? 1 : 0;
+        a.runcost_kind = q->runcost_kind; a.runcost = q->runcost_kind ? q->runcost : nullptr;
+        a.driftA = q->drift_matrix;
+    }
     if (a.dense) {
         tofs = (tofs + 3) & ~3LL;                                                // (16-byte table loads)
         a.tSB = tofs; tofs += (long long)a.DB0 * 4 * a.DB0 * 64;
         a.tSBT = tofs; tofs += (long long)a.DB0 * 4 * a.DB0 * 64;
+        if (a.driftA) { a.tA = tofs; tofs += (long long)a.DB0 * 4 * a.DB0 * 64; }   // dt A, behind the tables psp_genl_rollout_bwd reads
     }
     p->table_floats = tofs; p->n_params = pofs;
     p->ntile16 = (b.K_local + 15) / 16;
@@ -1327,9 +1352,11 @@ int* genl_nexec(const psp_genl_config* cfg, const GenlPlan& p, const float* ahat
 }
 }  // namespace
 
-int psp_genl_query(const psp_genl_config* cfg, psp_genl_sizes* out) {
+int psp_genl_query(const psp_genl_config* cfg, psp_genl_sizes* out) { return psp_genl_query_lq(cfg, nullptr, out); }
+
+int psp_genl_query_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, psp_genl_sizes* out) {
     GenlPlan p;
-    int rc = make_genl_plan(cfg, &p);
+    int rc = make_genl_plan(cfg, &p, coeffs);
     if (rc) return rc;
     if (!out) return fail(-1, "null output");
     memset(out, 0, sizeof(*out));
@@ -1350,8 +1377,14 @@ int psp_genl_query(const psp_genl_config* cfg, psp_genl_sizes* out) {
 int psp_genl_rollout_fwd(const psp_genl_config* cfg, const float* params, const float* x0, const float* t0,
                                     const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path, float* ahat,
                                     float* VN, float* YN, float* XN, float* tN, unsigned long long* kcount, void* stream) {
+    return psp_genl_rollout_fwd_lq(cfg, nullptr, params, x0, t0, xi, seed, iter, tables, path, ahat, VN, YN, XN, tN, kcount, stream);
+}
+
+int psp_genl_rollout_fwd_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const float* params, const float* x0,
+                            const float* t0, const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path, float* ahat,
+                            float* VN, float* YN, float* XN, float* tN, unsigned long long* kcount, void* stream) {
     GenlPlan p;
-    int rc = make_genl_plan(cfg, &p);
+    int rc = make_genl_plan(cfg, &p, coeffs);
     if (rc) return rc;
     if (!params || !x0 || !tables || !VN || !YN || !XN || !tN || !kcount || !ahat) return fail(-1, "null buffer passed to psp_genl_rollout_fwd");
     if (cfg->has_time && !t0) return fail(-1, "t0 missing");
@@ -1369,7 +1402,9 @@ int psp_genl_rollout_fwd(const psp_genl_config* cfg, const float* params, const 
     hipLaunchKernelGGL(psp::genl_tables_kernel, dim3(128), dim3(256), 0, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "genl_tables_kernel launch");
-    if (p.a.dense)
+    if (p.a.lq)
+        e = psp::genl_lq_launch_fwd(p.a, p.nw_fwd, p.ntile16, p.fwd_lds, st);        // (genl_lq_instance.hip)
+    else if (p.a.dense)
         e = p.nw_fwd == 1 ? psp::genl_launch_fwd<1, true>(p.a, p.ntile16, p.fwd_lds, st)
             : p.nw_fwd == 4 ? psp::genl_launch_fwd<4, true>(p.a, p.ntile16, p.fwd_lds, st) : psp::genl_launch_fwd<8, true>(p.a, p.ntile16, p.fwd_lds, st);
     else

@@ -130,6 +130,16 @@ class GenlConfig(C.Structure):
                 ("sigma_kind", C.c_int32), ("reserved", C.c_int32), ("sigma", C.c_void_p)]
 
 
+GENL_Z_SIGMA_T, GENL_Z_SIGMA = 0, 1             # psp_genl_coeffs.z_kind
+
+
+class GenlCoeffs(C.Structure):
+    """psp_genl_coeffs: the linear-quadratic coefficients beside a GenlConfig (psp_genl_query_lq / psp_genl_rollout_fwd_lq).  The
+    library checks ``struct_bytes`` itself; the struct is not part of psp_abi_struct_sizes*."""
+    _fields_ = [("struct_bytes", C.c_int32), ("z_kind", C.c_int32), ("runcost_kind", C.c_int32), ("reserved", C.c_int32),
+                ("drift_matrix", C.c_void_p), ("runcost", C.c_void_p)]
+
+
 class GenlSizes(C.Structure):
     _fields_ = [("table_bytes", C.c_int64), ("path_bytes", C.c_int64), ("ahat_bytes", C.c_int64), ("n_params", C.c_int64),
                 ("grad_partial_bytes", C.c_int64), ("n_blocks", C.c_int32), ("fwd_workgroups", C.c_int32),
@@ -167,6 +177,9 @@ SIGNATURES = {
     "psp_genl_rollout_fwd": (C.c_int, [C.POINTER(GenlConfig), _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P]),
     "psp_genl_rollout_bwd": (C.c_int, [C.POINTER(GenlConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psp_genl_query_lq": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlSizes)]),
+    "psp_genl_rollout_fwd_lq": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P,
+                                          _P, _P, _P, _P, _P, _P, _P, _P]),
     "psp_hjb_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "psp_hjb_family": (C.c_int, [C.c_int32, C.c_int32]),
     "psp_hjb_adjoint_sweep": (C.c_int, [C.POINTER(HjbConfig), _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -16,6 +16,13 @@ Details that differ from GeneralSolver and are absorbed by the parameter index m
 the net input is [t, x] with time FIRST (solver.py:343-344) and the reference feeds the STEP INDEX n as the time
 (Y_n(X, n), solver.py:336, 439), while the kernel's time register holds n * dt: the time rows are moved to the kernels' last
 input row and scaled by 1/dt on the way in (and the gradient on the way out).
+
+Linear-quadratic coefficients (LLGC with off-diagonal entries, LQGC: a dense sigma B, a dense drift matrix A, the running cost
+f(x) = sum_i p_i x_i^2): the ansatz takes Z = B grad_x V -- not B^T grad_x V as GeneralSolver does --, and h sees f at the state
+AFTER the move (solver.py:338, 471-478).  Such cases always run on the run-time-shaped kernels (csrc/genl_kernels.h,
+genl_fwd_kernel<NW, true, true>), whatever the net, through psp_genl_query_lq / psp_genl_rollout_fwd_lq with a psp_genl_coeffs
+beside the config (``lq_coeffs``); the backward call and the weights above are the same, because the kernel stores the tangent
+direction U = B^T u and f does not depend on the parameters while the state path is detached.
 """
 import ctypes as C
 
@@ -68,22 +75,76 @@ def value_eligibility(solver):
     over = _overridden(s.problem)
     if over is not None:
         return 'problem.%s is not the catalogue implementation native_spec() describes' % over
-    if spec['sigma'][0] not in (nat.SIGMA_IDENTITY, nat.SIGMA_SCALED_IDENTITY):
-        return 'a dense sigma is not built into the value-net kernels (identity / scaled identity are)'
-    if spec['drift'][0] == nat.DRIFT_DENSE:
-        return 'a dense drift matrix is not built into the value-net kernels (zero / diagonal / double well are)'
-    if spec['runcost'][0] != nat.RUNCOST_ZERO:
-        return 'a running cost f(x) is not built into the value-net kernels (h = -|z|^2 / 2 is)'
+    if spec['runcost'][0] not in (nat.RUNCOST_ZERO, nat.RUNCOST_DIAG_QUAD):
+        return 'running cost kind %r is not built into the value-net kernels (zero / diagonal quadratic are)' % (spec['runcost'][0],)
     if not nat.is_built():
         raise nat.NativeLibraryError('libpsp_hip.so is not built; run __graft_entry__.build()')
+    if needs_lq(spec):
+        # a dense sigma, a dense drift matrix or a running cost: the run-time-shaped family only, whatever the net
+        net = _deep_net(s, V, force=True)
+        if net is None:
+            return 'a dense sigma / dense drift / running cost runs on the run-time-shaped value-net kernels only, and the ' \
+                   'value net (input %d) is %s' % (s.d + 1, _deep_net(s, V, why=True, force=True))
+        g = nat.GenlConfig()
+        g.base.d, g.base.K_local, g.base.N, g.base.h_kind = s.d, 16, 1, nat.GH_QUAD
+        g.has_time, g.n_hidden = 1, len(net['dims']) - 2
+        for i, h in enumerate(net['dims'][1:-1]):
+            g.widths[i] = int(h)
+        q = nat.GenlCoeffs(struct_bytes=C.sizeof(nat.GenlCoeffs), z_kind=nat.GENL_Z_SIGMA)
+        lib = nat.load()
+        if lib.psp_genl_query_lq(C.byref(g), C.byref(q), C.byref(nat.GenlSizes())) != 0:     # (the 160 KiB LDS rule)
+            return lib.psp_last_error().decode()
+        return None
     if deep is None and not shapes.gen_candidates(s.d, dims[1]):
         return 'no compiled kernel instance covers d=%d, H=%d (see csrc/gen_instances.def)' % (s.d, dims[1])
     return None
 
 
-def _deep_net(solver, V, why=False):
+def needs_lq(spec):
+    """Whether a native_spec() carries a coefficient only the linear-quadratic instances of the run-time-shaped kernels take."""
+    return (spec['sigma'][0] == nat.SIGMA_DENSE or spec['drift'][0] == nat.DRIFT_DENSE
+            or spec['runcost'][0] == nat.RUNCOST_DIAG_QUAD)
+
+
+def _upload(M, shape, device, keep, what):
+    M = torch.as_tensor(M)
+    if tuple(M.shape) != shape:
+        raise ValueError('native_spec(): %s must have shape %s, got %s' % (what, shape, tuple(M.shape)))
+    t = M.detach().to(device=device, dtype=torch.float32).contiguous()      # row-major by VALUE (a transposed view is copied)
+    keep.append(t)
+    return t
+
+
+def lq_coeffs(gcfg, spec, device, keep):
+    """psp_genl_config.sigma_kind / sigma / base.sigma_scale / base.drift_kind / base.drift and the psp_genl_coeffs beside it from
+    a problem's ``native_spec()`` (gcfg.base.d set).  Matrices and vectors are uploaded row-major in fp32 and kept alive in
+    ``keep``.  Returns the nat.GenlCoeffs, or None where the spec needs none (identity sigma, element-wise drift, f = 0: the
+    plain entry points' behaviour, Z = s grad_x V either way)."""
+    d = int(gcfg.base.d)
+    cfg = gcfg.base
+    cfg.sigma_scale = float(spec['sigma'][2])
+    if spec['sigma'][0] == nat.SIGMA_DENSE:
+        gcfg.sigma_kind, gcfg.sigma = nat.GENL_SIGMA_DENSE, _upload(spec['sigma'][1], (d, d), device, keep, 'sigma').data_ptr()
+    else:
+        gcfg.sigma_kind, gcfg.sigma = nat.GENL_SIGMA_SCALED, None
+    q = nat.GenlCoeffs(struct_bytes=C.sizeof(nat.GenlCoeffs), z_kind=nat.GENL_Z_SIGMA)
+    kind, val = spec['drift']
+    if kind == nat.DRIFT_DENSE:
+        cfg.drift_kind, cfg.drift = nat.DRIFT_ZERO, None
+        q.drift_matrix = _upload(val, (d, d), device, keep, 'the drift matrix').data_ptr()
+    else:
+        cfg.drift_kind = kind
+        cfg.drift = _upload(val, (d,), device, keep, 'the drift vector').data_ptr() if val is not None else None
+    if spec['runcost'][0] == nat.RUNCOST_DIAG_QUAD:
+        q.runcost_kind = nat.RUNCOST_DIAG_QUAD
+        q.runcost = _upload(spec['runcost'][1], (d,), device, keep, 'the running-cost vector').data_ptr()
+    return q if needs_lq(spec) else None
+
+
+def _deep_net(solver, V, why=False, force=False):
     """The dense-concat description of a value net that is NOT the two-equal-hidden-layer relu^2 DenseNet of the templated kernels
-    (any depth 1-4, widths <= 128, relu^2 / tanh^2 / tanh: csrc/genl_kernels.h), or None (why=True: the reason instead)."""
+    (any depth 1-4, widths <= 128, relu^2 / tanh^2 / tanh: csrc/genl_kernels.h), or None (why=True: the reason instead).
+    force: also for a net the templated kernels would take (the linear-quadratic coefficients run on this family only)."""
     try:
         from . import plan_general_deep as pgd
     except ImportError:
@@ -94,7 +155,7 @@ def _deep_net(solver, V, why=False):
     dims = spec['dims']
     templated = (isinstance(V, DenseNet) and len(dims) == 4 and dims[1] == dims[2] and spec['act'] == 'relu2'
                  and bool(shapes.gen_candidates(solver.d, dims[1])))
-    if templated:
+    if templated and not force:
         return 'the templated kernels take it' if why else None
     L = len(dims) - 2
     if L < 1 or L > 4 or max(dims[1:-1]) > 128 or dims[0] > 112:
@@ -119,10 +180,11 @@ class ValueNativePlan:
         self.net = s.y_n[0]
         self.key = None
         self.H = self.net.nn_dims[1]
-        self.deep = _deep_net(s, self.net)              # value nets of other depths / activations: csrc/genl_kernels.h
-        self._flatten(self.net if self.deep is None else self.deep['params'])
         spec = s.problem.native_spec()
+        self.deep = _deep_net(s, self.net, force=needs_lq(spec))      # value nets of other depths / activations: csrc/genl_kernels.h
+        self._flatten(self.net if self.deep is None else self.deep['params'])
         self._keep = []
+        self.coeffs = None                                # psp_genl_coeffs (dense sigma / drift matrix / running cost), deep plans only
         if self.deep is not None:
             self.gcfg = nat.GenlConfig()
             cfg = self.gcfg.base
@@ -135,14 +197,16 @@ class ValueNativePlan:
         cfg.d_real = s.d
         cfg.sigma_scale = float(spec['sigma'][2])
         cfg.drift_kind = spec['drift'][0]
-        cfg.h_kind = nat.GH_QUAD                          # h = -|z|^2 / 2 (problems.py:46, 211, 321 with f = 0)
+        cfg.h_kind = nat.GH_QUAD                          # h = -|z|^2 / 2 (problems.py:46, 211, 321); f(x) travels in psp_genl_coeffs
         cfg.adaptive = 1 if s.adaptive_forward_process else 0
         cfg.noise_mode = nat.NOISE_PHILOX if noise == 'philox' else nat.NOISE_SUPPLIED
         cfg.store_path = 1
         cfg.domain_kind = nat.DOM_NONE
         cfg.per_sample_weights = 1
         drift_vec = spec['drift'][1]
-        if drift_vec is not None:
+        if self.deep is not None:
+            self.coeffs = lq_coeffs(self.gcfg, spec, dev, self._keep)
+        elif drift_vec is not None:
             probe = drift_vec.detach().to(device=dev, dtype=torch.float32).contiguous()
             cfg.drift = nat.ptr(probe)
         f32 = torch.float32
@@ -158,10 +222,8 @@ class ValueNativePlan:
                 g.widths[i] = int(h)
             g.activation, g.linear_layout = _ACT[self.deep['act']], 1 if self.deep['linear'] else 0
             g.time_first, g.time_scale = 1, 1.0 / cfg.dt               # input [t, x], and t is the step index (solver.py:336-338, 439)
-            if drift_vec is not None:
-                self._keep.append(probe)
             sz = nat.GenlSizes()
-            rc = self.lib.psp_genl_query(C.byref(g), C.byref(sz))
+            rc = self.lib.psp_genl_query_lq(C.byref(g), self._coeffs_ref(), C.byref(sz))
             if rc != 0:
                 raise PlanUnsupported(self.lib.psp_last_error().decode())
             assert sz.n_params == self.P, (sz.n_params, self.P)
@@ -208,6 +270,9 @@ class ValueNativePlan:
         self.x0_row = s.X_0.detach().to(device=dev, dtype=f32).reshape(1, -1)
         self.step = 0
         self.events = None
+
+    def _coeffs_ref(self):
+        return C.byref(self.coeffs) if self.coeffs is not None else None
 
     def _flatten(self, V):
         params = list(V) if isinstance(V, (list, tuple)) else list(V.W)      # registration order W1,b1,W2,b2,.. (include/psp.h)
@@ -257,10 +322,11 @@ class ValueNativePlan:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             ev[0].record()
         if self.deep is not None:
-            nat.check(lib.psp_genl_rollout_fwd(C.byref(self.gcfg), nat.ptr(self.flat), nat.ptr(x0), nat.ptr(self.t0), nat.ptr(xi),
-                                               int(s.seed) & 0xFFFFFFFFFFFFFFFF, l, nat.ptr(self.tables), nat.ptr(self.path),
-                                               nat.ptr(self.ahat_buf), nat.ptr(self.VN), nat.ptr(self.YN), nat.ptr(self.XN_k),
-                                               nat.ptr(self.tN), nat.ptr(self.kcount), st), 'psp_genl_rollout_fwd')
+            nat.check(lib.psp_genl_rollout_fwd_lq(C.byref(self.gcfg), self._coeffs_ref(), nat.ptr(self.flat), nat.ptr(x0),
+                                                  nat.ptr(self.t0), nat.ptr(xi), int(s.seed) & 0xFFFFFFFFFFFFFFFF, l,
+                                                  nat.ptr(self.tables), nat.ptr(self.path), nat.ptr(self.ahat_buf), nat.ptr(self.VN),
+                                                  nat.ptr(self.YN), nat.ptr(self.XN_k), nat.ptr(self.tN), nat.ptr(self.kcount), st),
+                      'psp_genl_rollout_fwd_lq')
         else:
             nat.check(lib.psp_gen_rollout_fwd(C.byref(cfg), nat.ptr(flat_k), nat.ptr(x0), nat.ptr(self.t0), nat.ptr(xi),
                                               int(s.seed) & 0xFFFFFFFFFFFFFFFF, l, nat.ptr(self.path), nat.ptr(self.ahat),

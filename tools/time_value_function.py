@@ -1,0 +1,82 @@
+"""Per-iteration time of Solver(approx_method='value_function') on LQGC with off-diagonal entries -- dense drift matrix, dense
+sigma, running cost -- two ways on the same GPU: the native plan (backend='native', noise='philox': the linear-quadratic
+instances of the run-time-shaped value-net kernels, psp_genl_rollout_fwd_lq + psp_genl_rollout_bwd) and the composite torch plan
+(backend='torch': autograd with create_graph=True through every step), which is what this configuration ran on before the
+kernels took these coefficients.
+
+Configuration: LQGC d = 20, off_diag = 0.1, T = 1, delta_t = 0.05 (N = 20), K = 4096, log-variance loss, adaptive forward process
+with the state path detached.
+
+Each plan is warmed up by `--warmup` single-iteration train() calls, then `--iters` single-iteration calls are timed one by one
+(host clock, a device synchronise before and after the timed block); the median is reported.
+
+    python tools/time_value_function.py [--iters 20] [--warmup 5] [--json profiles/value_lq_timing.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+import warnings
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import path_space_pde_solver_amd as psp  # noqa: E402
+
+CONFIG = dict(d=20, off_diag=0.1, T=1.0, delta_t=0.05, K=4096)
+MODES = [("native", dict(backend="native", noise="philox")), ("torch", dict(backend="torch"))]
+
+
+def build(dev, **kw):
+    pb = psp.LQGC(d=CONFIG["d"], off_diag=CONFIG["off_diag"], T=CONFIG["T"], delta_t=CONFIG["delta_t"], seed=42, device=dev)
+    return psp.Solver(name="lqgc_d20_value_function", problem=pb, lr=0.001, L=1, K=CONFIG["K"], delta_t=CONFIG["delta_t"],
+                      approx_method="value_function", time_approx="inner", loss_method="log-variance",
+                      adaptive_forward_process=True, detach_forward=True, early_stopping_time=None, u_l2_error_flag=False,
+                      seed=42, verbose=False, print_every=10 ** 9, device=dev, **kw)
+
+
+def timed_iteration(model):
+    model.L = 1
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    model.train()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("time_value_function.py needs the GPU: a CPU run says nothing about these times")
+    dev = torch.device("cuda:0")
+    out = {"config": dict(CONFIG, N=int(round(CONFIG["T"] / CONFIG["delta_t"])), problem="LQGC", loss_method="log-variance"),
+           "iters": a.iters, "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "plans": {}}
+    ms = {}
+    for name, kw in MODES:
+        model = build(dev, **kw)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            for _ in range(a.warmup):                              # code objects, plan buffers, the first launches
+                timed_iteration(model)
+            assert model.plan_name == name, (name, model.plan_name, model.plan_reason)
+            times = [timed_iteration(model) for _ in range(a.iters)]
+        ms[name] = 1e3 * statistics.median(times)
+        out["plans"][name] = {"noise": kw.get("noise", "reference"), "median_ms_per_iteration": ms[name],
+                              "min_max_ms": [1e3 * min(times), 1e3 * max(times)], "last_loss": model.loss_log[-1]}
+        print("%-7s %.3f ms per iteration (min %.3f, max %.3f)" % (name, ms[name], 1e3 * min(times), 1e3 * max(times)))
+    out["torch_over_native"] = ms["torch"] / ms["native"]
+    print(json.dumps(out))
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
