@@ -1,0 +1,105 @@
+"""float64 reference of ONE iteration of the control-ansatz `Solver` (rollout, loss, backward) -- CPU only.
+
+A plain torch-autograd restatement of oracle.pathspace_oracle.hjb_train (time_approx='inner', approx_method='control') in double
+precision.  Every number it starts from is the fp32 oracle's own, cast to double: OracleProblem.B / .X_0 / .extra (A, alpha, P, R,
+eta_, kappa_), the TanhMLP parameters, the step size (torch.tensor(delta_t), fp32, and its fp32 square root, as solver.py:39-40
+forms them) and the noise tensor (K, d, N + 1).  Nothing is drawn here: a generator yields other numbers in double.
+
+So the result is the exact (to double rounding) answer of the fp32 problem the kernels and the fp32 oracle are given, and the
+distance of either from it is that implementation's own arithmetic error.
+"""
+import numpy as np
+import torch
+
+F64 = torch.float64
+KINDS = ("LLGC", "LQGC", "DoubleWell_multidim")
+LOSSES = ("log-variance", "moment", "variance", "cross_entropy", "relative_entropy")
+
+
+def _coefficients(prob):
+    """(b, f, g) of the problem kind as double-precision closures over the oracle's fp32 data (pathspace_oracle.problem_*)."""
+    ex = prob.extra
+    if prob.kind == "LLGC":
+        A, alpha = ex["A"].to(F64), ex["alpha"].to(F64)
+        return (lambda x: x @ A.t()), (lambda x: torch.zeros(x.shape[0], dtype=F64)), (lambda x: (x @ alpha)[:, 0])
+    if prob.kind == "LQGC":
+        A, P, R = ex["A"].to(F64), ex["P"].to(F64), ex["R"].to(F64)
+        return (lambda x: x @ A.t()), (lambda x: torch.sum(x * (x @ P.t()), 1)), (lambda x: torch.sum(x * (x @ R.t()), 1))
+    if prob.kind == "DoubleWell_multidim":
+        eta, kappa = ex["eta_"].to(F64), ex["kappa_"].to(F64)
+        return ((lambda x: -4.0 * kappa * (x * (x ** 2 - 1.0))), (lambda x: torch.zeros(x.shape[0], dtype=F64)),
+                (lambda x: torch.sum(eta * (x - 1.0) ** 2, 1)))
+    raise NotImplementedError(prob.kind)
+
+
+def _loss(kind, D, Y, gX, Z_sum, adaptive):
+    """pathspace_oracle.hjb_loss (solver.py:164-192)."""
+    if kind == "moment":
+        return D.pow(2).mean()
+    if kind == "log-variance":
+        return D.pow(2).mean() - D.mean().pow(2)
+    if kind == "variance":
+        return torch.var(torch.exp(-gX + Y))
+    if kind == "cross_entropy":
+        return (Y * torch.exp(-gX + (Y.detach() if adaptive else 0.0))).mean()
+    if kind == "relative_entropy":
+        return (Z_sum + gX).mean()
+    raise NotImplementedError(kind)
+
+
+def iteration(prob, cfg, z, noise, weights=None):
+    """One iteration in float64.
+
+    prob: OracleProblem; cfg: HJBConfig (time_approx='inner', control ansatz, fixed X_0, no learnable Y_0); z: the fp32 TanhMLP
+    (read, never modified); noise: (K, d, N + 1) as hjb_train takes it; weights: optional (K,) -- the loss is then sum_k w_k D_k
+    (tests/test_gpu_range_guard._oracle_weighted_gradient).
+
+    Returns dict(D, loss, blocks=[dW1, db1, dW2, db2, dW3, db3], grad (flat, that order), h1, h2 (K, H) at step N // 2, N);
+    D is -(Zsum + g(X_N)) for the relative entropy, as the kernels define it (include/psp.h).
+    """
+    assert cfg.time_approx == "inner" and cfg.approx_method == "control" and not cfg.learn_Y_0 and not cfg.random_X_0
+    assert prob.kind in KINDS and cfg.loss_method in LOSSES
+    d = prob.d
+    xi = noise.detach().to(F64)
+    K = xi.shape[0]
+    N = int(np.floor(prob.T / cfg.delta_t))                            # solver.py:41
+    assert xi.shape == (K, d, N + 1), (tuple(xi.shape), (K, d, N + 1))
+    dt32 = torch.tensor(cfg.delta_t)                                   # solver.py:39-40: the fp32 step and its fp32 root
+    dt, sq = float(dt32), float(torch.sqrt(dt32))
+    B = prob.B.to(F64)
+    b, f, g = _coefficients(prob)
+    W1, b1, W2, b2, W3, b3 = params = [p.detach().to(F64).clone().requires_grad_(True) for p in z.parameters()]
+    assert W1.shape[1] == d + 1 and W3.shape[0] == d
+
+    def net(t, X):                                                     # the input is [t, x]: column 0 of W1 is the time column
+        h1 = torch.tanh(t * W1[:, 0] + X @ W1[:, 1:].t() + b1)
+        h2 = torch.tanh(h1 @ W2.t() + b2)
+        return h2 @ W3.t() + b3, h1, h2
+
+    X = prob.X_0.to(F64).repeat(K, 1)
+    Y = torch.zeros(K, dtype=F64)
+    Z_sum = torch.zeros(K, dtype=F64)
+    mid = {}
+    for n in range(N):
+        Z, h1, h2 = net(n * dt, X)
+        if n == N // 2:
+            mid = dict(h1=h1.detach().clone(), h2=h2.detach().clone())
+        c = -Z if cfg.adaptive_forward_process else torch.zeros_like(Z)
+        if cfg.detach_forward:
+            c = c.detach()
+        dW = xi[:, :, n + 1]
+        X = X + (b(X) + c @ B.t()) * dt + (dW @ B.t()) * sq
+        fX = f(X)                                                      # h and the running cost see the UPDATED state
+        Y = Y + (0.5 * torch.sum(Z ** 2, 1) + fX + torch.sum(Z * c, 1)) * dt + torch.sum(Z * dW, 1) * sq
+        if cfg.loss_method == "relative_entropy":
+            Z_sum = Z_sum + (0.5 * torch.sum(Z ** 2, 1) + fX) * dt
+    gX = g(X)
+    D = Y - gX
+    if weights is not None:
+        loss = (weights.detach().to(F64).cpu() * D).sum()
+    else:
+        loss = _loss(cfg.loss_method, D, Y, gX, Z_sum, cfg.adaptive_forward_process)
+    grads = torch.autograd.grad(loss, params, allow_unused=True)
+    blocks = [torch.zeros_like(p) if q is None else q.detach() for p, q in zip(params, grads)]
+    D_out = -(Z_sum + gX) if cfg.loss_method == "relative_entropy" else D
+    return dict(D=D_out.detach(), loss=float(loss.detach()), blocks=blocks, grad=torch.cat([q.reshape(-1) for q in blocks]), N=N, **mid)

@@ -1,14 +1,14 @@
 """Randomised differential test of the native Solver plan against the CPU oracle: 28 configurations drawn from a fixed
 seed over state dimension (1 .. 140), hidden width (3 .. 64), trajectory count (1 .. 300, mostly ragged), step count
 (1 .. 9), problem kind, loss, adaptive / detached flags, random initial points and learnable Y_0.  First iteration:
-D_k, gradient and loss with the bars of test_gpu_parity.py."""
+D_k, gradient (whole and per block) and loss with the bars of test_gpu_parity.py."""
 import math
 import random
 
 import pytest
 import torch
 
-from util_cases import flat_params, make_oracle, make_pkg_solver, orc
+from util_cases import assert_blocks, flat_params, make_oracle, make_pkg_solver, orc
 
 pytestmark = pytest.mark.gpu
 
@@ -71,6 +71,8 @@ def test_random_configuration_matches_oracle(i, mode):
     assert g.shape == g_ref.shape
     gmax = float(g_ref.abs().max())
     assert float((g - g_ref).abs().max()) <= 2e-4 * gmax + 1e-12, (case, float((g - g_ref).abs().max()), gmax)
+    # ... and each block [W1 time column, W1 x columns, b1, W2, b2, W3, b3] against its own maximum: b3 alone sets gmax
+    assert_blocks(g, g_ref, model.d, plan.H, 2e-4, tag="fuzz%d %s" % (i, mode))
     lref = ref["loss_log"][0]
     cond = float((D_ref.double() ** 2).mean()) / max(abs(lref), 1e-30)
     tol = min(1e-3, max(2e-5, 4 * 6e-8 * cond))

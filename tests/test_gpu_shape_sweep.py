@@ -1,13 +1,13 @@
 """Corners of the padded kernel-instance grid (native_shapes.py) against the CPU oracle: hidden widths that give 1, 2, 3
 and 4 hidden blocks, several state-block counts, ragged trajectory counts, both the feature-split forward (few tiles) and
-the tile-per-wave forward, detached and attached forward process.  First-iteration D and gradient, same tolerances as
-test_gpu_parity.py."""
+the tile-per-wave forward, detached and attached forward process.  First-iteration D and gradient (the whole vector and each of its seven blocks against
+that block's own maximum), same tolerances as test_gpu_parity.py."""
 import math
 
 import pytest
 import torch
 
-from util_cases import flat_params, make_oracle, make_pkg_solver, orc
+from util_cases import assert_blocks, flat_params, make_oracle, make_pkg_solver, orc
 
 pytestmark = pytest.mark.gpu
 HJB = dict(loss_method="log-variance", time_approx="inner", adaptive_forward_process=True, detach_forward=True,
@@ -62,4 +62,5 @@ def test_padded_shapes_match_oracle(kind, d, widths, K, detach):
     g_ref = torch.cat([x.reshape(-1) for x in tr["grads"]])
     assert g.shape == g_ref.shape
     assert float((g - g_ref).abs().max()) <= 2e-4 * float(g_ref.abs().max()), (plan.d_pad, plan.H_pad, plan.family)
+    assert_blocks(g, g_ref, d, widths[0], 2e-4, tag="%s d=%d H=%d K=%d -> (%d, %d)" % (kind, d, widths[0], K, plan.d_pad, plan.H_pad))
     assert math.isclose(model.loss_log[0], ref["loss_log"][0], rel_tol=1e-4)

@@ -9,7 +9,7 @@ import os
 import pytest
 import torch
 
-from util_cases import psp
+from util_cases import assert_blocks, psp
 
 pytestmark = pytest.mark.gpu
 
@@ -44,6 +44,7 @@ def test_split_backward_equals_fp32_mfma_backward(d, K, N):
     assert gmax > 0
     # fp32-grade split products: observed ~1e-6 of the gradient's scale; the bound is the parity suite's
     assert float((g1 - g0).abs().max()) <= 2e-5 * gmax
+    assert_blocks(g1, g0, d, 64, 2e-5, tag="x3 vs fp32 d=%d K=%d" % (d, K))      # ... and of each block's own maximum
     _, g2, _ = _run("1", prob, K, N, dev)
     assert torch.equal(g1, g2)                                            # run-to-run bit equality
     assert not torch.equal(g1, g0)                                        # the two switches do select different kernels
@@ -58,6 +59,7 @@ def test_split_backward_other_losses_and_problems():
         D1, g1, l1 = _run("1", prob, 300, 6, dev, loss=loss)
         assert torch.equal(D0, D1)
         assert float((g1 - g0).abs().max()) <= 2e-5 * float(g0.abs().max())
+        assert_blocks(g1, g0, d, 64, 2e-5, tag="x3 vs fp32 %s %s" % (type(prob).__name__, loss))
 
 
 def test_split_backward_survives_a_large_weight_spread():
@@ -70,6 +72,7 @@ def test_split_backward_survives_a_large_weight_spread():
     assert torch.equal(D0, D1)
     assert float(D0.abs().max()) / max(1e-30, float(D0.abs().min())) > 1e2
     assert float((g1 - g0).abs().max()) <= 2e-5 * float(g0.abs().max())
+    assert_blocks(g1, g0, 200, 64, 2e-5, tag="x3 vs fp32, large weight spread")
 
 
 @pytest.mark.parametrize("d,K,N", [(320, 2048, 12), (384, 1040, 20), (448, 1100, 18), (500, 2064, 10), (512, 1500, 16)])
@@ -97,6 +100,7 @@ def test_streaming_backward_above_256_against_fp32_on_the_same_store(d, K, N):
     scale = float(g2.abs().max())
     assert torch.isfinite(g3).all() and not torch.equal(g3, g2)
     assert float((g3 - g2).abs().max()) <= 2e-5 * scale
+    assert_blocks(g3, g2, plan.d_pad, plan.H_pad, 2e-5, tag="streaming x3 vs fp32 d=%d" % d)     # (the kernel-layout gradient)
     rs = rows2.abs().max(dim=1).values.clamp_min(1e-30)
     assert float(((rows3 - rows2).abs().max(dim=1).values / rs).max()) <= 1e-4
     for _ in range(2):

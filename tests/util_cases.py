@@ -64,6 +64,40 @@ def flat_params(module):
     return torch.cat([p.detach().reshape(-1).cpu() for p in module.parameters()])
 
 
+BLOCK_NAMES = ("W1t", "W1x", "b1", "W2", "b2", "W3", "b3")
+BLOCK_FLOOR = 1e-4          # a block's own maximum counts for at least this share of the whole gradient's
+
+
+def grad_blocks(g, d, H):
+    """The flat MySequential gradient [W1, b1, W2, b2, W3, b3] as seven blocks (BLOCK_NAMES): W1 (H, d + 1) is split into its
+    time column (input 0) and its x columns."""
+    g = g.detach().double().cpu().reshape(-1)
+    assert g.numel() == (d + 1) * H + H + H * H + H + d * H + d, (g.numel(), d, H)
+    sizes = [(d + 1) * H, H, H * H, H, d * H, d]
+    W1, b1, W2, b2, W3, b3 = torch.split(g, sizes)
+    W1 = W1.view(H, d + 1)
+    return [W1[:, 0], W1[:, 1:], b1, W2, b2, W3, b3]
+
+
+def block_errors(g, g_ref, d, H):
+    """One number per block of BLOCK_NAMES: max |g - g_ref| over the block / max(max |g_ref| over the block,
+    BLOCK_FLOOR * max |g_ref|).  The floor keeps a block that is (nearly) zero in the reference from being skipped or
+    dividing by zero: it is then held to BLOCK_FLOOR of the whole gradient."""
+    ref = grad_blocks(g_ref, d, H)
+    floor = BLOCK_FLOOR * max(float(r.abs().max()) for r in ref)
+    return [float((a - r).abs().max()) / max(float(r.abs().max()), floor, 1e-300) for a, r in zip(grad_blocks(g, d, H), ref)]
+
+
+def assert_blocks(g, g_ref, d, H, bound, tag="", extra=0.0):
+    """Prints the seven block errors in one line and asserts each against bound + extra (extra: an allowance the caller's flat
+    assertion already carries, e.g. the log-variance conditioning term).  Returns the errors."""
+    errs = block_errors(g, g_ref, d, H)
+    print("%s blocks %s (<= %.3g)" % (tag, "  ".join("%s %.2e" % (n, e) for n, e in zip(BLOCK_NAMES, errs)), bound + extra))
+    bad = [(n, e) for n, e in zip(BLOCK_NAMES, errs) if not e <= bound + extra]
+    assert not bad, (tag, bad, bound + extra)
+    return errs
+
+
 def general_oracle_run(case, L=None, trace=False):
     """Oracle run of a GeneralSolver / EllipticSolver golden case (families 'general', 'general_bounded', 'elliptic'): every
     solver switch of the case and its value net (kind 'densenet' | 'user_tanh2' | 'densenet_tanh' |
