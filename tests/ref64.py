@@ -1,5 +1,7 @@
 """float64 reference of ONE iteration of the control-ansatz `Solver` (rollout, loss, backward) -- CPU only.
 
+`iteration`: the tanh MLP of time_approx='inner'.  `iteration_dense` (below): DenseNet controls, 'outer' and 'inner'.
+
 A plain torch-autograd restatement of oracle.pathspace_oracle.hjb_train (time_approx='inner', approx_method='control') in double
 precision.  Every number it starts from is the fp32 oracle's own, cast to double: OracleProblem.B / .X_0 / .extra (A, alpha, P, R,
 eta_, kappa_), the TanhMLP parameters, the step size (torch.tensor(delta_t), fp32, and its fp32 square root, as solver.py:39-40
@@ -103,3 +105,81 @@ def iteration(prob, cfg, z, noise, weights=None):
     blocks = [torch.zeros_like(p) if q is None else q.detach() for p, q in zip(params, grads)]
     D_out = -(Z_sum + gX) if cfg.loss_method == "relative_entropy" else D
     return dict(D=D_out.detach(), loss=float(loss.detach()), blocks=blocks, grad=torch.cat([q.reshape(-1) for q in blocks]), N=N, **mid)
+
+
+def iteration_dense(prob, cfg, nets, noise, weights=None):
+    """One iteration in float64 with a DenseNet control (oracle.pathspace_oracle.DenseNetOracle: dense-concat layers, relu(.)**2,
+    weights stored (in, out)).
+
+    time_approx='outer': `nets` is the list of the N per-step nets DenseNet(d -> d), net n sees x at step n.  'inner': `nets` is
+    one DenseNet(d + 1 -> d) (or a list of one) and sees [t_n, x], where t_n is the fp32 product of the fp32 step index and the fp32
+    delta_t, cast to double -- the number control_eval forms (ones * n * dt32) and the one the plan's `tn` table holds
+    (plan_dense_native.py: arange(N, fp32) * dt), NOT the double product n * dt.  Adaptive or not, attached or detached, the three
+    problem kinds and the five losses of _coefficients / _loss; everything else as `iteration`: the inputs are the fp32 oracle's
+    own numbers cast to double, nothing is drawn here, `weights` (K,) makes the loss sum_k w_k D_k.
+
+    Returns dict(D, loss, sets=[[dW1, db1, dW2, db2, dW3, db3] per parameter set], grad (flat, the plan's order [set 0 | set 1 |
+    ...]), z1, z2 (K, H): the hidden layers' PRE-activations at step N // 2, N); D is -(Zsum + g(X_N)) for the relative entropy, as
+    the kernels define it (include/psp.h).
+    """
+    assert cfg.time_approx in ("outer", "inner") and cfg.approx_method == "control" and not cfg.learn_Y_0 and not cfg.random_X_0
+    assert prob.kind in KINDS and cfg.loss_method in LOSSES
+    outer = cfg.time_approx == "outer"
+    nets = list(nets) if isinstance(nets, (list, tuple)) else [nets]
+    d = prob.d
+    xi = noise.detach().to(F64)
+    K = xi.shape[0]
+    N = int(np.floor(prob.T / cfg.delta_t))
+    assert xi.shape == (K, d, N + 1), (tuple(xi.shape), (K, d, N + 1))
+    assert len(nets) == (N if outer else 1), (len(nets), N)
+    dt32 = torch.tensor(cfg.delta_t)
+    dt, sq = float(dt32), float(torch.sqrt(dt32))
+    B = prob.B.to(F64)
+    b, f, g = _coefficients(prob)
+    di = d + (0 if outer else 1)
+    sets = [[p.detach().to(F64).clone().requires_grad_(True) for p in net.parameters()] for net in nets]
+    for W1, b1, W2, b2, W3, b3 in sets:
+        H = W1.shape[1]
+        assert W1.shape == (di, H) and W2.shape == (di + H, H) and W3.shape == (di + 2 * H, d), (W1.shape, W2.shape, W3.shape)
+
+    def net(n, X):
+        W1, b1, W2, b2, W3, b3 = sets[n if outer else 0]
+        u = X
+        if not outer:
+            t = float(torch.tensor(float(n)) * dt32)                   # fp32 n * dt
+            u = torch.cat([torch.full((K, 1), t, dtype=F64), X], 1)
+        z1 = u @ W1 + b1
+        u = torch.cat([u, torch.relu(z1) ** 2], 1)
+        z2 = u @ W2 + b2
+        u = torch.cat([u, torch.relu(z2) ** 2], 1)
+        return u @ W3 + b3, z1, z2
+
+    X = prob.X_0.to(F64).repeat(K, 1)
+    Y = torch.zeros(K, dtype=F64)
+    Z_sum = torch.zeros(K, dtype=F64)
+    mid = {}
+    for n in range(N):
+        Z, z1, z2 = net(n, X)
+        if n == N // 2:
+            mid = dict(z1=z1.detach().clone(), z2=z2.detach().clone())
+        c = -Z if cfg.adaptive_forward_process else torch.zeros_like(Z)
+        if cfg.detach_forward:
+            c = c.detach()
+        dW = xi[:, :, n + 1]
+        X = X + (b(X) + c @ B.t()) * dt + (dW @ B.t()) * sq
+        fX = f(X)                                                      # the running cost sees the UPDATED state
+        Y = Y + (0.5 * torch.sum(Z ** 2, 1) + fX + torch.sum(Z * c, 1)) * dt + torch.sum(Z * dW, 1) * sq
+        if cfg.loss_method == "relative_entropy":
+            Z_sum = Z_sum + (0.5 * torch.sum(Z ** 2, 1) + fX) * dt
+    gX = g(X)
+    D = Y - gX
+    if weights is not None:
+        loss = (weights.detach().to(F64).cpu() * D).sum()
+    else:
+        loss = _loss(cfg.loss_method, D, Y, gX, Z_sum, cfg.adaptive_forward_process)
+    flat = [p for s in sets for p in s]
+    grads = torch.autograd.grad(loss, flat, allow_unused=True)
+    grads = [torch.zeros_like(p) if q is None else q.detach() for p, q in zip(flat, grads)]
+    D_out = -(Z_sum + gX) if cfg.loss_method == "relative_entropy" else D
+    return dict(D=D_out.detach(), loss=float(loss.detach()), sets=[grads[6 * i:6 * i + 6] for i in range(len(sets))],
+                grad=torch.cat([q.reshape(-1) for q in grads]), N=N, **mid)

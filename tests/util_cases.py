@@ -98,6 +98,56 @@ def assert_blocks(g, g_ref, d, H, bound, tag="", extra=0.0):
     return errs
 
 
+DENSE_BLOCK_NAMES = ("W1x", "b1", "W2x", "W2h1", "b2", "W3x", "W3h1", "W3h2", "b3")
+DENSE_TIME_BLOCK_NAMES = ("W1t", "W2t", "W3t")
+
+
+def dense_block_names(time_input):
+    return DENSE_BLOCK_NAMES + (DENSE_TIME_BLOCK_NAMES if time_input else ())
+
+
+def dense_grad_blocks(g, d, H, n_sets, time_input):
+    """The flat DenseNet-control gradient [set 0 | set 1 | ...] (each set W1, b1, W2, b2, W3, b3, weights (in, out)) as one list of
+    blocks per set, in the order of dense_block_names: the row groups of the dense-concat weights (W2 rows [t | x | h1], W3 rows
+    [t | x | h1 | h2]; the time row is row 0 of every layer's input block and exists with a time input only)."""
+    t = 1 if time_input else 0
+    di = d + t
+    sizes = [di * H, H, (di + H) * H, H, (di + 2 * H) * d, d]
+    g = g.detach().double().cpu().reshape(-1)
+    assert g.numel() == n_sets * sum(sizes), (g.numel(), n_sets, sum(sizes))
+    out = []
+    for s in g.view(n_sets, sum(sizes)):
+        W1, b1, W2, b2, W3, b3 = torch.split(s, sizes)
+        W1, W2, W3 = W1.view(di, H), W2.view(di + H, H), W3.view(di + 2 * H, d)
+        blocks = [W1[t:], b1, W2[t:di], W2[di:], b2, W3[t:di], W3[di:di + H], W3[di + H:], b3]
+        if time_input:
+            blocks += [W1[0], W2[0], W3[0]]
+        out.append(blocks)
+    return out
+
+
+def dense_block_errors(g, g_ref, d, H, n_sets, time_input):
+    """Per set, one number per block: max |g - g_ref| over the block / max(max |g_ref| over the block, BLOCK_FLOOR * max |g_ref|
+    over THAT SET).  The floor is relative to the set, not to the whole gradient, so that one large set cannot hide another."""
+    out = []
+    for got, ref in zip(dense_grad_blocks(g, d, H, n_sets, time_input), dense_grad_blocks(g_ref, d, H, n_sets, time_input)):
+        floor = BLOCK_FLOOR * max(float(r.abs().max()) for r in ref)
+        out.append([float((a - r).abs().max()) / max(float(r.abs().max()), floor, 1e-300) for a, r in zip(got, ref)])
+    return out
+
+
+def assert_dense_blocks(g, g_ref, d, H, n_sets, time_input, bound, tag=""):
+    """Prints one line per set and asserts every block of every set against `bound`.  Returns the errors (a list per set)."""
+    names = dense_block_names(time_input)
+    errs = dense_block_errors(g, g_ref, d, H, n_sets, time_input)
+    bad = []
+    for s, es in enumerate(errs):
+        print("%s set %d blocks %s (<= %.3g)" % (tag, s, "  ".join("%s %.2e" % (n, e) for n, e in zip(names, es)), bound))
+        bad += [(s, n, e) for n, e in zip(names, es) if not e <= bound]
+    assert not bad, (tag, bad, bound)
+    return errs
+
+
 def general_oracle_run(case, L=None, trace=False):
     """Oracle run of a GeneralSolver / EllipticSolver golden case (families 'general', 'general_bounded', 'elliptic'): every
     solver switch of the case and its value net (kind 'densenet' | 'user_tanh2' | 'densenet_tanh' |
