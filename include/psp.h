@@ -59,7 +59,9 @@ extern "C" {
                          *        K_test_log diagnostic sampled, evaluated and reduced on the device (PSP_TSAMPLE_*, PSP_VTRUE_*);
                          *        psp_genl_coeffs / psp_genl_query_lq / psp_genl_rollout_fwd_lq -- Z = sigma grad V, a dense drift matrix
                          *        and the diagonal running cost in the run-time-shaped value-net kernels (Solver's value-function
-                         *        ansatz on LLGC / LQGC); the struct carries its own size instead of joining psp_abi_struct_sizes* */
+                         *        ansatz on LLGC / LQGC); the struct carries its own size instead of joining psp_abi_struct_sizes*;
+                         *        psp_genl_ul2 / psp_genl_query_ul2 / psp_genl_ul2_stage / psp_genl_rollout_fwd_ul2 -- the u_L2 log of
+                         *        that ansatz inside the run-time-shaped forward kernel (PSP_UL2_*); its own size again */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
@@ -508,6 +510,50 @@ int psp_genl_query_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs,
 int psp_genl_rollout_fwd_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const float* params, const float* x0,
                             const float* t0, const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path,
                             float* ahat, float* VN, float* YN, float* XN, float* tN, unsigned long long* kcount, void* stream);
+
+/* The u_L2 log of the forward rollout (appended in 0.4.0, no version bump): what Solver(approx_method='value_function') logs
+ * whenever the problem has a reference control u* (reference solver.py:471-475, 491-494).  With Z_n the Z of the Y update above,
+ *   u_l2_out[k] = sum_{n < N} sum_i (-Z_{n,i} - u*_i(X_{n+1}, n dt))^2 dt        (u* at the state AFTER the move),
+ * sequential in n, fp32, one float per local trajectory.  The description of u* travels beside the config and the coefficients,
+ * which keep their layouts; its kinds are those of psp_dnet_config.ul2_kind (PSP_UL2_*, below), with the same semantics:
+ *   PSP_UL2_TABLE   u_ref  = (N, d) table of u*(t_n), DEVICE;
+ *   PSP_UL2_LINEAR  tables = (N, d, d) row-major gains M_n, u* = M_n X_{n+1}: one more d x d product per step from per-step
+ *                   operand tables that psp_genl_ul2_stage writes into the table scratch ONCE (behind the region every
+ *                   psp_genl_rollout_fwd* call rewrites); needs the linear-quadratic instances (a psp_genl_coeffs that asks for
+ *                   something);
+ *   PSP_UL2_GRID    u*_i = table_{group[i]}[row[n], cell(X_{n+1,i})], tables = (ntables, nrows, ncols), group = (d), row = (N);
+ *                   cell = floor((clamp(x, -xb, xhi) + xb) / dx) in fp32 with a true division, lowered by two for the globally
+ *                   last trajectory (k_offset + k == K_global - 1), a negative cell counting from the end of the row.
+ * The log is defined for runs that never stop: base.domain_kind = PSP_DOM_NONE and base.T = inf.  Two kernel shapes carry it:
+ * sigma = s I with an element-wise drift (TABLE, GRID) and the linear-quadratic one (all kinds); a dense sigma without
+ * psp_genl_coeffs is refused.  A NULL psp_genl_ul2 means the entry point without it exactly: same plan, instance and bits. */
+typedef struct psp_genl_ul2 {
+    int32_t struct_bytes;        /* sizeof(psp_genl_ul2): checked by the library (this struct is not in psp_abi_struct_sizes*) */
+    int32_t kind;                /* PSP_UL2_TABLE | PSP_UL2_LINEAR | PSP_UL2_GRID                                              */
+    float* u_l2_out;             /* DEVICE, K_local floats, written by every psp_genl_rollout_fwd_ul2 call                     */
+    const float* u_ref;          /* TABLE: (N, d); else NULL                                                                   */
+    const float* tables;         /* LINEAR: (N, d, d) gains (read by psp_genl_ul2_stage only); GRID: (ntables, nrows, ncols)    */
+    const int32_t* group;        /* GRID: (d) table of every coordinate, in [0, ntables)                                       */
+    const int32_t* row;          /* GRID: (N) row of step n, ceil(t_n / dt_ref) formed on the host, in [0, nrows)              */
+    int32_t ntables, nrows, ncols;
+    float xb, dx, xhi;           /* GRID: as psp_dnet_config.ul2_xb / ul2_dx / ul2_xhi                                         */
+    int64_t K_global;            /* GRID: locates the globally last trajectory                                                 */
+} psp_genl_ul2;
+/* psp_genl_query_lq with the log: table_bytes grows by the staged gains of PSP_UL2_LINEAR (N operand tables of
+ * ceil((d + has_time) / 16)^2 blocks of 256 floats, 16-byte aligned) and not at all for the other kinds; the LDS rule counts the
+ * image that keeps Z_n (LINEAR and GRID on the linear-quadratic instances).  <0 as psp_genl_query_lq, or: wrong struct_bytes, a
+ * kind out of range, a pointer the kind needs missing, a stopping domain or a finite T.  No GPU needed. */
+int psp_genl_query_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, psp_genl_sizes* out);
+/* PSP_UL2_LINEAR: writes the gains ul2->tables into the table scratch `tables` (psp_genl_query_ul2's table_bytes) in the layout
+ * the forward reads.  Call once per plan and per set of gains, before the first psp_genl_rollout_fwd_ul2; a no-op for the other
+ * kinds. */
+int psp_genl_ul2_stage(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, float* tables,
+                       void* stream);
+/* psp_genl_rollout_fwd_lq with the log (every other argument as there). */
+int psp_genl_rollout_fwd_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2,
+                             const float* params, const float* x0, const float* t0, const float* xi, uint64_t seed, uint32_t iter,
+                             float* tables, float* path, float* ahat, float* VN, float* YN, float* XN, float* tN,
+                             unsigned long long* kcount, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Solver.train with a DenseNet control (function_space.py:116-140: dense-concat layers, relu^2, weights (in, out)):

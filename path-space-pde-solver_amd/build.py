@@ -99,10 +99,13 @@ def _build(force, jobs, verbose, only):
     # the device-side K_test_log evaluation (psp_genl_test_error): both waves-per-tile instances in one unit
     vinst_src = os.path.join(CSRC, "genl_eval_instance.hip")
     tasks.append((vinst_src, os.path.join(OBJ, "genl_eval_inst.o"), NOSLP,
-                  [vinst_src, os.path.join(CSRC, "genl_eval_kernels.h"), os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr]))
+                  [vinst_src, os.path.join(CSRC, "genl_eval_kernels.h"), os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
     # the linear-quadratic instances of the run-time-shaped forward kernel (psp_genl_rollout_fwd_lq): three waves-per-tile variants
     lqinst_src = os.path.join(CSRC, "genl_lq_instance.hip")
-    tasks.append((lqinst_src, os.path.join(OBJ, "genl_lq_inst.o"), NOSLP, [lqinst_src, os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr]))
+    tasks.append((lqinst_src, os.path.join(OBJ, "genl_lq_inst.o"), NOSLP, [lqinst_src, os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
+    # the u_L2-log instances of that kernel (psp_genl_rollout_fwd_ul2: two shapes, three waves-per-tile variants) and the gain staging
+    ulinst_src = os.path.join(CSRC, "genl_ul2_instance.hip")
+    tasks.append((ulinst_src, os.path.join(OBJ, "genl_ul2_inst.o"), NOSLP, [ulinst_src, os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
     for d, H in instances("dense_instances.def"):
         tasks.append((dinst_src, os.path.join(OBJ, "dnet_inst_%d_%d.o" % (d, H)),
                       ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [dinst_src, dhdr, ugrid, whdr, hdr]))

@@ -53,8 +53,18 @@
 // of the same shape -- A operand: a table of dt A built next to tSB (rows and columns >= d zero: the time row never enters),
 // B operand: the X image in A -- accumulated into the accumulator of B w, so the boxes' proposal test sees it and no image is added.
 // B w and B^T u read different tables: three sigma products and the drift product per step.
+// u_L2 log (genl_fwd_kernel<NW, false, false, true> and <NW, true, true, true>; Solver's value-function ansatz with
+// u_l2_error_flag, reference solver.py:471-475, 491-494): per trajectory  sum_n |-Z_n - u*(X_{n+1}, n dt)|^2 dt  with the Z of the Y
+// update and u* at the state AFTER the move, for the three descriptions of u* of include/psp.h PSP_UL2_*: a table of u*(t_n); the
+// gains M_n of a u* linear in x -- one more d x d product per step, A operand = a per-step table of M_n staged ONCE per plan by
+// genl_ul2_stage_kernel behind everything genl_tables_kernel rewrites, B operand = the image of the moved state (the input blocks
+// of A are dead by then; columns >= d of the table are zero: the time row never enters); the double wells' grid tables with the cell
+// arithmetic of ugrid.h.  On the dense path the Z image takes B^T u before the move, so the kinds that need X_{n+1} keep Z in an
+// image of its own (ZLi, one more carve of DB0 blocks).  The sum is sequential in n, fp32, formed by every wave alike (as S and Pz
+// are) and written by one lane per trajectory.  Defined for runs that never stop (no domain, T = inf): every step is active.
 #pragma once
 #include "gen_kernels.h"
+#include "ugrid.h"
 
 namespace psp {
 
@@ -114,6 +124,22 @@ struct GenlArgs {
     const float* runcost;           // p (d)
     long long tA;                   // float offset of the A-operand table of dt A
 };
+// u_L2 log: the arguments of the LOGU instances travel BEHIND GenlArgs in an argument struct of their own, so that GenlArgs, the
+// kernels that take it and the offsets of their hidden arguments stay what they were
+struct GenlUl2Args {
+    int kind;                       // PSP_UL2_TABLE / LINEAR / GRID
+    int ntables, nrows, ncols;      // GRID
+    float* out;                     // (K_local)
+    const float* ref;               // TABLE: (N, d) u*(t_n); GRID: (G, nrows, ncols) tables; LINEAR: (N, d, d) gains (stage kernel only)
+    const int* group;               // GRID: (d) table of every coordinate
+    const int* row;                 // GRID: (N) table row of step n
+    float xb, dx, xhi;              // GRID: cell = floor((clamp(x, -xb, xhi) + xb) / dx) (ugrid.h)
+    int reserved;
+    long long Kglobal;              // GRID: the globally last trajectory's cell is lowered by two
+    long long tUL;                  // LINEAR: float offset of the N A-operand tables of M_n (layout of tSB), behind tA
+};
+struct GenlLogArgs { GenlArgs a; GenlUl2Args u; };
+enum { GUL2_TABLE = 0, GUL2_LINEAR = 1, GUL2_GRID = 2 };      // = PSP_UL2_*
 
 // padded feature index -> real index inside the concatenation a (or -1: padding)
 // (AP: pointer to the arguments -- a generic one in the tables kernel, the kernel-argument segment in the rollout kernels)
@@ -213,6 +239,11 @@ __global__ __launch_bounds__(256) void genl_tables_kernel(const GenlArgs a) {
 
 typedef const GenlArgs* KArgs;
 typedef const GenArgs* KGen;
+// argument struct of genl_fwd_kernel<.., LOGU> and its GenlArgs part
+template <bool LOGU> struct GenlFwdArgsOf { typedef GenlArgs type; };
+template <> struct GenlFwdArgsOf<true> { typedef GenlLogArgs type; };
+__device__ __forceinline__ KArgs genl_base(const GenlArgs* p) { return p; }
+__device__ __forceinline__ KArgs genl_base(const GenlLogArgs* p) { return &p->a; }
 
 // ---- activation as functions of the stored r (relu(z) or tanh(z)); `act` is a kernel argument: uniform branches
 __device__ __forceinline__ f32x4 gact_r(int act, f32x4 z) { return act == GACT_RELU2 ? relu4(z) : tanh4(z); }
@@ -358,6 +389,8 @@ __host__ __device__ inline int genl_fwd_lds_bytes(int TB) { return 2 * TB * 1024
 // dense sigma: three more images of DB0 blocks (Z then B u; w; u) behind the input blocks of G.  The hidden blocks of G hold dead
 // scratch once the input gradient is formed; where they are fewer than 3 DB0 the carve grows past G
 __host__ __device__ inline int genl_fwd_lds_bytes_dense(int TB, int DB0) { return (2 * TB > TB + 4 * DB0 ? 2 * TB : TB + 4 * DB0) * 1024; }
+// u_L2 log of the kinds that read X_{n+1} (LINEAR, GRID) on the dense path: one more image (-> ZLi) behind those three
+__host__ __device__ inline int genl_fwd_lds_bytes_dense_log(int TB, int DB0) { return (2 * TB > TB + 5 * DB0 ? 2 * TB : TB + 5 * DB0) * 1024; }
 
 // (NW = 4: two workgroups per CU at 256 registers a wave -- the step chain of a tile is bound by the L2 latency of its table
 //  operands and by its barriers, not by the matrix pipe, so two tiles in flight per CU are worth more than eight waves on one
@@ -368,19 +401,25 @@ __host__ __device__ inline int genl_fwd_lds_bytes_dense(int TB, int DB0) { retur
 //  three workgroups per CU instead of twelve, and every workgroup copies the tables).)
 // DENSE: sigma = B through the tables tSB / tSBT (header comment); a template parameter, so that the instances of sigma = s I
 // stay the code they were.  LQ (with DENSE only): the linear-quadratic coefficients of the header comment, as uniform run-time
-// branches inside instances of their own -- for the same reason
-template <int NW, bool DENSE = false, bool LQ = false>
-__global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(const GenlArgs ga_) {
+// branches inside instances of their own -- for the same reason.  LOGU: the u_L2 log of the header comment, the kind a uniform
+// run-time branch; instantiated as <NW, false, false, true> (TABLE, GRID) and <NW, true, true, true> (all three kinds)
+template <int NW, bool DENSE = false, bool LQ = false, bool LOGU = false>
+__global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(const typename GenlFwdArgsOf<LOGU>::type ga_) {
     static_assert(DENSE || !LQ, "the linear-quadratic coefficients run on the dense-sigma path");
-    PSP_COND_EXIT(ga_.g);
-    const KArgs ga = &ga_;
+    static_assert(!LOGU || DENSE == LQ, "the u_L2 log: the sigma = s I instance or the linear-quadratic one");
+    if constexpr (LOGU) { PSP_COND_EXIT(ga_.a.g); } else { PSP_COND_EXIT(ga_.g); }
+    const KArgs ga = genl_base(&ga_);
     const KGen a = &ga->g;
+    [[maybe_unused]] const GenlUl2Args* ul = nullptr;
+    if constexpr (LOGU) ul = &ga_.u;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* A = lds;
     float* G = A + ga->TB * 256;
     float* Zi = G + ga->DB0 * 256;                                   // DENSE: Z = B^T grad_x V, later B u
     float* Wi = Zi + ga->DB0 * 256;                                  //        w = xi sqrt(dt) + c dt
     float* Ui = Wi + ga->DB0 * 256;                                  //        u = w + dt Z (quadratic h only)
+    [[maybe_unused]] float* ZLi = nullptr;                           // LOGU, DENSE: Z_n kept until X_{n+1} exists (kinds LINEAR, GRID)
+    if constexpr (LOGU && DENSE) ZLi = Ui + ga->DB0 * 256;
     const float* __restrict__ T = ga->tables;
     const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -432,6 +471,10 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
     const float* vdr = a->drift;                                      // (d) kappa / diagonal of A, read per block below
     const size_t PBL = (size_t)2 * DB0 * 256;                        // path block: X image, U image
 
+    [[maybe_unused]] float ULsum = 0.f;                              // LOGU: sum_n |-Z_n - u*(X_{n+1}, t_n)|^2 dt of this lane's features
+    [[maybe_unused]] int ukind = 0;
+    [[maybe_unused]] bool lastk = false;                             // the reference's i[-1] -= 2 (ugrid.h)
+    if constexpr (LOGU) { ukind = ul->kind; lastk = (long long)a->k_offset + k == ul->Kglobal - 1; }
     int nex = a->N;
     for (int n = 0; n < a->N; ++n) {
         // every trajectory of the tile frozen: nothing changes any more (solver.py:1093-1097 / :742-744 leave the loop); all the
@@ -485,6 +528,30 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             return (drift * dt + sig * cdt + (sig * sqdt) * xi) * alivef;
         };
         float S = 0.f, Pz = 0.f;
+        [[maybe_unused]] float UL = 0.f;
+        // LOGU: this lane's part of |-Z_n - u*|^2 for state block b (the arithmetic of hjbd_fwd_kernel's LOGU branch); Xb = X_{n+1}
+        [[maybe_unused]] auto ul2_table_block = [&](int b, const f32x4& Z) __attribute__((always_inline)) {
+            const float* ur = ul->ref + (size_t)n * D;           // u* does not depend on X_{n+1}
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = 16 * b + 4 * r + qv;
+                if (f < D) { const float e = Z[r] + ur[f]; UL = fmaf(e, e, UL); }
+            }
+        };
+        [[maybe_unused]] auto ul2_grid_block = [&](int b, const f32x4& Z, const f32x4& Xb) __attribute__((always_inline)) {
+            const long long rowofs = (long long)min(max(ul->row[n], 0), ul->nrows - 1) * ul->ncols;
+            const long long tstride = (long long)ul->nrows * ul->ncols;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = 16 * b + 4 * r + qv;
+                if (f < D) {                                         // (padding coordinates read no table)
+                    const int cell = ugrid_cell(Xb[r], ul->xb, ul->xhi, ul->dx, lastk, ul->ncols);
+                    const int grp = min(max(ul->group[f], 0), ul->ntables - 1);
+                    const float e = -Z[r] - ul->ref[grp * tstride + rowofs + cell];
+                    UL = fmaf(e, e, UL);
+                }
+            }
+        };
         const float* BU = G;                                         // DENSE: the image that holds B u
         if constexpr (DENSE) {
             const int KSd = 4 * DB0;
@@ -504,6 +571,10 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
                     const f32x4 Z = img_get(Zi, b, lane);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { S = fmaf(Z[r], Z[r], S); Pz = fmaf(Z[r], xi[r], Pz); }
+                    if constexpr (LOGU) {
+                        if (ukind == GUL2_TABLE) ul2_table_block(b, Z);
+                        else if (w0) img_put(ZLi, b, Z, lane);       // its own image: Zi takes B^T u below
+                    }
                     const f32x4 cdt = a->adaptive ? (-dt) * Z : 0.f * Z;
                     const f32x4 w = sqdt * xi + cdt;
                     if (w0) {
@@ -578,6 +649,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
         for (int b = 0; b < GENL_MAXDB; ++b)
             if (b < DB0) {
                 f32x4 U, step;
+                [[maybe_unused]] f32x4 Zlog;
                 if constexpr (DENSE) {
                     U = actf * img_get(BU, b, lane);                 // act B u
                     step = move_block(b, U, U);                      // (reads B w from its image)
@@ -591,6 +663,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
                     if (a->h_kind == GH_QUAD) u += dt * Z;
                     U = (actf * sig) * u;
                     step = move_block(b, Z, xi);
+                    if constexpr (LOGU) Zlog = Z;
                 }
                 if (a->store_path && w0) {                            // the sample point is the state BEFORE the move
 #pragma unroll
@@ -604,7 +677,38 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
                     const bool fx = (16 * b + 4 * r + qv) < D;
                     X[b][r] = (fx && act) ? X[b][r] + step[r] : X[b][r];
                 }
+                if constexpr (LOGU && !DENSE) {                      // the log line follows the Euler step (solver.py:473-475)
+                    if (ukind == GUL2_TABLE) ul2_table_block(b, Zlog);
+                    else ul2_grid_block(b, Zlog, X[b]);
+                }
             }
+        if constexpr (LOGU && DENSE) {
+            if (ukind == GUL2_LINEAR) {                              // u* = M_n X_{n+1}: the input blocks of A are dead, Wi too
+                const int KSd = 4 * DB0;
+                if (w0) {
+#pragma unroll
+                    for (int b = 0; b < GENL_MAXDB; ++b) if (b < DB0) img_put(A, b, X[b], lane);
+                }
+                tile_sync<NW>();
+                for (int ob = wave; ob < DB0; ob += NW) {
+                    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                    genl_gemm1<8>(acc, T + ul->tUL + ((size_t)n * DB0 + ob) * KSd * 64, KSd, A, lane);
+                    img_put(Wi, ob, acc, lane);
+                }
+                tile_sync<NW>();
+#pragma unroll
+                for (int b = 0; b < GENL_MAXDB; ++b)
+                    if (b < DB0) {
+                        const f32x4 Zn = img_get(ZLi, b, lane), Us = img_get(Wi, b, lane);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { const float e = -Zn[r] - Us[r]; UL = fmaf(e, e, UL); }
+                    }
+            } else if (ukind == GUL2_GRID) {
+#pragma unroll
+                for (int b = 0; b < GENL_MAXDB; ++b) if (b < DB0) ul2_grid_block(b, img_get(ZLi, b, lane), X[b]);
+            }
+        }
+        if constexpr (LOGU) ULsum = fmaf(UL, dt, ULsum);
         S = qsum(S); Pz = qsum(Pz);
         float minus_h = 0.f, hy = 0.f;                               // Y update (solver.py:1141-1142): h sees V(X, t), not the running Y
         if (a->h_kind == GH_QUAD) minus_h = 0.5f * S;
@@ -662,6 +766,10 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
     if (w0 && lane == 0 && ga->nexec) ga->nexec[t16] = nex;
     // (no time input = EllipticSolver: t_N counts the active steps as m dt with one rounding, gen_kernels.h)
     if (kvalid && w0 && q == 0) { a->VN[k] = VN; a->YN[k] = Y; a->tN[k] = ga->has_time ? t : (float)msteps * dt; }
+    if constexpr (LOGU) {
+        const float ULt = qsum(ULsum);
+        if (kvalid && w0 && q == 0) ul->out[k] = ULt;
+    }
     if (kvalid && w0) {
 #pragma unroll
         for (int b = 0; b < GENL_MAXDB; ++b)
@@ -874,15 +982,19 @@ __global__ __launch_bounds__(64 * NW) void genl_bwd_kernel(const GenlArgs ga_) {
 }
 
 // host side: launches (the dynamic LDS size exceeds the 64 KiB default)
-template <int NW, bool DENSE = false, bool LQ = false> inline hipError_t genl_launch_fwd(const GenlArgs& a, int ntile16, int lds_bytes, hipStream_t st) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW, DENSE, LQ>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+template <int NW, bool DENSE = false, bool LQ = false, bool LOGU = false> inline hipError_t genl_launch_fwd(const typename GenlFwdArgsOf<LOGU>::type& a, int ntile16, int lds_bytes, hipStream_t st) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW, DENSE, LQ, LOGU>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((genl_fwd_kernel<NW, DENSE, LQ>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
+    hipLaunchKernelGGL((genl_fwd_kernel<NW, DENSE, LQ, LOGU>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
     return hipGetLastError();
 }
 // the linear-quadratic instances <NW, true, true> are compiled in a unit of their own (genl_lq_instance.hip), so that the unit
 // of the other instances holds the kernels it held; nw = 1, 4 or 8
 hipError_t genl_lq_launch_fwd(const GenlArgs& a, int nw, int ntile16, int lds_bytes, hipStream_t st);
+// the u_L2-log instances <NW, false, false, true> / <NW, true, true, true> (a.lq picks) and the kernel that stages the gains of
+// PSP_UL2_LINEAR (N tables behind u.tUL from u.ref): a unit of their own as well (genl_ul2_instance.hip)
+hipError_t genl_ul2_launch_fwd(const GenlLogArgs& a, int nw, int ntile16, int lds_bytes, hipStream_t st);
+hipError_t genl_ul2_launch_stage(const GenlLogArgs& a, hipStream_t st);
 template <int NW, int MS = GenlGeo<NW>::MAXSLOT> inline hipError_t genl_launch_bwd(const GenlArgs& a, int grid, int groups, int lds_bytes, hipStream_t st) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_bwd_kernel<NW, MS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;

@@ -1223,12 +1223,29 @@ int psp_gen_rollout_bwd(const psp_gen_config* cfg, const float* params, const fl
 
 // ---- value nets of any depth (genl_kernels.h) ----------------------------------------------------------------------------
 namespace {
-struct GenlPlan { psp::GenlArgs a; int ntile16; long long table_floats; long long n_params; int fwd_lds, bwd_lds, nw_fwd, nw_bwd,
+struct GenlPlan { psp::GenlArgs a; psp::GenlUl2Args u; int ul2_on; int ntile16; long long table_floats; long long n_params; int fwd_lds, bwd_lds, nw_fwd, nw_bwd,
                   bwd_grid, bwd_groups; };
 // q: the linear-quadratic coefficients of psp_genl_query_lq / psp_genl_rollout_fwd_lq (NULL or all zero: none -- the plan, the
 // table layout and the kernel instance of psp_genl_rollout_fwd)
-int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs* q = nullptr) {
+// u: the u_L2 log of psp_genl_query_ul2 / psp_genl_ul2_stage / psp_genl_rollout_fwd_ul2 (NULL: none -- nothing changes)
+int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs* q = nullptr, const psp_genl_ul2* u = nullptr) {
     if (!c) return fail(-1, "null config");
+    if (u) {
+        if (u->struct_bytes != (int32_t)sizeof(psp_genl_ul2)) return fail(-1, "psp_genl_ul2.struct_bytes is not sizeof(psp_genl_ul2)");
+        if (u->kind < PSP_UL2_TABLE || u->kind > PSP_UL2_GRID) return fail(-1, "psp_genl_ul2.kind out of range");
+        if (!u->u_l2_out) return fail(-1, "the u_L2 log needs psp_genl_ul2.u_l2_out");
+        if (u->kind == PSP_UL2_TABLE && !u->u_ref) return fail(-1, "PSP_UL2_TABLE needs psp_genl_ul2.u_ref");
+        if (u->kind != PSP_UL2_TABLE && !u->tables) return fail(-1, "PSP_UL2_LINEAR / PSP_UL2_GRID need psp_genl_ul2.tables");
+        if (u->kind == PSP_UL2_GRID) {
+            if (!u->group) return fail(-1, "PSP_UL2_GRID needs psp_genl_ul2.group");
+            if (!u->row) return fail(-1, "PSP_UL2_GRID needs psp_genl_ul2.row");
+            if (u->ntables <= 0 || u->nrows <= 0 || u->ncols <= 0) return fail(-1, "PSP_UL2_GRID: ntables / nrows / ncols must be positive");
+            if (!(u->xb > 0.f) || !(u->dx > 0.f)) return fail(-1, "PSP_UL2_GRID: xb / dx must be positive");
+            if (u->K_global <= 0) return fail(-1, "PSP_UL2_GRID: K_global must be positive");
+        }
+        if (c->base.domain_kind != PSP_DOM_NONE || !(c->base.T > 3.0e38f))
+            return fail(-1, "the u_L2 log is defined for runs that never stop (domain_kind = PSP_DOM_NONE, T = inf)");
+    }
     if (q) {
         static const psp_genl_coeffs zero = {};
         if (memcmp(q, &zero, sizeof(zero)) == 0) q = nullptr;
@@ -1263,6 +1280,7 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs*
     if (b.drift_kind != PSP_DRIFT_ZERO && !b.drift) return fail(-1, "drift vector missing (double-well kappa / diagonal of A)");
     psp::GenlArgs& a = p->a;
     memset(&a, 0, sizeof(a));
+    memset(&p->u, 0, sizeof(p->u)); p->ul2_on = 0;
     a.d = b.d; a.D0 = D0; a.has_time = c->has_time ? 1 : 0; a.L = L;
     a.act = c->activation; a.linear_layout = c->linear_layout ? 1 : 0;
     a.time_first = (c->has_time && c->time_first) ? 1 : 0;
@@ -1308,6 +1326,23 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs*
         a.tSBT = tofs; tofs += (long long)a.DB0 * 4 * a.DB0 * 64;
         if (a.driftA) { a.tA = tofs; tofs += (long long)a.DB0 * 4 * a.DB0 * 64; }   // dt A, behind the tables psp_genl_rollout_bwd reads
     }
+    if (u) {
+        // two instance shapes carry the log: sigma = s I with an element-wise drift, and the linear-quadratic one
+        if (a.dense && !a.lq)
+            return fail(-1, "the u_L2 log on the dense-sigma path runs on the linear-quadratic instances (give psp_genl_coeffs)");
+        if (u->kind == PSP_UL2_LINEAR && !a.lq)
+            return fail(-1, "PSP_UL2_LINEAR runs on the linear-quadratic instances (give psp_genl_coeffs)");
+        psp::GenlUl2Args& ua = p->u;
+        p->ul2_on = 1; ua.kind = u->kind; ua.out = u->u_l2_out;
+        ua.ref = u->kind == PSP_UL2_TABLE ? u->u_ref : u->tables;
+        ua.group = u->group; ua.row = u->row;
+        ua.ntables = u->ntables; ua.nrows = u->nrows; ua.ncols = u->ncols;
+        ua.xb = u->xb; ua.dx = u->dx; ua.xhi = u->xhi; ua.Kglobal = u->K_global;
+        if (u->kind == PSP_UL2_LINEAR) {                                         // the gains of every step, staged once per plan:
+            tofs = (tofs + 3) & ~3LL;                                            // behind everything genl_tables_kernel rewrites
+            ua.tUL = tofs; tofs += (long long)b.N * a.DB0 * 4 * a.DB0 * 64;
+        }
+    }
     p->table_floats = tofs; p->n_params = pofs;
     p->ntile16 = (b.K_local + 15) / 16;
     // waves per tile: one (no barriers, many tiles per CU) for small nets -- always for the smallest, for the others once the
@@ -1323,6 +1358,7 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs*
     if (force && force[0] == '4' && nw == 8) p->nw_fwd = 4;
     if (force && force[0] == '8') p->nw_fwd = 8;
     p->fwd_lds = a.dense ? psp::genl_fwd_lds_bytes_dense(a.TB, a.DB0) : psp::genl_fwd_lds_bytes(a.TB); p->bwd_lds = psp::genl_bwd_lds_bytes(a.TB, a.DB0, p->nw_bwd);
+    if (p->ul2_on && a.dense && p->u.kind != PSP_UL2_TABLE) p->fwd_lds = psp::genl_fwd_lds_bytes_dense_log(a.TB, a.DB0);   // Z_n kept until X_{n+1} exists
     a.table_floats = tofs;
     if (p->fwd_lds > kMaxLds || p->bwd_lds > kMaxLds)
         return fail(-3, "value net: the activation images exceed the 160 KiB LDS (sum of the padded widths too large)");
@@ -1355,8 +1391,12 @@ int* genl_nexec(const psp_genl_config* cfg, const GenlPlan& p, const float* ahat
 int psp_genl_query(const psp_genl_config* cfg, psp_genl_sizes* out) { return psp_genl_query_lq(cfg, nullptr, out); }
 
 int psp_genl_query_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, psp_genl_sizes* out) {
+    return psp_genl_query_ul2(cfg, coeffs, nullptr, out);
+}
+
+int psp_genl_query_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, psp_genl_sizes* out) {
     GenlPlan p;
-    int rc = make_genl_plan(cfg, &p, coeffs);
+    int rc = make_genl_plan(cfg, &p, coeffs, ul2);
     if (rc) return rc;
     if (!out) return fail(-1, "null output");
     memset(out, 0, sizeof(*out));
@@ -1383,8 +1423,29 @@ int psp_genl_rollout_fwd(const psp_genl_config* cfg, const float* params, const 
 int psp_genl_rollout_fwd_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const float* params, const float* x0,
                             const float* t0, const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path, float* ahat,
                             float* VN, float* YN, float* XN, float* tN, unsigned long long* kcount, void* stream) {
+    return psp_genl_rollout_fwd_ul2(cfg, coeffs, nullptr, params, x0, t0, xi, seed, iter, tables, path, ahat, VN, YN, XN, tN, kcount, stream);
+}
+
+int psp_genl_ul2_stage(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, float* tables, void* stream) {
+    if (!ul2) return fail(-1, "psp_genl_ul2_stage: null psp_genl_ul2");
     GenlPlan p;
-    int rc = make_genl_plan(cfg, &p, coeffs);
+    int rc = make_genl_plan(cfg, &p, coeffs, ul2);
+    if (rc) return rc;
+    if (!tables) return fail(-1, "null buffer passed to psp_genl_ul2_stage");
+    if (p.u.kind != PSP_UL2_LINEAR) return 0;                                    // nothing to stage
+    p.a.tables = tables; p.a.tables_w = tables;
+    const psp::GenlLogArgs la = {p.a, p.u};
+    hipError_t e = psp::genl_ul2_launch_stage(la, (hipStream_t)stream);          // (genl_ul2_instance.hip)
+    if (e != hipSuccess) return fail_hip(e, "genl_ul2_stage_kernel launch");
+    return 0;
+}
+
+int psp_genl_rollout_fwd_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, const float* params,
+                             const float* x0, const float* t0, const float* xi, uint64_t seed, uint32_t iter, float* tables,
+                             float* path, float* ahat, float* VN, float* YN, float* XN, float* tN, unsigned long long* kcount,
+                             void* stream) {
+    GenlPlan p;
+    int rc = make_genl_plan(cfg, &p, coeffs, ul2);
     if (rc) return rc;
     if (!params || !x0 || !tables || !VN || !YN || !XN || !tN || !kcount || !ahat) return fail(-1, "null buffer passed to psp_genl_rollout_fwd");
     if (cfg->has_time && !t0) return fail(-1, "t0 missing");
@@ -1402,7 +1463,10 @@ int psp_genl_rollout_fwd_lq(const psp_genl_config* cfg, const psp_genl_coeffs* c
     hipLaunchKernelGGL(psp::genl_tables_kernel, dim3(128), dim3(256), 0, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "genl_tables_kernel launch");
-    if (p.a.lq)
+    if (p.ul2_on) {
+        const psp::GenlLogArgs la = {p.a, p.u};
+        e = psp::genl_ul2_launch_fwd(la, p.nw_fwd, p.ntile16, p.fwd_lds, st);        // (genl_ul2_instance.hip)
+    } else if (p.a.lq)
         e = psp::genl_lq_launch_fwd(p.a, p.nw_fwd, p.ntile16, p.fwd_lds, st);        // (genl_lq_instance.hip)
     else if (p.a.dense)
         e = p.nw_fwd == 1 ? psp::genl_launch_fwd<1, true>(p.a, p.ntile16, p.fwd_lds, st)

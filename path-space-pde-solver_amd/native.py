@@ -140,6 +140,15 @@ class GenlCoeffs(C.Structure):
                 ("drift_matrix", C.c_void_p), ("runcost", C.c_void_p)]
 
 
+class GenlUl2(C.Structure):
+    """psp_genl_ul2: the u_L2 log beside a GenlConfig and a GenlCoeffs (psp_genl_query_ul2 / psp_genl_ul2_stage /
+    psp_genl_rollout_fwd_ul2).  The library checks ``struct_bytes`` itself; the struct is not part of psp_abi_struct_sizes*."""
+    _fields_ = [("struct_bytes", C.c_int32), ("kind", C.c_int32), ("u_l2_out", C.c_void_p), ("u_ref", C.c_void_p),
+                ("tables", C.c_void_p), ("group", C.c_void_p), ("row", C.c_void_p),
+                ("ntables", C.c_int32), ("nrows", C.c_int32), ("ncols", C.c_int32),
+                ("xb", C.c_float), ("dx", C.c_float), ("xhi", C.c_float), ("K_global", C.c_int64)]
+
+
 class GenlSizes(C.Structure):
     _fields_ = [("table_bytes", C.c_int64), ("path_bytes", C.c_int64), ("ahat_bytes", C.c_int64), ("n_params", C.c_int64),
                 ("grad_partial_bytes", C.c_int64), ("n_blocks", C.c_int32), ("fwd_workgroups", C.c_int32),
@@ -180,6 +189,10 @@ SIGNATURES = {
     "psp_genl_query_lq": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlSizes)]),
     "psp_genl_rollout_fwd_lq": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P,
                                           _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psp_genl_query_ul2": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlUl2), C.POINTER(GenlSizes)]),
+    "psp_genl_ul2_stage": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlUl2), _P, _P]),
+    "psp_genl_rollout_fwd_ul2": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlUl2), _P, _P, _P, _P,
+                                           C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "psp_hjb_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "psp_hjb_family": (C.c_int, [C.c_int32, C.c_int32]),
     "psp_hjb_adjoint_sweep": (C.c_int, [C.POINTER(HjbConfig), _P, _P, _P, _P, _P, _P, _P, _P]),

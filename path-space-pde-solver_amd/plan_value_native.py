@@ -23,6 +23,14 @@ AFTER the move (solver.py:338, 471-478).  Such cases always run on the run-time-
 genl_fwd_kernel<NW, true, true>), whatever the net, through psp_genl_query_lq / psp_genl_rollout_fwd_lq with a psp_genl_coeffs
 beside the config (``lq_coeffs``); the backward call and the weights above are the same, because the kernel stores the tangent
 direction U = B^T u and f does not depend on the parameters while the state path is detached.
+
+The u_L2 log (solver.py:471-475, 491-494; on by default whenever the problem has u_true): sum_n |-Z_n - u*(X_{n+1}, n dt)|^2 dt per
+trajectory, accumulated inside the forward kernel (genl_fwd_kernel<.., LOGU>) from the description of u* that
+plan_dense_native.ul2_reference builds once per plan -- a table of u*(t_n) (LLGC), the gains of a u* linear in x (LQGC, staged
+into the table scratch once by psp_genl_ul2_stage), the double wells' grid tables -- through psp_genl_query_ul2 /
+psp_genl_rollout_fwd_ul2 with a psp_genl_ul2 beside the config and the coefficients.  Only the run-time-shaped family has log
+instances (the templated (d, H) family does not: its instance list would double), so with the flag on EVERY net runs there
+(input <= 112); with the flag off nothing changes: the same family selection, the same calls.
 """
 import ctypes as C
 
@@ -55,9 +63,14 @@ def value_eligibility(solver):
         return 'detach_forward=False back-propagates through the state path (not native for the value-function ansatz)'
     if s.learn_Y_0:
         return 'learn_Y_0 has no meaning for the value-function ansatz (Y_0 = V(X_0, 0))'
-    if s.u_l2_error_flag or s.burgers_drift or s.compute_gradient_variance > 0 or s.log_gradient \
+    if s.burgers_drift or s.compute_gradient_variance > 0 or s.log_gradient \
             or s.metastability_logs is not None or s.IS_variance_K > 0:
-        return 'per-step / per-iteration diagnostics (u_L2, gradient logs, metastability, in-loop IS) are not native here'
+        return 'per-step / per-iteration diagnostics (gradient logs, metastability, in-loop IS) are not native here'
+    log = bool(s.u_l2_error_flag)
+    if log:
+        reason = _pdn().ul2_unsupported(s.problem, s.N, s.delta_t_np)
+        if reason is not None:
+            return reason
     nets = getattr(s, 'y_n', None)
     if not isinstance(nets, list) or len(nets) != 1:
         return 'y_n is not a single value net'
@@ -79,25 +92,48 @@ def value_eligibility(solver):
         return 'running cost kind %r is not built into the value-net kernels (zero / diagonal quadratic are)' % (spec['runcost'][0],)
     if not nat.is_built():
         raise nat.NativeLibraryError('libpsp_hip.so is not built; run __graft_entry__.build()')
-    if needs_lq(spec):
-        # a dense sigma, a dense drift matrix or a running cost: the run-time-shaped family only, whatever the net
+    if needs_lq(spec) or log:
+        # a dense sigma, a dense drift matrix or a running cost -- or the u_L2 log, which the templated kernels do not carry:
+        # the run-time-shaped family only, whatever the net
         net = _deep_net(s, V, force=True)
-        if net is None:
+        if net is None and needs_lq(spec):
             return 'a dense sigma / dense drift / running cost runs on the run-time-shaped value-net kernels only, and the ' \
                    'value net (input %d) is %s' % (s.d + 1, _deep_net(s, V, why=True, force=True))
+        if net is None:
+            return 'the u_L2 log (u_l2_error_flag=True) runs on the run-time-shaped value-net kernels only -- the templated ' \
+                   '(d, H) kernels have no log instances --, and the value net (input %d) is %s; pass u_l2_error_flag=False ' \
+                   'for the native plan' % (s.d + 1, _deep_net(s, V, why=True, force=True))
         g = nat.GenlConfig()
         g.base.d, g.base.K_local, g.base.N, g.base.h_kind = s.d, 16, 1, nat.GH_QUAD
+        g.base.T, g.base.domain_kind = float('inf'), nat.DOM_NONE
         g.has_time, g.n_hidden = 1, len(net['dims']) - 2
         for i, h in enumerate(net['dims'][1:-1]):
             g.widths[i] = int(h)
-        q = nat.GenlCoeffs(struct_bytes=C.sizeof(nat.GenlCoeffs), z_kind=nat.GENL_Z_SIGMA)
+        q = nat.GenlCoeffs(struct_bytes=C.sizeof(nat.GenlCoeffs), z_kind=nat.GENL_Z_SIGMA) if needs_lq(spec) else None
+        u = None
+        if log:                                           # (a query reads no pointer: any non-null value stands for the buffers)
+            probe = C.addressof(_PROBE)
+            u = nat.GenlUl2(struct_bytes=C.sizeof(nat.GenlUl2), kind=_pdn().ul2_kind(s.problem), u_l2_out=probe, u_ref=probe,
+                            tables=probe, group=probe, row=probe, ntables=1, nrows=1, ncols=1, xb=1.0, dx=1.0, K_global=1)
         lib = nat.load()
-        if lib.psp_genl_query_lq(C.byref(g), C.byref(q), C.byref(nat.GenlSizes())) != 0:     # (the 160 KiB LDS rule)
+        if lib.psp_genl_query_ul2(C.byref(g), C.byref(q) if q is not None else None, C.byref(u) if u is not None else None,
+                                  C.byref(nat.GenlSizes())) != 0:                        # (the 160 KiB LDS rule)
             return lib.psp_last_error().decode()
         return None
     if deep is None and not shapes.gen_candidates(s.d, dims[1]):
         return 'no compiled kernel instance covers d=%d, H=%d (see csrc/gen_instances.def)' % (s.d, dims[1])
     return None
+
+
+_PROBE = C.c_float(0.0)
+
+
+def _pdn():
+    try:
+        from . import plan_dense_native as pdn
+    except ImportError:
+        import plan_dense_native as pdn
+    return pdn
 
 
 def needs_lq(spec):
@@ -181,10 +217,12 @@ class ValueNativePlan:
         self.key = None
         self.H = self.net.nn_dims[1]
         spec = s.problem.native_spec()
-        self.deep = _deep_net(s, self.net, force=needs_lq(spec))      # value nets of other depths / activations: csrc/genl_kernels.h
+        self.log = bool(s.u_l2_error_flag)                # the u_L2 log: the run-time-shaped family, whatever the net
+        self.deep = _deep_net(s, self.net, force=needs_lq(spec) or self.log)     # value nets of other depths / activations: csrc/genl_kernels.h
         self._flatten(self.net if self.deep is None else self.deep['params'])
         self._keep = []
         self.coeffs = None                                # psp_genl_coeffs (dense sigma / drift matrix / running cost), deep plans only
+        self.ul2, self.ul2_cfg = None, None               # per-trajectory u_L2 (K_local) and its psp_genl_ul2, with the log on
         if self.deep is not None:
             self.gcfg = nat.GenlConfig()
             cfg = self.gcfg.base
@@ -223,7 +261,11 @@ class ValueNativePlan:
             g.activation, g.linear_layout = _ACT[self.deep['act']], 1 if self.deep['linear'] else 0
             g.time_first, g.time_scale = 1, 1.0 / cfg.dt               # input [t, x], and t is the step index (solver.py:336-338, 439)
             sz = nat.GenlSizes()
-            rc = self.lib.psp_genl_query_lq(C.byref(g), self._coeffs_ref(), C.byref(sz))
+            if self.log:
+                self._make_ul2()
+                rc = self.lib.psp_genl_query_ul2(C.byref(g), self._coeffs_ref(), C.byref(self.ul2_cfg), C.byref(sz))
+            else:
+                rc = self.lib.psp_genl_query_lq(C.byref(g), self._coeffs_ref(), C.byref(sz))
             if rc != 0:
                 raise PlanUnsupported(self.lib.psp_last_error().decode())
             assert sz.n_params == self.P, (sz.n_params, self.P)
@@ -231,6 +273,9 @@ class ValueNativePlan:
             self.pad = _IdentityPad(self.P)
             self.flat_k = self.flat
             self.tables = torch.empty(sz.table_bytes // 4, dtype=f32, device=dev)
+            if self.ul2_cfg is not None:                  # PSP_UL2_LINEAR: the gains go into the table scratch once
+                nat.check(self.lib.psp_genl_ul2_stage(C.byref(g), self._coeffs_ref(), C.byref(self.ul2_cfg), nat.ptr(self.tables),
+                                                      nat.stream_ptr(dev)), 'psp_genl_ul2_stage')
             self.ahat_buf = torch.zeros((sz.ahat_bytes + 3) // 4, dtype=f32, device=dev)      # coefficients, then the tiles' step counts
             self.ahat = self.ahat_buf[:(s.N + 1) * self.Kpad].view(s.N + 1, self.Kpad)
         else:
@@ -270,6 +315,35 @@ class ValueNativePlan:
         self.x0_row = s.X_0.detach().to(device=dev, dtype=f32).reshape(1, -1)
         self.step = 0
         self.events = None
+
+    def _make_ul2(self):
+        """psp_genl_ul2 from plan_dense_native.ul2_reference (unpadded: the kernel reads (N, d) / (N, d, d) / (d) arrays)."""
+        s, dev = self.s, self.dev
+        try:
+            ref = _pdn().ul2_reference(s.problem, s.N, s.delta_t_np, s.d, s.K, self.lo)
+        except ValueError as e:
+            raise PlanUnsupported(str(e))
+        if ref is None:
+            raise PlanUnsupported(_pdn().ul2_unsupported(s.problem, s.N, s.delta_t_np))
+
+        def up(t, dtype=torch.float32):
+            t = t.detach().to(device=dev, dtype=dtype).contiguous()
+            self._keep.append(t)
+            return t.data_ptr()
+
+        self.ul2 = torch.zeros(self.K_local, dtype=torch.float32, device=dev)
+        u = nat.GenlUl2(struct_bytes=C.sizeof(nat.GenlUl2), kind=ref['kind'], K_global=int(s.K))
+        u.u_l2_out = self.ul2.data_ptr()
+        if ref['kind'] == nat.UL2_TABLE:
+            u.u_ref = up(ref['table'])
+        elif ref['kind'] == nat.UL2_LINEAR:
+            u.tables = up(ref['gains'])
+        else:
+            u.tables = up(ref['tables'])
+            u.group, u.row = up(ref['group'], torch.int32), up(ref['row'], torch.int32)
+            u.ntables, u.nrows, u.ncols = ref['tables'].shape[0], ref['nrows'], ref['ncols']
+            u.xb, u.dx, u.xhi = ref['xb'], ref['dx'], ref['xhi']
+        self.ul2_ref, self.ul2_cfg = ref, u
 
     def _coeffs_ref(self):
         return C.byref(self.coeffs) if self.coeffs is not None else None
@@ -321,7 +395,13 @@ class ValueNativePlan:
         if self.events is not None:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             ev[0].record()
-        if self.deep is not None:
+        if self.ul2_cfg is not None:
+            nat.check(lib.psp_genl_rollout_fwd_ul2(C.byref(self.gcfg), self._coeffs_ref(), C.byref(self.ul2_cfg), nat.ptr(self.flat),
+                                                   nat.ptr(x0), nat.ptr(self.t0), nat.ptr(xi), int(s.seed) & 0xFFFFFFFFFFFFFFFF, l,
+                                                   nat.ptr(self.tables), nat.ptr(self.path), nat.ptr(self.ahat_buf), nat.ptr(self.VN),
+                                                   nat.ptr(self.YN), nat.ptr(self.XN_k), nat.ptr(self.tN), nat.ptr(self.kcount), st),
+                      'psp_genl_rollout_fwd_ul2')
+        elif self.deep is not None:
             nat.check(lib.psp_genl_rollout_fwd_lq(C.byref(self.gcfg), self._coeffs_ref(), nat.ptr(self.flat), nat.ptr(x0),
                                                   nat.ptr(self.t0), nat.ptr(xi), int(s.seed) & 0xFFFFFFFFFFFFFFFF, l,
                                                   nat.ptr(self.tables), nat.ptr(self.path), nat.ptr(self.ahat_buf), nat.ptr(self.VN),
@@ -340,8 +420,13 @@ class ValueNativePlan:
         Dd = self.D.double()
         r = (self.vsteps - self.ysteps)[:, :self.K_local]
         r[0].zero_()                                              # the term starts at n = 1 (solver.py:438)
-        stats = torch.stack([Dd.sum(), (Dd * Dd).sum(), (r.double() ** 2).sum()])
+        stats = [Dd.sum(), (Dd * Dd).sum(), (r.double() ** 2).sum()]
+        if self.ul2 is not None:                                  # the local sum of the log rides on the same collective
+            stats.append(self.ul2.double().sum())
+        stats = torch.stack(stats)
         sharding.allreduce_sum_(stats)                            # collective 1
+        if self.ul2 is not None and ul2_out is not None:
+            ul2_out[l:l + 1] = (stats[3:4] / K).to(torch.float32)  # mean over the GLOBAL K, no host sync
         self.sums.copy_(stats[:2])
         loss = sharding.loss_from_sums(self.sums, s.K, s.loss_method) + stats[2] / K
         loss_out[l] = loss.to(torch.float32)
