@@ -60,7 +60,9 @@ extern "C" {
                          *        psp_genl_coeffs / psp_genl_query_lq / psp_genl_rollout_fwd_lq -- Z = sigma grad V, a dense drift matrix
                          *        and the diagonal running cost in the run-time-shaped value-net kernels (Solver's value-function
                          *        ansatz on LLGC / LQGC); the struct carries its own size instead of joining psp_abi_struct_sizes*;
-                         *        psp_genl_ul2 / psp_genl_query_ul2 / psp_genl_ul2_stage / psp_genl_rollout_fwd_ul2 -- the u_L2 log of
+                         *        psp_genl_adj / psp_genl_query_adj / psp_genl_adjoint_sweep -- the adjoint sweep of the state path for the value-function
+ *        ansatz with detach_forward=False (csrc/genl_adj_kernels.h).
+ *        psp_genl_ul2 / psp_genl_query_ul2 / psp_genl_ul2_stage / psp_genl_rollout_fwd_ul2 -- the u_L2 log of
                          *        that ansatz inside the run-time-shaped forward kernel (PSP_UL2_*); its own size again */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
@@ -554,6 +556,43 @@ int psp_genl_rollout_fwd_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* 
                              const float* params, const float* x0, const float* t0, const float* xi, uint64_t seed, uint32_t iter,
                              float* tables, float* path, float* ahat, float* VN, float* YN, float* XN, float* tN,
                              unsigned long long* kcount, void* stream);
+
+/* Adjoint sweep of the state path (appended in 0.4.0, no version bump; csrc/genl_adj_kernels.h): what
+ * Solver(approx_method='value_function') needs with adaptive_forward_process=True and detach_forward=False (the constructor
+ * defaults; reference solver.py:449-478: c = -Z stays attached, so the states carry the parameters).  At a fixed sample the loss
+ * still sees the parameters only through V(X_n, n) and grad_x V(X_n, n): psp_genl_rollout_bwd stays the gradient kernel, and the
+ * sweep -- one workgroup per 16-trajectory tile, n = N-1 .. 0 -- rewrites what it consumes.  With g_n = grad_x V(X_n, n), Z_n = B g_n:
+ *   lambda = lam_N;  for n = N-1 .. 0:
+ *     Lam = lambda + mu_{n+1} dt grad f(X_{n+1});      U_n = mu_{n+1} U_fwd - dt B^T (mu_{n+1} Z_n + B^T Lam);
+ *     lambda = Lam + dt J_b(X_n)^T Lam + a_n g_n + grad_x^2 V(X_n, n) U_n
+ * (U_fwd: the direction psp_genl_rollout_fwd* stored; J_b: the drift matrix, or the diagonal Jacobian of base.drift_kind).
+ * On return the path store holds U_n, `ahat` holds a_n and `ws` holds 1 on executed samples, 0 on the padding rows and at n = N:
+ * call psp_genl_rollout_bwd(cfg, params, tables, path, ahat, ws, NULL, ...) exactly as without the sweep.
+ * Defined for: base.adaptive = 1, base.h_kind = PSP_GH_QUAD, base.domain_kind = PSP_DOM_NONE, base.T = inf,
+ * base.per_sample_weights = base.store_path = 1, and the orientation Z = sigma grad V (PSP_GENL_Z_SIGMA; sigma = s I without
+ * coefficients is its own transpose).  The struct travels beside the config, the coefficients and the log, which keep their layouts. */
+typedef struct psp_genl_adj {
+    int32_t struct_bytes;        /* sizeof(psp_genl_adj): checked by the library (this struct is not in psp_abi_struct_sizes*)    */
+    int32_t reserved;
+    const float* mu;             /* DEVICE, (N + 1) x 16 ceil(K/16): mu_n, the adjoint of Y_n (mu_N = dLoss/dD; row 0 unused)       */
+    const float* resid_coeff;    /* DEVICE, (N + 1) x 16 ceil(K/16): a_n (a_0 = mu_1, a_n = dLoss/dV(X_n, n) for n >= 1)            */
+    const float* lam_N;          /* DEVICE, K_local x d: the adjoint of X_N from the terminal cost, -dLoss/dD grad g(X_N)          */
+    float* lam0_out;             /* DEVICE, K_local x d: dLoss/dX_0 per trajectory, or NULL                                       */
+    int64_t drift_t_offset;      /* float offset of the sweep's table of (dt A)^T inside the table scratch: WRITTEN by
+                                  * psp_genl_query_adj, read by psp_genl_adjoint_sweep (pass the same struct)                     */
+} psp_genl_adj;
+/* psp_genl_query_ul2 for a plan that runs the sweep: table_bytes grows by the table of (dt A)^T (a drift matrix only; behind
+ * everything the forward and psp_genl_ul2_stage write, so those calls produce the same bytes), the LDS rule also counts the sweep's
+ * images (four of the whole concatenation, three of the input blocks), waves_per_tile is the sweep's as well; writes
+ * adj->drift_t_offset.  `ul2` may be NULL.  <0 as psp_genl_query_ul2, or: wrong struct_bytes, a stopping domain or a finite T,
+ * base.adaptive = 0, another h than PSP_GH_QUAD, the orientation PSP_GENL_Z_SIGMA_T.  No GPU needed; reads no pointer of `adj`. */
+int psp_genl_query_adj(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, psp_genl_adj* adj,
+                       psp_genl_sizes* out);
+/* The sweep itself, between psp_genl_rollout_fwd* and psp_genl_rollout_bwd of the same cfg / coeffs / params / tables / path.
+ * `ahat` and `ws`: the coefficient and tangent-weight arrays of psp_genl_rollout_bwd (written; distinct from adj->mu /
+ * adj->resid_coeff). */
+int psp_genl_adjoint_sweep(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_adj* adj, const float* params,
+                           float* tables, float* path, float* ahat, float* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Solver.train with a DenseNet control (function_space.py:116-140: dense-concat layers, relu^2, weights (in, out)):

@@ -93,7 +93,7 @@ def _build(force, jobs, verbose, only):
     ugrid = os.path.join(CSRC, "ugrid.h")
     ehdr = os.path.join(CSRC, "hjbe_kernels.h")
     einst_src = os.path.join(CSRC, "hjbe_instance.hip")
-    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, os.path.join(CSRC, "hjb_basis_kernels.h"), ghdr, whdr, dhdr, ehdr, ugrid, os.path.join(CSRC, "genl_kernels.h"), os.path.join(CSRC, "genl_eval_kernels.h"), inc, idef, gdef, wdef, ddef])]
+    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, os.path.join(CSRC, "hjb_basis_kernels.h"), ghdr, whdr, dhdr, ehdr, ugrid, os.path.join(CSRC, "genl_kernels.h"), os.path.join(CSRC, "genl_eval_kernels.h"), os.path.join(CSRC, "genl_adj_kernels.h"), inc, idef, gdef, wdef, ddef])]
     # the reference-control / uncontrolled evaluation rollout (psp_is_rollout): every d bucket and control kind in one unit
     tasks.append((einst_src, os.path.join(OBJ, "hjbe_inst.o"), NOSLP, [einst_src, ehdr, ugrid, hdr]))
     # the device-side K_test_log evaluation (psp_genl_test_error): both waves-per-tile instances in one unit
@@ -106,6 +106,10 @@ def _build(force, jobs, verbose, only):
     # the u_L2-log instances of that kernel (psp_genl_rollout_fwd_ul2: two shapes, three waves-per-tile variants) and the gain staging
     ulinst_src = os.path.join(CSRC, "genl_ul2_instance.hip")
     tasks.append((ulinst_src, os.path.join(OBJ, "genl_ul2_inst.o"), NOSLP, [ulinst_src, os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
+    # the adjoint sweep of the state path for the value-function ansatz (psp_genl_adjoint_sweep): three waves-per-tile variants
+    adjinst_src = os.path.join(CSRC, "genl_adj_instance.hip")
+    tasks.append((adjinst_src, os.path.join(OBJ, "genl_adj_inst.o"), NOSLP,
+                  [adjinst_src, os.path.join(CSRC, "genl_adj_kernels.h"), os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
     for d, H in instances("dense_instances.def"):
         tasks.append((dinst_src, os.path.join(OBJ, "dnet_inst_%d_%d.o" % (d, H)),
                       ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [dinst_src, dhdr, ugrid, whdr, hdr]))

@@ -16,6 +16,7 @@
 #include "hjbd_kernels.h"
 #include "genl_kernels.h"
 #include "genl_eval_kernels.h"
+#include "genl_adj_kernels.h"
 #include "hjbe_kernels.h"
 
 #define X(D_, H_) PSP_DECLARE_DNET_INSTANCE(D_, H_)
@@ -1501,6 +1502,72 @@ int psp_genl_rollout_bwd(const psp_genl_config* cfg, const float* params, const 
     hipLaunchKernelGGL(reduce_grad_kernel, dim3((P + 31) / 32), dim3(256), 0, st, grad_partial, p.bwd_grid, P, grad_out);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "reduce_grad_kernel launch");
+    return 0;
+}
+
+// ---- adjoint sweep of the state path, value-function ansatz (genl_adj_kernels.h) ------------------------------------------------
+namespace {
+// every check psp_genl_query_adj and psp_genl_adjoint_sweep share; *tAT: where the table of (dt A)^T goes when nothing else follows
+// the tables of `u` (behind everything genl_tables_kernel and psp_genl_ul2_stage write), *table_floats: the scratch with it
+int make_genl_adj_plan(const psp_genl_config* c, const psp_genl_coeffs* q, const psp_genl_ul2* u, const psp_genl_adj* adj, GenlPlan* p,
+                       long long* tAT, long long* table_floats, int* lds) {
+    if (!adj) return fail(-1, "null psp_genl_adj");
+    if (adj->struct_bytes != (int32_t)sizeof(psp_genl_adj)) return fail(-1, "psp_genl_adj.struct_bytes is not sizeof(psp_genl_adj)");
+    int rc = make_genl_plan(c, p, q, u);
+    if (rc) return rc;
+    const psp_gen_config& b = c->base;
+    if (b.domain_kind != PSP_DOM_NONE || !(b.T > 3.0e38f))
+        return fail(-1, "the adjoint sweep is defined for runs that never stop (domain_kind = PSP_DOM_NONE, T = inf)");
+    if (!b.adaptive) return fail(-1, "the adjoint sweep needs base.adaptive = 1 (without the control in the drift the state path carries no parameter dependence)");
+    if (b.h_kind != PSP_GH_QUAD) return fail(-1, "the adjoint sweep is defined for h = -|z|^2 / 2 - f(x) only (PSP_GH_QUAD)");
+    if (p->a.dense && !(p->a.lq && p->a.z_sigma))
+        return fail(-1, "the adjoint sweep runs in the orientation Z = sigma grad V (PSP_GENL_Z_SIGMA), not PSP_GENL_Z_SIGMA_T");
+    if (!b.per_sample_weights || !b.store_path) return fail(-1, "the adjoint sweep needs base.per_sample_weights = 1 and base.store_path = 1");
+    long long tofs = (p->table_floats + 3) & ~3LL;
+    *tAT = tofs;
+    if (p->a.driftA) tofs += (long long)p->a.DB0 * 4 * p->a.DB0 * 64;
+    *table_floats = tofs;
+    *lds = psp::genl_adj_lds_bytes(p->a.TB, p->a.DB0);
+    if (*lds > kMaxLds) return fail(-3, "value net: the images of the adjoint sweep exceed the 160 KiB LDS (sum of the padded widths too large)");
+    return 0;
+}
+}  // namespace
+
+int psp_genl_query_adj(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, psp_genl_adj* adj,
+                       psp_genl_sizes* out) {
+    GenlPlan p;
+    long long tAT = 0, tf = 0;
+    int lds = 0;
+    int rc = make_genl_adj_plan(cfg, coeffs, ul2, adj, &p, &tAT, &tf, &lds);
+    if (rc) return rc;
+    rc = psp_genl_query_ul2(cfg, coeffs, ul2, out);
+    if (rc) return rc;
+    out->table_bytes = tf * 4;
+    adj->drift_t_offset = tAT;
+    return 0;
+}
+
+int psp_genl_adjoint_sweep(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_adj* adj, const float* params,
+                           float* tables, float* path, float* ahat, float* ws, void* stream) {
+    GenlPlan p;
+    long long tAT = 0, tf = 0;
+    int lds = 0;
+    int rc = make_genl_adj_plan(cfg, coeffs, nullptr, adj, &p, &tAT, &tf, &lds);
+    if (rc) return rc;
+    if (!params || !tables || !path || !ahat || !ws || !adj->mu || !adj->resid_coeff || !adj->lam_N)
+        return fail(-1, "null buffer passed to psp_genl_adjoint_sweep");
+    if (p.a.driftA && (adj->drift_t_offset < tAT || (adj->drift_t_offset & 3) != 0))
+        return fail(-1, "psp_genl_adj.drift_t_offset is not the one psp_genl_query_adj wrote");
+    psp::GenlAdjArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.a = p.a;
+    aa.a.tables = tables; aa.a.tables_w = tables;
+    aa.a.g.params = params; aa.a.g.path = path;
+    aa.mu = adj->mu; aa.resid = adj->resid_coeff; aa.lamN = adj->lam_N; aa.lam0 = adj->lam0_out;
+    aa.coef_out = ahat; aa.wt_out = ws;
+    aa.tAT = adj->drift_t_offset;
+    hipError_t e = psp::genl_adj_launch(aa, p.nw_fwd, p.ntile16, lds, (hipStream_t)stream);       // (genl_adj_instance.hip)
+    if (e != hipSuccess) return fail_hip(e, "genl_adj_kernel launch");
     return 0;
 }
 

@@ -149,6 +149,13 @@ class GenlUl2(C.Structure):
                 ("xb", C.c_float), ("dx", C.c_float), ("xhi", C.c_float), ("K_global", C.c_int64)]
 
 
+class GenlAdj(C.Structure):
+    """psp_genl_adj: the adjoint sweep of the state path beside a GenlConfig, a GenlCoeffs and a GenlUl2 (psp_genl_query_adj /
+    psp_genl_adjoint_sweep).  The library checks ``struct_bytes`` itself and psp_genl_query_adj writes ``drift_t_offset``."""
+    _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("mu", C.c_void_p), ("resid_coeff", C.c_void_p),
+                ("lam_N", C.c_void_p), ("lam0_out", C.c_void_p), ("drift_t_offset", C.c_int64)]
+
+
 class GenlSizes(C.Structure):
     _fields_ = [("table_bytes", C.c_int64), ("path_bytes", C.c_int64), ("ahat_bytes", C.c_int64), ("n_params", C.c_int64),
                 ("grad_partial_bytes", C.c_int64), ("n_blocks", C.c_int32), ("fwd_workgroups", C.c_int32),
@@ -193,6 +200,9 @@ SIGNATURES = {
     "psp_genl_ul2_stage": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlUl2), _P, _P]),
     "psp_genl_rollout_fwd_ul2": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlUl2), _P, _P, _P, _P,
                                            C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psp_genl_query_adj": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlUl2), C.POINTER(GenlAdj),
+                                     C.POINTER(GenlSizes)]),
+    "psp_genl_adjoint_sweep": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlAdj), _P, _P, _P, _P, _P, _P]),
     "psp_hjb_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "psp_hjb_family": (C.c_int, [C.c_int32, C.c_int32]),
     "psp_hjb_adjoint_sweep": (C.c_int, [C.POINTER(HjbConfig), _P, _P, _P, _P, _P, _P, _P, _P]),

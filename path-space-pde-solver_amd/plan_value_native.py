@@ -31,6 +31,16 @@ into the table scratch once by psp_genl_ul2_stage), the double wells' grid table
 psp_genl_rollout_fwd_ul2 with a psp_genl_ul2 beside the config and the coefficients.  Only the run-time-shaped family has log
 instances (the templated (d, H) family does not: its instance list would double), so with the flag on EVERY net runs there
 (input <= 112); with the flag off nothing changes: the same family selection, the same calls.
+
+Gradients through the state path (adaptive_forward_process=True with detach_forward=False -- the constructor defaults; solver.py:
+456-469 keeps c = -Z attached): refused unless Solver(value_state_path='native').  With it the plan is forward (unchanged),
+psp_genl_adjoint_sweep, backward (unchanged).  At a fixed sample the loss still sees theta only through V(X_n, n) and
+grad_x V(X_n, n), so the backward kernel's form  sum_{n,k} grad_theta [a_{n,k} V + grad_x V . U_{n,k}]  holds; what changes is
+which a and U a sample gets.  The sweep (csrc/genl_adj_kernels.h, one workgroup per 16-trajectory tile, n = N-1 .. 0) runs the
+adjoint lambda of the states from lambda_N = -w^D grad g(X_N) -- formed here by autograd on X_N, so the kernel does not know the
+terminal cost --, the weights mu_n (mu_{n+1} = WS[n] above) and a_n (= AV above), rewrites the stored directions with
+U_n = mu_{n+1} U_fwd - dt B^T (mu_{n+1} Z_n + B^T Lam) and fills the coefficient and tangent-weight arrays of the backward.
+Only the run-time-shaped family has a sweep: every net goes through _deep_net(..., force=True), as with the log.
 """
 import ctypes as C
 
@@ -59,8 +69,10 @@ def value_eligibility(solver):
         return "only approx_method='value_function' with time_approx='inner' (with 'outer' the reference itself fails)"
     if s.loss_method not in ('log-variance', 'moment'):
         return "loss_method %r is not native for the value-function ansatz (log-variance, moment)" % s.loss_method
-    if s.adaptive_forward_process and not s.detach_forward:
-        return 'detach_forward=False back-propagates through the state path (not native for the value-function ansatz)'
+    attached = state_path_attached(s)
+    if attached and getattr(s, 'value_state_path', 'torch') != 'native':
+        return "detach_forward=False back-propagates through the state path (not native for the value-function ansatz by " \
+               "default; value_state_path='native' runs the adjoint sweep of the run-time-shaped kernels)"
     if s.learn_Y_0:
         return 'learn_Y_0 has no meaning for the value-function ansatz (Y_0 = V(X_0, 0))'
     if s.burgers_drift or s.compute_gradient_variance > 0 or s.log_gradient \
@@ -92,13 +104,16 @@ def value_eligibility(solver):
         return 'running cost kind %r is not built into the value-net kernels (zero / diagonal quadratic are)' % (spec['runcost'][0],)
     if not nat.is_built():
         raise nat.NativeLibraryError('libpsp_hip.so is not built; run __graft_entry__.build()')
-    if needs_lq(spec) or log:
-        # a dense sigma, a dense drift matrix or a running cost -- or the u_L2 log, which the templated kernels do not carry:
-        # the run-time-shaped family only, whatever the net
+    if needs_lq(spec) or log or attached:
+        # a dense sigma, a dense drift matrix or a running cost -- or the u_L2 log or the adjoint sweep of the state path, which the
+        # templated kernels do not carry: the run-time-shaped family only, whatever the net
         net = _deep_net(s, V, force=True)
         if net is None and needs_lq(spec):
             return 'a dense sigma / dense drift / running cost runs on the run-time-shaped value-net kernels only, and the ' \
                    'value net (input %d) is %s' % (s.d + 1, _deep_net(s, V, why=True, force=True))
+        if net is None and not log:
+            return "the adjoint sweep of the state path (value_state_path='native') runs on the run-time-shaped value-net " \
+                   'kernels only, and the value net (input %d) is %s' % (s.d + 1, _deep_net(s, V, why=True, force=True))
         if net is None:
             return 'the u_L2 log (u_l2_error_flag=True) runs on the run-time-shaped value-net kernels only -- the templated ' \
                    '(d, H) kernels have no log instances --, and the value net (input %d) is %s; pass u_l2_error_flag=False ' \
@@ -106,6 +121,7 @@ def value_eligibility(solver):
         g = nat.GenlConfig()
         g.base.d, g.base.K_local, g.base.N, g.base.h_kind = s.d, 16, 1, nat.GH_QUAD
         g.base.T, g.base.domain_kind = float('inf'), nat.DOM_NONE
+        g.base.adaptive, g.base.per_sample_weights, g.base.store_path = (1 if s.adaptive_forward_process else 0), 1, 1
         g.has_time, g.n_hidden = 1, len(net['dims']) - 2
         for i, h in enumerate(net['dims'][1:-1]):
             g.widths[i] = int(h)
@@ -116,8 +132,13 @@ def value_eligibility(solver):
             u = nat.GenlUl2(struct_bytes=C.sizeof(nat.GenlUl2), kind=_pdn().ul2_kind(s.problem), u_l2_out=probe, u_ref=probe,
                             tables=probe, group=probe, row=probe, ntables=1, nrows=1, ncols=1, xb=1.0, dx=1.0, K_global=1)
         lib = nat.load()
-        if lib.psp_genl_query_ul2(C.byref(g), C.byref(q) if q is not None else None, C.byref(u) if u is not None else None,
-                                  C.byref(nat.GenlSizes())) != 0:                        # (the 160 KiB LDS rule)
+        qr, ur = C.byref(q) if q is not None else None, C.byref(u) if u is not None else None
+        if attached:                                      # the sweep's images count as well
+            adj = nat.GenlAdj(struct_bytes=C.sizeof(nat.GenlAdj))
+            rc = lib.psp_genl_query_adj(C.byref(g), qr, ur, C.byref(adj), C.byref(nat.GenlSizes()))
+        else:
+            rc = lib.psp_genl_query_ul2(C.byref(g), qr, ur, C.byref(nat.GenlSizes()))
+        if rc != 0:                                       # (the 160 KiB LDS rule)
             return lib.psp_last_error().decode()
         return None
     if deep is None and not shapes.gen_candidates(s.d, dims[1]):
@@ -126,6 +147,11 @@ def value_eligibility(solver):
 
 
 _PROBE = C.c_float(0.0)
+
+
+def state_path_attached(solver):
+    """Whether the loss back-propagates through the state path: the control -Z in the drift stays attached (solver.py:456-469)."""
+    return bool(solver.adaptive_forward_process and not solver.detach_forward)
 
 
 def _pdn():
@@ -218,7 +244,9 @@ class ValueNativePlan:
         self.H = self.net.nn_dims[1]
         spec = s.problem.native_spec()
         self.log = bool(s.u_l2_error_flag)                # the u_L2 log: the run-time-shaped family, whatever the net
-        self.deep = _deep_net(s, self.net, force=needs_lq(spec) or self.log)     # value nets of other depths / activations: csrc/genl_kernels.h
+        self.attached = state_path_attached(s)            # the adjoint sweep of the state path: the run-time-shaped family as well
+        self.adj = None                                   # its psp_genl_adj
+        self.deep = _deep_net(s, self.net, force=needs_lq(spec) or self.log or self.attached)     # value nets of other depths / activations: csrc/genl_kernels.h
         self._flatten(self.net if self.deep is None else self.deep['params'])
         self._keep = []
         self.coeffs = None                                # psp_genl_coeffs (dense sigma / drift matrix / running cost), deep plans only
@@ -263,6 +291,11 @@ class ValueNativePlan:
             sz = nat.GenlSizes()
             if self.log:
                 self._make_ul2()
+            if self.attached:
+                self.adj = nat.GenlAdj(struct_bytes=C.sizeof(nat.GenlAdj))
+                rc = self.lib.psp_genl_query_adj(C.byref(g), self._coeffs_ref(), C.byref(self.ul2_cfg) if self.log else None,
+                                                 C.byref(self.adj), C.byref(sz))
+            elif self.log:
                 rc = self.lib.psp_genl_query_ul2(C.byref(g), self._coeffs_ref(), C.byref(self.ul2_cfg), C.byref(sz))
             else:
                 rc = self.lib.psp_genl_query_lq(C.byref(g), self._coeffs_ref(), C.byref(sz))
@@ -295,6 +328,13 @@ class ValueNativePlan:
         self.sizes = sz
         self.path = torch.empty(sz.path_bytes // 4, dtype=f32, device=dev)
         self.ws = torch.zeros(s.N + 1, self.Kpad, dtype=f32, device=dev)
+        if self.adj is not None:                          # the sweep's inputs: mu_n, a_n, the terminal adjoint; its dLoss/dX_0
+            self.mu = torch.zeros(s.N + 1, self.Kpad, dtype=f32, device=dev)
+            self.resid = torch.zeros(s.N + 1, self.Kpad, dtype=f32, device=dev)
+            self.lamN = torch.zeros(self.K_local, s.d, dtype=f32, device=dev)
+            self.lam0 = torch.zeros(self.K_local, s.d, dtype=f32, device=dev)
+            self.adj.mu, self.adj.resid_coeff = self.mu.data_ptr(), self.resid.data_ptr()
+            self.adj.lam_N, self.adj.lam0_out = self.lamN.data_ptr(), self.lam0.data_ptr()
         self.vsteps = torch.zeros(s.N, self.Kpad, dtype=f32, device=dev)
         self.ysteps = torch.zeros(s.N, self.Kpad, dtype=f32, device=dev)
         cfg.v_steps_out, cfg.y_steps_out = nat.ptr(self.vsteps), nat.ptr(self.ysteps)
@@ -433,6 +473,8 @@ class ValueNativePlan:
         wD = sharding.loss_weights(self.D, self.sums, s.K, s.loss_method)            # (K_local)
         tail = torch.flip(torch.cumsum(torch.flip(r, [0]), 0), [0])                 # tail[m] = sum_{n >= m} r_n
         ws, av = self.ws, self.ahat
+        if self.adj is not None:                                  # the sweep writes ws and av from mu (= WS shifted by one) and a_n
+            ws, av = self.mu[1:], self.resid
         ws.zero_()
         av.zero_()
         # WS[m] = w^D - (2/K) sum_{n > m} r_n  (m = 0..N-1);  AV[0] = WS[0] + ... = w^D - (2/K) sum_{n >= 1} r_n
@@ -440,6 +482,17 @@ class ValueNativePlan:
         ws[N - 1, :self.K_local] = wD
         av[1:N, :self.K_local] = (2.0 / K) * r[1:]
         av[0, :self.K_local] = ws[0, :self.K_local]
+        if self.adj is not None:
+            # lambda_N = -w^D grad g(X_N) by autograd on X_N (the kernel stays independent of the terminal cost), then the sweep:
+            # it rewrites the stored directions and fills the coefficient and tangent-weight arrays the backward reads
+            with torch.enable_grad():
+                xN = XN.detach().clone().requires_grad_(True)
+                dg, = torch.autograd.grad(s.problem.g(xN).sum(), xN)
+            torch.mul(dg.to(torch.float32), -wD.unsqueeze(1), out=self.lamN)
+            ws = self.ws
+            nat.check(lib.psp_genl_adjoint_sweep(C.byref(self.gcfg), self._coeffs_ref(), C.byref(self.adj), nat.ptr(self.flat),
+                                                 nat.ptr(self.tables), nat.ptr(self.path), nat.ptr(self.ahat_buf), nat.ptr(ws), st),
+                      'psp_genl_adjoint_sweep')
         if ev is not None:
             ev[2].record()
         if self.deep is not None:

@@ -66,7 +66,7 @@ class Solver:
                  log_gradient=False, burgers_drift=False, verbose=True,
                  device=None, backend='auto', noise='reference', widths=(30, 30), mlp_dtype='auto',
                  path_budget_bytes=None, path_chunks=None, chunk_mode='auto', use_graph='auto', range_guard=True,
-                 path_noise='auto', state_basis='auto'):
+                 path_noise='auto', state_basis='auto', value_state_path='torch'):
         self.problem, self.name = problem, name
         self.date = date.today().strftime('%Y-%m-%d')
         self.d, self.T = problem.d, problem.T
@@ -104,6 +104,12 @@ class Solver:
         if state_basis not in ('auto', 'x', 'sigma'):
             raise ValueError("state_basis must be 'auto', 'x' or 'sigma'")
         self.state_basis = state_basis
+        # value-function ansatz with adaptive_forward_process=True and detach_forward=False (gradients through the state path):
+        # 'torch' (default) runs the composite plan, 'native' the adjoint sweep of the run-time-shaped value-net kernels between
+        # their forward and backward (plan_value_native.py, csrc/genl_adj_kernels.h)
+        if value_state_path not in ('torch', 'native'):
+            raise ValueError("value_state_path must be 'torch' or 'native'")
+        self.value_state_path = value_state_path
         # native plan: HBM budget of the path store kept for the backward pass (None: a third of the HBM); a larger store is
         # processed in K-chunks (plan_native.py).  path_chunks forces a chunk count; chunk_mode 'auto' | 'two_gradient' | 'recompute'
         self.path_budget_bytes, self.path_chunks, self.chunk_mode = path_budget_bytes, path_chunks, chunk_mode
@@ -289,7 +295,7 @@ class Solver:
         nets = nets + tuple(id(v) for v in getattr(self, 'y_n', []))
         return (nets, self.noise, self.K, self.N, float(self.delta_t_np), self.loss_method, self.approx_method,
                 self.time_approx, bool(self.learn_Y_0), bool(self.adaptive_forward_process), bool(self.detach_forward),
-                bool(self.random_X_0), bool(self.u_l2_error_flag), self.mlp_dtype, getattr(self, 'range_guard', True), getattr(self, 'path_noise', 'auto'), getattr(self, 'state_basis', 'auto'), os.environ.get('PSP_STATE_BASIS', ''), self.path_budget_bytes, self.path_chunks,
+                bool(self.random_X_0), bool(self.u_l2_error_flag), self.mlp_dtype, getattr(self, 'range_guard', True), getattr(self, 'path_noise', 'auto'), getattr(self, 'state_basis', 'auto'), getattr(self, 'value_state_path', 'torch'), os.environ.get('PSP_STATE_BASIS', ''), self.path_budget_bytes, self.path_chunks,
                 self.chunk_mode, id(self.problem), id(self.y_0) if hasattr(self, 'y_0') else None)
 
     def _choose_plan(self):
