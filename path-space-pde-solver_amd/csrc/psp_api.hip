@@ -47,17 +47,38 @@ int fail_hip(hipError_t e, const char* where) {
     return -10;
 }
 
-typedef psp::HjbInstance (*InstanceFn)();
-struct Entry { int d, H; InstanceFn fn; };
-const Entry kTable[] = {
+// one (d, H) -> instance table per kernel family (the .def files list what build.py compiled)
+template <class Inst> struct Entry { int d, H; Inst (*fn)(); };
+template <class Inst, size_t N> bool find_in(const Entry<Inst> (&table)[N], int d, int H, Inst* out) {
+    for (const Entry<Inst>& e : table)
+        if (e.d == d && e.H == H) { *out = e.fn(); return true; }
+    return false;
+}
+template <class Inst, size_t N> constexpr int table_count(const Entry<Inst> (&)[N]) { return (int)N; }
+template <class Inst, size_t N> int table_get(const Entry<Inst> (&table)[N], int i, int32_t* d, int32_t* H) {
+    if (i < 0 || i >= (int)N || !d || !H) return fail(-1, "instance index out of range");
+    *d = table[i].d; *H = table[i].H;
+    return 0;
+}
+
+const Entry<psp::HjbInstance> kTable[] = {
 #define X(D_, H_) {D_, H_, &psp_instance_##D_##_##H_},
 #include "instances.def"
 #undef X
 };
-
-const Entry kWideTable[] = {
+const Entry<psp::HjbInstance> kWideTable[] = {
 #define X(D_, H_) {D_, H_, &psp_wide_instance_##D_##_##H_},
 #include "wide_instances.def"
+#undef X
+};
+const Entry<psp::GenInstance> kGenTable[] = {
+#define X(D_, H_) {D_, H_, &psp_gen_instance_##D_##_##H_},
+#include "gen_instances.def"
+#undef X
+};
+const Entry<psp::DnetInstance> kDnetTable[] = {
+#define X(D_, H_) {D_, H_, &psp_dnet_instance_##D_##_##H_},
+#include "dense_instances.def"
 #undef X
 };
 
@@ -66,41 +87,50 @@ const Entry kWideTable[] = {
 bool find_instance(int d, int H, psp::HjbInstance* out) {
     static const char* fw = getenv("PSP_FORCE_WIDE");
     const bool force_wide = fw && fw[0] == '1';
-    if (!force_wide)
-        for (const Entry& e : kTable)
-            if (e.d == d && e.H == H) { *out = e.fn(); return true; }
-    for (const Entry& e : kWideTable)
-        if (e.d == d && e.H == H) { *out = e.fn(); return true; }
-    if (force_wide)
-        for (const Entry& e : kTable)
-            if (e.d == d && e.H == H) { *out = e.fn(); return true; }
-    return false;
+    if (!force_wide && find_in(kTable, d, H, out)) return true;
+    if (find_in(kWideTable, d, H, out)) return true;
+    return force_wide && find_in(kTable, d, H, out);
 }
 
-typedef psp::GenInstance (*GenInstanceFn)();
-struct GenEntry { int d, H; GenInstanceFn fn; };
-const GenEntry kGenTable[] = {
-#define X(D_, H_) {D_, H_, &psp_gen_instance_##D_##_##H_},
-#include "gen_instances.def"
-#undef X
-};
-bool find_gen_instance(int d, int H, psp::GenInstance* out) {
-    for (const GenEntry& e : kGenTable)
-        if (e.d == d && e.H == H) { *out = e.fn(); return true; }
-    return false;
+// launch one of the small kernels below and report a refused launch as "<kernel> launch: <HIP error>" (0, or the code of fail_hip)
+template <auto Kernel, class... Args>
+int launch_checked(const char* what, dim3 grid, dim3 block, size_t lds_bytes, void* stream, Args... args) {
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, (hipStream_t)stream, args...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail_hip(e, what);
 }
+#define PSP_LAUNCH(kernel, ...) launch_checked<kernel>(#kernel " launch", __VA_ARGS__)
+using psp::genl_tables_kernel;     // (so that its message reads "genl_tables_kernel launch" like the others)
 
-typedef psp::DnetInstance (*DnetInstanceFn)();
-struct DnetEntry { int d, H; DnetInstanceFn fn; };
-const DnetEntry kDnetTable[] = {
-#define X(D_, H_) {D_, H_, &psp_dnet_instance_##D_##_##H_},
-#include "dense_instances.def"
-#undef X
-};
-bool find_dnet_instance(int d, int H, psp::DnetInstance* out) {
-    for (const DnetEntry& e : kDnetTable)
-        if (e.d == d && e.H == H) { *out = e.fn(); return true; }
-    return false;
+// Range guard of the split-product mode (include/psp.h: range_flag), either-or shape: the split kernel runs where
+// range_flag[0] == 0 and its fp32-MFMA twin where it is 1 -- both are enqueued, on the same grid and the same output layout.
+// Without a flag the split kernel runs alone, unpredicated.  cond / cond_want: the predicate fields of the launches' arguments.
+template <class Split, class Fp32>
+hipError_t launch_either(const int* range_flag, const int*& cond, int& cond_want, Split split, Fp32 fp32) {
+    if (!range_flag) return split();
+    const int* const cond0 = cond;
+    const int want0 = cond_want;
+    cond = range_flag; cond_want = 0;
+    hipError_t e = split();
+    if (e == hipSuccess) { cond_want = 1; e = fp32(); }
+    cond = cond0; cond_want = want0;
+    return e;
+}
+// ... raise-then-redo shape (forwards): the split kernel runs unpredicated, `raise` enqueues the kernel that sets range_flag[0]
+// from what it left (and returns 0 or a failure code), then the fp32-MFMA kernel runs where the flag is 1 and overwrites it.
+// what: the "<kernel> launch" of a refused split / fp32 launch.
+template <class Split, class Raise, class Fp32>
+int launch_redo(const int* range_flag, const int*& cond, int& cond_want, const char* what, Split split, Raise raise, Fp32 fp32) {
+    hipError_t e = split();
+    if (e == hipSuccess && range_flag) {
+        if (const int rc = raise()) return rc;
+        const int* const cond0 = cond;
+        const int want0 = cond_want;
+        cond = range_flag; cond_want = 1;
+        e = fp32();
+        cond = cond0; cond_want = want0;
+    }
+    return e == hipSuccess ? 0 : fail_hip(e, what);
 }
 
 constexpr int kMaxLds = 160 * 1024;
@@ -125,6 +155,20 @@ int n_cus() {
     return cus;
 }
 
+// tile-per-wave kernels: one 16-trajectory tile per wave; 1..8 waves per workgroup so that small K still spreads over CUs
+// (wide family: 1..4 waves, one per SIMD)
+int tile_waves(int ntile16, bool wide) {
+    const int cus = n_cus(), cap = wide ? 4 : 8;
+    const int fw = (ntile16 + cus - 1) / cus;
+    return fw < 1 ? 1 : fw > cap ? cap : fw;
+}
+
+// the coefficient kinds and the noise mode that psp_hjb_config and psp_is_config share
+template <class Cfg> bool coeff_kinds_ok(const Cfg& c) {
+    return c.drift_kind >= 0 && c.drift_kind <= 3 && c.sigma_kind >= 0 && c.sigma_kind <= 2 && c.runcost_kind >= 0 &&
+           c.runcost_kind <= 1 && c.term_kind >= 0 && c.term_kind <= 2 && c.noise_mode >= 0 && c.noise_mode <= 1;
+}
+
 int make_plan(const psp_hjb_config* c, Plan* p) {
     if (!c) return fail(-1, "null config");
     if (c->d <= 0 || c->H <= 0 || c->K_local <= 0 || c->N <= 0) return fail(-1, "non-positive d/H/K/N");
@@ -132,10 +176,7 @@ int make_plan(const psp_hjb_config* c, Plan* p) {
         snprintf(g_err, sizeof(g_err), "no compiled HJB kernel instance for d=%d H=%d", c->d, c->H);
         return -2;
     }
-    if (c->drift_kind < 0 || c->drift_kind > 3 || c->sigma_kind < 0 || c->sigma_kind > 2 ||
-        c->runcost_kind < 0 || c->runcost_kind > 1 || c->term_kind < 0 || c->term_kind > 2 ||
-        c->loss_kind < 0 || c->loss_kind > 3 || c->noise_mode < 0 || c->noise_mode > 1 || c->store_path < 0 ||
-        c->store_path > 4)
+    if (!coeff_kinds_ok(*c) || c->loss_kind < 0 || c->loss_kind > 3 || c->store_path < 0 || c->store_path > 4)
         return fail(-1, "config enum out of range");
     if (c->store_path == 4) {                                  // the backward regenerates xi: only where the image IS xi
         if (p->inst.wide) return fail(-2, "store_path 4 (xi regenerated by the backward) exists in the narrow kernel family only");
@@ -153,12 +194,7 @@ int make_plan(const psp_hjb_config* c, Plan* p) {
     p->ntile16 = (c->K_local + 15) / 16;
     if ((long long)c->N * p->ntile16 >= (1LL << 31)) return fail(-1, "N * ceil(K/16) must stay below 2^31");
     const int cus = n_cus();
-    // forward: one 16-trajectory tile per wave; 1..8 waves per workgroup so that small K still spreads over CUs
-    // (wide family: 1..4 waves, one per SIMD)
-    int fw = (p->ntile16 + cus - 1) / cus;
-    if (fw < 1) fw = 1;
-    if (fw > 8) fw = 8;
-    if (p->inst.wide && fw > 4) fw = 4;   // wide family: one wave per SIMD
+    int fw = tile_waves(p->ntile16, p->inst.wide);
     if (p->inst.wide && c->mlp_dtype == PSP_MLP_F16X3) fw = 4;   // its split-product forward shares the table stream between FOUR waves
     // ... unless the cooperative forward serves the launch (hjbc_kernels.h: on-device noise, no running cost, no u_L2 log): TWO tiles
     // per workgroup; the range guard's fp32 twin then runs hjbw_fwd_kernel on the same grid with two waves per workgroup
@@ -208,14 +244,20 @@ int make_plan(const psp_hjb_config* c, Plan* p) {
     return 0;
 }
 
+// the problem description every kernel that takes an HjbArgs reads the same way: coefficients, sizes, step, image kind.
+// Each caller adds its buffers and what only it sets (the other fields stay zero)
+void fill_problem(const psp_hjb_config* c, int ntile16, psp::HjbArgs* a) {
+    a->drift = c->drift; a->sigma = c->sigma; a->runcost = c->runcost; a->term = c->term;
+    a->drift_kind = c->drift_kind; a->sigma_kind = c->sigma_kind; a->runcost_kind = c->runcost_kind; a->term_kind = c->term_kind;
+    a->K_local = c->K_local; a->N = c->N; a->ntile16 = ntile16;
+    a->dt = c->dt; a->sqdt = c->sqrt_dt; a->sigma_scale = c->sigma_scale;
+    a->adaptive = c->adaptive; a->store_path = c->store_path;
+}
+
 void fill_args(const psp_hjb_config* c, const Plan& p, psp::HjbArgs* a) {
     memset(a, 0, sizeof(*a));
-    a->drift = c->drift; a->sigma = c->sigma; a->runcost = c->runcost; a->term = c->term;
-    a->k_offset = c->k_offset; a->K_global = c->K_global; a->K_local = c->K_local; a->N = c->N;
-    a->ntile16 = p.ntile16; a->dt = c->dt; a->sqdt = c->sqrt_dt; a->sigma_scale = c->sigma_scale;
-    a->drift_kind = c->drift_kind; a->sigma_kind = c->sigma_kind; a->runcost_kind = c->runcost_kind;
-    a->term_kind = c->term_kind; a->adaptive = c->adaptive; a->loss_kind = c->loss_kind;
-    a->noise_mode = c->noise_mode; a->store_path = c->store_path;
+    fill_problem(c, p.ntile16, a);
+    a->k_offset = c->k_offset; a->K_global = c->K_global; a->loss_kind = c->loss_kind; a->noise_mode = c->noise_mode;
     a->uref = c->u_ref; a->ul2 = c->u_l2_out;
     a->iter_dev = c->iter_dev;
     // diagnostic stamp buffer: [forward: fwd_grid x 8 waves x 8][backward: bwd_grid x 4 waves x 8]
@@ -236,12 +278,10 @@ struct GenPlan {
     int ntile16, fwd_waves, fwd_grid, bwd_grid;
 };
 
-int n_cus();
-
 int make_gen_plan(const psp_gen_config* c, GenPlan* p) {
     if (!c) return fail(-1, "null config");
     if (c->d <= 0 || c->H <= 0 || c->K_local <= 0 || c->N <= 0) return fail(-1, "non-positive d/H/K/N");
-    if (!find_gen_instance(c->d, c->H, &p->inst)) {
+    if (!find_in(kGenTable, c->d, c->H, &p->inst)) {
         snprintf(g_err, sizeof(g_err), "no compiled GeneralSolver kernel instance for d=%d H=%d", c->d, c->H);
         return -2;
     }
@@ -260,9 +300,7 @@ int make_gen_plan(const psp_gen_config* c, GenPlan* p) {
         return fail(-3, "split-product forward tables do not fit the 160 KiB LDS for this (d,H)");
     p->ntile16 = (c->K_local + 15) / 16;
     const int cus = n_cus();
-    int fw = (p->ntile16 + cus - 1) / cus;
-    if (fw < 1) fw = 1;
-    if (fw > 8) fw = 8;
+    const int fw = tile_waves(p->ntile16, false);
     p->fwd_waves = fw;
     p->fwd_grid = (p->ntile16 + fw - 1) / fw;
     const long long nround = ((long long)(c->N + 1) * p->ntile16 + 3) / 4;
@@ -289,8 +327,9 @@ void fill_gen_args(const psp_gen_config* c, const GenPlan& p, psp::GenArgs* a) {
 }
 
 // ---- small kernels -------------------------------------------------------------------
-__global__ void reduce_partials_kernel(const double* __restrict__ part, int n, double* __restrict__ out) {
-    // single workgroup, fixed summation order: thread t sums entries t, t+256, ... then a tree
+// the n pairs of `part` summed by a single workgroup of 256 threads in a fixed order: thread t sums entries t, t+256, ... then
+// a tree; thread 0 gets the two sums
+__device__ __forceinline__ void block_pair_sum(const double* __restrict__ part, int n, double* sum0, double* sum1) {
     __shared__ double s0[256], s1[256];
     double a = 0.0, b = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) { a += part[2 * i]; b += part[2 * i + 1]; }
@@ -300,27 +339,26 @@ __global__ void reduce_partials_kernel(const double* __restrict__ part, int n, d
         if ((int)threadIdx.x < w) { s0[threadIdx.x] += s0[threadIdx.x + w]; s1[threadIdx.x] += s1[threadIdx.x + w]; }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { out[0] = s0[0]; out[1] = s1[0]; }
+    if (threadIdx.x == 0) { *sum0 = s0[0]; *sum1 = s1[0]; }
+}
+
+__global__ void reduce_partials_kernel(const double* __restrict__ part, int n, double* __restrict__ out) {
+    double sD = 0.0, sD2 = 0.0;
+    block_pair_sum(part, n, &sD, &sD2);
+    if (threadIdx.x == 0) { out[0] = sD; out[1] = sD2; }
 }
 
 // partial sums -> (sum D, sum D^2) and the loss value (single rank: local sums are global)
 __global__ void reduce_partials_loss_kernel(const double* __restrict__ part, int n, double* __restrict__ out, int loss_kind,
                                             double invK, float* __restrict__ loss_log, const uint32_t* __restrict__ index_dev) {
-    __shared__ double s0[256], s1[256];
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) { a += part[2 * i]; b += part[2 * i + 1]; }
-    s0[threadIdx.x] = a; s1[threadIdx.x] = b;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) { s0[threadIdx.x] += s0[threadIdx.x + w]; s1[threadIdx.x] += s1[threadIdx.x + w]; }
-        __syncthreads();
-    }
+    double sD = 0.0, sD2 = 0.0;
+    block_pair_sum(part, n, &sD, &sD2);
     if (threadIdx.x == 0) {
-        out[0] = s0[0]; out[1] = s1[0];
+        out[0] = sD; out[1] = sD2;
         if (loss_log) {
-            const double m = s0[0] * invK;
-            double loss = s1[0] * invK - m * m;                       // log-variance: mean(D^2) - mean(D)^2 (solver.py:167-168)
-            if (loss_kind == PSP_LOSS_MOMENT) loss = s1[0] * invK;    // :165-166
+            const double m = sD * invK;
+            double loss = sD2 * invK - m * m;                         // log-variance: mean(D^2) - mean(D)^2 (solver.py:167-168)
+            if (loss_kind == PSP_LOSS_MOMENT) loss = sD2 * invK;      // :165-166
             if (loss_kind == PSP_LOSS_REL_ENTROPY) loss = -m;         // D = -(Zsum + g) (:179-180)
             loss_log[index_dev ? *index_dev : 0u] = (float)loss;
         }
@@ -366,8 +404,20 @@ __global__ void iter_advance_kernel(psp_iter_state* st, double b1, double b2) {
     st->iter += 1u; st->step += 1u; st->beta1_pow *= b1; st->beta2_pow *= b2;
 }
 
-// Adam with the bias corrections of the step held in a device psp_iter_state (same arithmetic as adam_kernel: the host
-// path forms step_size = lr / (1 - b1^step) and sqrt(1 - b2^step) in double and rounds to fp32, so does every thread here)
+// torch.optim.Adam single-tensor semantics (torch/optim/adam.py, _single_tensor_adam) for parameter i with gradient gi.
+// step_size = lr / (1 - b1^step) and bc2_sqrt = sqrt(1 - b2^step) come from the caller, formed in
+// double and rounded to fp32
+__device__ __forceinline__ void adam_update(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, long long i, float gi,
+                                            float b1, float b2, float eps, float step_size, float bc2_sqrt) {
+    const float mi = m[i] + (gi - m[i]) * (1.0f - b1);              // exp_avg.lerp_(grad, 1-beta1)
+    const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;             // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2)
+    m[i] = mi; v[i] = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = p[i] - step_size * (mi / denom);                         // param.addcdiv_(exp_avg, denom, -step_size)
+}
+
+// Adam with the bias corrections of the step held in a device psp_iter_state (the host path of psp_adam_step forms step_size
+// and bc2_sqrt in double and rounds to fp32, so does every thread here)
 __global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                 float* __restrict__ v, long long n, const psp_iter_state* __restrict__ st, float lr, float b1,
                                 float b2, float eps) {
@@ -375,12 +425,7 @@ __global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__
     if (i >= n) return;
     const float step_size = (float)((double)lr / (1.0 - st->beta1_pow));
     const float bc2_sqrt = (float)sqrt(1.0 - st->beta2_pow);
-    const float gi = g[i];
-    const float mi = m[i] + (gi - m[i]) * (1.0f - b1);
-    const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - step_size * (mi / denom);
+    adam_update(p, m, v, i, g[i], b1, b2, eps, step_size, bc2_sqrt);
 }
 
 // Launch-bound sizes (graph replay): partial gradients -> gradient -> Adam -> iteration state, ONE launch instead of three.
@@ -419,6 +464,8 @@ __global__ void reduce_grad_adam_advance_kernel(const float* __restrict__ part, 
         grad_out[i] = gi;
         const float step_size = (float)((double)lr / (1.0 - b1p));
         const float bc2_sqrt = (float)sqrt(1.0 - b2p);
+        // Spelled out, not adam_update(): inlined here the compiler contracts the second-moment line as fma(b2, v, ((1 - b2) g) g),
+        // in the two kernels above as fma((1 - b2) g, g, b2 v).  Sharing the function moves every graph-replay result by an ulp
         const float mi = m[i] + (gi - m[i]) * (1.0f - b1);
         const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;
         m[i] = mi; v[i] = vi;
@@ -443,18 +490,12 @@ __global__ void reduce_grad_kernel(const float* __restrict__ part, int nwg, int 
     if (p < P && threadIdx.x < 32) out[p] = g;
 }
 
-// torch.optim.Adam single-tensor semantics (torch/optim/adam.py, _single_tensor_adam)
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long long n, float lr, float b1, float b2, float eps,
                             float step_size, float bc2_sqrt) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float gi = g[i];
-    const float mi = m[i] + (gi - m[i]) * (1.0f - b1);              // exp_avg.lerp_(grad, 1-beta1)
-    const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;             // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2)
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - step_size * (mi / denom);                         // param.addcdiv_(exp_avg, denom, -step_size)
+    adam_update(p, m, v, i, g[i], b1, b2, eps, step_size, bc2_sqrt);
 }
 
 __global__ void philox_fill_kernel(float* __restrict__ out, int N, int K, int d, long long k_offset,
@@ -545,9 +586,7 @@ int is_validate(const psp_is_config* c, int* lds_bytes) {
     }
     if (c->control_kind < PSP_ISC_NONE || c->control_kind > PSP_ISC_GRID)
         return fail(-1, "control_kind out of range (PSP_ISC_NONE, PSP_ISC_TABLE, PSP_ISC_LINEAR, PSP_ISC_GRID)");
-    if (c->drift_kind < 0 || c->drift_kind > 3 || c->sigma_kind < 0 || c->sigma_kind > 2 || c->runcost_kind < 0 ||
-        c->runcost_kind > 1 || c->term_kind < 0 || c->term_kind > 2 || c->noise_mode < 0 || c->noise_mode > 1)
-        return fail(-1, "config enum out of range");
+    if (!coeff_kinds_ok(*c)) return fail(-1, "config enum out of range");
     if (c->k_offset < 0 || c->K_global < (int64_t)c->K_local + c->k_offset) return fail(-1, "K_global must cover k_offset + K_local");
     if (!c->x0) return fail(-1, "null x0 in psp_is_config");
     if (c->drift_kind != PSP_DRIFT_ZERO && !c->drift) return fail(-1, "drift parameters missing");
@@ -614,15 +653,13 @@ int make_dnet_plan(const psp_dnet_config* c, DnetPlan* p) {
     if (!c) return fail(-1, "null config");
     const psp_hjb_config& b = c->base;
     if (b.d <= 0 || b.H <= 0 || b.K_local <= 0 || b.N <= 0) return fail(-1, "non-positive d/H/K/N");
-    if (!find_dnet_instance(b.d, b.H, &p->inst)) {
+    if (!find_in(kDnetTable, b.d, b.H, &p->inst)) {
         snprintf(g_err, sizeof(g_err), "no compiled DenseNet-control kernel instance for d=%d H=%d", b.d, b.H);
         return -2;
     }
     if (c->d_real <= 0 || c->d_real > b.d || c->H_real <= 0 || c->H_real > b.H)
         return fail(-1, "d_real / H_real must lie in [1, d] / [1, H] of the instance");
-    if (b.drift_kind < 0 || b.drift_kind > 3 || b.sigma_kind < 0 || b.sigma_kind > 2 || b.runcost_kind < 0 ||
-        b.runcost_kind > 1 || b.term_kind < 0 || b.term_kind > 2 || b.noise_mode < 0 || b.noise_mode > 1 ||
-        b.store_path < 0 || b.store_path > 3 || b.loss_kind < 0 || b.loss_kind > 3)
+    if (!coeff_kinds_ok(b) || b.store_path < 0 || b.store_path > 3 || b.loss_kind < 0 || b.loss_kind > 3)
         return fail(-1, "config enum out of range");
     if (p->inst.lds_bytes > kMaxLds) return fail(-3, "DenseNet-control kernel images do not fit the 160 KiB LDS");
     if (b.mlp_dtype == PSP_MLP_F16X3 && (!p->inst.launch_fwd_x3 || p->inst.lds_bytes_x3 > kMaxLds))
@@ -666,12 +703,8 @@ int make_dnet_plan(const psp_dnet_config* c, DnetPlan* p) {
 }
 }  // namespace
 
-extern "C" int psp_dnet_instance_count(void) { return (int)(sizeof(kDnetTable) / sizeof(kDnetTable[0])); }
-extern "C" int psp_dnet_instance_get(int32_t i, int32_t* d, int32_t* H) {
-    if (i < 0 || i >= psp_dnet_instance_count() || !d || !H) return fail(-1, "instance index out of range");
-    *d = kDnetTable[i].d; *H = kDnetTable[i].H;
-    return 0;
-}
+extern "C" int psp_dnet_instance_count(void) { return table_count(kDnetTable); }
+extern "C" int psp_dnet_instance_get(int32_t i, int32_t* d, int32_t* H) { return table_get(kDnetTable, i, d, H); }
 
 extern "C" int psp_dnet_query(const psp_dnet_config* cfg, psp_dnet_sizes* out) {
     DnetPlan p;
@@ -695,10 +728,7 @@ extern "C" int psp_dnet_terminal_reduce(const psp_dnet_config* cfg, const double
     int rc = make_dnet_plan(cfg, &p);
     if (rc) return rc;
     if (!fwd_partial || !sums_out) return fail(-1, "null buffer passed to psp_dnet_terminal_reduce");
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, fwd_partial, p.grid, sums_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "reduce_partials_kernel launch");
-    return 0;
+    return PSP_LAUNCH(reduce_partials_kernel, dim3(1), dim3(256), 0, stream, fwd_partial, p.grid, sums_out);
 }
 
 extern "C" int psp_dnet_rollout_bwd(const psp_dnet_config* cfg, const float* params, const float* images, const float* w,
@@ -717,13 +747,9 @@ extern "C" int psp_dnet_rollout_bwd(const psp_dnet_config* cfg, const float* par
     // split-product outer products where the stored image is the Brownian increment itself (detached adaptive run: the power-of-two
     // scale of the weight-carrying tiles then needs nothing but the weights); guarded by the fp32 kernel like the other split kernels
     const bool x3 = b->mlp_dtype == PSP_MLP_F16X3 && b->adaptive && b->store_path == 1 && p.inst.launch_bwd_x3;
-    const bool guard = x3 && b->range_flag != nullptr;
-    if (guard) { a.h.cond = b->range_flag; a.h.cond_want = 0; }
-    hipError_t e = x3 ? p.inst.launch_bwd_x3(a, p.bwd_grid, (hipStream_t)stream) : p.inst.launch_bwd(a, p.bwd_grid, (hipStream_t)stream);
-    if (e == hipSuccess && guard) {
-        a.h.cond_want = 1;
-        e = p.inst.launch_bwd(a, p.bwd_grid, (hipStream_t)stream);
-    }
+    auto fp32 = [&]() { return p.inst.launch_bwd(a, p.bwd_grid, (hipStream_t)stream); };
+    const hipError_t e = !x3 ? fp32() : launch_either(b->range_flag, a.h.cond, a.h.cond_want,
+                                                      [&]() { return p.inst.launch_bwd_x3(a, p.bwd_grid, (hipStream_t)stream); }, fp32);
     if (e != hipSuccess) return fail_hip(e, "hjbd_bwd_kernel launch");
     return 0;
 }
@@ -741,21 +767,14 @@ extern "C" int psp_dnet_adjoint_sweep(const psp_dnet_config* cfg, const float* p
     psp::DnetArgs a;
     memset(&a, 0, sizeof(a));
     psp::HjbArgs& h = a.h;
-    h.drift = b->drift; h.sigma = b->sigma; h.runcost = b->runcost; h.term = b->term;
-    h.K_local = b->K_local; h.N = b->N; h.ntile16 = p.ntile16; h.dt = b->dt; h.sqdt = b->sqrt_dt; h.sigma_scale = b->sigma_scale;
-    h.drift_kind = b->drift_kind; h.sigma_kind = b->sigma_kind; h.runcost_kind = b->runcost_kind; h.term_kind = b->term_kind;
-    h.adaptive = b->adaptive; h.store_path = b->store_path;
+    fill_problem(b, p.ntile16, &h);
     h.params = params; h.XN = const_cast<float*>(XN); h.adj_mu = mu; h.adj_nu = nu; h.adj_wT = wT;
     a.tbl = tables; a.pimg = images;
     a.d_real = cfg->d_real; a.h_real = cfg->H_real; a.time_input = cfg->time_input ? 1 : 0; a.per_step = cfg->per_step ? 1 : 0;
     const bool x3 = b->mlp_dtype == PSP_MLP_F16X3 && p.inst.launch_adj_x3 && p.inst.lds_bytes_x3 <= kMaxLds;
-    const bool guard = x3 && b->range_flag != nullptr;       // range guard (psp_hjb_config.range_flag): both sweeps, predicated
-    if (guard) { h.cond = b->range_flag; h.cond_want = 0; }
-    hipError_t e = x3 ? p.inst.launch_adj_x3(a, p.grid, (hipStream_t)stream) : p.inst.launch_adj(a, p.grid, (hipStream_t)stream);
-    if (e == hipSuccess && guard) {
-        h.cond_want = 1;
-        e = p.inst.launch_adj(a, p.grid, (hipStream_t)stream);
-    }
+    auto fp32 = [&]() { return p.inst.launch_adj(a, p.grid, (hipStream_t)stream); };
+    const hipError_t e = !x3 ? fp32() : launch_either(b->range_flag, h.cond, h.cond_want,           // range guard: both sweeps, predicated
+                                                      [&]() { return p.inst.launch_adj_x3(a, p.grid, (hipStream_t)stream); }, fp32);
     if (e != hipSuccess) return fail_hip(e, "hjbd_adj_kernel launch");
     return 0;
 }
@@ -793,12 +812,8 @@ extern "C" int psp_dnet_rollout_fwd(const psp_dnet_config* cfg, const float* par
     psp::DnetArgs a;
     memset(&a, 0, sizeof(a));
     psp::HjbArgs& h = a.h;
-    h.drift = b->drift; h.sigma = b->sigma; h.runcost = b->runcost; h.term = b->term;
-    h.k_offset = b->k_offset; h.K_global = b->K_global; h.K_local = b->K_local; h.N = b->N;
-    h.ntile16 = p.ntile16; h.dt = b->dt; h.sqdt = b->sqrt_dt; h.sigma_scale = b->sigma_scale;
-    h.drift_kind = b->drift_kind; h.sigma_kind = b->sigma_kind; h.runcost_kind = b->runcost_kind;
-    h.term_kind = b->term_kind; h.adaptive = b->adaptive; h.loss_kind = b->loss_kind;
-    h.noise_mode = b->noise_mode; h.store_path = b->store_path;
+    fill_problem(b, p.ntile16, &h);
+    h.k_offset = b->k_offset; h.K_global = b->K_global; h.loss_kind = b->loss_kind; h.noise_mode = b->noise_mode;
     h.params = params; h.x0 = x0; h.x0_stride = x0_stride; h.y0 = y0; h.xi = xi; h.tfeat = tfeat;
     h.D = D_out; h.Fint = Fint_out; h.XN = XN_out; h.Yout = Y_out; h.fwd_partial = fwd_partial;
     h.seed_lo = (uint32_t)seed; h.seed_hi = (uint32_t)(seed >> 32); h.iter = iter;
@@ -815,15 +830,13 @@ extern "C" int psp_dnet_rollout_fwd(const psp_dnet_config* cfg, const float* par
     }
     const bool x3 = b->mlp_dtype == PSP_MLP_F16X3 && p.inst.launch_fwd_x3 && p.inst.lds_bytes_x3 <= kMaxLds;
     if (b->mlp_dtype == PSP_MLP_F16X3 && !x3) return fail(-3, "split-product forward images do not fit the 160 KiB LDS for this (d,H)");
-    hipError_t e = x3 ? p.inst.launch_fwd_x3(a, p.grid, (hipStream_t)stream) : p.inst.launch_fwd(a, p.grid, (hipStream_t)stream);
-    if (e == hipSuccess && x3 && b->range_flag) {
-        // range guard (psp_hjb_config.range_flag): non-finite partials -> flag -> the fp32-MFMA rollout, predicated
-        hipLaunchKernelGGL(range_flag_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, fwd_partial, 2 * p.grid,
-                           b->range_flag);
-        if ((e = hipGetLastError()) != hipSuccess) return fail_hip(e, "range_flag_partials_kernel launch");
-        h.cond = b->range_flag; h.cond_want = 1;
-        e = p.inst.launch_fwd(a, p.grid, (hipStream_t)stream);
-    }
+    auto fp32 = [&]() { return p.inst.launch_fwd(a, p.grid, (hipStream_t)stream); };
+    if (x3)     // range guard (psp_hjb_config.range_flag): non-finite partials -> flag -> the fp32-MFMA rollout, predicated
+        return launch_redo(b->range_flag, h.cond, h.cond_want, "hjbd_fwd_kernel launch",
+                           [&]() { return p.inst.launch_fwd_x3(a, p.grid, (hipStream_t)stream); },
+                           [&]() { return PSP_LAUNCH(range_flag_partials_kernel, dim3(1), dim3(256), 0, stream, fwd_partial, 2 * p.grid, b->range_flag); },
+                           fp32);
+    const hipError_t e = fp32();
     if (e != hipSuccess) return fail_hip(e, "hjbd_fwd_kernel launch");
     return 0;
 }
@@ -854,16 +867,14 @@ int psp_hjb_family(int32_t d, int32_t H) {
     return inst.wide ? 2 : 1;
 }
 
-int psp_hjb_instance_count(void) {
-    return (int)(sizeof(kTable) / sizeof(kTable[0]) + sizeof(kWideTable) / sizeof(kWideTable[0]));
-}
+int psp_hjb_instance_count(void) { return table_count(kTable) + table_count(kWideTable); }
 
-int psp_hjb_instance_get(int32_t i, int32_t* d, int32_t* H, int32_t* family) {
-    const int nn = (int)(sizeof(kTable) / sizeof(kTable[0])), nw = (int)(sizeof(kWideTable) / sizeof(kWideTable[0]));
-    if (i < 0 || i >= nn + nw || !d || !H || !family) return fail(-1, "instance index out of range");
-    const Entry& e = i < nn ? kTable[i] : kWideTable[i - nn];
-    *d = e.d; *H = e.H; *family = i < nn ? 1 : 2;
-    return 0;
+int psp_hjb_instance_get(int32_t i, int32_t* d, int32_t* H, int32_t* family) {      // the narrow table, then the wide one
+    const int nn = table_count(kTable);
+    if (!family) return fail(-1, "instance index out of range");
+    const int rc = i < nn ? table_get(kTable, i, d, H) : table_get(kWideTable, i - nn, d, H);
+    if (rc == 0) *family = i < nn ? 1 : 2;
+    return rc;
 }
 
 int psp_hjb_query(const psp_hjb_config* cfg, psp_hjb_sizes* out) {
@@ -906,17 +917,13 @@ int psp_hjb_rollout_fwd(const psp_hjb_config* cfg, const float* params, const fl
         if (!p.inst.launch_fwd_bf16) return fail(-3, "the bf16 control-net mode exists for the narrow kernel family only");
         e = p.inst.launch_fwd_bf16(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream);      // make_plan kept the tile-per-wave forward
     } else if (cfg->mlp_dtype == PSP_MLP_F16X3) {
-        e = p.fwd_coop ? p.inst.launch_fwd_coop(a, p.fwd_grid, p.fwd_waves, (hipStream_t)stream)
-                       : p.inst.launch_fwd_x3(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream);
-        if (e == hipSuccess && cfg->range_flag) {
-            // range guard: non-finite partials -> flag -> the fp32-MFMA forward of the same launch, predicated on the flag
-            // (same grid, same partials / D / path-store layout; it overwrites what the split kernel left)
-            hipLaunchKernelGGL(range_flag_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, fwd_partial,
-                               2 * p.fwd_grid, cfg->range_flag);
-            if ((e = hipGetLastError()) != hipSuccess) return fail_hip(e, "range_flag_partials_kernel launch");
-            a.cond = cfg->range_flag; a.cond_want = 1;
-            e = p.inst.launch_fwd(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream);
-        }
+        // range guard: non-finite partials -> flag -> the fp32-MFMA forward of the same launch, predicated on the flag
+        // (same grid, same partials / D / path-store layout; it overwrites what the split kernel left)
+        return launch_redo(cfg->range_flag, a.cond, a.cond_want, "hjb_fwd_kernel launch",
+                           [&]() { return p.fwd_coop ? p.inst.launch_fwd_coop(a, p.fwd_grid, p.fwd_waves, (hipStream_t)stream)
+                                                     : p.inst.launch_fwd_x3(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream); },
+                           [&]() { return PSP_LAUNCH(range_flag_partials_kernel, dim3(1), dim3(256), 0, stream, fwd_partial, 2 * p.fwd_grid, cfg->range_flag); },
+                           [&]() { return p.inst.launch_fwd(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream); });
     } else if (cfg->mlp_dtype != PSP_MLP_FP32) {
         return fail(-1, "mlp_dtype out of range for the HJB rollout (fp32, bf16_fwd or f16x3)");
     } else {
@@ -958,11 +965,7 @@ int psp_hjb_terminal_reduce(const psp_hjb_config* cfg, const double* fwd_partial
     int rc = make_plan(cfg, &p);
     if (rc) return rc;
     if (!fwd_partial || !sums_out) return fail(-1, "null buffer passed to psp_hjb_terminal_reduce");
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, fwd_partial,
-                       p.fwd_grid, sums_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "reduce_partials_kernel launch");
-    return 0;
+    return PSP_LAUNCH(reduce_partials_kernel, dim3(1), dim3(256), 0, stream, fwd_partial, p.fwd_grid, sums_out);
 }
 
 int psp_hjb_terminal_reduce_loss(const psp_hjb_config* cfg, const double* fwd_partial, double* sums_out, float* loss_log,
@@ -974,11 +977,8 @@ int psp_hjb_terminal_reduce_loss(const psp_hjb_config* cfg, const double* fwd_pa
     if (loss_log && cfg->loss_kind == PSP_LOSS_WEIGHTS)
         return fail(-1, "psp_hjb_terminal_reduce_loss: the caller forms the loss of a PSP_LOSS_WEIGHTS run");
     if (cfg->K_global <= 0) return fail(-1, "K_global must be positive");
-    hipLaunchKernelGGL(reduce_partials_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, fwd_partial, p.fwd_grid,
-                       sums_out, cfg->loss_kind, 1.0 / (double)cfg->K_global, loss_log, index_dev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "reduce_partials_loss_kernel launch");
-    return 0;
+    return PSP_LAUNCH(reduce_partials_loss_kernel, dim3(1), dim3(256), 0, stream, fwd_partial, p.fwd_grid, sums_out, cfg->loss_kind,
+                      1.0 / (double)cfg->K_global, loss_log, index_dev);
 }
 
 int psp_iter_state_init(psp_iter_state* host_out, uint32_t iter, int32_t step, float beta1, float beta2) {
@@ -991,21 +991,15 @@ int psp_iter_state_init(psp_iter_state* host_out, uint32_t iter, int32_t step, f
 
 int psp_iter_state_advance(psp_iter_state* dev_state, float beta1, float beta2, void* stream) {
     if (!dev_state) return fail(-1, "null state passed to psp_iter_state_advance");
-    hipLaunchKernelGGL(iter_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dev_state, (double)beta1, (double)beta2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "iter_advance_kernel launch");
-    return 0;
+    return PSP_LAUNCH(iter_advance_kernel, dim3(1), dim3(1), 0, stream, dev_state, (double)beta1, (double)beta2);
 }
 
 int psp_adam_step_dev(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                       const psp_iter_state* dev_state, float lr, float beta1, float beta2, float eps, void* stream) {
     if (!params || !grad || !exp_avg || !exp_avg_sq || !dev_state) return fail(-1, "null buffer passed to psp_adam_step_dev");
     if (n <= 0) return fail(-1, "psp_adam_step_dev needs n > 0");
-    hipLaunchKernelGGL(adam_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, grad,
-                       exp_avg, exp_avg_sq, (long long)n, dev_state, lr, beta1, beta2, eps);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "adam_dev_kernel launch");
-    return 0;
+    return PSP_LAUNCH(adam_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, params, grad, exp_avg, exp_avg_sq,
+                      (long long)n, dev_state, lr, beta1, beta2, eps);
 }
 
 namespace {
@@ -1016,14 +1010,7 @@ hipError_t launch_hjb_bwd(const psp_hjb_config* cfg, const Plan& p, psp::HjbArgs
                         (p.inst.wide || p.inst.bwd2_x3_lds_bytes() <= kMaxLds);   // (else the fp32 backward: same results, same store)
     auto fp32 = [&]() { return p.inst.launch_bwd2(a, p.bwd_grid, st); };
     if (!bwd_x3) return fp32();
-    const bool guard = cfg->range_flag != nullptr;
-    if (guard) { a.cond = cfg->range_flag; a.cond_want = 0; }
-    hipError_t e = p.inst.launch_bwd2_x3(a, p.bwd_grid, st);
-    if (e != hipSuccess || !guard) return e;
-    a.cond_want = 1;
-    e = fp32();
-    a.cond = nullptr; a.cond_want = 0;
-    return e;
+    return launch_either(cfg->range_flag, a.cond, a.cond_want, [&]() { return p.inst.launch_bwd2_x3(a, p.bwd_grid, st); }, fp32);
 }
 }  // namespace
 
@@ -1046,11 +1033,7 @@ int psp_hjb_rollout_bwd(const psp_hjb_config* cfg, const float* params, const fl
     hipError_t e = launch_hjb_bwd(cfg, p, a, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "backward kernel launch");
     const int P = p.inst.n_params;
-    hipLaunchKernelGGL(reduce_grad_kernel, dim3((P + 31) / 32), dim3(256), 0, (hipStream_t)stream,
-                       grad_partial, p.bwd_grid, P, grad_out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "reduce_grad_kernel launch");
-    return 0;
+    return PSP_LAUNCH(reduce_grad_kernel, dim3((P + 31) / 32), dim3(256), 0, stream, grad_partial, p.bwd_grid, P, grad_out);
 }
 
 int psp_hjb_rollout_bwd_step(const psp_hjb_config* cfg, float* params, const float* path, const float* D, const double* sums,
@@ -1071,11 +1054,8 @@ int psp_hjb_rollout_bwd_step(const psp_hjb_config* cfg, float* params, const flo
     hipError_t e = launch_hjb_bwd(cfg, p, a, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "backward kernel launch");
     const int P = p.inst.n_params;
-    hipLaunchKernelGGL(reduce_grad_adam_advance_kernel, dim3((P + 31) / 32), dim3(256), 0, (hipStream_t)stream, grad_partial,
-                       p.bwd_grid, P, grad_out, params, exp_avg, exp_avg_sq, dev_state, ticket, lr, beta1, beta2, eps);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "reduce_grad_adam_advance_kernel launch");
-    return 0;
+    return PSP_LAUNCH(reduce_grad_adam_advance_kernel, dim3((P + 31) / 32), dim3(256), 0, stream, grad_partial, p.bwd_grid, P, grad_out,
+                      params, exp_avg, exp_avg_sq, dev_state, ticket, lr, beta1, beta2, eps);
 }
 
 int psp_hjb_adjoint_sweep(const psp_hjb_config* cfg, const float* params, float* path, const float* XN,
@@ -1101,36 +1081,24 @@ int psp_hjb_adjoint_sweep(const psp_hjb_config* cfg, const float* params, float*
         return 0;
     }
     // one wave per 16-trajectory tile, like the forward kernels (the recursion is sequential in time)
-    int fw = (p.ntile16 + n_cus() - 1) / n_cus();
-    if (fw < 1) fw = 1;
-    if (fw > (p.inst.wide ? 4 : 8)) fw = p.inst.wide ? 4 : 8;
+    const int fw = tile_waves(p.ntile16, p.inst.wide);
     const int grid = (p.ntile16 + fw - 1) / fw;
     const bool adj_x3 = cfg->mlp_dtype == PSP_MLP_F16X3 && p.inst.launch_adj_x3;    // (make_plan checked the LDS fit of the forward carve)
-    const bool guard = adj_x3 && cfg->range_flag != nullptr;                         // range guard: both sweeps, predicated
-    if (guard) { a.cond = cfg->range_flag; a.cond_want = 0; }
-    hipError_t e = adj_x3 ? p.inst.launch_adj_x3(a, grid, fw * 64, (hipStream_t)stream)
-                          : p.inst.launch_adj(a, grid, fw * 64, (hipStream_t)stream);
-    if (e == hipSuccess && guard) {
-        a.cond_want = 1;
-        e = p.inst.launch_adj(a, grid, fw * 64, (hipStream_t)stream);
-    }
+    auto fp32 = [&]() { return p.inst.launch_adj(a, grid, fw * 64, (hipStream_t)stream); };
+    const hipError_t e = !adj_x3 ? fp32() : launch_either(cfg->range_flag, a.cond, a.cond_want,    // range guard: both sweeps, predicated
+                                                          [&]() { return p.inst.launch_adj_x3(a, grid, fw * 64, (hipStream_t)stream); }, fp32);
     if (e != hipSuccess) return fail_hip(e, "hjb_adj_kernel launch");
     return 0;
 }
 
 int psp_gen_supported(int32_t d, int32_t H) {
     psp::GenInstance inst;
-    return find_gen_instance(d, H, &inst) ? 1 : 0;
+    return find_in(kGenTable, d, H, &inst) ? 1 : 0;
 }
 
-int psp_gen_instance_count(void) { return (int)(sizeof(kGenTable) / sizeof(kGenTable[0])); }
+int psp_gen_instance_count(void) { return table_count(kGenTable); }
 
-int psp_gen_instance_get(int32_t i, int32_t* d, int32_t* H) {
-    const int n = (int)(sizeof(kGenTable) / sizeof(kGenTable[0]));
-    if (i < 0 || i >= n || !d || !H) return fail(-1, "instance index out of range");
-    *d = kGenTable[i].d; *H = kGenTable[i].H;
-    return 0;
-}
+int psp_gen_instance_get(int32_t i, int32_t* d, int32_t* H) { return table_get(kGenTable, i, d, H); }
 
 int psp_gen_query(const psp_gen_config* cfg, psp_gen_sizes* out) {
     GenPlan p;
@@ -1166,24 +1134,18 @@ int psp_gen_rollout_fwd(const psp_gen_config* cfg, const float* params, const fl
     if (cfg->mlp_dtype < PSP_MLP_FP32 || cfg->mlp_dtype > PSP_MLP_F16X3) return fail(-1, "mlp_dtype out of range");
     if (cfg->mlp_dtype == PSP_MLP_F16X3 && (!p.inst.launch_fwd_x3 || p.inst.fwd_x3_lds_bytes() > kMaxLds))
         return fail(-3, "split-product forward tables do not fit the 160 KiB LDS for this (d,H)");
-    if (cfg->mlp_dtype == PSP_MLP_F16X3 && cfg->range_flag) {
-        hipLaunchKernelGGL(snapshot_u64_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, kcount,
-                           reinterpret_cast<unsigned long long*>(cfg->range_flag + 2));
-        hipError_t es = hipGetLastError();
-        if (es != hipSuccess) return fail_hip(es, "snapshot_u64_kernel launch");
-    }
-    hipError_t e = cfg->mlp_dtype == PSP_MLP_F16X3 ? p.inst.launch_fwd_x3(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream)
-                   : cfg->mlp_dtype != PSP_MLP_FP32 ? p.inst.launch_fwd_bf16(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream)
-                                                    : p.inst.launch_fwd(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream);
-    if (e == hipSuccess && cfg->mlp_dtype == PSP_MLP_F16X3 && cfg->range_flag) {
+    auto fp32 = [&]() { return p.inst.launch_fwd(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream); };
+    if (cfg->mlp_dtype == PSP_MLP_F16X3) {
         // range guard (psp_gen_config.range_flag): a non-finite V(X_N) / Y_N -> flag -> the fp32-MFMA forward, predicated.
         // kcount accumulates (atomicAdd): the flag kernel takes back what the split kernel added when it raises the flag
-        hipLaunchKernelGGL(range_flag_arrays_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, VN, YN, cfg->K_local,
-                           cfg->range_flag, kcount, reinterpret_cast<const unsigned long long*>(cfg->range_flag + 2));
-        if ((e = hipGetLastError()) != hipSuccess) return fail_hip(e, "range_flag_arrays_kernel launch");
-        a.cond = cfg->range_flag; a.cond_want = 1;
-        e = p.inst.launch_fwd(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream);
+        unsigned long long* const kcount_before = cfg->range_flag ? reinterpret_cast<unsigned long long*>(cfg->range_flag + 2) : nullptr;
+        if (cfg->range_flag && (rc = PSP_LAUNCH(snapshot_u64_kernel, dim3(1), dim3(1), 0, stream, kcount, kcount_before))) return rc;
+        return launch_redo(cfg->range_flag, a.cond, a.cond_want, "gen_fwd_kernel launch",
+                           [&]() { return p.inst.launch_fwd_x3(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream); },
+                           [&]() { return PSP_LAUNCH(range_flag_arrays_kernel, dim3(1), dim3(1024), 0, stream, VN, YN, cfg->K_local, cfg->range_flag, kcount, kcount_before); },
+                           fp32);
     }
+    const hipError_t e = cfg->mlp_dtype != PSP_MLP_FP32 ? p.inst.launch_fwd_bf16(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream) : fp32();
     if (e != hipSuccess) return fail_hip(e, "gen_fwd_kernel launch");
     return 0;
 }
@@ -1203,22 +1165,14 @@ int psp_gen_rollout_bwd(const psp_gen_config* cfg, const float* params, const fl
     if (cfg->mlp_dtype < PSP_MLP_FP32 || cfg->mlp_dtype > PSP_MLP_F16X3) return fail(-1, "mlp_dtype out of range");
     // (PSP_MLP_F16X3 with shared trajectory weights: the split-product consumers; per-sample weights keep the fp32 kernel)
     const bool bwd_x3 = cfg->mlp_dtype == PSP_MLP_F16X3 && !cfg->per_sample_weights && p.inst.launch_bwd2_x3;
-    const bool guard = bwd_x3 && cfg->range_flag != nullptr;     // range guard: split and fp32-MFMA backward, predicated
-    if (guard) { a.cond = cfg->range_flag; a.cond_want = 0; }
-    hipError_t e = cfg->mlp_dtype == PSP_MLP_BF16 ? p.inst.launch_bwd2_bf16(a, p.bwd_grid, (hipStream_t)stream)
-                   : bwd_x3 ? p.inst.launch_bwd2_x3(a, p.bwd_grid, (hipStream_t)stream)
-                            : p.inst.launch_bwd2(a, p.bwd_grid, (hipStream_t)stream);
-    if (e == hipSuccess && guard) {
-        a.cond_want = 1;
-        e = p.inst.launch_bwd2(a, p.bwd_grid, (hipStream_t)stream);
-    }
+    auto fp32 = [&]() { return p.inst.launch_bwd2(a, p.bwd_grid, (hipStream_t)stream); };
+    const hipError_t e = cfg->mlp_dtype == PSP_MLP_BF16 ? p.inst.launch_bwd2_bf16(a, p.bwd_grid, (hipStream_t)stream)
+                         : !bwd_x3 ? fp32()
+                                   : launch_either(cfg->range_flag, a.cond, a.cond_want,       // range guard: split and fp32-MFMA backward, predicated
+                                                   [&]() { return p.inst.launch_bwd2_x3(a, p.bwd_grid, (hipStream_t)stream); }, fp32);
     if (e != hipSuccess) return fail_hip(e, "gen_bwd2_kernel launch");
     const int P = p.inst.n_params;
-    hipLaunchKernelGGL(reduce_grad_kernel, dim3((P + 31) / 32), dim3(256), 0, (hipStream_t)stream,
-                       grad_partial, p.bwd_grid, P, grad_out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "reduce_grad_kernel launch");
-    return 0;
+    return PSP_LAUNCH(reduce_grad_kernel, dim3((P + 31) / 32), dim3(256), 0, stream, grad_partial, p.bwd_grid, P, grad_out);
 }
 
 
@@ -1461,9 +1415,8 @@ int psp_genl_rollout_fwd_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* 
     g.Vsteps = cfg->base.v_steps_out; g.Ysteps = cfg->base.y_steps_out;
     g.seed_lo = (uint32_t)seed; g.seed_hi = (uint32_t)(seed >> 32); g.iter = iter;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(psp::genl_tables_kernel, dim3(128), dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "genl_tables_kernel launch");
+    if ((rc = PSP_LAUNCH(genl_tables_kernel, dim3(128), dim3(256), 0, st, a))) return rc;
+    hipError_t e;
     if (p.ul2_on) {
         const psp::GenlLogArgs la = {p.a, p.u};
         e = psp::genl_ul2_launch_fwd(la, p.nw_fwd, p.ntile16, p.fwd_lds, st);        // (genl_ul2_instance.hip)
@@ -1499,10 +1452,7 @@ int psp_genl_rollout_bwd(const psp_genl_config* cfg, const float* params, const 
                                      : psp::genl_launch_bwd<8>(p.a, p.bwd_grid, p.bwd_groups, p.bwd_lds, st);
     if (e != hipSuccess) return fail_hip(e, "genl_bwd_kernel launch");
     const int P = (int)p.n_params;
-    hipLaunchKernelGGL(reduce_grad_kernel, dim3((P + 31) / 32), dim3(256), 0, st, grad_partial, p.bwd_grid, P, grad_out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "reduce_grad_kernel launch");
-    return 0;
+    return PSP_LAUNCH(reduce_grad_kernel, dim3((P + 31) / 32), dim3(256), 0, st, grad_partial, p.bwd_grid, P, grad_out);
 }
 
 // ---- adjoint sweep of the state path, value-function ansatz (genl_adj_kernels.h) ------------------------------------------------
@@ -1657,10 +1607,8 @@ int psp_genl_test_error(const psp_genl_eval_config* cfg, const float* params, co
     ea.partial = partial; ea.log_out = log_out; ea.slot_dev = slot_dev; ea.slot = slot; ea.log_slots = cfg->log_slots;
     ea.x_out = x_out; ea.t_out = t_out; ea.v_out = v_out; ea.vtrue_out = vtrue_out; ea.keep_out = keep_out;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(psp::genl_tables_kernel, dim3(128), dim3(256), 0, st, ea.n);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail_hip(err, "genl_tables_kernel launch");
-    err = psp::genl_eval_launch(ea, e.nw, e.grid, e.lds, st);
+    if (const int rct = PSP_LAUNCH(genl_tables_kernel, dim3(128), dim3(256), 0, st, ea.n)) return rct;
+    const hipError_t err = psp::genl_eval_launch(ea, e.nw, e.grid, e.lds, st);
     if (err != hipSuccess) return fail_hip(err, "genl_eval_kernel launch");
     return 0;
 }
@@ -1757,11 +1705,8 @@ int psp_adam_step(float* params, const float* grad, float* exp_avg, float* exp_a
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
     const float step_size = (float)((double)lr / bc1);
     const float bc2_sqrt = (float)sqrt(bc2);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params,
-                       grad, exp_avg, exp_avg_sq, (long long)n, lr, beta1, beta2, eps, step_size, bc2_sqrt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "adam_kernel launch");
-    return 0;
+    return PSP_LAUNCH(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, params, grad, exp_avg, exp_avg_sq,
+                      (long long)n, lr, beta1, beta2, eps, step_size, bc2_sqrt);
 }
 
 // sigma-basis plans (include/psp.h): W~1x = W1x B into the kernel-layout parameters, dW1x = dW~1x B^T on the reduced gradient
@@ -1792,24 +1737,17 @@ int psp_philox_normal_fill(float* out, int32_t N, int32_t K_local, int32_t d, in
                            uint64_t seed, uint32_t iter, void* stream) {
     if (!out || N <= 0 || K_local <= 0 || d <= 0) return fail(-1, "bad arguments to psp_philox_normal_fill");
     const long long n0 = (long long)K_local * d;
-    hipLaunchKernelGGL(zero_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n0);
+    if (const int rc = PSP_LAUNCH(zero_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, stream, out, n0)) return rc;
     const long long total = (long long)N * K_local * (((d + 15) / 16) * 4);
-    hipLaunchKernelGGL(philox_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       out, N, K_local, d, (long long)k_offset, (uint32_t)seed, (uint32_t)(seed >> 32), iter);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "philox_fill_kernel launch");
-    return 0;
+    return PSP_LAUNCH(philox_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out, N, K_local, d,
+                      (long long)k_offset, (uint32_t)seed, (uint32_t)(seed >> 32), iter);
 }
 
 int psp_hjb_control_eval(int32_t d, int32_t H, const float* params, const float* X, int32_t K, float t,
                          float* minus_Z_out, void* stream) {
     if (!params || !X || !minus_Z_out || d <= 0 || H <= 0 || K <= 0)
         return fail(-1, "bad arguments to psp_hjb_control_eval");
-    hipLaunchKernelGGL(control_eval_kernel, dim3(K), dim3(64), 2 * H * sizeof(float), (hipStream_t)stream, d, H,
-                       params, X, K, t, minus_Z_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "control_eval_kernel launch");
-    return 0;
+    return PSP_LAUNCH(control_eval_kernel, dim3(K), dim3(64), 2 * H * sizeof(float), stream, d, H, params, X, K, t, minus_Z_out);
 }
 
 }  // extern "C"

@@ -249,6 +249,14 @@ SIGNATURES = {
     "psp_gen_rollout_bwd": (C.c_int, [C.POINTER(GenConfig), _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+# the structs each psp_abi_struct_sizes* call reports, in its order
+ABI_STRUCTS = (
+    ("psp_abi_struct_sizes", (HjbConfig, HjbSizes, GenConfig, GenSizes, DnetConfig, DnetSizes)),
+    ("psp_abi_struct_sizes2", (GenlConfig, GenlSizes)),
+    ("psp_abi_struct_sizes3", (IsConfig,)),
+    ("psp_abi_struct_sizes4", (GenlEvalConfig, GenlEvalSizes)),
+)
+
 _lib = None
 
 
@@ -272,29 +280,13 @@ def load():
             raise NativeLibraryError("%s does not export %s (stale build?)" % (LIB_PATH, name))
         fn.restype = res
         fn.argtypes = args
-    sizes = (C.c_int32 * 6)()
-    lib.psp_abi_struct_sizes(C.byref(sizes))
-    mine = [C.sizeof(t) for t in (HjbConfig, HjbSizes, GenConfig, GenSizes, DnetConfig, DnetSizes)]
-    if list(sizes) != mine:          # a stale build or a drifted struct declaration would corrupt kernel arguments silently
-        raise NativeLibraryError("%s was built for other struct layouts (library %s, binding %s): rebuild it"
-                                 % (LIB_PATH, list(sizes), mine))
-    sizes2 = (C.c_int32 * 2)()
-    lib.psp_abi_struct_sizes2(C.byref(sizes2))
-    mine2 = [C.sizeof(GenlConfig), C.sizeof(GenlSizes)]
-    if list(sizes2) != mine2:
-        raise NativeLibraryError("%s was built for other struct layouts (library %s, binding %s): rebuild it"
-                                 % (LIB_PATH, list(sizes2), mine2))
-    sizes3 = (C.c_int32 * 1)()
-    lib.psp_abi_struct_sizes3(C.byref(sizes3))
-    if list(sizes3) != [C.sizeof(IsConfig)]:
-        raise NativeLibraryError("%s was built for other struct layouts (library %s, binding %s): rebuild it"
-                                 % (LIB_PATH, list(sizes3), [C.sizeof(IsConfig)]))
-    sizes4 = (C.c_int32 * 2)()
-    lib.psp_abi_struct_sizes4(C.byref(sizes4))
-    mine4 = [C.sizeof(GenlEvalConfig), C.sizeof(GenlEvalSizes)]
-    if list(sizes4) != mine4:
-        raise NativeLibraryError("%s was built for other struct layouts (library %s, binding %s): rebuild it"
-                                 % (LIB_PATH, list(sizes4), mine4))
+    for symbol, structs in ABI_STRUCTS:
+        sizes = (C.c_int32 * len(structs))()
+        getattr(lib, symbol)(C.byref(sizes))
+        mine = [C.sizeof(t) for t in structs]
+        if list(sizes) != mine:      # a stale build or a drifted struct declaration would corrupt kernel arguments silently
+            raise NativeLibraryError("%s was built for other struct layouts (library %s, binding %s): rebuild it"
+                                     % (LIB_PATH, list(sizes), mine))
     _lib = lib
     return lib
 
@@ -334,52 +326,47 @@ def family(d, H):
     return int(load().psp_hjb_family(int(d), int(H)))
 
 
+def _instances(family, n_fields):
+    """The rows of psp_<family>_instance_get, `n_fields` int32 each."""
+    lib = load()
+    count, get = getattr(lib, "psp_%s_instance_count" % family), getattr(lib, "psp_%s_instance_get" % family)
+    out = []
+    for i in range(count()):
+        row = [C.c_int32() for _ in range(n_fields)]
+        check(get(i, *[C.byref(v) for v in row]), "psp_%s_instance_get" % family)
+        out.append(tuple(v.value for v in row))
+    return out
+
+
 def instances():
     """[(d, H, family)] of the compiled HJB kernel instances (family 1 narrow, 2 wide)."""
-    lib = load()
-    out = []
-    for i in range(lib.psp_hjb_instance_count()):
-        d, H, f = C.c_int32(), C.c_int32(), C.c_int32()
-        check(lib.psp_hjb_instance_get(i, C.byref(d), C.byref(H), C.byref(f)), 'psp_hjb_instance_get')
-        out.append((d.value, H.value, f.value))
-    return out
+    return _instances("hjb", 3)
 
 
 def gen_instances():
     """[(d, H)] of the compiled GeneralSolver kernel instances."""
-    lib = load()
-    out = []
-    for i in range(lib.psp_gen_instance_count()):
-        d, H = C.c_int32(), C.c_int32()
-        check(lib.psp_gen_instance_get(i, C.byref(d), C.byref(H)), 'psp_gen_instance_get')
-        out.append((d.value, H.value))
-    return out
+    return _instances("gen", 2)
 
 
 def dnet_instances():
     """[(d, H)] of the compiled DenseNet-control forward kernels."""
+    return _instances("dnet", 2)
+
+
+def _query(symbol, cfg, sizes):
+    """One size query without raising: (rc, sizes, message)."""
     lib = load()
-    out = []
-    for i in range(lib.psp_dnet_instance_count()):
-        d, H = C.c_int32(), C.c_int32()
-        check(lib.psp_dnet_instance_get(i, C.byref(d), C.byref(H)), 'psp_dnet_instance_get')
-        out.append((d.value, H.value))
-    return out
+    rc = getattr(lib, symbol)(C.byref(cfg), C.byref(sizes))
+    return rc, sizes, (lib.psp_last_error().decode() if rc else '')
 
 
 def gen_query_rc(cfg):
-    sizes = GenSizes()
-    lib = load()
-    rc = lib.psp_gen_query(C.byref(cfg), C.byref(sizes))
-    return rc, sizes, (lib.psp_last_error().decode() if rc else '')
+    return _query("psp_gen_query", cfg, GenSizes())
 
 
 def query_rc(cfg):
     """psp_hjb_query without raising: (rc, sizes, message)."""
-    sizes = HjbSizes()
-    lib = load()
-    rc = lib.psp_hjb_query(C.byref(cfg), C.byref(sizes))
-    return rc, sizes, (lib.psp_last_error().decode() if rc else '')
+    return _query("psp_hjb_query", cfg, HjbSizes())
 
 
 def gen_supported(d, H):
@@ -387,12 +374,12 @@ def gen_supported(d, H):
 
 
 def gen_query(cfg):
-    sizes = GenSizes()
-    check(load().psp_gen_query(C.byref(cfg), C.byref(sizes)), "psp_gen_query")
+    rc, sizes, _ = gen_query_rc(cfg)
+    check(rc, "psp_gen_query")
     return sizes
 
 
 def query(cfg):
-    sizes = HjbSizes()
-    check(load().psp_hjb_query(C.byref(cfg), C.byref(sizes)), "psp_hjb_query")
+    rc, sizes, _ = query_rc(cfg)
+    check(rc, "psp_hjb_query")
     return sizes

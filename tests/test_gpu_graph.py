@@ -4,13 +4,14 @@ step / bias corrections) read from device memory instead of host arguments.
 
 Equality: D of every iteration and the loss log agree to 1e-6 relative (the rollout kernels are the same; Adam's bias
 corrections come from running fp64 products beta^step instead of pow(), which can move a parameter by one ulp)."""
+import ctypes as C
 import math
 
 import pytest
 import torch
 
 from conftest import load_golden
-from util_cases import flat_params, make_pkg_solver
+from util_cases import flat_params, make_pkg_solver, psp
 
 pytestmark = pytest.mark.gpu
 
@@ -86,3 +87,28 @@ def test_adam_state_is_handed_to_the_nets_own_optimiser_and_back():
     for x, y in zip(got, six.loss_log):
         assert math.isclose(x, y, rel_tol=1e-6), (got, six.loss_log)
     assert float((flat_params(a.z_n) - flat_params(six.z_n)).abs().max()) <= 1e-6
+
+
+@pytest.mark.parametrize("step", [1, 2, 7])
+def test_adam_host_step_and_device_state_share_one_arithmetic(step):
+    """psp_adam_step (bias corrections formed on the host from `step`) and psp_adam_step_dev (formed by every thread from a
+    device psp_iter_state that psp_iter_state_init set to the same step) leave the same bits in p, m and v.  n = 1000 is no
+    multiple of the 256-thread workgroup or of 32, so the last workgroup is partly idle."""
+    nat = psp.native
+    lib = nat.load()
+    n, lr, b1, b2, eps = 1000, 1e-3, 0.9, 0.999, 1e-8
+    gen = torch.Generator().manual_seed(100 + step)
+    p, g, m, v = (torch.randn(n, generator=gen) for _ in range(4))
+    v = v.square()
+    host = [t.to(dev()) for t in (p, g, m, v)]
+    devs = [t.to(dev()) for t in (p, g, m, v)]
+    st = nat.IterState()
+    nat.check(lib.psp_iter_state_init(C.byref(st), 0, step, b1, b2), "psp_iter_state_init")
+    state = torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(dev())
+    stream = nat.stream_ptr(dev())
+    nat.check(lib.psp_adam_step(*[nat.ptr(t) for t in host], n, step, lr, b1, b2, eps, stream), "psp_adam_step")
+    nat.check(lib.psp_adam_step_dev(*[nat.ptr(t) for t in devs], n, nat.ptr(state), lr, b1, b2, eps, stream), "psp_adam_step_dev")
+    torch.cuda.synchronize()
+    assert not torch.equal(host[0], p.to(dev())) and bool(torch.isfinite(host[0]).all())      # (the step did something)
+    for name, a, b in zip("pgmv", host, devs):
+        assert torch.equal(a, b), (name, int((a != b).sum()), float((a - b).abs().max()))

@@ -114,12 +114,20 @@ def test_in_range_run_never_takes_the_fallback(name):
         assert math.isclose(a, b, rel_tol=1e-4)
 
 
-def test_dense_control_rollout_is_guarded():
-    """time_approx='outer' (hjbd_fwd_kernel<.., X3>): nets scaled down so that the relu^2 layers stay finite in fp32 at |x| = 7e4."""
+@pytest.mark.parametrize("flags", [
+    dict(),                                                            # the golden case's own flags
+    dict(adaptive_forward_process=True, detach_forward=True),          # backward: hjbd_bwd_kernel<.., X3> and its fp32 twin
+    dict(adaptive_forward_process=True, detach_forward=False),         # attached: the pair of psp_dnet_adjoint_sweep runs too
+], ids=["golden_flags", "adaptive_detached", "adaptive_attached"])
+def test_dense_control_rollout_is_guarded(flags):
+    """time_approx='outer' (hjbd_fwd_kernel<.., X3>): nets scaled down so that the relu^2 layers stay finite in fp32 at |x| = 7e4.
+    The guarded run is the mlp_dtype='fp32' run bit for bit, through the forward, the backward and (attached) the sweep."""
     rec = load_golden("llgc_d12_outer_moment")
+    L = 2
 
     def run(mlp, **kw):
-        model = make_pkg_solver(rec["case"], dev(), backend="native", mlp_dtype=mlp, L=2, **kw)
+        kw.update(flags)
+        model = make_pkg_solver(rec["case"], dev(), backend="native", mlp_dtype=mlp, L=L, **kw)
         with torch.no_grad():
             for net in model.z_n:
                 for p in net.parameters():
@@ -133,8 +141,9 @@ def test_dense_control_rollout_is_guarded():
 
     ref, got = run("fp32"), run("f16x3")
     assert all(math.isfinite(v) for v in ref.loss_log), ref.loss_log
-    assert got._native_plan.matrix_mode == "f16x3" and got.range_fallback_iterations == 2
+    assert got._native_plan.matrix_mode == "f16x3" and got.range_fallback_iterations == L
     assert got.loss_log == ref.loss_log
+    assert torch.equal(got._native_plan.grad, ref._native_plan.grad)
     raw = run("f16x3", range_guard=False)
     assert not math.isfinite(raw.loss_log[0])
 
