@@ -696,6 +696,71 @@ int psp_dnet_rollout_bwd(const psp_dnet_config* cfg, const float* params, const 
                          float* partial, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Solver.train with a linear, affine or constant control per time step (appended in 0.4.0, no version bump; csrc/aff_kernels.h):
+ * time_approx='outer' with z_n a list of function_space.Linear / Affine / Constant (reference function_space.py:24-63; the
+ * notebook `Ornstein-Uhlenbeck - quadratic costs - linear ansatz.ipynb`).  The kernels see the EFFECTIVE maps only,
+ *     Z_n(x) = M_n x + c_n,
+ * and return (dM_n, dc_n); what lies between them and the modules' parameters (Linear: M = Q^-1 B^T F) is the caller's.
+ * base.d names the compiled bucket (psp_aff_instance_get: 16, 32, 64), d_real <= base.d the real dimension; EVERY array is zero
+ * padded to base.d: maps (N, d, d) row-major, shifts (N, d), problem vectors / matrices, x0, supplied noise, the u_L2 reference.
+ * base.H must be 0 and base.mlp_dtype PSP_MLP_FP32 (fp32 arithmetic only; -3 otherwise); base.u_ref, iter_dev and range_flag are
+ * not read.  Per step the rollout is that of psp_dnet_rollout_fwd (solver.py:449-486), every coefficient kind of psp_hjb_config,
+ * the same Philox counters, (sum D, sum D^2) per workgroup in fp64.
+ * u_L2 log: on when base.u_l2_out is set;  u_l2_out[k] = sum_n |-Z_n(X_n) - u*(X_{n+1}, t_n)|^2 dt  with ul2_kind
+ *   PSP_UL2_TABLE: ul2_ref = (N, d) u*(t_n);  PSP_UL2_LINEAR: ul2_ref = (N, d, d) gains, u* = M*_n x;  PSP_UL2_GRID: -3.
+ * Path store (base.store_path 1 / 2 / 3, images as for psp_dnet_*): N x K_local rows of 2 d floats, [X_n | image].
+ * Call sequence per iteration:
+ *     psp_aff_rollout_fwd -> psp_aff_terminal_reduce -> [weights from D on the caller's side]
+ *     -> psp_aff_adjoint_sweep (store_path 2 / 3 only: gradients through the state path, relative entropy attached)
+ *     -> psp_aff_rollout_bwd -> [sum the slices, chain rule, all-reduce] -> psp_adam_step
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct psp_aff_config {
+    psp_hjb_config base;
+    int32_t struct_bytes;     /* sizeof(psp_aff_config): checked by the library (this struct is not in psp_abi_struct_sizes*) */
+    int32_t d_real;
+    int32_t has_matrix;       /* 1: the control has maps M_n (Linear, Affine)                                                 */
+    int32_t has_bias;         /* 1: the control has shifts c_n (Affine, Constant); at least one of the two                    */
+    int32_t ul2_kind;         /* PSP_UL2_TABLE | PSP_UL2_LINEAR, read when base.u_l2_out is set                               */
+    int32_t reserved;
+    const float* ul2_ref;     /* the kind's reference data (above), DEVICE                                                    */
+} psp_aff_config;
+
+typedef struct psp_aff_sizes {
+    int64_t path_bytes;        /* N x K_local x 2 d floats (0 when store_path = 0)                                            */
+    int64_t fwd_partial_bytes; /* per-workgroup (sum D, sum D^2) fp64 pairs                                                   */
+    int64_t partial_bytes;     /* N x slices partial gradients of padded_params floats                                       */
+    int32_t fwd_workgroups, fwd_threads;
+    int32_t slices;            /* trajectory slices per time step of psp_aff_rollout_bwd                                      */
+    int32_t padded_params;     /* d * d + d: [dM (d x d row-major) | dc (d)] in the bucket's width                            */
+    int32_t bwd_workgroups;
+    int32_t lds_bytes;         /* the forward workgroup's LDS (the sweep's is smaller)                                        */
+} psp_aff_sizes;
+
+int psp_aff_instance_count(void);
+int psp_aff_instance_get(int32_t i, int32_t* d);
+/* Every check the entry points below make of the config, and the sizes, without a launch (no GPU needed).  -1 invalid argument
+ * (wrong struct_bytes, enum out of range, missing pointer), -2 no bucket of that width, -3 H / mlp_dtype / PSP_UL2_GRID / LDS. */
+int psp_aff_query(const psp_aff_config* cfg, psp_aff_sizes* out);
+/* maps: (N, d, d) or NULL (!has_matrix); shifts: (N, d) or NULL (!has_bias); x0, x0_stride, y0, xi, seed, iter, D_out, XN_out,
+ * Y_out as for psp_hjb_rollout_fwd (XN_out rows are base.d floats); path: path_bytes or NULL with store_path = 0. */
+int psp_aff_rollout_fwd(const psp_aff_config* cfg, const float* maps, const float* shifts, const float* x0, int32_t x0_stride,
+                        const float* y0, const float* xi, uint64_t seed, uint32_t iter, float* path, float* D_out, float* XN_out,
+                        float* Y_out, double* fwd_partial, void* stream);
+int psp_aff_terminal_reduce(const psp_aff_config* cfg, const double* fwd_partial, double* sums_out, void* stream);
+/* Gradients THROUGH the state path (adaptive_forward_process=True with detach_forward=False) and the attached relative entropy;
+ * mu, nu, wT as for psp_hjb_adjoint_sweep (nu / wT may be NULL; store_path 3 needs nu and reads no mu-term: mu must be 0).  With
+ * lambda_N = wT grad g(X_N), for n = N-1 .. 0:
+ *     Lam     = lambda + (mu + nu) dt grad f(X_{n+1})
+ *     delta_n = mu (xi_{n+1} sqrt(dt) - Z_n dt) + nu Z_n dt - dt B^T Lam
+ *     lambda  = Lam + dt J_b(X_n)^T Lam + M_n^T delta_n
+ * and the image slot of step n in `path` becomes delta_n / sqrt(dt): psp_aff_rollout_bwd then runs with w = 1. */
+int psp_aff_adjoint_sweep(const psp_aff_config* cfg, const float* maps, float* path, const float* XN, const float* mu,
+                          const float* nu, const float* wT, void* stream);
+/* partial[(n * slices + s)] = [sum_k delta_{n,k} X_{n,k}^T | sum_k delta_{n,k}] over the trajectories of slice s, with
+ * delta_{n,k} = w_k sqrt(dt) image_{n,k}; w: (K_local).  Every thread sums sequentially: equal arguments give equal bits. */
+int psp_aff_rollout_bwd(const psp_aff_config* cfg, const float* path, const float* w, float* partial, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Importance-sampling evaluation under the problem's REFERENCE control u* or under no control (utilities.do_importance_sampling_me,
  * reference utilities.py:287-359, with control='true' and simulate_naive=True; csrc/hjbe_kernels.h).  Forward only, one lane per
  * trajectory, no net.  Per step n (t_n = n dt), from X_0 = x0:

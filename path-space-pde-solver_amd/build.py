@@ -93,9 +93,12 @@ def _build(force, jobs, verbose, only):
     ugrid = os.path.join(CSRC, "ugrid.h")
     ehdr = os.path.join(CSRC, "hjbe_kernels.h")
     einst_src = os.path.join(CSRC, "hjbe_instance.hip")
-    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, os.path.join(CSRC, "hjb_basis_kernels.h"), ghdr, whdr, dhdr, ehdr, ugrid, os.path.join(CSRC, "genl_kernels.h"), os.path.join(CSRC, "genl_eval_kernels.h"), os.path.join(CSRC, "genl_adj_kernels.h"), inc, idef, gdef, wdef, ddef])]
+    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, os.path.join(CSRC, "hjb_basis_kernels.h"), ghdr, whdr, dhdr, ehdr, os.path.join(CSRC, "aff_kernels.h"), ugrid, os.path.join(CSRC, "genl_kernels.h"), os.path.join(CSRC, "genl_eval_kernels.h"), os.path.join(CSRC, "genl_adj_kernels.h"), inc, idef, gdef, wdef, ddef])]
     # the reference-control / uncontrolled evaluation rollout (psp_is_rollout): every d bucket and control kind in one unit
     tasks.append((einst_src, os.path.join(OBJ, "hjbe_inst.o"), NOSLP, [einst_src, ehdr, ugrid, hdr]))
+    # the linear / affine / constant control kernels (psp_aff_*): the three d buckets in one unit
+    ainst_src = os.path.join(CSRC, "aff_instance.hip")
+    tasks.append((ainst_src, os.path.join(OBJ, "aff_inst.o"), NOSLP, [ainst_src, os.path.join(CSRC, "aff_kernels.h"), hdr]))
     # the device-side K_test_log evaluation (psp_genl_test_error): both waves-per-tile instances in one unit
     vinst_src = os.path.join(CSRC, "genl_eval_instance.hip")
     tasks.append((vinst_src, os.path.join(OBJ, "genl_eval_inst.o"), NOSLP,

@@ -108,6 +108,19 @@ class IsConfig(C.Structure):
                 ("u_xb", C.c_float), ("u_dx", C.c_float), ("u_xhi", C.c_float)]
 
 
+class AffConfig(C.Structure):
+    """psp_aff_config: a linear / affine / constant control per time step (psp_aff_*).  The library checks ``struct_bytes``
+    itself; the struct is not part of psp_abi_struct_sizes*."""
+    _fields_ = [("base", HjbConfig), ("struct_bytes", C.c_int32), ("d_real", C.c_int32), ("has_matrix", C.c_int32),
+                ("has_bias", C.c_int32), ("ul2_kind", C.c_int32), ("reserved", C.c_int32), ("ul2_ref", C.c_void_p)]
+
+
+class AffSizes(C.Structure):
+    _fields_ = [("path_bytes", C.c_int64), ("fwd_partial_bytes", C.c_int64), ("partial_bytes", C.c_int64),
+                ("fwd_workgroups", C.c_int32), ("fwd_threads", C.c_int32), ("slices", C.c_int32), ("padded_params", C.c_int32),
+                ("bwd_workgroups", C.c_int32), ("lds_bytes", C.c_int32)]
+
+
 class DnetSizes(C.Structure):
     _fields_ = [("table_bytes", C.c_int64), ("fwd_partial_bytes", C.c_int64), ("n_params_per_set", C.c_int64),
                 ("fwd_workgroups", C.c_int32), ("reserved", C.c_int32),
@@ -215,6 +228,14 @@ SIGNATURES = {
     "psp_dnet_ul2_stage": (C.c_int, [C.POINTER(DnetConfig), _P, _P]),
     "psp_dnet_rollout_fwd": (C.c_int, [C.POINTER(DnetConfig), _P, _P, C.c_int32, _P, _P, C.c_uint64, C.c_uint32, _P,
                                        _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psp_aff_instance_count": (C.c_int, []),
+    "psp_aff_instance_get": (C.c_int, [C.c_int32, C.POINTER(C.c_int32)]),
+    "psp_aff_query": (C.c_int, [C.POINTER(AffConfig), C.POINTER(AffSizes)]),
+    "psp_aff_rollout_fwd": (C.c_int, [C.POINTER(AffConfig), _P, _P, _P, C.c_int32, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P,
+                                      _P, _P, _P]),
+    "psp_aff_terminal_reduce": (C.c_int, [C.POINTER(AffConfig), _P, _P, _P]),
+    "psp_aff_adjoint_sweep": (C.c_int, [C.POINTER(AffConfig), _P, _P, _P, _P, _P, _P, _P]),
+    "psp_aff_rollout_bwd": (C.c_int, [C.POINTER(AffConfig), _P, _P, _P, _P]),
     "psp_gen_instance_count": (C.c_int, []),
     "psp_gen_instance_get": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "psp_hjb_instance_count": (C.c_int, []),
@@ -346,6 +367,11 @@ def instances():
 def gen_instances():
     """[(d, H)] of the compiled GeneralSolver kernel instances."""
     return _instances("gen", 2)
+
+
+def aff_instances():
+    """[d] of the compiled linear-control buckets."""
+    return [t[0] for t in _instances("aff", 1)]
 
 
 def dnet_instances():

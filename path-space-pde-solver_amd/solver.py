@@ -38,6 +38,7 @@ try:
     from .plan_native import HjbNativePlan, PlanUnsupported, native_eligibility
     from .plan_dense_native import DenseNativePlan, dense_eligibility
     from .plan_value_native import ValueNativePlan, value_eligibility
+    from .plan_affine_native import AffineNativePlan, affine_eligibility, control_class
     from . import native as _nat
     from .general_solver import GeneralSolver, EllipticSolver  # noqa: F401  (reference: `from solver import GeneralSolver`)
     from .utilities import do_importance_sampling_me
@@ -46,6 +47,7 @@ except ImportError:  # flat import: this directory itself is on sys.path, as wit
     from plan_native import HjbNativePlan, PlanUnsupported, native_eligibility
     from plan_dense_native import DenseNativePlan, dense_eligibility
     from plan_value_native import ValueNativePlan, value_eligibility
+    from plan_affine_native import AffineNativePlan, affine_eligibility, control_class
     import native as _nat
     from general_solver import GeneralSolver, EllipticSolver  # noqa: F401
     from utilities import do_importance_sampling_me
@@ -355,7 +357,18 @@ class Solver:
                 self._native_plan = plan
             return plan
         z = getattr(self, 'z_n', None)                  # (approx_method='value_function' has y_n instead)
-        if isinstance(z, list) or isinstance(z, DenseNet):
+        if control_class(z) is not None:                # a list of Linear / Affine / Constant modules, one per time step
+            affine_reason = affine_eligibility(self)
+            if affine_reason is None:
+                self.plan_name, self.plan_reason = 'native', None
+                plan = getattr(self, '_native_plan', None)
+                if plan is None or not isinstance(plan, AffineNativePlan) or getattr(plan, 'key', None) != self._plan_key():
+                    plan = AffineNativePlan(self, noise=self.noise)
+                    plan.key = self._plan_key()
+                    self._native_plan = plan
+                return plan
+            reason = affine_reason
+        elif isinstance(z, list) or isinstance(z, DenseNet):
             reason = dense_reason
         if self.backend == 'native':
             raise PlanUnsupported('native plan unavailable: ' + reason)

@@ -208,6 +208,50 @@ def _is_dense_native(problem, model, K, delta_t, logw_only=False):
     return _stats(D - 2.0 * Fint)
 
 
+def _affine_is_reason(problem, model):
+    """None if the learned control is a Linear or Constant list that psp_is_rollout evaluates as u = -Z_n (PSP_ISC_LINEAR /
+    PSP_ISC_TABLE; plan_affine_native.is_control_tables), else the reason."""
+    try:
+        from .plan_affine_native import control_class
+        from .function_space import Linear, Constant
+    except ImportError:
+        from plan_affine_native import control_class
+        from function_space import Linear, Constant
+    if getattr(model, 'approx_method', 'control') != 'control' or getattr(model, 'time_approx', None) != 'outer':
+        return "not a per-step control (approx_method='control', time_approx='outer')"
+    cls = control_class(getattr(model, 'z_n', None))
+    if cls not in (Linear, Constant):
+        return 'the learned control is not a list of Linear or of Constant modules (Affine keeps the composite evaluation)'
+    if len(model.z_n) != model.N:
+        return 'z_n does not hold one module per time step'
+    return _coeff_reason(problem, model)
+
+
+def _is_affine_native(problem, model, K, delta_t, logw_only=False):
+    """The controlled sweep of utilities.py:296-330 for a Linear / Constant list on the reference-control rollout kernel: the
+    learned control IS a table of gains / of vectors, u = -Z_idx(n) with idx the step map of solver.py:360-362, 352-353."""
+    try:
+        from .plan_affine_native import is_control_tables
+    except ImportError:
+        from plan_affine_native import is_control_tables
+    dev = model.device
+    N = int(np.ceil(problem.T / delta_t))
+    philox = getattr(model, 'noise', 'reference') == 'philox'
+    kind, table = is_control_tables(model, N, delta_t)
+    cfg, keep = _is_config(problem, model, K, delta_t, nat.ISC_NONE, philox)
+    cfg.control_kind = kind
+    cfg.u_ref = nat.ptr(table)
+    reason = _is_query(cfg)
+    if reason is not None:
+        raise NotImplementedError('native IS evaluation unavailable: ' + reason)
+    xi = None if philox else _ref_noise(N, K, problem.d, dev)
+    model._is_calls = getattr(model, '_is_calls', 0) + 1
+    logw, _ = _is_rollout(problem, model, K, cfg, xi, model._is_calls, False)
+    if logw_only:
+        return logw, xi
+    return _stats(logw)
+
+
 def _is_composite(problem, model, K, delta_t):
     dev = model.device
     sq_dt = np.sqrt(delta_t)
@@ -242,6 +286,8 @@ def do_importance_sampling_me(problem, model, K, control='approx', simulate_naiv
         out = _is_native(problem, model, K, delta_t)
     elif _dense_reason(problem, model) is None:
         out = _is_dense_native(problem, model, K, delta_t)
+    elif _affine_is_reason(problem, model) is None:
+        out = _is_affine_native(problem, model, K, delta_t)
     else:
         if getattr(model, 'backend', 'auto') == 'native':
             raise NotImplementedError('native IS evaluation unavailable: ' + reason)
