@@ -916,6 +916,58 @@ int psp_comm_init(void** comm_out, int32_t nranks, int32_t rank, const unsigned 
 int psp_comm_destroy(void* comm);
 int psp_allreduce(void* buf, int64_t n, int32_t dtype, void* comm, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * PINN loss (appended in 0.4.0, no version bump; csrc/pinn_kernels.h): GeneralSolver.train_PINN / EllipticSolver.train_PINN
+ * (reference solver.py:1208-1323, :828-931).  For a dense-concat value net (the nets psp_genl_query takes) and K points,
+ *     R_k = [dV/dt] + s^2/2 Laplace_x V + b(x) . grad_x V + h(x, V, s grad_x V)            s = sigma_scale
+ * by forward-Laplacian propagation (value, one tangent per input column and a Laplacian row through the net: no nested
+ * differentiation), and the parameter gradient of any loss of R by the hand-written adjoint of that propagation:
+ *     psp_pinn_residual -> [host: loss, rbar = dLoss/dR: 2 a0 R / K, or 2 a0 (R - mean R) / (K - 1) for the variance] ->
+ *     psp_pinn_backward -> [+ the K_boundary-sized terms by autograd] -> psp_adam_step
+ * Flat parameters: registration order W_1, b_1, .., W_out, b_out; net input [x] or [x, t].  Every product is fp32 MFMA.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct psp_pinn_config {
+    int32_t d, K;             /* state dimension, points of this call                                                          */
+    int32_t has_time;         /* 1: net input [x, t] and R carries dV/dt (GeneralSolver); 0: [x] (EllipticSolver)               */
+    int32_t n_hidden;         /* L, 1 .. 4                                                                                      */
+    int32_t widths[4];        /* H_1 .. H_L, each <= 128; d + has_time <= 112                                                   */
+    int32_t activation;       /* PSP_ACT_*                                                                                      */
+    int32_t linear_layout;    /* 0: weights stored (in, out) (DenseNet); 1: (out, in) (nn.Linear, DenseNet_tanh)                */
+    int32_t drift_kind;       /* PSP_DRIFT_ZERO, PSP_DRIFT_DIAG or PSP_DRIFT_DOUBLE_WELL                                       */
+    int32_t h_kind;           /* PSP_GH_ZERO .. PSP_GH_EXPBALL_SIN, as psp_gen_config.h_kind; h must not read t (h_par[3] = 0)  */
+    int32_t sigma_kind;       /* PSP_GENL_SIGMA_SCALED only: the Laplacian form needs sigma = s I (a dense B is refused)        */
+    int32_t reserved;
+    float sigma_scale;        /* s                                                                                              */
+    float h_par[4];           /* PSP_GH_EXPBALL_*: al, d, e, tau (= 0)                                                         */
+    float reserved_f;
+    const float* drift;       /* DOUBLE_WELL: kappa (d); DIAG: a (d); DEVICE; else NULL                                         */
+} psp_pinn_config;
+
+typedef struct psp_pinn_sizes {
+    int64_t n_params;
+    int64_t scratch_bytes;        /* V, the Laplacian parts, grad V and the adjoint's seed coefficients of the K points:
+                                   * written by psp_pinn_residual, read by psp_pinn_backward                                     */
+    int64_t grad_partial_bytes;   /* per-workgroup partial gradients of psp_pinn_backward                                       */
+    int32_t dir_blocks;           /* blocks of 14 input columns per point: a tile is (point, block)                             */
+    int32_t tiles;
+    int32_t bwd_workgroups;
+    int32_t lds_fwd_bytes, lds_bwd_bytes;
+    int32_t reserved;
+} psp_pinn_sizes;
+
+/* Every check of a psp_pinn_config and the sizes, without a launch (no GPU needed).  -1 invalid argument, -2 net outside the
+ * limits of psp_genl_query, -3 LDS, -4 a dense sigma. */
+int psp_pinn_query(const psp_pinn_config* cfg, psp_pinn_sizes* out);
+/* x (K, d), t (K; NULL without a time input) -> R_out (K); `scratch`: psp_pinn_sizes.scratch_bytes. */
+int psp_pinn_residual(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, float* scratch,
+                      float* R_out, void* stream);
+/* grad_out (n_params) = sum_k rbar_k dR_k/dtheta, for the SAME cfg / params / x / t / scratch as the psp_pinn_residual call
+ * before it.  grad_partial (psp_pinn_sizes.grad_partial_bytes) is summed in a fixed order. */
+int psp_pinn_backward(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, const float* scratch,
+                      const float* rbar, float* grad_partial, float* grad_out, void* stream);
+/* sizeof(psp_pinn_config), sizeof(psp_pinn_sizes). */
+int psp_abi_struct_sizes5(int32_t out[2]);
+
 /* Diagnostics: device buffer that receives per-wave phase cycle sums (8 u64 per wave of the
  * backward kernel).  Returns 1 if the library was built with -DPSP_STAMPS (diagnostic build,
  * never the shipped one), 0 otherwise (the pointer is then ignored). NULL clears it. */

@@ -93,7 +93,7 @@ def _build(force, jobs, verbose, only):
     ugrid = os.path.join(CSRC, "ugrid.h")
     ehdr = os.path.join(CSRC, "hjbe_kernels.h")
     einst_src = os.path.join(CSRC, "hjbe_instance.hip")
-    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, os.path.join(CSRC, "hjb_basis_kernels.h"), ghdr, whdr, dhdr, ehdr, os.path.join(CSRC, "aff_kernels.h"), ugrid, os.path.join(CSRC, "genl_kernels.h"), os.path.join(CSRC, "genl_eval_kernels.h"), os.path.join(CSRC, "genl_adj_kernels.h"), inc, idef, gdef, wdef, ddef])]
+    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, os.path.join(CSRC, "hjb_basis_kernels.h"), ghdr, whdr, dhdr, ehdr, os.path.join(CSRC, "aff_kernels.h"), ugrid, os.path.join(CSRC, "genl_kernels.h"), os.path.join(CSRC, "genl_eval_kernels.h"), os.path.join(CSRC, "genl_adj_kernels.h"), os.path.join(CSRC, "pinn_kernels.h"), inc, idef, gdef, wdef, ddef])]
     # the reference-control / uncontrolled evaluation rollout (psp_is_rollout): every d bucket and control kind in one unit
     tasks.append((einst_src, os.path.join(OBJ, "hjbe_inst.o"), NOSLP, [einst_src, ehdr, ugrid, hdr]))
     # the linear / affine / constant control kernels (psp_aff_*): the three d buckets in one unit
@@ -113,6 +113,9 @@ def _build(force, jobs, verbose, only):
     adjinst_src = os.path.join(CSRC, "genl_adj_instance.hip")
     tasks.append((adjinst_src, os.path.join(OBJ, "genl_adj_inst.o"), NOSLP,
                   [adjinst_src, os.path.join(CSRC, "genl_adj_kernels.h"), os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
+    # the PINN loss (psp_pinn_*): forward-Laplacian residual, per-sample finish, adjoint with the weight gradients
+    pinst_src = os.path.join(CSRC, "pinn_instance.hip")
+    tasks.append((pinst_src, os.path.join(OBJ, "pinn_inst.o"), NOSLP, [pinst_src, os.path.join(CSRC, "pinn_kernels.h")]))
     for d, H in instances("dense_instances.def"):
         tasks.append((dinst_src, os.path.join(OBJ, "dnet_inst_%d_%d.o" % (d, H)),
                       ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [dinst_src, dhdr, ugrid, whdr, hdr]))

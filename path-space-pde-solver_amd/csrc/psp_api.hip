@@ -19,6 +19,7 @@
 #include "genl_adj_kernels.h"
 #include "hjbe_kernels.h"
 #include "aff_kernels.h"
+#include "pinn_kernels.h"
 
 #define X(D_, H_) PSP_DECLARE_DNET_INSTANCE(D_, H_)
 #include "dense_instances.def"
@@ -1894,6 +1895,113 @@ int psp_hjb_control_eval(int32_t d, int32_t H, const float* params, const float*
     if (!params || !X || !minus_Z_out || d <= 0 || H <= 0 || K <= 0)
         return fail(-1, "bad arguments to psp_hjb_control_eval");
     return PSP_LAUNCH(control_eval_kernel, dim3(K), dim3(64), 2 * H * sizeof(float), stream, d, H, params, X, K, t, minus_Z_out);
+}
+
+// ---- the PINN loss (pinn_kernels.h) ---------------------------------------------------------------------------------------
+namespace {
+struct PinnPlan { psp::PinnArgs a; int lds_fwd, lds_bwd; int64_t scratch_floats; };
+// every check of a psp_pinn_config (the three entry points share it) and the launch geometry
+int make_pinn_plan(const psp_pinn_config* c, PinnPlan* p) {
+    if (!c) return fail(-1, "null config");
+    if (c->d <= 0 || c->K <= 0) return fail(-1, "psp_pinn: d and K must be positive");
+    if (c->has_time != 0 && c->has_time != 1) return fail(-1, "psp_pinn: has_time must be 0 or 1");
+    if (c->sigma_kind != PSP_GENL_SIGMA_SCALED)
+        return fail(-4, "psp_pinn: a dense sigma is not a Laplacian (PSP_GENL_SIGMA_SCALED only)");
+    if (c->n_hidden < 1 || c->n_hidden > 4) return fail(-2, "psp_pinn: 1 to 4 hidden layers");
+    const int n_in = c->d + c->has_time;
+    if (n_in > 112) return fail(-2, "psp_pinn: net input (d + has_time) above 112");
+    for (int i = 0; i < c->n_hidden; ++i)
+        if (c->widths[i] < 1 || c->widths[i] > 128) return fail(-2, "psp_pinn: hidden widths must lie in 1 .. 128");
+    if (c->activation < PSP_ACT_RELU2 || c->activation > PSP_ACT_TANH) return fail(-1, "psp_pinn: activation out of range");
+    if (c->linear_layout != 0 && c->linear_layout != 1) return fail(-1, "psp_pinn: linear_layout must be 0 or 1");
+    if (c->drift_kind != PSP_DRIFT_ZERO && c->drift_kind != PSP_DRIFT_DIAG && c->drift_kind != PSP_DRIFT_DOUBLE_WELL)
+        return fail(-1, "psp_pinn: drift_kind must be PSP_DRIFT_ZERO, _DIAG or _DOUBLE_WELL");
+    if (c->drift_kind != PSP_DRIFT_ZERO && !c->drift) return fail(-1, "psp_pinn: this drift_kind needs the drift vector");
+    if (c->h_kind < PSP_GH_ZERO || c->h_kind > PSP_GH_EXPBALL_SIN) return fail(-1, "psp_pinn: h_kind out of range");
+    if (c->h_kind >= PSP_GH_EXPBALL_LIN && c->h_par[3] != 0.f) return fail(-1, "psp_pinn: an h that reads t is not built");
+    if ((int64_t)c->K * ((n_in + psp::kPinnDirs - 1) / psp::kPinnDirs) > (1 << 24)) return fail(-1, "psp_pinn: K too large");
+    psp::PinnArgs& a = p->a;
+    memset(&a, 0, sizeof(a));
+    a.d = c->d; a.n_in = n_in; a.K = c->K; a.L = c->n_hidden; a.act = c->activation;
+    a.nblk = (n_in + psp::kPinnDirs - 1) / psp::kPinnDirs;
+    a.ntiles = a.K * a.nblk;
+    int fan = n_in, off = 0;
+    for (int i = 0; i <= a.L; ++i) {
+        const int H = i < a.L ? c->widths[i] : 1;
+        if (i < a.L) a.H[i] = H;
+        a.fan[i] = fan;
+        a.offW[i] = off; off += fan * H;
+        a.offb[i] = off; off += H;
+        a.sk[i] = c->linear_layout ? 1 : H;
+        a.sc[i] = c->linear_layout ? fan : 1;
+        fan += H;
+    }
+    a.TOT = a.fan[a.L];
+    a.AST = psp::pinn_row_stride(a.TOT);
+    a.P = off;
+    a.G = a.ntiles < psp::kPinnMaxWg ? a.ntiles : psp::kPinnMaxWg;
+    a.drift_kind = c->drift_kind; a.h_kind = c->h_kind; a.s = c->sigma_scale;
+    for (int i = 0; i < 4; ++i) a.h_par[i] = c->h_par[i];
+    a.drift = c->drift;
+    p->lds_fwd = psp::pinn_lds_bytes(a.AST, a.L, false);
+    p->lds_bwd = psp::pinn_lds_bytes(a.AST, a.L, true);
+    if (p->lds_bwd > kMaxLds) return fail(-3, "psp_pinn: the activation images exceed the LDS");
+    p->scratch_floats = (int64_t)a.K * (2 + a.nblk + 2 * n_in);
+    return 0;
+}
+void pinn_scratch(PinnPlan* p, float* scratch) {
+    psp::PinnArgs& a = p->a;
+    const size_t K = (size_t)a.K;
+    a.V = scratch; a.lap = a.V + K; a.gradV = a.lap + K * a.nblk; a.cV = a.gradV + K * a.n_in; a.cG = a.cV + K;
+}
+}  // namespace
+
+int psp_abi_struct_sizes5(int32_t out[2]) {
+    if (!out) return fail(-1, "null output");
+    out[0] = (int32_t)sizeof(psp_pinn_config); out[1] = (int32_t)sizeof(psp_pinn_sizes);
+    return 0;
+}
+
+int psp_pinn_query(const psp_pinn_config* cfg, psp_pinn_sizes* out) {
+    PinnPlan p;
+    const int rc = make_pinn_plan(cfg, &p);
+    if (rc) return rc;
+    if (!out) return fail(-1, "null output");
+    memset(out, 0, sizeof(*out));
+    out->n_params = p.a.P;
+    out->scratch_bytes = p.scratch_floats * 4;
+    out->grad_partial_bytes = (int64_t)p.a.G * p.a.P * 4;
+    out->dir_blocks = p.a.nblk; out->tiles = p.a.ntiles; out->bwd_workgroups = p.a.G;
+    out->lds_fwd_bytes = p.lds_fwd; out->lds_bwd_bytes = p.lds_bwd;
+    return 0;
+}
+
+int psp_pinn_residual(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, float* scratch,
+                      float* R_out, void* stream) {
+    PinnPlan p;
+    const int rc = make_pinn_plan(cfg, &p);
+    if (rc) return rc;
+    if (!params || !x || !scratch || !R_out) return fail(-1, "null buffer passed to psp_pinn_residual");
+    if (cfg->has_time && !t) return fail(-1, "psp_pinn_residual: a net with a time input needs t");
+    pinn_scratch(&p, scratch);
+    p.a.params = params; p.a.x = x; p.a.t = t; p.a.R = R_out;
+    const hipError_t e = psp::pinn_launch_forward(p.a, p.lds_fwd, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "pinn_forward_kernel launch");
+    return 0;
+}
+
+int psp_pinn_backward(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, const float* scratch,
+                      const float* rbar, float* grad_partial, float* grad_out, void* stream) {
+    PinnPlan p;
+    const int rc = make_pinn_plan(cfg, &p);
+    if (rc) return rc;
+    if (!params || !x || !scratch || !rbar || !grad_partial || !grad_out) return fail(-1, "null buffer passed to psp_pinn_backward");
+    if (cfg->has_time && !t) return fail(-1, "psp_pinn_backward: a net with a time input needs t");
+    pinn_scratch(&p, const_cast<float*>(scratch));
+    p.a.params = params; p.a.x = x; p.a.t = t; p.a.rbar = rbar; p.a.gpart = grad_partial;
+    const hipError_t e = psp::pinn_launch_backward(p.a, p.lds_bwd, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "pinn_backward_kernel launch");
+    return PSP_LAUNCH(reduce_grad_kernel, dim3((p.a.P + 31) / 32), dim3(256), 0, stream, grad_partial, p.a.G, p.a.P, grad_out);
 }
 
 }  // extern "C"

@@ -21,7 +21,10 @@ Execution plans, resolved once in ``train()``:
     ``sample_center`` and the ``K_test_log`` diagnostic included;
   * composite (this file): the reference op sequence with torch autograd on ``self.device`` (CPU runs, user-defined
     coefficients or nets: never an error).
-PINN and the BSDE-2/3/4 variants are outside the scope of this build.
+The PINN baseline of the notebooks is ``train_PINN()`` (reference solver.py:1208-1323, :828-931): the strong-form residual
+  R = [dV/dt] + B[0,0]^2/2 Laplace V + b . grad V + h(x, V, B grad V)   on fresh domain points,   loss = alpha0 mean(R^2) + data terms,
+on the forward-Laplacian kernels of csrc/pinn_kernels.h (plan_pinn_native.py) or, op for op as the reference writes it, on torch
+autograd (``_train_pinn_composite``).  ``train()`` does not dispatch to it.  The BSDE-2/3/4 variants are outside the scope of this build.
 """
 import time
 import warnings
@@ -99,6 +102,12 @@ def neumann_residual(V, Xb_in, g_val, d):
 _DOMAINS = ('unbounded', 'unbounded_square', 'sphere', 'two_spheres', 'square')
 
 
+def _owns_parameters(plan):
+    """A native plan makes the net's tensors views of its flat buffer; train() and train_PINN() keep a plan each, and whichever was
+    built last owns the parameters -- the other must be rebuilt, not reused on a stale copy."""
+    return plan.params[0].data_ptr() == plan.flat.data_ptr()
+
+
 class GeneralSolver:
     elliptic = False
 
@@ -166,6 +175,8 @@ class GeneralSolver:
     def _check_scope(self):
         if self.approx_method != 'Y':
             raise NotImplementedError("approx_method='Z' is outside this build's scope")
+        if self.loss_method == 'PINN':
+            raise NotImplementedError("loss_method 'PINN' is not dispatched from train(): call train_PINN()")
         if self.loss_method not in ('diffusion', 'BSDE'):
             raise NotImplementedError("loss_method %r: only 'diffusion' and 'BSDE' are built" % self.loss_method)
         if self.problem.boundary not in _DOMAINS and not (self.elliptic and self.problem.boundary == 'square-corner'):
@@ -300,7 +311,7 @@ class GeneralSolver:
             self.plan_name = 'native'
             plan = getattr(self, '_gen_plan', None)
             key = self._plan_key()
-            if plan is None or plan.net is not self.V or plan.key != key:
+            if plan is None or plan.net is not self.V or plan.key != key or not _owns_parameters(plan):
                 plan = pgd.GeneralDeepPlan(self) if deep else pgn.GeneralNativePlan(self)   # owns the flat parameters and Adam moments
                 plan.key = key
                 self._gen_plan = plan
@@ -415,6 +426,117 @@ class GeneralSolver:
                 print('%d - loss = %.4e, v L2 error = %.4e, n = %d, active: %d/%d, %.2f'
                       % (l, self.loss_log[-1], self.V_L2_log[-1], n_done, int(torch.sum(~stopped)), K,
                          np.mean(self.times[-self.print_every:])))
+
+
+    # ---- PINN baseline (reference solver.py:1208-1323; EllipticSolver :828-931) ---------------------------------------------
+    _PINN_DOMAINS = _DOMAINS
+
+    def _check_scope_pinn(self):
+        if self.approx_method != 'Y':
+            raise NotImplementedError("train_PINN: approx_method=%r is outside this build's scope ('Y' is built)" % self.approx_method)
+        if self.problem.boundary not in self._PINN_DOMAINS:
+            raise NotImplementedError("train_PINN: boundary %r is not built" % self.problem.boundary)
+        if getattr(self, 'solve_linear_L2_projection', False):
+            raise NotImplementedError('train_PINN: solve_linear_L2_projection is not built')
+
+    def train_PINN(self):
+        """The reference's public PINN loop.  Like the reference's, it does not seed: it continues the generators where they
+        stand (the reference's train() seeds and then calls it)."""
+        self._check_scope_pinn()
+        self._check_test_log()
+        plan = self._choose_pinn_plan()
+        if plan is not None:
+            return plan.train()
+        self._train_pinn_composite()
+
+    def _choose_pinn_plan(self):
+        """backend / plan_name / plan_reason as in _choose_plan, for the forward-Laplacian kernels (plan_pinn_native.py)."""
+        if self.backend == 'torch':
+            self.plan_name, self.plan_reason = 'torch', "backend='torch' requested"
+            return None
+        try:
+            try:
+                from . import plan_pinn_native as ppn
+            except ImportError:
+                import plan_pinn_native as ppn
+            reason = ppn.pinn_eligibility(self)
+        except ImportError:
+            ppn, reason = None, 'the native PINN plan is not built yet'
+        if reason is None:
+            self.plan_name, self.plan_reason = 'native', None
+            plan = getattr(self, '_pinn_plan', None)
+            key = self._plan_key() + (bool(self.PINN_log_variance), bool(self.boundary_loss))
+            if plan is None or plan.net is not self.V or plan.key != key or not _owns_parameters(plan):
+                plan = ppn.PinnNativePlan(self)
+                plan.key = key
+                self._pinn_plan = plan
+            return plan
+        if self.backend == 'native':
+            raise NotImplementedError('native plan unavailable: ' + reason)
+        if self.device.type == 'cuda':
+            warnings.warn('path-space train_PINN: running the composite torch plan (%s)' % reason)
+        self.plan_name, self.plan_reason = 'torch', reason
+        return None
+
+    def _pinn_second_derivatives(self, X, X_in, grad, K):
+        """B[0,0]^2 times the sum of the pure second derivatives in the space columns: one autograd.grad per input column, as
+        the reference does it (solver.py:1273-1282 / :891-899); ``full_hessian``: trace(B B^T Hess V) sample by sample."""
+        pb, dev, d = self.problem, self.device, self.d
+        second = torch.zeros(X.shape[0]).to(dev)
+        if self.full_hessian:
+            for i, x in enumerate(X):
+                hess = torch.autograd.functional.hessian(self.V, x.unsqueeze(0), create_graph=True).squeeze()
+                second[i] = torch.sum(torch.diagonal(torch.mm(torch.mm(pb.B, pb.B.t()), hess)))
+            return second
+        for k in range(grad.shape[1]):
+            col = torch.autograd.grad(grad[:, k], X_in, grad_outputs=torch.ones(K).to(dev), create_graph=True)[0][:, k]
+            if k != d:                                            # the time column is differentiated and dropped, as there
+                second = second + col
+        return pb.B[0, 0] ** 2 * second
+
+    def _pinn_log_tail(self, l, loss, t_0, modus):
+        self.loss_log.append(loss.item())
+        if self.K_test_log is not None:
+            self._log_test_error(modus)
+        self.times.append(time.time() - t_0)
+        if self.verbose and l % self.print_every == 0:
+            print('%d - loss = %.4e - v L2 error = %.4e - %.2f'
+                  % (l, self.loss_log[-1], self.V_L2_log[-1], np.mean(self.times[-self.print_every:])))
+
+    def _train_pinn_composite(self):
+        pb, dev, d = self.problem, self.device, self.d
+        bounded = self.bounded
+        for l in range(self.L):
+            t_0 = time.time()
+            if bounded:
+                X_b = self._sample_boundary()
+            X = self.sample_domain()
+            K = self.K                                            # 'two_spheres': the rejection step sets it every iteration
+            t_n = torch.rand(K, 1).to(dev) * pb.T
+            X_t_n = torch.cat([X, t_n], 1)
+            X = X.detach().requires_grad_(True)
+            X_t_n = X_t_n.detach().requires_grad_(True)
+            V_eval = self.V(X_t_n).squeeze()
+            grad = torch.autograd.grad(V_eval, X_t_n, grad_outputs=torch.ones(K).to(dev), create_graph=True)[0]
+            second = self._pinn_second_derivatives(X, X_t_n, grad, K)
+            # h receives t_n as (K, 1): a time-dependent h broadcasts to (K, K) and the mean runs over that matrix (solver.py:1284-1285)
+            loss = self.alpha[0] * torch.mean((grad[:, d:].squeeze() + 0.5 * second + torch.sum(pb.b(X) * grad[:, :d], 1)
+                                               + pb.h(t_n, X, self.V(X_t_n).squeeze(), torch.mm(pb.B, grad[:, :d].t()).t())) ** 2)
+            if self.log_loss_parts:
+                self.loss_log_domain.append(loss.item() / self.alpha[0])
+            if self.boundary_loss:
+                Kb = self.K_boundary
+                if bounded:
+                    t_b = torch.rand(Kb, 1).to(dev) * pb.T
+                X_T = torch.cat([X[:Kb, :], pb.T * torch.ones(Kb).to(dev).unsqueeze(1)], 1)
+                loss = loss + self.alpha[1] * torch.mean((self.V(X_T).squeeze() - pb.f(X[:Kb, :])) ** 2)
+                if bounded:
+                    loss = loss + self.alpha[2] * self.boundary_residual(torch.cat([X_b, t_b], 1), X_b, t_b)
+            self.V.zero_grad()
+            loss.backward()
+            self.V.optim.step()
+            self.V_L2_log.append(0)
+            self._pinn_log_tail(l, loss, t_0, 'parabolic')
 
 
 class EllipticSolver(GeneralSolver):
@@ -539,3 +661,37 @@ class EllipticSolver(GeneralSolver):
                 print('%d - loss = %.4e, v L2 error = %.4e, n = %d, active: %d/%d, %.2f'
                       % (l, self.loss_log[-1], self.V_L2_log[-1], n_done, int(torch.sum(~stopped)), K,
                          np.mean(self.times[-self.print_every:])))
+
+    _PINN_DOMAINS = ('sphere', 'two_spheres', 'square', 'square-corner')
+
+    def _train_pinn_composite(self):
+        pb, dev = self.problem, self.device
+        for l in range(self.L):
+            t_0 = time.time()
+            X_b = self._sample_boundary()
+            X = self.sample_domain()
+            K = self.K
+            X = X.detach().requires_grad_(True)
+            V_eval = self.V(X).squeeze()
+            grad = torch.autograd.grad(V_eval, X, grad_outputs=torch.ones(K).to(dev), create_graph=True)[0]
+            second = self._pinn_second_derivatives(X, X, grad, K)
+            res = (0.5 * second + torch.sum(pb.b(X) * grad, 1)
+                   + pb.h(X, self.V(X).squeeze(), torch.mm(pb.B, grad.t()).t()))
+            loss = self.alpha[0] * (torch.var(res) if self.PINN_log_variance else torch.mean(res ** 2))
+            if self.log_loss_parts:
+                self.loss_log_domain.append(loss.item() / self.alpha[0])
+            if self.boundary_loss:                                # Dirichlet data whatever boundary_type says (solver.py:909-910)
+                loss = loss + self.alpha[1] * torch.mean((self.V(X_b).squeeze() - self._g_on_boundary(X_b)) ** 2)
+            if self.log_loss_parts:
+                self.loss_log_boundary.append(torch.mean((self.V(X_b).squeeze() - self._g_on_boundary(X_b)) ** 2).item())
+            self.V.zero_grad()
+            loss.backward()
+            self.V.optim.step()
+            self.V_L2_log.append(self._pinn_v_l2(X))             # after the step (solver.py:919)
+            self._pinn_log_tail(l, loss, t_0, 'elliptic')
+
+    def _pinn_v_l2(self, X):
+        with torch.no_grad():
+            Xd = X.detach()
+            err = (self.V(Xd).squeeze() - torch.as_tensor(self.problem.v_true(Xd)).float().squeeze()) ** 2
+        return torch.mean(err.cpu() * self.delta_t_np).item()

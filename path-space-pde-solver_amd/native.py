@@ -189,6 +189,20 @@ class GenlEvalSizes(C.Structure):
                 ("workgroups", C.c_int32), ("waves_per_tile", C.c_int32), ("lds_bytes", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PinnConfig(C.Structure):
+    """psp_pinn_config: the PINN residual of a dense-concat value net (psp_pinn_query / psp_pinn_residual / psp_pinn_backward)."""
+    _fields_ = [("d", C.c_int32), ("K", C.c_int32), ("has_time", C.c_int32), ("n_hidden", C.c_int32), ("widths", C.c_int32 * 4),
+                ("activation", C.c_int32), ("linear_layout", C.c_int32), ("drift_kind", C.c_int32), ("h_kind", C.c_int32),
+                ("sigma_kind", C.c_int32), ("reserved", C.c_int32), ("sigma_scale", C.c_float), ("h_par", C.c_float * 4),
+                ("reserved_f", C.c_float), ("drift", C.c_void_p)]
+
+
+class PinnSizes(C.Structure):
+    _fields_ = [("n_params", C.c_int64), ("scratch_bytes", C.c_int64), ("grad_partial_bytes", C.c_int64),
+                ("dir_blocks", C.c_int32), ("tiles", C.c_int32), ("bwd_workgroups", C.c_int32), ("lds_fwd_bytes", C.c_int32),
+                ("lds_bwd_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
 _P = C.c_void_p
 SIGNATURES = {
     "psp_version": (C.c_int, []),
@@ -202,6 +216,10 @@ SIGNATURES = {
     "psp_genl_eval_query": (C.c_int, [C.POINTER(GenlEvalConfig), C.POINTER(GenlEvalSizes)]),
     "psp_genl_test_error": (C.c_int, [C.POINTER(GenlEvalConfig), _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, C.c_int32, _P,
                                       _P, _P, _P, _P, _P, _P]),
+    "psp_abi_struct_sizes5": (C.c_int, [C.POINTER(C.c_int32 * 2)]),
+    "psp_pinn_query": (C.c_int, [C.POINTER(PinnConfig), C.POINTER(PinnSizes)]),
+    "psp_pinn_residual": (C.c_int, [C.POINTER(PinnConfig), _P, _P, _P, _P, _P, _P]),
+    "psp_pinn_backward": (C.c_int, [C.POINTER(PinnConfig), _P, _P, _P, _P, _P, _P, _P, _P]),
     "psp_genl_query": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlSizes)]),
     "psp_genl_rollout_fwd": (C.c_int, [C.POINTER(GenlConfig), _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P]),
@@ -276,6 +294,7 @@ ABI_STRUCTS = (
     ("psp_abi_struct_sizes2", (GenlConfig, GenlSizes)),
     ("psp_abi_struct_sizes3", (IsConfig,)),
     ("psp_abi_struct_sizes4", (GenlEvalConfig, GenlEvalSizes)),
+    ("psp_abi_struct_sizes5", (PinnConfig, PinnSizes)),
 )
 
 _lib = None

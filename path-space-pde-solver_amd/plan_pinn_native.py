@@ -1,0 +1,241 @@
+"""Native (HIP) execution plan of GeneralSolver.train_PINN / EllipticSolver.train_PINN (reference solver.py:1208-1323, :828-931).
+
+Per iteration:
+    host RNG in the reference's order (boundary batch, domain sample with the 'two_spheres' rejection, t ~ U(0, T), boundary times)
+    the K_boundary-sized data terms (terminal, Dirichlet / Neumann) by torch autograd into p.grad, as the diffusion-loss plans do
+    psp_pinn_residual   -> R_k = [V_t] + s^2/2 Lap V + b . grad V + h(x, V, s grad V) by forward-Laplacian propagation
+    loss = alpha0 mean(R^2) or alpha0 var(R) (PINN_log_variance); rbar = dLoss/dR, two K-vector operations in torch
+    psp_pinn_backward   -> flat gradient of the domain part (hand-written adjoint, fp32-MFMA weight gradients, fixed-order sum)
+    psp_adam_step
+The reference differentiates the net d + 1 times per iteration (one autograd.grad per input column, each through the graph of
+the gradient); here the value, every tangent and the Laplacian row pass through the net once, in one kernel.
+
+Scope: a dense-concat value net the run-time-shaped kernels take (plan_general_deep.value_net_spec: 1-4 hidden layers, widths
+<= 128, input <= 112, relu^2 / tanh / tanh^2), a catalogue problem with a scaled-identity sigma whose h does not read t, any domain,
+one rank.  ``pinn_eligibility`` names what keeps a configuration on the composite plan.
+"""
+import ctypes as C
+import time
+
+import torch
+
+try:
+    from . import native as nat
+    from . import sharding
+    from .plan_general_native import GeneralNativePlan
+    from .plan_general_deep import value_net_spec, deep_eligibility, _ACT
+except ImportError:
+    import native as nat
+    import sharding
+    from plan_general_native import GeneralNativePlan
+    from plan_general_deep import value_net_spec, deep_eligibility, _ACT
+
+
+def pinn_eligibility(solver):
+    """None if the forward-Laplacian kernels take this solver's train_PINN(), else the reason it runs on the composite plan."""
+    s = solver
+    if s.full_hessian:
+        return 'full_hessian=True takes trace(B B^T Hess V) sample by sample (composite only)'
+    if getattr(s, 'mlp_dtype', 'auto') not in ('auto', 'fp32'):
+        return 'mlp_dtype=%r: the PINN kernels are fp32 MFMA only' % s.mlp_dtype
+    if getattr(s, 'noise', 'reference') != 'reference':
+        return "noise=%r: train_PINN draws its points from the host generator (noise='reference')" % s.noise
+    if sharding.dist_info()[2] > 1:
+        return 'more than one rank: the PINN kernels are single-rank'
+    spec_fn = getattr(s.problem, 'general_native_spec', None)
+    if spec_fn is None:
+        return 'problem has no general_native_spec() (coefficients outside the native catalogue)'
+    try:
+        from .problems import coefficients_overridden
+    except ImportError:
+        from problems import coefficients_overridden
+    over = coefficients_overridden(s.problem)
+    if over is not None:
+        return 'problem.%s is not the catalogue implementation general_native_spec() describes' % over
+    spec = spec_fn()
+    if spec.get('sigma') is not None:
+        return 'a dense sigma: the kernels propagate the Laplacian of a scaled identity'
+    if spec['h'] >= nat.GH_EXPBALL_LIN and len(spec.get('h_par', ())) > 3 and spec['h_par'][3] != 0.0:
+        return 'h reads t: the reference hands it t_n as (K, 1) and the residual broadcasts to (K, K) (composite only)'
+    if spec['drift'][0] not in (nat.DRIFT_ZERO, nat.DRIFT_DIAG, nat.DRIFT_DOUBLE_WELL):
+        return 'a dense drift is not in the PINN kernels'
+    if not nat.is_built():
+        raise nat.NativeLibraryError('libpsp_hip.so is not built; run __graft_entry__.build()')
+    why = deep_eligibility(s)                                     # the net: structure, depth, widths
+    if why is not None:
+        return why
+    if s.device.type != 'cuda':
+        return 'device is %s (the HIP kernels need a GPU)' % s.device
+    return None
+
+
+class PinnNativePlan:
+    def __init__(self, solver):
+        s = solver
+        self.s, self.lib, self.dev = s, nat.load(), s.device
+        self.net, self.key = s.V, None
+        self.elliptic = bool(s.elliptic)
+        net = value_net_spec(s.V, s.d + (0 if self.elliptic else 1))
+        assert not isinstance(net, str), net
+        self.net_spec = net
+        GeneralNativePlan._flatten(self, net['params'])          # self.params / P / flat / grad: the net's tensors become views
+        spec = s.problem.general_native_spec()
+        self._keep = []
+        cfg = nat.PinnConfig()
+        cfg.d, cfg.K = s.d, s.K_original
+        cfg.has_time, cfg.n_hidden = (0 if self.elliptic else 1), len(net['dims']) - 2
+        for i, h in enumerate(net['dims'][1:-1]):
+            cfg.widths[i] = int(h)
+        cfg.activation, cfg.linear_layout = _ACT[net['act']], (1 if net['linear'] else 0)
+        cfg.drift_kind, cfg.h_kind = spec['drift'][0], spec['h']
+        cfg.sigma_kind, cfg.sigma_scale = nat.GENL_SIGMA_SCALED, float(spec['sigma_scale'])
+        for i, v in enumerate(spec.get('h_par', ())):
+            cfg.h_par[i] = float(v)
+        if spec['drift'][1] is not None:
+            t = spec['drift'][1].detach().to(device=self.dev, dtype=torch.float32).contiguous()
+            self._keep.append(t)
+            cfg.drift = nat.ptr(t)
+        self.cfg = cfg
+        sz = nat.PinnSizes()                                       # sized for the largest batch an iteration can see
+        nat.check(self.lib.psp_pinn_query(C.byref(cfg), C.byref(sz)), 'psp_pinn_query')
+        assert sz.n_params == self.P, (sz.n_params, self.P)
+        self.sizes, self.K_cap = sz, s.K_original
+        dev, f32 = self.dev, torch.float32
+        self.scratch = torch.empty(sz.scratch_bytes // 4, dtype=f32, device=dev)
+        self.grad_partial = torch.empty(sz.grad_partial_bytes // 4, dtype=f32, device=dev)
+        self.R = torch.empty(self.K_cap, dtype=f32, device=dev)
+        self.rbar = torch.empty(self.K_cap, dtype=f32, device=dev)
+        self.m = torch.zeros(self.P, dtype=f32, device=dev)
+        self.v = torch.zeros(self.P, dtype=f32, device=dev)
+        self.step = 0
+        self.test_log = GeneralNativePlan._device_test_log(self)
+
+    _adam_hyper = GeneralNativePlan._adam_hyper
+    _read_test_log = GeneralNativePlan._read_test_log
+
+    def _data_terms(self, X, X_b, t_b):
+        """The K_boundary-sized terms of solver.py:1288-1303 / :909-912, differentiated by autograd into p.grad.  Returns
+        (weighted sum or None, the unweighted boundary residual the elliptic class logs)."""
+        s, pb, dev = self.s, self.s.problem, self.dev
+        if not s.boundary_loss and not (self.elliptic and s.log_loss_parts):
+            return None, None
+        if self.elliptic:
+            res = torch.mean((s.V(X_b).squeeze() - s._g_on_boundary(X_b)) ** 2)
+            if not s.boundary_loss:
+                return None, res.detach()
+            term = s.alpha[1] * res
+        else:
+            Kb, res = s.K_boundary, None
+            X_T = torch.cat([X[:Kb, :], pb.T * torch.ones(Kb, device=dev).unsqueeze(1)], 1)
+            term = s.alpha[1] * torch.mean((s.V(X_T).squeeze() - pb.f(X[:Kb, :])) ** 2)
+            if s.bounded:
+                term = term + s.alpha[2] * s.boundary_residual(torch.cat([X_b, t_b], 1), X_b, t_b)
+        term.backward()
+        return term.detach(), (res.detach() if res is not None else None)
+
+    def residual(self, X, t):
+        """R (K,) of the points X (K, d) [and times t (K,)] with the current parameters; leaves the backward's scratch."""
+        K = X.shape[0]
+        if K <= 0 or K > self.K_cap:
+            raise RuntimeError('batch of %d points outside the plan capacity %d' % (K, self.K_cap))
+        self.cfg.K = K
+        self._x = X.detach().to(torch.float32).contiguous()
+        self._t = None if t is None else t.detach().to(torch.float32).reshape(-1).contiguous()
+        st = nat.stream_ptr(self.dev)
+        nat.check(self.lib.psp_pinn_residual(C.byref(self.cfg), nat.ptr(self.flat), nat.ptr(self._x), nat.ptr(self._t),
+                                             nat.ptr(self.scratch), nat.ptr(self.R), st), 'psp_pinn_residual')
+        return self.R[:K]
+
+    def backward(self, rbar):
+        """self.grad = sum_k rbar_k dR_k/dtheta for the batch of the last residual() call."""
+        K = self.cfg.K
+        self.rbar[:K].copy_(rbar)
+        st = nat.stream_ptr(self.dev)
+        nat.check(self.lib.psp_pinn_backward(C.byref(self.cfg), nat.ptr(self.flat), nat.ptr(self._x), nat.ptr(self._t),
+                                             nat.ptr(self.scratch), nat.ptr(self.rbar), nat.ptr(self.grad_partial),
+                                             nat.ptr(self.grad), st), 'psp_pinn_backward')
+        return self.grad
+
+    def iteration(self, l):
+        s, pb, dev, ell = self.s, self.s.problem, self.dev, self.elliptic
+        for p in self.params:
+            p.grad = None
+        # ---- host RNG in the reference's order
+        X_b = s._sample_boundary() if s.bounded else None
+        X = s.sample_domain()
+        K = s.K                                                  # 'two_spheres': the rejection step has just set it
+        t_n = t_b = None
+        if not ell:
+            t_n = torch.rand(K, 1).to(dev) * pb.T
+            if s.boundary_loss and s.bounded:
+                t_b = torch.rand(s.K_boundary, 1).to(dev) * pb.T
+        term, res_b = self._data_terms(X, X_b, t_b)
+        R = self.residual(X, t_n)
+        a0 = s.alpha[0]
+        if ell and s.PINN_log_variance:
+            loss = a0 * torch.var(R)
+            rbar = (2.0 * a0 / (K - 1)) * (R - torch.mean(R))
+        else:
+            loss = a0 * torch.mean(R ** 2)
+            rbar = (2.0 * a0 / K) * R
+        parts = (loss / a0, res_b) if s.log_loss_parts else None
+        self.backward(rbar)
+        if term is not None:
+            loss = loss + term
+            self.grad += torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in self.params])
+        self.step += 1
+        lr, b1, b2, eps = self._adam_hyper()
+        st = nat.stream_ptr(dev)
+        nat.check(self.lib.psp_adam_step(nat.ptr(self.flat), nat.ptr(self.grad), nat.ptr(self.m), nat.ptr(self.v),
+                                         self.P, self.step, lr, b1, b2, eps, st), 'psp_adam_step')
+        v_l2 = None
+        if ell:                                                  # solver.py:919: after the step, on this iteration's points
+            with torch.no_grad():
+                err = (s.V(X).squeeze() - torch.as_tensor(pb.v_true(X)).float().to(dev).squeeze()) ** 2
+            v_l2 = torch.mean(err * s.delta_t_np)
+        if s.K_test_log is not None and self.test_log is not None:
+            self.test_log.enqueue(self.flat, s.seed, l, l, st)
+        elif s.K_test_log is not None:
+            s._log_test_error('elliptic' if ell else 'parabolic')
+        return loss, v_l2, parts
+
+    def train(self):
+        s = self.s
+        if self.test_log is None:
+            return self._train_loop()
+        self.test_log.begin(max(1, s.L))
+        try:
+            self._train_loop()
+        except BaseException:
+            try:
+                self._read_test_log()
+            except Exception:
+                pass
+            raise
+        self._read_test_log()
+
+    def _train_loop(self):
+        s = self.s
+        losses, vl2, parts = [], [], []
+        t_block = time.time()
+        for l in range(s.L):
+            loss, v, pr = self.iteration(l)
+            losses.append(loss)
+            if v is not None:
+                vl2.append(v)
+            if pr is not None:
+                parts.append(pr)
+            if (s.verbose and l % s.print_every == 0) or l == s.L - 1:
+                vals = torch.stack(losses).cpu().tolist()          # one sync per block
+                now = time.time()
+                s.loss_log += vals
+                s.V_L2_log += torch.stack(vl2).cpu().tolist() if vl2 else [0] * len(vals)
+                for dom, bnd in parts:
+                    s.loss_log_domain.append(dom.item())
+                    if bnd is not None:
+                        s.loss_log_boundary.append(bnd.item())
+                s.times += [(now - t_block) / len(vals)] * len(vals)
+                t_block = now
+                if s.verbose and l % s.print_every == 0:
+                    print('%d - loss = %.4e - v L2 error = %.4e - %.4f s/iter' % (l, s.loss_log[-1], s.V_L2_log[-1], s.times[-1]))
+                losses, vl2, parts = [], [], []
