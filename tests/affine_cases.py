@@ -92,3 +92,70 @@ def assert_first_iteration(model, case, tag=""):
     assert max(per) <= 2e-4, per
     assert math.isclose(model.loss_log[0], ref["loss_log"][0], rel_tol=tol), (model.loss_log[0], ref["loss_log"][0])
     return plan, ref
+
+
+def cus():
+    """The CU count make_aff_plan plans with: the device's, or 256 (the library's own fallback) without one."""
+    return int(torch.cuda.get_device_properties(0).multi_processor_count) if torch.cuda.is_available() else 256
+
+
+def k_big():
+    """The first trajectory count with 256-thread workgroups (make_aff_plan: K > 64 CUs) and 17 valid lanes in the last one."""
+    return 64 * cus() + 17
+
+
+K_BIG = k_big()
+
+
+def _sweep_case(kind, d, K, dt, T, control, loss="log-variance", detach=True, adaptive=True, random_x0=False, off_diag=None,
+                u_l2=False):
+    if kind == "DoubleWell_multidim":
+        kwargs = dict(d=d, d_1=d // 2, d_2=d - d // 2, T=T, eta=0.05, kappa=1.0)
+    elif kind == "LQGC":
+        kwargs = dict(d=d, off_diag=0.05 if off_diag is None else off_diag, T=T, seed=42, delta_t=dt)
+    else:
+        kwargs = dict(d=d, off_diag=0.3 / d ** 0.5 if off_diag is None else off_diag, T=T, seed=42)
+    solver = dict(loss_method=loss, time_approx="outer", adaptive_forward_process=adaptive, detach_forward=detach,
+                  early_stopping_time=None, L=1, lr=0.1, seed=42, delta_t=dt, K=K, u_l2_error_flag=u_l2, random_X_0=random_x0)
+    return dict(name="affsweep", family="solver", problem=dict(kind=kind, kwargs=kwargs), solver=solver, control=control)
+
+
+LIN, AFF, CON = dict(kind="Linear"), dict(kind="Affine", init=dict(scale=0.1, seed0=50)), dict(kind="Constant")
+SWEEP = {
+    # ragged K, bucket 16
+    "d5_K37": _sweep_case("LQGC", 5, 37, 0.05, 0.2, LIN),
+    "d5_K37_attached": _sweep_case("LQGC", 5, 37, 0.05, 0.2, LIN, detach=False),
+    # a single step: with X_0 = 0 a Linear control has an identically zero gradient there, hence random_X_0
+    "d20_K16_N1_randx0": _sweep_case("LQGC", 20, 16, 0.05, 0.05, LIN, random_x0=True),
+    "d20_K16_N1_randx0_attached": _sweep_case("LQGC", 20, 16, 0.05, 0.05, LIN, loss="moment", detach=False, random_x0=True),
+    # exact bucket 64, dense A and B
+    "d64_K50_N10": _sweep_case("LLGC", 64, 50, 0.02, 0.2, AFF),
+    "d64_K50_N10_attached": _sweep_case("LLGC", 64, 50, 0.02, 0.2, AFF, detach=False),
+    # bucket 64 with padding; running and terminal quadratic costs
+    "d33": _sweep_case("LQGC", 33, 40, 0.05, 0.15, LIN),
+    "d33_attached_cross_entropy": _sweep_case("LQGC", 33, 40, 0.05, 0.15, LIN, loss="cross_entropy", detach=False),
+    # element-wise drift and its Jacobian, SHIFTED_QUAD
+    "dw_d6_affine": _sweep_case("DoubleWell_multidim", 6, 48, 0.05, 0.2, AFF),
+    "dw_d6_affine_attached": _sweep_case("DoubleWell_multidim", 6, 48, 0.05, 0.2, AFF, detach=False),
+    "dw_d6_affine_nonadaptive": _sweep_case("DoubleWell_multidim", 6, 48, 0.05, 0.2, AFF, adaptive=False),
+    # many workgroups and slices
+    "K5000_d20": _sweep_case("LLGC", 20, 5000, 0.05, 0.15, LIN),
+    "K5000_d20_relative_entropy": _sweep_case("LLGC", 20, 5000, 0.05, 0.15, LIN, loss="relative_entropy", detach=False),
+    # chain rule with G = Q^-1 B^T != I
+    "d7_gains": _sweep_case("LQGC", 7, 40, 0.05, 0.2, dict(kind="Linear", gains=3)),
+    "d7_gains_attached": _sweep_case("LQGC", 7, 40, 0.05, 0.2, dict(kind="Linear", gains=3), detach=False),
+    "d12_constant_variance": _sweep_case("LLGC", 12, 40, 0.05, 0.2, CON, loss="variance"),
+    # 256-thread workgroups with a ragged last one, slices of several LDS stages
+    "Kbig_d20_N3": _sweep_case("LLGC", 20, K_BIG, 0.05, 0.15, AFF),
+    "Kbig_d20_N3_attached": _sweep_case("LLGC", 20, K_BIG, 0.05, 0.15, AFF, detach=False),
+    # off_diag = 0, the constructors' default: diagonal drift, identity sigma
+    "d12_llgc_diag": _sweep_case("LLGC", 12, 40, 0.05, 0.2, AFF, off_diag=0.0),
+    "d12_llgc_diag_attached": _sweep_case("LLGC", 12, 40, 0.05, 0.2, AFF, detach=False, off_diag=0.0),
+    "d12_lqgc_diag": _sweep_case("LQGC", 12, 40, 0.05, 0.2, LIN, off_diag=0.0),
+    "d12_lqgc_diag_attached": _sweep_case("LQGC", 12, 40, 0.05, 0.2, LIN, detach=False, off_diag=0.0),
+}
+BIG_K = ("Kbig_d20_N3", "Kbig_d20_N3_attached")
+DIAGONAL = ("d12_llgc_diag", "d12_llgc_diag_attached", "d12_lqgc_diag", "d12_lqgc_diag_attached")
+# the u_L2 log next to a bucket-64 LINEAR reference: only the log entry and the plan are asserted at solver level, the values are
+# compared at kernel level (tests/test_gpu_affine_kernels.py)
+UL2_D33 = _sweep_case("LQGC", 33, 40, 0.05, 0.15, LIN, u_l2=True)

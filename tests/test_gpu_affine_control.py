@@ -7,7 +7,7 @@ import math
 import pytest
 import torch
 
-from affine_cases import GOLDEN, assert_first_iteration, build_modules, make_affine_solver
+from affine_cases import BIG_K, DIAGONAL, GOLDEN, SWEEP, UL2_D33, assert_first_iteration, build_modules, make_affine_solver
 from conftest import load_golden
 from util_cases import psp
 
@@ -25,46 +25,6 @@ def test_first_iteration_D_and_gradient_match_oracle(name):
     assert_first_iteration(model, case)
 
 
-def _sweep_case(kind, d, K, dt, T, control, loss="log-variance", detach=True, adaptive=True, random_x0=False):
-    if kind == "DoubleWell_multidim":
-        kwargs = dict(d=d, d_1=d // 2, d_2=d - d // 2, T=T, eta=0.05, kappa=1.0)
-    elif kind == "LQGC":
-        kwargs = dict(d=d, off_diag=0.05, T=T, seed=42, delta_t=dt)
-    else:
-        kwargs = dict(d=d, off_diag=0.3 / d ** 0.5, T=T, seed=42)
-    solver = dict(loss_method=loss, time_approx="outer", adaptive_forward_process=adaptive, detach_forward=detach,
-                  early_stopping_time=None, L=1, lr=0.1, seed=42, delta_t=dt, K=K, u_l2_error_flag=False, random_X_0=random_x0)
-    return dict(name="affsweep", family="solver", problem=dict(kind=kind, kwargs=kwargs), solver=solver, control=control)
-
-
-LIN, AFF, CON = dict(kind="Linear"), dict(kind="Affine", init=dict(scale=0.1, seed0=50)), dict(kind="Constant")
-SWEEP = {
-    # ragged K, bucket 16
-    "d5_K37": _sweep_case("LQGC", 5, 37, 0.05, 0.2, LIN),
-    "d5_K37_attached": _sweep_case("LQGC", 5, 37, 0.05, 0.2, LIN, detach=False),
-    # a single step: with X_0 = 0 a Linear control has an identically zero gradient there, hence random_X_0
-    "d20_K16_N1_randx0": _sweep_case("LQGC", 20, 16, 0.05, 0.05, LIN, random_x0=True),
-    "d20_K16_N1_randx0_attached": _sweep_case("LQGC", 20, 16, 0.05, 0.05, LIN, loss="moment", detach=False, random_x0=True),
-    # exact bucket 64, dense A and B
-    "d64_K50_N10": _sweep_case("LLGC", 64, 50, 0.02, 0.2, AFF),
-    "d64_K50_N10_attached": _sweep_case("LLGC", 64, 50, 0.02, 0.2, AFF, detach=False),
-    # bucket 64 with padding; running and terminal quadratic costs
-    "d33": _sweep_case("LQGC", 33, 40, 0.05, 0.15, LIN),
-    "d33_attached_cross_entropy": _sweep_case("LQGC", 33, 40, 0.05, 0.15, LIN, loss="cross_entropy", detach=False),
-    # element-wise drift and its Jacobian, SHIFTED_QUAD
-    "dw_d6_affine": _sweep_case("DoubleWell_multidim", 6, 48, 0.05, 0.2, AFF),
-    "dw_d6_affine_attached": _sweep_case("DoubleWell_multidim", 6, 48, 0.05, 0.2, AFF, detach=False),
-    "dw_d6_affine_nonadaptive": _sweep_case("DoubleWell_multidim", 6, 48, 0.05, 0.2, AFF, adaptive=False),
-    # many workgroups and slices
-    "K5000_d20": _sweep_case("LLGC", 20, 5000, 0.05, 0.15, LIN),
-    "K5000_d20_relative_entropy": _sweep_case("LLGC", 20, 5000, 0.05, 0.15, LIN, loss="relative_entropy", detach=False),
-    # chain rule with G = Q^-1 B^T != I
-    "d7_gains": _sweep_case("LQGC", 7, 40, 0.05, 0.2, dict(kind="Linear", gains=3)),
-    "d7_gains_attached": _sweep_case("LQGC", 7, 40, 0.05, 0.2, dict(kind="Linear", gains=3), detach=False),
-    "d12_constant_variance": _sweep_case("LLGC", 12, 40, 0.05, 0.2, CON, loss="variance"),
-}
-
-
 @pytest.mark.parametrize("tag", sorted(SWEEP))
 def test_shape_sweep_matches_oracle(tag):
     case = SWEEP[tag]
@@ -72,6 +32,22 @@ def test_shape_sweep_matches_oracle(tag):
     plan, _ = assert_first_iteration(model, case, tag=tag)
     if case["control"].get("gains") is not None:
         assert plan.G is not None
+    if tag in BIG_K:
+        assert plan.sizes.fwd_threads == 256 and plan.sizes.slices * 32 < plan.K_local, (plan.sizes.fwd_threads, plan.sizes.slices)
+    if tag in DIAGONAL:
+        assert (plan.cfg.base.drift_kind, plan.cfg.base.sigma_kind) == (psp.native.DRIFT_DIAG, psp.native.SIGMA_IDENTITY)
+
+
+def test_u_l2_log_next_to_a_bucket_64_linear_reference():
+    """u_l2_error_flag=True at d = 33: the LINEAR reference (N, 64, 64) next to dense A, B and the maps.  Only the log entry and the
+    plan are asserted here; the values are compared with float64 at kernel level (tests/test_gpu_affine_kernels.py)."""
+    model = make_affine_solver(UL2_D33, dev(), backend="native", L=1)
+    model.train()
+    plan = model._native_plan
+    assert model.plan_name == "native" and isinstance(plan, psp.plan_affine_native.AffineNativePlan)
+    assert plan.d_pad == 64 and plan.cfg.ul2_kind == psp.native.UL2_LINEAR and plan.ul2 is not None
+    print("u_L2 log", model.u_L2_loss)
+    assert len(model.u_L2_loss) == 1 and math.isfinite(model.u_L2_loss[0]) and model.u_L2_loss[0] > 0.0
 
 
 @pytest.mark.parametrize("name", GOLDEN)
