@@ -946,7 +946,10 @@ typedef struct psp_pinn_config {
 typedef struct psp_pinn_sizes {
     int64_t n_params;
     int64_t scratch_bytes;        /* V, the Laplacian parts, grad V and the adjoint's seed coefficients of the K points:
-                                   * written by psp_pinn_residual, read by psp_pinn_backward                                     */
+                                   * written by psp_pinn_residual, read by psp_pinn_backward.  Layout, in floats, for the K of
+                                   * the call (n_in = d + has_time): V (K), Laplacian parts (K, dir_blocks), grad V (K, n_in),
+                                   * dR/dV (K), dR/d grad V (K, n_in) = K (2 + dir_blocks + 2 n_in) floats; a larger buffer
+                                   * is left untouched behind them (the kernel tests read the first three)                       */
     int64_t grad_partial_bytes;   /* per-workgroup partial gradients of psp_pinn_backward                                       */
     int32_t dir_blocks;           /* blocks of 14 input columns per point: a tile is (point, block)                             */
     int32_t tiles;

@@ -58,8 +58,10 @@ def h_pde(kind, par, x, y, z):
     return torch.zeros_like(y)
 
 
-def residual(case, params=None, dtype=torch.float64, create_graph=True, preacts=None):
-    """R (K,) of ``case`` (see make_case) in ``dtype``; differentiable in ``params`` (default: the case's, cast)."""
+def terms(case, params=None, dtype=torch.float64, create_graph=True, preacts=None, lap_cols=None, detach_y=False):
+    """(V (K,), grad V (K, n_in), Lap V over the first ``lap_cols`` input columns (K,), R (K,)) of ``case`` in ``dtype``, all on
+    the graph of ``params``.  The two switches state wrong residuals for the tests of the tests: ``lap_cols`` other than d sums
+    second derivatives over other columns, ``detach_y`` cuts h's dependence on V out of the gradient (R itself is unchanged)."""
     if params is None:
         params = [p.to(dtype) for p in case["params"]]
     d = case["d"]
@@ -69,16 +71,79 @@ def residual(case, params=None, dtype=torch.float64, create_graph=True, preacts=
     V = net(params, case["act"], inp, case["linear"], preacts)
     g, = torch.autograd.grad(V.sum(), inp, create_graph=True)
     lap = torch.zeros_like(V)
-    for j in range(d):
+    for j in range(d if lap_cols is None else lap_cols):
         lap = lap + torch.autograd.grad(g[:, j].sum(), inp, create_graph=create_graph, retain_graph=True)[0][:, j]
     s = case["s"]
     xs = inp[:, :d].detach()
     vec = None if case["drift"] is None else case["drift"].to(dtype)
     R = 0.5 * s * s * lap + torch.sum(drift(case["drift_kind"], vec, xs) * g[:, :d], 1) \
-        + h_pde(case["h_kind"], case["h_par"], xs, V, s * g[:, :d])
+        + h_pde(case["h_kind"], case["h_par"], xs, V.detach() if detach_y else V, s * g[:, :d])
     if case["parabolic"]:
         R = R + g[:, d]
-    return R
+    return V, g, lap, R
+
+
+def residual(case, params=None, dtype=torch.float64, create_graph=True, preacts=None):
+    """R (K,) of ``case`` (see make_case) in ``dtype``; differentiable in ``params`` (default: the case's, cast)."""
+    return terms(case, params, dtype, create_graph, preacts)[3]
+
+
+def parts(case, dtype=torch.float64, **switches):
+    """(V (K,), grad V (K, n_in), the Laplacian summed over the space columns (K,), R (K,)) in ``dtype``, detached: what the
+    forward kernel leaves in its scratch, what the finish kernel sums, and the residual."""
+    return tuple(v.detach() for v in terms(case, None, dtype, create_graph=False, **switches))
+
+
+def flat_grad(grads, params):
+    return torch.cat([(torch.zeros_like(p) if g is None else g).reshape(-1) for g, p in zip(grads, params)])
+
+
+def weighted_grads(case, rbars, dtype=torch.float64, **switches):
+    """[d(sum_k rbar_k R_k)/dtheta for rbar in rbars], flat in registration order, in ``dtype``: one residual graph for all."""
+    params = [p.to(dtype).clone().requires_grad_(True) for p in case["params"]]
+    R = terms(case, params, dtype, **switches)[3]
+    out = []
+    for rbar in rbars:
+        out.append(flat_grad(torch.autograd.grad(torch.sum(rbar.to(dtype) * R), params, allow_unused=True, retain_graph=True),
+                             params))
+    return out
+
+
+def weighted_grad(case, rbar, dtype=torch.float64, **switches):
+    """d(sum_k rbar_k R_k)/dtheta: what psp_pinn_backward returns for the weights ``rbar`` (K,)."""
+    return weighted_grads(case, [rbar], dtype, **switches)[0]
+
+
+def per_sample_grad(case, k, dtype=torch.float64):
+    """dR_k/dtheta: weighted_grad with a one-hot weight."""
+    return weighted_grad(case, one_hot(case["K"], k), dtype)
+
+
+def one_hot(K, k):
+    w = torch.zeros(K, dtype=torch.float64)
+    w[k] = 1.0
+    return w
+
+
+def mean_square_rbar(alpha0, K):
+    """R -> dLoss/dR of alpha0 mean(R^2)."""
+    return lambda R: (2.0 * alpha0 / K) * R
+
+
+def variance_rbar(alpha0, K):
+    """R -> dLoss/dR of alpha0 var(R) (unbiased)."""
+    return lambda R: (2.0 * alpha0 / (K - 1)) * (R - R.mean())
+
+
+def blocks(case, flat):
+    """A flat gradient split into its named blocks W1, b1, .., Wout, bout (registration order), as an ordered dict of views."""
+    n, off, out = len(case["params"]) // 2, 0, {}
+    for i, p in enumerate(case["params"]):
+        layer = "out" if i // 2 == n - 1 else str(i // 2 + 1)
+        out[("W" if i % 2 == 0 else "b") + layer] = flat[off:off + p.numel()]
+        off += p.numel()
+    assert off == flat.numel(), (off, flat.numel())
+    return out
 
 
 def loss_and_grad(case, alpha0=1.0, log_variance=False, dtype=torch.float64):

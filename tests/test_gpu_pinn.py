@@ -4,7 +4,6 @@
 Kernel bounds: with e(v) = max|v - v64| / max|v64|, the kernels must stay within 8 e(fp32 torch autograd on CPU, same inputs)
 + 1e-6 -- the factor allows for another summation order over up to K (d + 2) rows, the constant for a yardstick that happens to
 be exact.  Solver level: the project's parity contract, 1e-4 relative per iteration of the loss log."""
-import ctypes as C
 import functools
 
 import pytest
@@ -13,11 +12,9 @@ import torch
 import ref64_pinn as r64
 from conftest import load_golden
 from pinn_cases import COMPOSITE_ONLY, GPU_SHAPES, NATIVE_SCOPE, build, probe_values, seed_like_reference_train
-from util_cases import psp
+from pinn_kernel_cases import Native
 
 pytestmark = pytest.mark.gpu
-nat = psp.native
-ACT = {"relu2": nat.ACT_RELU2, "tanh2": nat.ACT_TANH2, "tanh": nat.ACT_TANH}
 ALPHA0 = 1.3
 
 
@@ -36,48 +33,6 @@ def reference(name, log_variance=False):
     R64, _, g64 = r64.loss_and_grad(case, alpha0=ALPHA0, log_variance=log_variance)
     R32, _, g32 = r64.loss_and_grad(case, alpha0=ALPHA0, log_variance=log_variance, dtype=torch.float32)
     return case, R64, g64, rel_err(R32, R64), rel_err(g32, g64)
-
-
-class Native:
-    """One case on the device through psp_pinn_query / psp_pinn_residual / psp_pinn_backward."""
-
-    def __init__(self, case):
-        self.lib, d = nat.load(), dev()
-        f32 = torch.float32
-        c = nat.PinnConfig()
-        c.d, c.K, c.has_time, c.n_hidden = case["d"], case["K"], int(case["parabolic"]), len(case["arch"])
-        for i, h in enumerate(case["arch"]):
-            c.widths[i] = h
-        c.activation, c.linear_layout = ACT[case["act"]], int(case["linear"])
-        c.drift_kind, c.h_kind, c.sigma_scale = case["drift_kind"], case["h_kind"], case["s"]
-        for i, v in enumerate(case["h_par"]):
-            c.h_par[i] = v
-        self.drift = None if case["drift"] is None else case["drift"].to(d, f32).contiguous()
-        c.drift = nat.ptr(self.drift)
-        self.cfg, self.sz = c, nat.PinnSizes()
-        nat.check(self.lib.psp_pinn_query(C.byref(c), C.byref(self.sz)), "psp_pinn_query")
-        self.params = torch.cat([p.reshape(-1) for p in case["params"]]).to(d, f32).contiguous()
-        assert self.params.numel() == self.sz.n_params
-        self.x = case["x"].to(d, f32).contiguous()
-        self.t = case["t"].to(d, f32).contiguous() if case["parabolic"] else None
-        self.scratch = torch.empty(self.sz.scratch_bytes // 4, dtype=f32, device=d)
-        self.partial = torch.empty(self.sz.grad_partial_bytes // 4, dtype=f32, device=d)
-        self.R = torch.empty(case["K"], dtype=f32, device=d)
-        self.grad = torch.empty(self.sz.n_params, dtype=f32, device=d)
-
-    def residual(self):
-        nat.check(self.lib.psp_pinn_residual(C.byref(self.cfg), nat.ptr(self.params), nat.ptr(self.x), nat.ptr(self.t),
-                                             nat.ptr(self.scratch), nat.ptr(self.R), None), "psp_pinn_residual")
-        torch.cuda.synchronize()
-        return self.R
-
-    def backward(self, rbar):
-        rbar = rbar.to(torch.float32).contiguous()
-        nat.check(self.lib.psp_pinn_backward(C.byref(self.cfg), nat.ptr(self.params), nat.ptr(self.x), nat.ptr(self.t),
-                                             nat.ptr(self.scratch), nat.ptr(rbar), nat.ptr(self.partial), nat.ptr(self.grad),
-                                             None), "psp_pinn_backward")
-        torch.cuda.synchronize()
-        return self.grad
 
 
 @pytest.mark.parametrize("name", sorted(GPU_SHAPES))
