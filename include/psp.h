@@ -63,7 +63,9 @@ extern "C" {
                          *        psp_genl_adj / psp_genl_query_adj / psp_genl_adjoint_sweep -- the adjoint sweep of the state path for the value-function
  *        ansatz with detach_forward=False (csrc/genl_adj_kernels.h).
  *        psp_genl_ul2 / psp_genl_query_ul2 / psp_genl_ul2_stage / psp_genl_rollout_fwd_ul2 -- the u_L2 log of
-                         *        that ansatz inside the run-time-shaped forward kernel (PSP_UL2_*); its own size again */
+                         *        that ansatz inside the run-time-shaped forward kernel (PSP_UL2_*); its own size again;
+                         *        psp_pinn_config.n_dirs (the former `reserved`) / dirs (appended) -- second-order directions of a
+                         *        dense sigma in the PINN kernels (PSP_GENL_SIGMA_DENSE, PSP_GH_EXPBALL_SIN_FULL) */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
@@ -925,6 +927,14 @@ int psp_allreduce(void* buf, int64_t n, int32_t dtype, void* comm, void* stream)
  *     psp_pinn_residual -> [host: loss, rbar = dLoss/dR: 2 a0 R / K, or 2 a0 (R - mean R) / (K - 1) for the variance] ->
  *     psp_pinn_backward -> [+ the K_boundary-sized terms by autograd] -> psp_adam_step
  * Flat parameters: registration order W_1, b_1, .., W_out, b_out; net input [x] or [x, t].  Every product is fp32 MFMA.
+ *
+ * A dense constant sigma B (sigma_kind = PSP_GENL_SIGMA_DENSE; EllipticSolver(full_hessian=True)): the second-order term is
+ *     1/2 trace(B B^T Hess_x V) = 1/2 sum_j dirs_j^T (Hess_x V) dirs_j          for any table with sum_j dirs_j dirs_j^T = B B^T
+ * (the caller factors B B^T; rank(B B^T) <= d rows suffice).  The propagation is linear in its directions, so the kernels seed
+ * n_dirs further tangent rows with the table's rows (time column 0) instead of unit vectors and count those in the Laplacian row;
+ * sigma_scale is not read, the scale sits in the directions.  The unit directions e_0 .. e_{n_in-1} that give grad V and dV/dt
+ * run first and are no longer counted; the library leaves them out where nothing reads grad V (drift_kind = PSP_DRIFT_ZERO,
+ * has_time = 0; every h accepted here reads x and V only).  PSP_GH_QUAD, which reads z = B^T grad V, is refused (-1).
  * ------------------------------------------------------------------------------------------------ */
 typedef struct psp_pinn_config {
     int32_t d, K;             /* state dimension, points of this call                                                          */
@@ -934,13 +944,15 @@ typedef struct psp_pinn_config {
     int32_t activation;       /* PSP_ACT_*                                                                                      */
     int32_t linear_layout;    /* 0: weights stored (in, out) (DenseNet); 1: (out, in) (nn.Linear, DenseNet_tanh)                */
     int32_t drift_kind;       /* PSP_DRIFT_ZERO, PSP_DRIFT_DIAG or PSP_DRIFT_DOUBLE_WELL                                       */
-    int32_t h_kind;           /* PSP_GH_ZERO .. PSP_GH_EXPBALL_SIN, as psp_gen_config.h_kind; h must not read t (h_par[3] = 0)  */
-    int32_t sigma_kind;       /* PSP_GENL_SIGMA_SCALED only: the Laplacian form needs sigma = s I (a dense B is refused)        */
-    int32_t reserved;
-    float sigma_scale;        /* s                                                                                              */
+    int32_t h_kind;           /* PSP_GH_ZERO .. PSP_GH_EXPBALL_SIN_FULL, as psp_gen_config.h_kind; h must not read t
+                               * (h_par[3] = 0); PSP_GH_EXPBALL_SIN_FULL on either sigma_kind; no PSP_GH_QUAD with _DENSE       */
+    int32_t sigma_kind;       /* PSP_GENL_SIGMA_SCALED: sigma = s I, the Laplacian; PSP_GENL_SIGMA_DENSE: the table `dirs`       */
+    int32_t n_dirs;           /* PSP_GENL_SIGMA_DENSE: rows of `dirs`, 1 .. d; ignored with _SCALED                             */
+    float sigma_scale;        /* s (PSP_GENL_SIGMA_SCALED)                                                                      */
     float h_par[4];           /* PSP_GH_EXPBALL_*: al, d, e, tau (= 0)                                                         */
     float reserved_f;
     const float* drift;       /* DOUBLE_WELL: kappa (d); DIAG: a (d); DEVICE; else NULL                                         */
+    const float* dirs;        /* PSP_GENL_SIGMA_DENSE: (n_dirs, d) row-major, fp32, DEVICE; NULL there is -4; else ignored      */
 } psp_pinn_config;
 
 typedef struct psp_pinn_sizes {
@@ -949,17 +961,22 @@ typedef struct psp_pinn_sizes {
                                    * written by psp_pinn_residual, read by psp_pinn_backward.  Layout, in floats, for the K of
                                    * the call (n_in = d + has_time): V (K), Laplacian parts (K, dir_blocks), grad V (K, n_in),
                                    * dR/dV (K), dR/d grad V (K, n_in) = K (2 + dir_blocks + 2 n_in) floats; a larger buffer
-                                   * is left untouched behind them (the kernel tests read the first three)                       */
+                                   * is left untouched behind them (the kernel tests read the first three).
+                                   * PSP_GENL_SIGMA_DENSE: V (K), Laplacian parts (K, dir_blocks), grad V (K, n_grad), dR/dV (K),
+                                   * dR/d grad V (K, n_grad) = K (2 + dir_blocks + 2 n_grad) floats, n_grad = 0 where the unit
+                                   * directions are left out (see above), else n_in                                             */
     int64_t grad_partial_bytes;   /* per-workgroup partial gradients of psp_pinn_backward                                       */
-    int32_t dir_blocks;           /* blocks of 14 input columns per point: a tile is (point, block)                             */
+    int32_t dir_blocks;           /* blocks of 14 directions per point: a tile is (point, block).  Directions: the n_in input
+                                   * columns; PSP_GENL_SIGMA_DENSE: n_grad + n_dirs                                              */
     int32_t tiles;
     int32_t bwd_workgroups;
     int32_t lds_fwd_bytes, lds_bwd_bytes;
     int32_t reserved;
 } psp_pinn_sizes;
 
-/* Every check of a psp_pinn_config and the sizes, without a launch (no GPU needed).  -1 invalid argument, -2 net outside the
- * limits of psp_genl_query, -3 LDS, -4 a dense sigma. */
+/* Every check of a psp_pinn_config and the sizes, without a launch (no GPU needed; `dirs` is only tested for NULL).  -1 invalid
+ * argument (n_dirs outside 1 .. d, PSP_GH_QUAD with a table, K * dir_blocks above 2^24, ..), -2 net outside the limits of
+ * psp_genl_query, -3 LDS, -4 a dense sigma without its table. */
 int psp_pinn_query(const psp_pinn_config* cfg, psp_pinn_sizes* out);
 /* x (K, d), t (K; NULL without a time input) -> R_out (K); `scratch`: psp_pinn_sizes.scratch_bytes. */
 int psp_pinn_residual(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, float* scratch,

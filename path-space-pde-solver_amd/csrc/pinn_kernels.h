@@ -8,9 +8,17 @@
 // independent of every other tile: it carries the value row (row 0), its own partial-Laplacian row (row 1) and kPinnDirs tangent
 // rows -- the 16 rows of one v_mfma_f32_16x16x4_f32 operand.  Only Lap V is summed over a sample's direction blocks.
 //
+// Nothing in the recursion needs the directions to be unit vectors.  A sample's directions are, in this order, n_grad gradient
+// directions e_0 .. e_{n_in-1} (they give grad V and V_t; the space ones are counted in S only on the scaled-identity path, where
+// they are the second-order directions as well) and n_hess second-order directions u_j read from the table `dirs` (n_hess, d),
+// time column 0.  With sum_j u_j u_j^T = B B^T the row D ends as sum_j u_j^T (Hess_x V) u_j = trace(B B^T Hess_x V): a dense
+// sigma.  The u_j are counted in S, their first derivatives are not stored and their tangent rows get adjoint seed 0.  The
+// directions counted in S are the global indices [cnt_lo, cnt_hi): [0, d) with a scaled identity (n_grad = n_in, n_hess = 0, seeds
+// 1.0, lap_coef = s^2 / 2), [n_grad, n_grad + n_hess) with a table (lap_coef = 1 / 2: the scale sits in the directions).
+//
 //   pinn_forward_kernel   per tile: V, V'_j of its directions, its part of Lap V           -> scratch
-//   pinn_finish_kernel    per sample: R = [V_t] + s^2/2 Lap V + b . grad V + h(x, V, s grad V) and the seed coefficients
-//                         dR/dV, dR/dV'_j of the adjoint (dR/dLap V = s^2/2 is a constant)
+//   pinn_finish_kernel    per sample: R = [V_t] + lap_coef Lap V + b . grad V + h(x, V, s grad V) and the seed coefficients
+//                         dR/dV, dR/dV'_j of the adjoint (dR/dLap V = lap_coef is a constant)
 //   pinn_backward_kernel  per tile: the forward again (everything stays in LDS), the adjoint sweep, every weight gradient as MFMA
 //                         outer products over the 16 rows; a workgroup adds the tiles it owns into its own partial gradient
 //                         (first tile stores), the partials are summed in a fixed order by reduce_grad_kernel.
@@ -29,23 +37,28 @@ constexpr int kPinnThreads = 256;      // four waves
 constexpr int kPinnMaxWg = 256;        // partial gradients of the backward kernel
 
 enum { PINN_DRIFT_ZERO = 0, PINN_DRIFT_DIAG = 2, PINN_DRIFT_DWELL = 3 };                      // PSP_DRIFT_*
-enum { PINN_H_ZERO = 0, PINN_H_QUAD = 1, PINN_H_ALLEN_CAHN = 2, PINN_H_EXP_LIN = 3, PINN_H_EXP_SQ = 4, PINN_H_EXP_SIN = 5 };   // PSP_GH_*
+enum { PINN_H_ZERO = 0, PINN_H_QUAD = 1, PINN_H_ALLEN_CAHN = 2, PINN_H_EXP_LIN = 3, PINN_H_EXP_SQ = 4, PINN_H_EXP_SIN = 5,
+       PINN_H_EXP_SIN_FULL = 6 };      // PSP_GH_*; 6 = GH_EXPBALL_SIN_FULL (genl_kernels.h): (sum_i x_i)^2 in the linear part
 enum { PINN_ACT_RELU2 = 0, PINN_ACT_TANH2 = 1, PINN_ACT_TANH = 2 };                           // PSP_ACT_*
 
 struct PinnArgs {
     int d, n_in, K, L, act;
     int nblk, ntiles;                  // direction blocks per sample, tiles = K * nblk (tile = k * nblk + blk)
+    int n_grad, n_hess;                // gradient directions (0 or n_in), second-order directions of the table
+    int cnt_lo, cnt_hi;                // global direction indices [cnt_lo, cnt_hi) are counted in S
     int TOT, AST;                      // columns of the concatenation, its LDS row stride
     int H[4], fan[5];                  // widths; fan[i] = inputs of layer i = first column of h_i; fan[L] = TOT
     int offW[5], offb[5], sk[5], sc[5];   // flat-parameter offsets and the (k, column) strides of every weight; [L]: output layer
     int P, G;                          // parameters; workgroups (= partial gradients) of the backward kernel
     int drift_kind, h_kind;
     float s, h_par[4];
+    float lap_coef;                    // dR / dLap V: s^2 / 2, or 1 / 2 with a direction table
     const float* drift;
+    const float* dirs;                 // (n_hess, d) or null
     const float* params;
     const float* x;                    // (K, d)
     const float* t;                    // (K) or null
-    float* V;                          // scratch: V (K), lap (K, nblk), gradV (K, n_in), cV (K), cG (K, n_in)
+    float* V;                          // scratch: V (K), lap (K, nblk), gradV (K, n_grad), cV (K), cG (K, n_grad)
     float* lap;
     float* gradV;
     float* cV;
@@ -113,11 +126,16 @@ __device__ __forceinline__ void pinn_rows_times_w(const float* A, int ast, int f
 __device__ __forceinline__ void pinn_forward_tile(const PinnArgs& a, int k, int blk, float* Act, float* Zp, float* red) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ast = a.AST, n_in = a.n_in, d = a.d;
+    const int j0 = blk * kPinnDirs - 2;                            // row r >= 2 carries the direction j0 + r
     for (int idx = tid; idx < 16 * n_in; idx += kPinnThreads) {
         const int r = idx / n_in, c = idx - r * n_in;
         float v = 0.f;
         if (r == 0) v = c < d ? a.x[(size_t)k * d + c] : a.t[k];
-        else if (r >= 2) v = (blk * kPinnDirs + r - 2 == c) ? 1.f : 0.f;
+        else if (r >= 2) {
+            const int j = j0 + r;
+            if (j < a.n_grad) v = j == c ? 1.f : 0.f;
+            else if (j < a.n_grad + a.n_hess) v = c < d ? a.dirs[(size_t)(j - a.n_grad) * d + c] : 0.f;
+        }
         Act[r * ast + c] = v;
     }
     __syncthreads();
@@ -134,7 +152,7 @@ __device__ __forceinline__ void pinn_forward_tile(const PinnArgs& a, int k, int 
             float S = 0.f;
             for (int r = 2; r < 16; ++r) {
                 const float zp = Z[r * kPinnZS + c];
-                if (blk * kPinnDirs + r - 2 < d) S = fmaf(zp, zp, S);
+                if (j0 + r >= a.cnt_lo && j0 + r < a.cnt_hi) S = fmaf(zp, zp, S);
                 Act[r * ast + fan + c] = p1 * zp;
             }
             Act[fan + c] = p0;
@@ -177,7 +195,7 @@ __global__ __launch_bounds__(kPinnThreads) void pinn_forward_kernel(const PinnAr
             else if (tid == 1) a.lap[(size_t)k * a.nblk + blk] = o;
             else {
                 const int j = blk * kPinnDirs + tid - 2;
-                if (j < a.n_in) a.gradV[(size_t)k * a.n_in + j] = o;
+                if (j < a.n_grad) a.gradV[(size_t)k * a.n_grad + j] = o;
             }
         }
         // (the next tile writes `red` only behind the barriers of its forward)
@@ -190,20 +208,22 @@ __global__ void pinn_finish_kernel(const PinnArgs a) {
     if (k >= a.K) return;
     const int d = a.d, n_in = a.n_in;
     const float s = a.s, y = a.V[k];
-    const float* g = a.gradV + (size_t)k * n_in;
+    const float* g = a.gradV + (size_t)k * n_in;                   // (read only with n_grad = n_in)
     const float* x = a.x + (size_t)k * d;
     float* cg = a.cG + (size_t)k * n_in;
     float lap = 0.f;
     for (int b = 0; b < a.nblk; ++b) lap += a.lap[(size_t)k * a.nblk + b];
-    float bg = 0.f, g2 = 0.f, rr = 0.f;
+    float bg = 0.f, g2 = 0.f, rr = 0.f, sx = 0.f;
     for (int j = 0; j < d; ++j) {
         const float xj = x[j];
+        rr = fmaf(xj, xj, rr);
+        sx += xj;
+        if (a.n_grad == 0) continue;                               // no drift, no time input, an h that does not read z
         float bj = 0.f;
         if (a.drift_kind == PINN_DRIFT_DWELL) bj = -(4.0f * a.drift[j] * (xj * (xj * xj - 1.0f)));
         else if (a.drift_kind == PINN_DRIFT_DIAG) bj = a.drift[j] * xj;
         bg = fmaf(bj, g[j], bg);
         g2 = fmaf(g[j], g[j], g2);
-        rr = fmaf(xj, xj, rr);
         cg[j] = a.h_kind == PINN_H_QUAD ? bj - s * s * g[j] : bj;       // h = -|s grad V|^2 / 2
     }
     float h = 0.f, hy = 0.f;
@@ -211,7 +231,8 @@ __global__ void pinn_finish_kernel(const PinnArgs a) {
     else if (a.h_kind == PINN_H_ALLEN_CAHN) { h = y - y * y * y; hy = 1.0f - 3.0f * y * y; }
     else if (a.h_kind >= PINN_H_EXP_LIN) {                           // the exponential-on-the-ball family (gen_kernels.h)
         const float al = a.h_par[0];
-        const float lin = 2.0f * al * (2.0f * al * rr + a.h_par[1]) + a.h_par[2];
+        const float rl = a.h_kind == PINN_H_EXP_SIN_FULL ? sx * sx : rr;    // the exponent keeps |x|^2
+        const float lin = 2.0f * al * (2.0f * al * rl + a.h_par[1]) + a.h_par[2];
         float nl = 0.f, nly = 0.f;
         if (a.h_kind != PINN_H_EXP_LIN) {
             const float arg = expf(2.0f * al * rr) - y * y;
@@ -221,8 +242,8 @@ __global__ void pinn_finish_kernel(const PinnArgs a) {
         h = nl - y * lin;
         hy = nly - lin;
     }
-    float R = 0.5f * s * s * lap + bg + h;
-    if (n_in > d) { R += g[d]; cg[d] = 1.0f; }
+    float R = a.lap_coef * lap + bg + h;
+    if (n_in > d) { R += g[d]; cg[d] = 1.0f; }                     // (a time input implies n_grad = n_in)
     a.R[k] = R;
     a.cV[k] = hy;
 }
@@ -235,7 +256,7 @@ __global__ __launch_bounds__(kPinnThreads) void pinn_backward_kernel(const PinnA
     float* sd = red + 64 + 16;
     float* Adj = sd + 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = lane & 15, kq = lane >> 4;
-    const int ast = a.AST, tot = a.TOT, L = a.L, d = a.d;
+    const int ast = a.AST, tot = a.TOT, L = a.L;
     float* gp = a.gpart + (size_t)blockIdx.x * a.P;
     bool first = true;
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x, first = false) {
@@ -245,10 +266,10 @@ __global__ __launch_bounds__(kPinnThreads) void pinn_backward_kernel(const PinnA
             const float rb = a.rbar[k];
             float v;
             if (tid == 0) v = blk == 0 ? rb * a.cV[k] : 0.f;       // the value itself enters R once per sample
-            else if (tid == 1) v = 0.5f * a.s * a.s * rb;
+            else if (tid == 1) v = a.lap_coef * rb;
             else {
                 const int j = blk * kPinnDirs + tid - 2;
-                v = j < a.n_in ? rb * a.cG[(size_t)k * a.n_in + j] : 0.f;
+                v = j < a.n_grad ? rb * a.cG[(size_t)k * a.n_grad + j] : 0.f;
             }
             sd[tid] = v;
         }
@@ -278,7 +299,8 @@ __global__ __launch_bounds__(kPinnThreads) void pinn_backward_kernel(const PinnA
                 float S = 0.f, dot = 0.f;
                 for (int r = 2; r < 16; ++r) {
                     const float zp = Z[r * kPinnZS + c], hbr = Adj[r * ast + col];
-                    const bool space = blk * kPinnDirs + r - 2 < d;
+                    const int j = blk * kPinnDirs + r - 2;
+                    const bool space = j >= a.cnt_lo && j < a.cnt_hi;
                     if (space) S = fmaf(zp, zp, S);
                     dot = fmaf(zp, hbr, dot);
                     Z[r * kPinnZS + c] = space ? fmaf(2.f * p2 * zp, dhb, p1 * hbr) : p1 * hbr;

@@ -1905,8 +1905,11 @@ int make_pinn_plan(const psp_pinn_config* c, PinnPlan* p) {
     if (!c) return fail(-1, "null config");
     if (c->d <= 0 || c->K <= 0) return fail(-1, "psp_pinn: d and K must be positive");
     if (c->has_time != 0 && c->has_time != 1) return fail(-1, "psp_pinn: has_time must be 0 or 1");
-    if (c->sigma_kind != PSP_GENL_SIGMA_SCALED)
-        return fail(-4, "psp_pinn: a dense sigma is not a Laplacian (PSP_GENL_SIGMA_SCALED only)");
+    if (c->sigma_kind != PSP_GENL_SIGMA_SCALED && c->sigma_kind != PSP_GENL_SIGMA_DENSE)
+        return fail(-1, "psp_pinn: sigma_kind out of range");
+    const bool dense = c->sigma_kind == PSP_GENL_SIGMA_DENSE;
+    if (dense && !c->dirs) return fail(-4, "psp_pinn: a dense sigma needs its direction table (dirs)");
+    if (dense && (c->n_dirs < 1 || c->n_dirs > c->d)) return fail(-1, "psp_pinn: n_dirs must lie in 1 .. d");
     if (c->n_hidden < 1 || c->n_hidden > 4) return fail(-2, "psp_pinn: 1 to 4 hidden layers");
     const int n_in = c->d + c->has_time;
     if (n_in > 112) return fail(-2, "psp_pinn: net input (d + has_time) above 112");
@@ -1917,14 +1920,23 @@ int make_pinn_plan(const psp_pinn_config* c, PinnPlan* p) {
     if (c->drift_kind != PSP_DRIFT_ZERO && c->drift_kind != PSP_DRIFT_DIAG && c->drift_kind != PSP_DRIFT_DOUBLE_WELL)
         return fail(-1, "psp_pinn: drift_kind must be PSP_DRIFT_ZERO, _DIAG or _DOUBLE_WELL");
     if (c->drift_kind != PSP_DRIFT_ZERO && !c->drift) return fail(-1, "psp_pinn: this drift_kind needs the drift vector");
-    if (c->h_kind < PSP_GH_ZERO || c->h_kind > PSP_GH_EXPBALL_SIN) return fail(-1, "psp_pinn: h_kind out of range");
+    if (c->h_kind < PSP_GH_ZERO || c->h_kind > PSP_GH_EXPBALL_SIN_FULL) return fail(-1, "psp_pinn: h_kind out of range");
     if (c->h_kind >= PSP_GH_EXPBALL_LIN && c->h_par[3] != 0.f) return fail(-1, "psp_pinn: an h that reads t is not built");
-    if ((int64_t)c->K * ((n_in + psp::kPinnDirs - 1) / psp::kPinnDirs) > (1 << 24)) return fail(-1, "psp_pinn: K too large");
+    if (dense && c->h_kind == PSP_GH_QUAD) return fail(-1, "psp_pinn: an h that reads z = B grad V is not built for dense directions");
+    // the gradient directions are dropped where nothing reads grad V: no drift, no time input, an h that does not read z
+    const int n_hess = dense ? c->n_dirs : 0;
+    const int n_grad = (dense && c->drift_kind == PSP_DRIFT_ZERO && !c->has_time) ? 0 : n_in;
+    const int nblk = (n_grad + n_hess + psp::kPinnDirs - 1) / psp::kPinnDirs;
+    if ((int64_t)c->K * nblk > (1 << 24)) return fail(-1, "psp_pinn: K too large");
     psp::PinnArgs& a = p->a;
     memset(&a, 0, sizeof(a));
     a.d = c->d; a.n_in = n_in; a.K = c->K; a.L = c->n_hidden; a.act = c->activation;
-    a.nblk = (n_in + psp::kPinnDirs - 1) / psp::kPinnDirs;
+    a.nblk = nblk;
     a.ntiles = a.K * a.nblk;
+    a.n_grad = n_grad; a.n_hess = n_hess;
+    a.cnt_lo = dense ? n_grad : 0; a.cnt_hi = dense ? n_grad + n_hess : c->d;
+    a.lap_coef = dense ? 0.5f : 0.5f * c->sigma_scale * c->sigma_scale;
+    a.dirs = dense ? c->dirs : nullptr;
     int fan = n_in, off = 0;
     for (int i = 0; i <= a.L; ++i) {
         const int H = i < a.L ? c->widths[i] : 1;
@@ -1946,13 +1958,13 @@ int make_pinn_plan(const psp_pinn_config* c, PinnPlan* p) {
     p->lds_fwd = psp::pinn_lds_bytes(a.AST, a.L, false);
     p->lds_bwd = psp::pinn_lds_bytes(a.AST, a.L, true);
     if (p->lds_bwd > kMaxLds) return fail(-3, "psp_pinn: the activation images exceed the LDS");
-    p->scratch_floats = (int64_t)a.K * (2 + a.nblk + 2 * n_in);
+    p->scratch_floats = (int64_t)a.K * (2 + a.nblk + 2 * n_grad);
     return 0;
 }
 void pinn_scratch(PinnPlan* p, float* scratch) {
     psp::PinnArgs& a = p->a;
     const size_t K = (size_t)a.K;
-    a.V = scratch; a.lap = a.V + K; a.gradV = a.lap + K * a.nblk; a.cV = a.gradV + K * a.n_in; a.cG = a.cV + K;
+    a.V = scratch; a.lap = a.V + K; a.gradV = a.lap + K * a.nblk; a.cV = a.gradV + K * a.n_grad; a.cG = a.cV + K;
 }
 }  // namespace
 

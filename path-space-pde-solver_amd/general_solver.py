@@ -465,7 +465,8 @@ class GeneralSolver:
         if reason is None:
             self.plan_name, self.plan_reason = 'native', None
             plan = getattr(self, '_pinn_plan', None)
-            key = self._plan_key() + (bool(self.PINN_log_variance), bool(self.boundary_loss))
+            key = self._plan_key() + (bool(self.PINN_log_variance), bool(self.boundary_loss), bool(self.full_hessian),
+                                     getattr(self, 'hessian', 'reference'))
             if plan is None or plan.net is not self.V or plan.key != key or not _owns_parameters(plan):
                 plan = ppn.PinnNativePlan(self)
                 plan.key = key
@@ -551,7 +552,13 @@ class EllipticSolver(GeneralSolver):
                  K_test_log=None, PINN_log_variance=False, log_loss_parts=False, boundary_loss=True,
                  boundary_type='Dirichlet', variance_moment_split=False, full_hessian=False, uniform_square=False,
                  device=None, backend='auto', noise='reference', mlp_dtype='auto', v_l2_error_flag=True, range_guard=True,
-                 test_log='reference'):
+                 test_log='reference', hessian='reference'):
+        if hessian not in ('reference', 'directions'):
+            raise ValueError("hessian must be 'reference' or 'directions', got %r" % (hessian,))
+        # train_PINN(full_hessian=True): 'reference' takes trace(B B^T Hess V) from one autograd.functional.hessian call per
+        # sample, as the reference does (composite plan); 'directions' lets the native plan take it as sum_j u_j^T Hess V u_j
+        # over a factor of B B^T (plan_pinn_native.direction_table), the same number up to fp32 rounding
+        self.hessian = hessian
         self.v_l2_error_flag = v_l2_error_flag   # False: skip the V_L2 diagnostic of solver.py:738 on the native plan (timed runs)
         super().__init__(problem, name, seed=seed, delta_t=delta_t, N=N, lr=lr, L=L, K=K, K_boundary=K_boundary,
                          alpha=alpha, adaptive_forward_process=adaptive_forward_process, detach_forward=detach_forward,

@@ -193,8 +193,8 @@ class PinnConfig(C.Structure):
     """psp_pinn_config: the PINN residual of a dense-concat value net (psp_pinn_query / psp_pinn_residual / psp_pinn_backward)."""
     _fields_ = [("d", C.c_int32), ("K", C.c_int32), ("has_time", C.c_int32), ("n_hidden", C.c_int32), ("widths", C.c_int32 * 4),
                 ("activation", C.c_int32), ("linear_layout", C.c_int32), ("drift_kind", C.c_int32), ("h_kind", C.c_int32),
-                ("sigma_kind", C.c_int32), ("reserved", C.c_int32), ("sigma_scale", C.c_float), ("h_par", C.c_float * 4),
-                ("reserved_f", C.c_float), ("drift", C.c_void_p)]
+                ("sigma_kind", C.c_int32), ("n_dirs", C.c_int32), ("sigma_scale", C.c_float), ("h_par", C.c_float * 4),
+                ("reserved_f", C.c_float), ("drift", C.c_void_p), ("dirs", C.c_void_p)]
 
 
 class PinnSizes(C.Structure):

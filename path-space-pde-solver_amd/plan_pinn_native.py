@@ -10,9 +10,15 @@ Per iteration:
 The reference differentiates the net d + 1 times per iteration (one autograd.grad per input column, each through the graph of
 the gradient); here the value, every tangent and the Laplacian row pass through the net once, in one kernel.
 
+EllipticSolver(full_hessian=True, hessian='directions') with a dense constant sigma B: the reference takes trace(B B^T Hess V)
+from one autograd.functional.hessian call per sample (the default, hessian='reference', keeps doing that on the composite plan:
+the plan a configuration runs on does not change under its user).  Here B B^T is factored once on the host (``direction_table``) into r = rank(B)
+vectors u_j with sum_j u_j u_j^T = B B^T, and the same kernels carry the u_j as tangent rows: 1/2 sum_j u_j^T Hess V u_j.
+
 Scope: a dense-concat value net the run-time-shaped kernels take (plan_general_deep.value_net_spec: 1-4 hidden layers, widths
-<= 128, input <= 112, relu^2 / tanh / tanh^2), a catalogue problem with a scaled-identity sigma whose h does not read t, any domain,
-one rank.  ``pinn_eligibility`` names what keeps a configuration on the composite plan.
+<= 128, input <= 112, relu^2 / tanh / tanh^2), a catalogue problem whose h does not read t, with a scaled-identity sigma or --
+EllipticSolver with full_hessian=True and hessian='directions' only -- a dense one, any domain, one rank.  ``pinn_eligibility`` names what keeps a
+configuration on the composite plan.
 """
 import ctypes as C
 import time
@@ -34,8 +40,13 @@ except ImportError:
 def pinn_eligibility(solver):
     """None if the forward-Laplacian kernels take this solver's train_PINN(), else the reason it runs on the composite plan."""
     s = solver
-    if s.full_hessian:
-        return 'full_hessian=True takes trace(B B^T Hess V) sample by sample (composite only)'
+    full = bool(s.full_hessian)
+    if full and not s.elliptic:
+        return ('full_hessian=True on GeneralSolver: the reference hands a d-column point to a net of d + 1 inputs there, '
+                'so there is no reference behaviour to match (composite only)')
+    if full and getattr(s, 'hessian', 'reference') != 'directions':
+        return ("full_hessian=True takes trace(B B^T Hess V) sample by sample, as the reference does; "
+                "EllipticSolver(hessian='directions') runs it on the direction-table kernels")
     if getattr(s, 'mlp_dtype', 'auto') not in ('auto', 'fp32'):
         return 'mlp_dtype=%r: the PINN kernels are fp32 MFMA only' % s.mlp_dtype
     if getattr(s, 'noise', 'reference') != 'reference':
@@ -53,8 +64,12 @@ def pinn_eligibility(solver):
     if over is not None:
         return 'problem.%s is not the catalogue implementation general_native_spec() describes' % over
     spec = spec_fn()
-    if spec.get('sigma') is not None:
-        return 'a dense sigma: the kernels propagate the Laplacian of a scaled identity'
+    dense = spec.get('sigma') is not None
+    if dense and not full:
+        return ('a dense sigma without full_hessian: the reference takes B[0,0]^2 times the Laplacian for it, which is no '
+                'operator of the problem (composite only)')
+    if dense and spec['h'] == nat.GH_QUAD:
+        return 'an h that reads z = B grad V is not in the PINN kernels for a dense sigma'
     if spec['h'] >= nat.GH_EXPBALL_LIN and len(spec.get('h_par', ())) > 3 and spec['h_par'][3] != 0.0:
         return 'h reads t: the reference hands it t_n as (K, 1) and the residual broadcasts to (K, K) (composite only)'
     if spec['drift'][0] not in (nat.DRIFT_ZERO, nat.DRIFT_DIAG, nat.DRIFT_DOUBLE_WELL):
@@ -65,8 +80,20 @@ def pinn_eligibility(solver):
     if why is not None:
         return why
     if s.device.type != 'cuda':
+        if full:
+            return 'full_hessian=True runs on the direction-table kernels, which need a GPU: device is %s' % s.device
         return 'device is %s (the HIP kernels need a GPU)' % s.device
     return None
+
+
+def direction_table(B):
+    """(r, d) float64 rows u_j = sqrt(lambda_j) q_j over the eigenpairs of B B^T above the default tolerance of
+    torch.linalg.matrix_rank (largest eigenvalue times d times the float64 epsilon): sum_j u_j u_j^T = B B^T, so
+    sum_j u_j^T H u_j = trace(B B^T H) for every symmetric H, in r = rank(B) directions."""
+    B = torch.as_tensor(B).detach().to(device='cpu', dtype=torch.float64)
+    lam, Q = torch.linalg.eigh(B @ B.t())
+    keep = lam > lam.abs().max() * B.shape[0] * torch.finfo(torch.float64).eps
+    return (Q[:, keep] * torch.sqrt(lam[keep])).t().contiguous()
 
 
 class PinnNativePlan:
@@ -88,7 +115,12 @@ class PinnNativePlan:
             cfg.widths[i] = int(h)
         cfg.activation, cfg.linear_layout = _ACT[net['act']], (1 if net['linear'] else 0)
         cfg.drift_kind, cfg.h_kind = spec['drift'][0], spec['h']
-        cfg.sigma_kind, cfg.sigma_scale = nat.GENL_SIGMA_SCALED, float(spec['sigma_scale'])
+        if spec.get('sigma') is None:                              # (full_hessian with s I is s^2 times the Laplacian)
+            cfg.sigma_kind, cfg.sigma_scale = nat.GENL_SIGMA_SCALED, float(spec['sigma_scale'])
+        else:                                                      # trace(B B^T Hess V) as sum_j u_j^T Hess V u_j
+            dirs = direction_table(spec['sigma']).to(device=self.dev, dtype=torch.float32).contiguous()
+            self._keep.append(dirs)
+            cfg.sigma_kind, cfg.n_dirs, cfg.dirs = nat.GENL_SIGMA_DENSE, dirs.shape[0], nat.ptr(dirs)
         for i, v in enumerate(spec.get('h_par', ())):
             cfg.h_par[i] = float(v)
         if spec['drift'][1] is not None:
