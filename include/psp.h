@@ -697,6 +697,29 @@ int psp_dnet_adjoint_sweep(const psp_dnet_config* cfg, const float* params, floa
 int psp_dnet_rollout_bwd(const psp_dnet_config* cfg, const float* params, const float* images, const float* w,
                          float* partial, void* stream);
 
+/* Gradient-variance diagnostic (Solver(compute_gradient_variance=m), reference solver.py:225-281) for a DenseNet control.
+ * Trajectories are independent and net n sees one input per trajectory, so the per-trajectory gradient G_k of Y_N[k] with respect
+ * to a layer of net n is rank one (activation row x delta row) and its SECOND moment over k is a sum of outer products of the
+ * squared operands.  psp_dnet_rollout_bwd_sq takes the arguments and checks of psp_dnet_rollout_bwd and writes
+ *     partial[item] = sum_k (w_k sqrt(dt) per-trajectory gradient)^2      (element-wise square, same padded layout and slices)
+ * always on the fp32 MFMAs (base.mlp_dtype and base.range_flag are not read). */
+int psp_dnet_rollout_bwd_sq(const psp_dnet_config* cfg, const float* params, const float* images, const float* w,
+                            float* partial, void* stream);
+/* psp_gradvar_finish reduces the slices of up to four such partial buffers, each (N * slices, padded_params), and combines the raw
+ * moments in double.  With c the per-trajectory factor (moment: c = r = Y_N - g(X_N); log-variance: c = r - mean r),
+ *     pS = S[c] = sum_k c_k G_k      pQ = Q[c] = sum_k c_k^2 G_k o G_k      pS2 = S[c^2]      pS1 = S[1]      csums = (sum c, sum c^2)
+ * and B = gg (PSP_LOSS_MOMENT; the (N, n_params_per_set) gradient of g(X_N[0]), NULL -> 0 and pS2 may be NULL) or pS1 / K
+ * (PSP_LOSS_LOG_VARIANCE; pS2 and pS1 required):
+ *     sum f = 2 (S - B sum c)     sum f^2 = 4 (Q - 2 B S2 + B^2 sum c^2)     mean = sum f / K     var = (sum f^2 - (sum f)^2 / K) / (K - 1)
+ * var is clamped at 0 before the root; rel = sqrt(var) / mean in fp32 with NaN -> 0 (inf and negative values stay).  gather_index:
+ * (n_params_per_set) int64 padded position of every real parameter.  Outputs mean / var / rel: (N, n_params_per_set) fp32 in the
+ * DenseNet's registration order; rel_mean_out: one float, the mean of rel; step_sums: scratch of N doubles.  csums is a DEVICE
+ * pointer (no host sync).  One workgroup per step and one final reduction; plain stores, no atomics. */
+int psp_gradvar_finish(const float* pS, const float* pQ, const float* pS2, const float* pS1, const float* gg,
+                       const int64_t* gather_index, int32_t N, int32_t slices, int64_t padded_params, int64_t n_params_per_set,
+                       int32_t K, int32_t loss_kind, const double* csums, float* mean_out, float* var_out, float* rel_out,
+                       double* step_sums, float* rel_mean_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Solver.train with a linear, affine or constant control per time step (appended in 0.4.0, no version bump; csrc/aff_kernels.h):
  * time_approx='outer' with z_n a list of function_space.Linear / Affine / Constant (reference function_space.py:24-63; the

@@ -961,8 +961,14 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_adj_kernel(const
 // most 3e-8 absolute, fp32's own epsilon.  Stated range: the network factors between G and dz2 / dz1 stay below 256 and
 // h = r^2 below 65504.  The partial gradient is scaled back when it is written (exact).  Phase (1) runs its three adjoint
 // products through gemm_Tx on split tables of the same size as the fp32 ones.
-template <int D, int H, int PASS = 0, bool X3 = false>
+// SQ (fp32 products only): the SECOND moment of the per-trajectory gradients.  The per-trajectory gradient of every layer is rank
+// one (activation row x column-operand row), so  sum_k (w_k sqrt(dt) per-trajectory gradient)^2  is the same sum of outer products
+// with both operands squared element-wise: phase (1) is unchanged (dz2 / dz1 are linear in the weighted G), phase (2) squares the
+// row operand and every column tile before the MFMAs, and the bias sums add the squared column tiles.  Items, flush and the
+// layout of partial[item] are those of the first moment.
+template <int D, int H, int PASS = 0, bool X3 = false, bool SQ = false>
 __global__ __launch_bounds__(256) void hjbd_bwd_kernel(const DnetArgs da) {
+    static_assert(!(SQ && X3), "the squared outer products run on the fp32 MFMAs only");
     PSP_COND_EXIT(da.h);
     GradCheck<X3> gchk;                                      // backward side of the range guard (hjb_kernels.h)
     using W = DGeo<D, H>;
@@ -1223,6 +1229,10 @@ __global__ __launch_bounds__(256) void hjbd_bwd_kernel(const DnetArgs da) {
 #pragma unroll
                     for (int m = 0; m < 2 * HB; ++m) ct[DB - C0 + m] = tile_get(ex + m * 256, lane);
                 }
+                if constexpr (SQ) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) ct[c] = ct[c] * ct[c];
+                }
                 if (sub == 0) {
 #pragma unroll
                     for (int c = 0; c < NC; ++c) bs[c] += hsum4(ct[c]);
@@ -1232,7 +1242,8 @@ __global__ __launch_bounds__(256) void hjbd_bwd_kernel(const DnetArgs da) {
                     const int i = sub + 4 * li;            // row item (wave-uniform): x block, h1 block or h2 block
                     if (i < NRI) {
                         const f32x4 raw = ax[cur][li];
-                        const f32x4 A = (i < DB) ? raw : raw * raw;             // h = r^2
+                        const f32x4 A1 = (i < DB) ? raw : raw * raw;            // h = r^2
+                        const f32x4 A = SQ ? A1 * A1 : A1;
                         const int ncol = (i < DB) ? DB + 2 * HB : ((i < DB + HB) ? DB + HB : DB);   // h2 rows meet G only, h1 rows G and dz2
 #pragma unroll
                         for (int c = 0; c < NC; ++c)
@@ -1302,6 +1313,7 @@ struct DnetInstance {
     hipError_t (*launch_adj_x3)(const DnetArgs&, int grid, hipStream_t);
     hipError_t (*launch_bwd_x3)(const DnetArgs&, int grid, hipStream_t);   // split-product weight-gradient outer products
     hipError_t (*launch_ul2_stage)(const DnetArgs&, hipStream_t);          // u_L2 log, kind 1: the gain tables (hjbd_tables_kernel(.., 4))
+    hipError_t (*launch_bwd_sq)(const DnetArgs&, int grid, hipStream_t);   // squared outer products (hjbd_bwd_kernel<.., SQ>), fp32
 };
 
 template <int D, int H>
@@ -1423,12 +1435,31 @@ struct DnetLaunch {
             return hipErrorNotSupported;
         }
     }
+    template <int PASS>
+    static hipError_t bwd_pass_sq(const DnetArgs& a, int grid, hipStream_t s) {
+        const int bytes = W::bwd_lds_floats * 4;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_bwd_kernel<D, H, PASS, false, true>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((hjbd_bwd_kernel<D, H, PASS, false, true>), dim3(grid), dim3(256), bytes, s, a);
+        return hipGetLastError();
+    }
+    static hipError_t bwd_sq(const DnetArgs& a, int grid, hipStream_t s) {       // second moment of the per-trajectory gradients
+        if constexpr (kPasses == 1) {
+            return bwd_pass_sq<0>(a, grid, s);
+        } else if constexpr (kPasses == 2) {
+            hipError_t e = bwd_pass_sq<1>(a, grid, s);
+            return e != hipSuccess ? e : bwd_pass_sq<2>(a, grid, s);
+        } else {
+            return hipErrorNotSupported;
+        }
+    }
     static DnetInstance instance() {
         // (set / shared table sizes: the larger of the fp32 and the split layouts -- the caller allocates one region for both)
         return DnetInstance{D, H, W::lds_floats * 4, W::set_floats > W::set_floats_x3 ? W::set_floats : W::set_floats_x3, W::vec_floats,
                             W::oSets > W::oSets_x ? W::oSets : W::oSets_x, &fwd,
                             W::PBI, W::PP, W::bwd_lds_floats * 4, kPasses, &bwd, &adj, W::lds_floats_x3 * 4, &fwd_x3, &adj_x3, &bwd_x3,
-                            &ul2_stage};
+                            &ul2_stage, &bwd_sq};
     }
 };
 

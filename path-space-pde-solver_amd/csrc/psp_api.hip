@@ -756,6 +756,117 @@ extern "C" int psp_dnet_rollout_bwd(const psp_dnet_config* cfg, const float* par
     return 0;
 }
 
+extern "C" int psp_dnet_rollout_bwd_sq(const psp_dnet_config* cfg, const float* params, const float* images, const float* w,
+                                       float* partial, void* stream) {
+    DnetPlan p;
+    int rc = make_dnet_plan(cfg, &p);
+    if (rc) return rc;
+    if (!p.bwd_ok || !p.inst.launch_bwd_sq)
+        return fail(-3, "the hand-written DenseNet-control backward does not cover this instance (accumulator tiles)");
+    if (!params || !images || !w || !partial) return fail(-1, "null buffer passed to psp_dnet_rollout_bwd_sq");
+    const psp_hjb_config* b = &cfg->base;
+    psp::DnetArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h.params = params; a.h.K_local = b->K_local; a.h.N = b->N; a.h.ntile16 = p.ntile16; a.h.sqdt = b->sqrt_dt; a.h.dt = b->dt;
+    a.pimg = const_cast<float*>(images); a.wts = w; a.partial = partial; a.slices = p.slices;
+    a.d_real = cfg->d_real; a.h_real = cfg->H_real; a.time_input = cfg->time_input ? 1 : 0; a.per_step = cfg->per_step ? 1 : 0;
+    // always the fp32 MFMAs, never predicated on the range flag: squares of ~1/K-scaled tiles have no place on the f16 pipe
+    const hipError_t e = p.inst.launch_bwd_sq(a, p.bwd_grid, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "hjbd_bwd_kernel (squared outer products) launch");
+    return 0;
+}
+
+// ---- gradient-variance diagnostic: slices -> moments -> sqrt(var) / mean, one workgroup per time step -----------------------
+namespace {
+struct GradvarArgs {
+    const float *pS, *pQ, *pS2, *pS1, *gg;
+    const long long* gidx;
+    const double* csums;
+    float *mean, *var, *rel;
+    double* step_sums;
+    long long Pset, PP;
+    int N, slices, K, kind;
+};
+// The raw moments are combined in double: sum f = 2 (S - B sum c), sum f^2 = 4 (Q - 2 B S2 + B^2 sum c^2) with B = Gg (moment;
+// 0 without it) or S[1] / K (log-variance).  mean, var are rounded to fp32 and rel formed in fp32 from them, as the reference's
+// fp32 tensors are; var is clamped at 0 BEFORE the root (a rounding-negative raw moment must not turn into a NaN that the NaN -> 0
+// rule then hides); NaN -> 0 (0 / 0 of a dead unit), inf and negative values stay.
+__global__ __launch_bounds__(256) void gradvar_finish_kernel(const GradvarArgs a) {
+    __shared__ double red[256];
+    const int n = blockIdx.x;
+    const double K = (double)a.K, sc = a.csums[0], sc2 = a.csums[1];
+    double acc = 0.0;
+    for (long long q = threadIdx.x; q < a.Pset; q += blockDim.x) {
+        const long long col = a.gidx[q];
+        double S = 0.0, Q = 0.0, S2 = 0.0, S1 = 0.0;
+        for (int sl = 0; sl < a.slices; ++sl) {
+            const size_t o = ((size_t)n * a.slices + sl) * (size_t)a.PP + (size_t)col;
+            S += (double)a.pS[o];
+            Q += (double)a.pQ[o];
+            if (a.pS2) S2 += (double)a.pS2[o];
+            if (a.pS1) S1 += (double)a.pS1[o];
+        }
+        const double B = a.kind == 1 ? S1 / K : (a.gg ? (double)a.gg[(size_t)n * a.Pset + q] : 0.0);
+        const double sf = 2.0 * (S - B * sc);
+        const double sf2 = 4.0 * (Q - 2.0 * B * S2 + B * B * sc2);
+        double var = (sf2 - sf * sf / K) / (K - 1.0);
+        if (var < 0.0) var = 0.0;
+        const float mf = (float)(sf / K), vf = (float)var;
+        // fp32 root and quotient, correctly rounded (through double: 53 >= 2 * 24 + 2 bits make both roundings exact), so that rel is
+        // bit for bit what torch.sqrt(var) / mean gives for the fp32 mean and var written above
+        const float root = (float)sqrt((double)vf);
+        float r = (float)((double)root / (double)mf);
+        if (r != r) r = 0.f;
+        const size_t o = (size_t)n * a.Pset + q;
+        a.mean[o] = mf; a.var[o] = vf; a.rel[o] = r;
+        acc += (double)r;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.step_sums[n] = red[0];
+}
+__global__ __launch_bounds__(64) void gradvar_mean_kernel(const double* __restrict__ step_sums, int N, long long Pset,
+                                                          float* __restrict__ out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        double s = 0.0;
+        for (int n = 0; n < N; ++n) s += step_sums[n];
+        out[0] = (float)(s / ((double)N * (double)Pset));
+    }
+}
+}  // namespace
+
+extern "C" int psp_gradvar_finish(const float* pS, const float* pQ, const float* pS2, const float* pS1, const float* gg,
+                                  const int64_t* gather_index, int32_t N, int32_t slices, int64_t padded_params,
+                                  int64_t n_params_per_set, int32_t K, int32_t loss_kind, const double* csums,
+                                  float* mean_out, float* var_out, float* rel_out, double* step_sums, float* rel_mean_out,
+                                  void* stream) {
+    if (!pS || !pQ || !gather_index || !csums || !mean_out || !var_out || !rel_out || !step_sums || !rel_mean_out)
+        return fail(-1, "null buffer passed to psp_gradvar_finish");
+    if (N <= 0 || slices <= 0 || padded_params <= 0 || n_params_per_set <= 0 || n_params_per_set > padded_params)
+        return fail(-1, "psp_gradvar_finish: N, slices, padded_params, n_params_per_set must be positive, n_params_per_set <= padded_params");
+    if (K < 2) return fail(-1, "psp_gradvar_finish: the unbiased variance needs K >= 2");
+    if (loss_kind != PSP_LOSS_MOMENT && loss_kind != PSP_LOSS_LOG_VARIANCE)
+        return fail(-1, "psp_gradvar_finish: loss_kind must be PSP_LOSS_MOMENT or PSP_LOSS_LOG_VARIANCE");
+    if (loss_kind == PSP_LOSS_LOG_VARIANCE && (!pS2 || !pS1)) return fail(-1, "psp_gradvar_finish: log-variance needs S[c^2] and S[1]");
+    if (loss_kind == PSP_LOSS_MOMENT && gg && !pS2) return fail(-1, "psp_gradvar_finish: moment with Gg needs S[c^2]");
+    GradvarArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pS = pS; a.pQ = pQ; a.pS2 = pS2; a.pS1 = loss_kind == PSP_LOSS_LOG_VARIANCE ? pS1 : nullptr;
+    a.gg = loss_kind == PSP_LOSS_MOMENT ? gg : nullptr;
+    a.gidx = reinterpret_cast<const long long*>(gather_index); a.csums = csums;
+    a.mean = mean_out; a.var = var_out; a.rel = rel_out; a.step_sums = step_sums;
+    a.Pset = n_params_per_set; a.PP = padded_params; a.N = N; a.slices = slices; a.K = K;
+    a.kind = loss_kind == PSP_LOSS_LOG_VARIANCE ? 1 : 0;
+    int rc = PSP_LAUNCH(gradvar_finish_kernel, dim3(N), dim3(256), 0, stream, a);
+    if (rc) return rc;
+    return PSP_LAUNCH(gradvar_mean_kernel, dim3(1), dim3(64), 0, stream, (const double*)step_sums, (int)N, (long long)n_params_per_set,
+                      rel_mean_out);
+}
+
 extern "C" int psp_dnet_adjoint_sweep(const psp_dnet_config* cfg, const float* params, float* images, const float* XN,
                                       const float* mu, const float* nu, const float* wT, float* tables, void* stream) {
     DnetPlan p;

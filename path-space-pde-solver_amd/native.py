@@ -242,6 +242,9 @@ SIGNATURES = {
     "psp_dnet_query": (C.c_int, [C.POINTER(DnetConfig), C.POINTER(DnetSizes)]),
     "psp_dnet_terminal_reduce": (C.c_int, [C.POINTER(DnetConfig), _P, _P, _P]),
     "psp_dnet_rollout_bwd": (C.c_int, [C.POINTER(DnetConfig), _P, _P, _P, _P, _P]),
+    "psp_dnet_rollout_bwd_sq": (C.c_int, [C.POINTER(DnetConfig), _P, _P, _P, _P, _P]),
+    "psp_gradvar_finish": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
+                                     _P, _P, _P, _P, _P, _P]),
     "psp_dnet_adjoint_sweep": (C.c_int, [C.POINTER(DnetConfig), _P, _P, _P, _P, _P, _P, _P, _P]),
     "psp_dnet_ul2_stage": (C.c_int, [C.POINTER(DnetConfig), _P, _P]),
     "psp_dnet_rollout_fwd": (C.c_int, [C.POINTER(DnetConfig), _P, _P, C.c_int32, _P, _P, C.c_uint64, C.c_uint32, _P,

@@ -25,6 +25,9 @@ weights -- the scheme of plan_native.py / psp_hjb_adjoint_sweep.
 The u_L2 log (solver.py:471-472, 491-494; on by default whenever the problem has u_true) is accumulated per trajectory inside
 the forward kernel from a description of u* built once per plan by ul2_reference (below): a table of u*(t_n), the gains M_n of
 a u* linear in x, or the double wells' grid tables with the reference's index arithmetic.
+The gradient-variance diagnostic (Solver(compute_gradient_variance=m), solver.py:234-281, 496-497) runs on the same images for
+time_approx='outer': DenseNativePlan.gradient_moments forms the first and second moments of the per-trajectory gradients from
+psp_dnet_rollout_bwd / psp_dnet_rollout_bwd_sq launches and psp_gradvar_finish instead of 2 K N backward passes.
 """
 import ctypes as C
 
@@ -146,8 +149,7 @@ def dense_eligibility(solver):
         return 'loss_method %r is not native for a DenseNet control (%s are)' % (solver.loss_method, ', '.join(_LOSSES))
     if solver.loss_method == 'relative_entropy' and not solver.adaptive_forward_process:
         return 'relative_entropy with a non-adaptive forward process is not native for a DenseNet control'
-    if solver.burgers_drift or solver.compute_gradient_variance > 0 or solver.log_gradient \
-            or solver.metastability_logs is not None:
+    if solver.burgers_drift or solver.log_gradient or solver.metastability_logs is not None:
         return 'per-step / per-iteration diagnostics (gradient logs, metastability) are not native here'
     if solver.u_l2_error_flag:
         reason = ul2_unsupported(solver.problem, solver.N, solver.delta_t_np)
@@ -174,7 +176,52 @@ def dense_eligibility(solver):
         raise nat.NativeLibraryError('libpsp_hip.so is not built; run __graft_entry__.build()')
     if _instance_for(solver.d, dims0[1]) is None:
         return 'no compiled DenseNet-control instance covers d=%d, H=%d (csrc/dense_instances.def)' % (solver.d, dims0[1])
+    if solver.compute_gradient_variance > 0:
+        return gradient_variance_unsupported(solver, _instance_for(solver.d, dims0[1]))
     return None
+
+
+def gradient_variance_unsupported(solver, instance, world=None):
+    """None if DenseNativePlan.gradient_moments covers compute_gradient_variance > 0 for this solver on the (d, H) `instance`, else
+    the precise reason (the composite plan then runs the reference's per-trajectory backward passes)."""
+    import os
+    if solver.time_approx != 'outer':
+        return ("compute_gradient_variance indexes one net per time step (reference solver.py:248): it needs time_approx='outer'")
+    if solver.loss_method not in ('moment', 'log-variance'):
+        return ("compute_gradient_variance is defined for loss_method 'moment' and 'log-variance' only (the reference fails on %r)"
+                % solver.loss_method)
+    if solver.adaptive_forward_process and solver.detach_forward:
+        return ('compute_gradient_variance with adaptive_forward_process=True and detach_forward=True differentiates g(X_N), which '
+                'does not depend on the parameters there: the composite plan raises autograd\'s error as the reference does')
+    if instance[0] > 128:
+        return ('the native gradient moments run on the hand-written DenseNet-control backward, which covers d <= 128 '
+                '(instance (%d, %d))' % tuple(instance))
+    if os.environ.get('PSP_DENSE_BWD', 'kernel') == 'gemm':
+        return 'the native gradient moments run on the hand-written DenseNet-control backward (PSP_DENSE_BWD=gemm is set)'
+    if world is None:
+        world = sharding.dist_info()[2]
+    if world > 1:
+        return 'the native gradient moments are single-rank (world size %d)' % world
+    return None
+
+
+def gradvar_combine(S, Q, S2, S1, Gg, K, loss_method, sum_c, sum_c2):
+    """What psp_gradvar_finish computes from the slice-summed, gathered sums (torch, float64 in, fp32 out): (mean, var, rel,
+    mean(rel)).  S = S[c], Q = Q[c], S2 = S[c^2], S1 = S[1] (log-variance), Gg (moment; None: 0).  var is clamped at 0 before the
+    root, rel = sqrt(var) / mean in fp32 with NaN -> 0; inf and negative values stay."""
+    K = float(K)
+    if loss_method == 'log-variance':
+        B = S1.double() / K
+    else:
+        B = Gg.double() if Gg is not None else torch.zeros_like(S, dtype=torch.float64)
+    S2 = S2.double() if S2 is not None else torch.zeros_like(S, dtype=torch.float64)
+    sf = 2.0 * (S.double() - B * sum_c)
+    sf2 = 4.0 * (Q.double() - 2.0 * B * S2 + B * B * sum_c2)
+    var = ((sf2 - sf * sf / K) / (K - 1.0)).clamp_min(0.0)
+    mean32, var32 = (sf / K).to(torch.float32), var.to(torch.float32)
+    rel = torch.sqrt(var32) / mean32
+    rel[rel != rel] = 0
+    return mean32, var32, rel, rel.double().mean().to(torch.float32)
 
 
 class DenseNativePlan:
@@ -318,6 +365,11 @@ class DenseNativePlan:
         self.tn = (torch.arange(s.N, device=dev, dtype=f32) * b.dt)        # fp32 n * dt, as the kernel forms it
         self.step = 0
         self.events = None
+        # gradient-variance diagnostic (Solver(compute_gradient_variance=m)): moments of the latest logged iteration, and the
+        # device log Solver._train_native reads back with the losses
+        self.gv_mean = self.gv_var = self.gv_rel = None
+        self.gv_log, self.gv_count = None, 0
+        self._gv = None
         self.learn_y0 = bool(s.learn_Y_0)
         if self.learn_y0:
             self.y0_param = s.y_0.Y_0
@@ -417,6 +469,96 @@ class DenseNativePlan:
         assert idx.numel() == self.Pset, (idx.numel(), self.Pset)
         return idx
 
+    # ---- gradient-variance diagnostic ---------------------------------------------------------------------------------------
+    def begin_gradient_log(self, L):
+        """Called by Solver._train_native before the first iteration: one device slot per logged iteration."""
+        m = int(self.s.compute_gradient_variance)
+        self.gv_count = 0
+        self.gv_log = torch.zeros((L + m - 1) // m, dtype=torch.float32, device=self.dev) if m > 0 else None
+
+    def _gv_buffers(self):
+        if self._gv is None:
+            reason = gradient_variance_unsupported(self.s, (self.d_pad, self.H_pad), self.world)
+            if reason is None and not self.kernel_bwd:
+                reason = 'the native gradient moments run on the hand-written DenseNet-control backward'
+            if reason is not None:
+                raise PlanUnsupported(reason)
+            N, f32, dev = self.s.N, torch.float32, self.dev
+            g = dict(part=[torch.zeros_like(self.partial) for _ in range(4)],
+                     mean=torch.zeros(N, self.Pset, dtype=f32, device=dev), var=torch.zeros(N, self.Pset, dtype=f32, device=dev),
+                     rel=torch.zeros(N, self.Pset, dtype=f32, device=dev), step_sums=torch.zeros(N, dtype=torch.float64, device=dev),
+                     csums=torch.zeros(2, dtype=torch.float64, device=dev), scalar=torch.zeros(1, dtype=f32, device=dev),
+                     ones=torch.ones(self.K_local, dtype=f32, device=dev))
+            if self.attached:
+                g.update(snap=torch.empty_like(self.images), Gg=torch.zeros(N, self.Pset, dtype=f32, device=dev),
+                         one=torch.ones(self.K_local, dtype=f32, device=dev), zero=torch.zeros(self.K_local, dtype=f32, device=dev),
+                         e0=torch.zeros(self.K_local, dtype=f32, device=dev))
+                g['e0'][0] = 1.0                              # global trajectory 0 (single rank: k_offset = 0)
+            if self._gidx is None:
+                self._gidx = self._gather_index()
+            self._gv = g
+        return self._gv
+
+    def _gv_launch(self, name, w, partial):
+        self.wpad[:self.K_local].copy_(w)
+        nat.check(getattr(self.lib, name)(C.byref(self.cfg), nat.ptr(self.flat), nat.ptr(self.images), nat.ptr(self.wpad),
+                                          nat.ptr(partial), nat.stream_ptr(self.dev)), name)
+
+    def _gv_sweep(self, mu, wT):
+        nat.check(self.lib.psp_dnet_adjoint_sweep(C.byref(self.cfg), nat.ptr(self.flat), nat.ptr(self.images), nat.ptr(self.XN_k),
+                                                  nat.ptr(mu), None, nat.ptr(wT), nat.ptr(self.tables), nat.stream_ptr(self.dev)),
+                  'psp_dnet_adjoint_sweep')
+
+    def gradient_moments(self, out=None):
+        """The reference's get_gradient_variances (solver.py:234-281) from sums over the trajectories instead of 2 K N backward
+        passes.  Call after the forward of an iteration (self.D, self.sums, the images).  With G_k = dY_N[k] / dtheta_n (rank one per
+        layer), S[c] = sum_k c_k G_k (hjbd_bwd_kernel, w = c) and Q[c] = sum_k c_k^2 G_k o G_k (hjbd_bwd_kernel<.., SQ>, w = c):
+            moment,       c = r:           sum f = 2 (S[r] - Gg sum r)        sum f^2 = 4 (Q[r] - 2 Gg S[r^2] + Gg^2 sum r^2)
+            log-variance, s = r - mean r:  sum f = 2 (S[s] - Gbar sum s)      sum f^2 = 4 (Q[s] - 2 Gbar S[s^2] + Gbar^2 sum s^2),  Gbar = S[1] / K
+        (Gg cancels for log-variance).  Images: non-adaptive -- the forward's image is dY_k / dZ_n / sqrt(dt) already; attached -- the
+        images are snapshotted, one adjoint sweep with mu = 1 and an explicit wT = 0 (NULL would mean nu - mu, i.e. Y - g) turns the xi
+        slot into the G images, a second sweep from the restored snapshot with mu = 0, wT = e_0 gives Gg (the reference differentiates
+        g at trajectory 0 for every k), and the snapshot is restored before the training sweep, whose gradient is therefore
+        bit-identical to a run without the diagnostic.  psp_gradvar_finish reduces the slices and combines in double; results in
+        self.gv_mean / gv_var / gv_rel (N, Pset), the scalar mean(rel) into `out` (a 1-element device tensor).  No host sync."""
+        s, g = self.s, self._gv_buffers()
+        K = float(s.K)
+        moment = s.loss_method == 'moment'
+        r = self.D
+        c = r if moment else r - (self.sums[0] / K).to(r.dtype)
+        cd = c.double()
+        g['csums'][0], g['csums'][1] = cd.sum(), (cd * cd).sum()
+        pS, pQ, pS2, pS1 = g['part']
+        Gg = None
+        if self.attached:
+            g['snap'].copy_(self.images)
+            if moment:
+                self._gv_sweep(g['zero'], g['e0'])
+                self._gv_launch('psp_dnet_rollout_bwd', g['ones'], pS)
+                torch.index_select(pS.view(s.N, self.slices, self.PP).sum(1), 1, self._gidx, out=g['Gg'])
+                Gg = g['Gg']
+                self.images.copy_(g['snap'])
+            self._gv_sweep(g['one'], g['zero'])
+        self._gv_launch('psp_dnet_rollout_bwd', c, pS)
+        self._gv_launch('psp_dnet_rollout_bwd_sq', c, pQ)
+        need_S2 = (not moment) or Gg is not None
+        if need_S2:
+            self._gv_launch('psp_dnet_rollout_bwd', c * c, pS2)
+        if not moment:
+            self._gv_launch('psp_dnet_rollout_bwd', g['ones'], pS1)
+        if self.attached:
+            self.images.copy_(g['snap'])
+        nat.check(self.lib.psp_gradvar_finish(nat.ptr(pS), nat.ptr(pQ), nat.ptr(pS2) if need_S2 else None,
+                                              nat.ptr(pS1) if not moment else None, nat.ptr(Gg), nat.ptr(self._gidx), s.N, self.slices,
+                                              self.PP, self.Pset, s.K, nat.LOSS_MOMENT if moment else nat.LOSS_LOG_VARIANCE,
+                                              nat.ptr(g['csums']), nat.ptr(g['mean']), nat.ptr(g['var']), nat.ptr(g['rel']),
+                                              nat.ptr(g['step_sums']), nat.ptr(g['scalar']), nat.stream_ptr(self.dev)),
+                  'psp_gradvar_finish')
+        self.gv_mean, self.gv_var, self.gv_rel = g['mean'], g['var'], g['rel']
+        if out is not None:
+            out.copy_(g['scalar'])
+        return g['scalar']
+
     def _gradient(self, w):
         if self.kernel_bwd:
             return self._gradient_kernel(w)
@@ -504,6 +646,12 @@ class DenseNativePlan:
             ul2_out[l:l + 1] = m
         if ev is not None:
             ev[2].record()
+        m_gv = int(s.compute_gradient_variance)
+        if m_gv > 0 and l % m_gv == 0:                            # solver.py:496-497: before the gradient step
+            if self.gv_log is None or self.gv_count >= self.gv_log.numel():
+                self.begin_gradient_log(max(int(s.L), l + 1))
+            self.gradient_moments(out=self.gv_log[self.gv_count:self.gv_count + 1])
+            self.gv_count += 1
         if self.attached:
             # per-trajectory weights mu = dL/dY_N, nu = dL/dZsum_N (global K and global mean: rank-independent), as in
             # plan_native.py; the sweep leaves dL/dZ_n / sqrt(dt) in the xi slot of the images

@@ -271,6 +271,53 @@ class Solver:
         self.optimization_step()
         return loss
 
+    # ---- per-sample gradient moments (solver.py:225-281) --------------------------------------
+    def flatten_gradient(self, k, grads, grads_flat):
+        """Row k of ``grads_flat`` <- the tensors of ``grads`` flattened one after the other; returns ``grads_flat``."""
+        grads = [g.reshape(-1) for g in grads]
+        if grads:
+            row = torch.cat(grads)
+            grads_flat[k, :row.numel()] = row
+        return grads_flat
+
+    def get_gradient_variances(self, X, Y):
+        """The reference's gradient-variance diagnostic, composite plan: for every net n of ``z_n`` the per-trajectory loss
+        gradients f_k (K rows of p entries), their mean and unbiased variance over k, and sqrt(var) / mean with NaN -> 0 (inf and
+        negative values stay).  Returns the (N, p) matrix; train() logs its mean.  Two quirks of the reference are kept: the
+        terminal-cost gradient is taken at trajectory 0 for every k, and the nets other than z_n[n] are ignored.
+        Deliberate difference: the (K, p) work tensors live on self.device (the reference's are CPU tensors, which makes its own
+        assignments fail on a GPU run).  adaptive_forward_process with detach_forward=True raises autograd's RuntimeError, as in
+        the reference (g(X_N) does not depend on the parameters there)."""
+        if self.approx_method != 'control' or self.time_approx != 'outer':
+            raise NotImplementedError("compute_gradient_variance needs a control net per time step (time_approx='outer'), "
+                                      "as in the reference")
+        if self.loss_method not in ('moment', 'log-variance'):
+            raise NotImplementedError("compute_gradient_variance is defined for loss_method 'moment' and 'log-variance' only "
+                                      "(the reference fails on %r)" % self.loss_method)
+        dev = self.device
+        grads_mean = torch.zeros(self.N, self.p, device=dev)
+        grads_var = torch.zeros(self.N, self.p, device=dev)
+        resid = (Y - self.g(X)).detach().unsqueeze(1)
+        for n in range(self.N):
+            theta = [q for q in self.z_n[n].parameters() if q.requires_grad]
+            G = torch.zeros(self.K, self.p, device=dev)
+            for k in range(self.K):
+                gk = torch.autograd.grad(Y[k], theta, retain_graph=True, allow_unused=True)
+                G = self.flatten_gradient(k, [g for g in gk if g is not None], G)
+            if self.adaptive_forward_process:
+                g0 = torch.autograd.grad(self.g(X[0, :].unsqueeze(0)).sum(), theta, retain_graph=True, allow_unused=True)
+                row = self.flatten_gradient(0, [g for g in g0 if g is not None], torch.zeros(1, self.p, device=dev))
+                G = G - row                    # row 0 for every k
+            if self.loss_method == 'moment':
+                f = 2 * resid * G
+            else:
+                f = 2 * (resid - resid.mean(0, keepdim=True)) * (G - G.mean(0, keepdim=True))
+            grads_mean[n, :] = f.mean(0)
+            grads_var[n, :] = f.var(0)
+        rel = torch.sqrt(grads_var) / grads_mean
+        rel[rel != rel] = 0
+        return rel
+
     def initialize_training_data(self):
         """Initial state, accumulators and the iteration's Brownian increments drawn on the CPU
         generator and moved to the device (solver.py:364-382)."""
@@ -399,6 +446,9 @@ class Solver:
         ul2 = torch.zeros(self.L, dtype=torch.float32, device=self.device) if self.u_l2_error_flag else None
         y0_hist = torch.zeros(self.L, dtype=torch.float32, device=self.device) if self.learn_Y_0 else None
         done = 0
+        gv_done = 0
+        if self.compute_gradient_variance > 0 and hasattr(plan, 'begin_gradient_log'):
+            plan.begin_gradient_log(self.L)          # mean(sqrt(var) / mean) of the per-sample gradients, one device slot per logged l
         t_block = time.time()
         for l in range(self.L):
             if self.learn_Y_0:
@@ -423,6 +473,9 @@ class Solver:
                 self.times += [per] * len(vals)
                 if self.learn_Y_0:
                     self.Y_0_log += y0_hist[done:l + 1].cpu().tolist()
+                if getattr(plan, 'gv_count', 0) > gv_done:          # read back with the block: no sync of its own
+                    self.grads_rel_error_log += plan.gv_log[gv_done:plan.gv_count].cpu().tolist()
+                    gv_done = plan.gv_count
                 done, t_block = l + 1, now
                 if self.verbose and l % self.print_every == 0:
                     msg = '%d - loss: %.4e - u L2: %.4e - time/iter: %.4fs' % (l, self.loss_log[-1], self.u_L2_loss[-1], per)
@@ -445,8 +498,6 @@ class Solver:
         if self.approx_method == 'value_function' and self.time_approx != 'inner':
             # the reference itself fails here: Y_n(X, n) turns the STEP index into ceil(n / delta_t) (solver.py:342-345)
             raise NotImplementedError("approx_method='value_function' needs time_approx='inner' (as in the reference)")
-        if self.compute_gradient_variance > 0:
-            raise NotImplementedError('per-sample gradient-variance diagnostics are not implemented')
         if self.loss_method == 'log-variance-repa':
             # the reference alternates per iteration between a FROZEN copy of the control in Z (even l) and a detached drift (odd
             # l), solver.py:444-447, 468-469; only the sign flip of its loss (:169-170) is restated here, so refuse rather than
@@ -492,6 +543,8 @@ class Solver:
                 if self.u_l2_error_flag:
                     ref = torch.tensor(self.u_true(X.cpu().detach(), n * self.delta_t_np)).t().float().to(dev)
                     u_L2 = u_L2 + torch.sum((-Z - ref) ** 2 * dt, 1)
+            if self.compute_gradient_variance > 0 and l % self.compute_gradient_variance == 0:      # solver.py:496-497
+                self.grads_rel_error_log.append(torch.mean(self.get_gradient_variances(X, Y)).item())
             loss = self.gradient_descent(X, Y, Z_sum, l, extra.mean())
             if self.log_gradient:
                 flat = torch.cat([q.grad.reshape(-1) for q in self.z_n.parameters() if q.grad is not None])
