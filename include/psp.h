@@ -968,11 +968,12 @@ typedef struct psp_pinn_config {
     int32_t linear_layout;    /* 0: weights stored (in, out) (DenseNet); 1: (out, in) (nn.Linear, DenseNet_tanh)                */
     int32_t drift_kind;       /* PSP_DRIFT_ZERO, PSP_DRIFT_DIAG or PSP_DRIFT_DOUBLE_WELL                                       */
     int32_t h_kind;           /* PSP_GH_ZERO .. PSP_GH_EXPBALL_SIN_FULL, as psp_gen_config.h_kind; h must not read t
-                               * (h_par[3] = 0); PSP_GH_EXPBALL_SIN_FULL on either sigma_kind; no PSP_GH_QUAD with _DENSE       */
+                               * (h_par[3] = 0; psp_pinn_pairs_* below take one that does); PSP_GH_EXPBALL_SIN_FULL on either
+                               * sigma_kind; no PSP_GH_QUAD with _DENSE                                                          */
     int32_t sigma_kind;       /* PSP_GENL_SIGMA_SCALED: sigma = s I, the Laplacian; PSP_GENL_SIGMA_DENSE: the table `dirs`       */
     int32_t n_dirs;           /* PSP_GENL_SIGMA_DENSE: rows of `dirs`, 1 .. d; ignored with _SCALED                             */
     float sigma_scale;        /* s (PSP_GENL_SIGMA_SCALED)                                                                      */
-    float h_par[4];           /* PSP_GH_EXPBALL_*: al, d, e, tau (= 0)                                                         */
+    float h_par[4];           /* PSP_GH_EXPBALL_*: al, d, e, tau (= 0; any tau in psp_pinn_pairs_*)                            */
     float reserved_f;
     const float* drift;       /* DOUBLE_WELL: kappa (d); DIAG: a (d); DEVICE; else NULL                                         */
     const float* dirs;        /* PSP_GENL_SIGMA_DENSE: (n_dirs, d) row-major, fp32, DEVICE; NULL there is -4; else ignored      */
@@ -1010,6 +1011,39 @@ int psp_pinn_backward(const psp_pinn_config* cfg, const float* params, const flo
                       const float* rbar, float* grad_partial, float* grad_out, void* stream);
 /* sizeof(psp_pinn_config), sizeof(psp_pinn_sizes). */
 int psp_abi_struct_sizes5(int32_t out[2]);
+
+/* ------------------------------------------------------------------------------------------------
+ * PINN loss with an h that reads t (appended in 0.4.0, no version bump; csrc/pinn_kernels.h): the reference hands h the times
+ * as a (K, 1) column (solver.py:1284-1285), so for PSP_GH_EXPBALL_SQ / PSP_GH_EXPBALL_SIN with tau = h_par[3] != 0 the residual
+ * is a (K, K) matrix over (time i, sample j) and the loss its mean square:
+ *     R[i, j] = A_j + nl(exp(2 al |x_j|^2 + 2 tau t_i) - y_j^2)       nl = identity (_SQ) or sin (_SIN), y_j = V(x_j, t_j)
+ *     A_j     = dV/dt_j + s^2/2 Laplace_x V_j + b . grad_x V_j - y_j lin_j,    lin_j = 2 al (2 al |x_j|^2 + dd) + e
+ *     loss    = alpha0 / K^2 sum_ij R[i, j]^2
+ * Everything that passes through the net is per sample, so the gradient is sum_j (rho_j dA_j/dtheta + nu_j dy_j/dtheta) with
+ *     rho_j = 2 alpha0 / K^2 sum_i R[i, j],      nu_j = 2 alpha0 / K^2 sum_i R[i, j] nl'(arg_ij) (-2 y_j):
+ *     psp_pinn_pairs_residual -> psp_pinn_pairs_reduce -> psp_pinn_pairs_backward(rbar = rho, vadd = nu) -> psp_adam_step
+ * Nothing is read on the host.  Every sum has a fixed order (lane partials over i, a butterfly over the 64 lanes, the K
+ * per-sample sums of squares in index order in double; no atomics): the same bits on every run.
+ * psp_pinn_config and psp_pinn_sizes are the ones above, the scratch has the same layout and size; its dR/dV slot holds
+ * dA/dV = -lin_j.  The three entry points above keep refusing h_par[3] != 0; these take any tau, and with tau = 0 every h_kind
+ * (R[i, j] = R_j then, and psp_pinn_pairs_backward with vadd = NULL is psp_pinn_backward).
+ * Limits beyond those of psp_pinn_query (-1): has_time = 1, PSP_GENL_SIGMA_SCALED, tau != 0 only with _SQ / _SIN, and
+ * K <= 16384 -- a condition, not a measurement: the pair kernel visits K^2 <= 2.7e8 pairs per call and stages the K times in
+ * 4 K <= 64 KiB of LDS (the reference materialises the (K, K) matrix).
+ * ------------------------------------------------------------------------------------------------ */
+/* Every check and the sizes without a launch (no GPU needed); pair_work_bytes_out: the buffer psp_pinn_pairs_reduce needs. */
+int psp_pinn_pairs_query(const psp_pinn_config* cfg, psp_pinn_sizes* sizes_out, int64_t* pair_work_bytes_out);
+/* x (K, d), t (K) -> A_out (K), the residual without its pair term; `scratch`: psp_pinn_sizes.scratch_bytes. */
+int psp_pinn_pairs_residual(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, float* scratch,
+                            float* A_out, void* stream);
+/* The K x K pairs of the SAME cfg / x / t / scratch / A as the psp_pinn_pairs_residual call before it -> loss_out (1 float),
+ * rho_out (K), nu_out (K), all DEVICE; pair_work: pair_work_bytes of psp_pinn_pairs_query. */
+int psp_pinn_pairs_reduce(const psp_pinn_config* cfg, const float* x, const float* t, const float* scratch, const float* A,
+                          float alpha0, void* pair_work, float* loss_out, float* rho_out, float* nu_out, void* stream);
+/* grad_out (n_params) = sum_j (rbar_j dA_j/dtheta + vadd_j dy_j/dtheta); vadd (K) may be NULL (= 0).  grad_partial as in
+ * psp_pinn_backward. */
+int psp_pinn_pairs_backward(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, const float* scratch,
+                            const float* rbar, const float* vadd, float* grad_partial, float* grad_out, void* stream);
 
 /* Diagnostics: device buffer that receives per-wave phase cycle sums (8 u64 per wave of the
  * backward kernel).  Returns 1 if the library was built with -DPSP_STAMPS (diagnostic build,

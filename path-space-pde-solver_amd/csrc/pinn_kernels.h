@@ -25,6 +25,17 @@
 // Every matrix product is fp32 MFMA; the activations sit in LDS row-major with a stride = 4 (mod 64) floats, which spreads the
 // A-operand read (16 rows x 4 k) over all banks.  Weights are read from global memory (L2) through (k, column) strides, so the
 // (in, out) layout of DenseNet and the (out, in) layout of nn.Linear need no copy.
+//
+// An h that reads t (psp_pinn_pairs_*): the reference hands h the times as a (K, 1) column, so the residual is the (K, K) matrix
+//     R[i, j] = A_j + nl(exp(2 al |x_j|^2 + 2 tau t_i) - y_j^2)         i: times, j: samples, y_j = V(x_j, t_j)
+// and the loss is alpha0 / K^2 sum_ij R[i, j]^2.  Everything that passes through the net is per sample j:
+//   pinn_finish_kernel<true>   writes A_j (the residual without the pair term) where R goes, dA/dV = -lin_j in the dR/dV slot
+//   pinn_pair_kernel           one wave per sample j, the lanes over the times i (staged once per workgroup in LDS): lane partials of
+//                              sum_i R, sum_i R^2, sum_i R nl' in i order, a butterfly over the lanes, then
+//                              rho_j = c sum_i R, nu_j = c (-2 y_j) sum_i R nl', c = 2 alpha0 / K^2, and sum_i R^2 in double -> work[j]
+//   pinn_pair_loss_kernel      one wave: lane l adds its run of work[j] in index order in double, lane 0 adds the 64 runs in lane
+//                              order: loss = alpha0 / K^2 sum.  No atomics anywhere: the same bits on every run.
+//   pinn_backward_kernel<true> rbar = rho, and nu_j added to the value row's seed of sample j (direction block 0)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,13 +77,34 @@ struct PinnArgs {
     float* R;                          // (K) residual
     const float* rbar;                 // (K) dLoss/dR
     float* gpart;                      // (G, P)
+    int pairs;                         // psp_pinn_pairs_*: the finish kernel leaves the pair term of h out
+    const float* vadd;                 // (K) added to the value-row seed, or null
 };
+
+struct PinnPairArgs {
+    int d, K, h_kind;
+    float al, tau2;                    // h_par[0], 2 h_par[3]
+    float coef;                        // 2 alpha0 / K^2
+    double loss_coef;                  // alpha0 / K^2
+    const float* x;                    // (K, d)
+    const float* t;                    // (K)
+    const float* V;                    // (K) of the scratch
+    const float* A;                    // (K) of pinn_finish_kernel<true>
+    float* rho;                        // (K)
+    float* nu;                         // (K)
+    double* work;                      // (K) sum_i R[i, j]^2
+    float* loss;                       // (1)
+};
+
+constexpr int kPinnPairMaxK = 16384;   // K^2 <= 2.7e8 pairs; the staged times take 4 K <= 64 KiB of LDS
+constexpr int kPinnPairMaxWg = 1024;
 
 inline int pinn_row_stride(int tot) { int a = (tot + 3) & ~3; while ((a & 63) != 4) a += 4; return a; }
 inline int pinn_lds_bytes(int ast, int L, bool backward) { return 4 * ((backward ? 2 : 1) * 16 * ast + L * 16 * kPinnZS + 64 + 16 + 16); }
 
 hipError_t pinn_launch_forward(const PinnArgs& a, int lds_bytes, hipStream_t stream);
 hipError_t pinn_launch_backward(const PinnArgs& a, int lds_bytes, hipStream_t stream);
+hipError_t pinn_launch_pairs(const PinnPairArgs& a, hipStream_t stream);
 
 #ifdef PSP_PINN_KERNELS
 
@@ -202,7 +234,9 @@ __global__ __launch_bounds__(kPinnThreads) void pinn_forward_kernel(const PinnAr
     }
 }
 
-// One thread per sample: the residual and what the adjoint is seeded with.
+// One thread per sample: the residual and what the adjoint is seeded with.  kPairs: without the pair term nl(..) of
+// PINN_H_EXP_SQ / PINN_H_EXP_SIN, which pinn_pair_kernel adds per (time, sample).
+template <bool kPairs>
 __global__ void pinn_finish_kernel(const PinnArgs a) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.K) return;
@@ -234,7 +268,7 @@ __global__ void pinn_finish_kernel(const PinnArgs a) {
         const float rl = a.h_kind == PINN_H_EXP_SIN_FULL ? sx * sx : rr;    // the exponent keeps |x|^2
         const float lin = 2.0f * al * (2.0f * al * rl + a.h_par[1]) + a.h_par[2];
         float nl = 0.f, nly = 0.f;
-        if (a.h_kind != PINN_H_EXP_LIN) {
+        if (a.h_kind != PINN_H_EXP_LIN && !(kPairs && (a.h_kind == PINN_H_EXP_SQ || a.h_kind == PINN_H_EXP_SIN))) {
             const float arg = expf(2.0f * al * rr) - y * y;
             if (a.h_kind == PINN_H_EXP_SQ) { nl = arg; nly = -2.0f * y; }
             else { nl = sinf(arg); nly = -2.0f * y * cosf(arg); }
@@ -248,6 +282,8 @@ __global__ void pinn_finish_kernel(const PinnArgs a) {
     a.cV[k] = hy;
 }
 
+// kVadd: a.vadd[k] joins the value-row seed of sample k (its direction block 0).
+template <bool kVadd>
 __global__ __launch_bounds__(kPinnThreads) void pinn_backward_kernel(const PinnArgs a) {
     extern __shared__ float pinn_lds[];
     float* Act = pinn_lds;
@@ -265,7 +301,10 @@ __global__ __launch_bounds__(kPinnThreads) void pinn_backward_kernel(const PinnA
         if (tid < 16) {                                            // dLoss / d(V, Lap V, V'_j) of this tile's rows
             const float rb = a.rbar[k];
             float v;
-            if (tid == 0) v = blk == 0 ? rb * a.cV[k] : 0.f;       // the value itself enters R once per sample
+            if (tid == 0) {                                        // the value itself enters R once per sample
+                v = blk == 0 ? rb * a.cV[k] : 0.f;
+                if (kVadd && blk == 0) v += a.vadd[k];
+            }
             else if (tid == 1) v = a.lap_coef * rb;
             else {
                 const int j = blk * kPinnDirs + tid - 2;
@@ -361,6 +400,61 @@ __global__ __launch_bounds__(kPinnThreads) void pinn_backward_kernel(const PinnA
             }
             __syncthreads();
         }
+    }
+}
+
+// The (K, K) part of an h that reads t.  Wave w of workgroup g takes the samples j = 4 g + w, + 4 gridDim.x, ..
+__global__ __launch_bounds__(kPinnThreads) void pinn_pair_kernel(const PinnPairArgs a) {
+    extern __shared__ float pinn_lds[];                            // 2 tau t_i, i < K
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, K = a.K, d = a.d;
+    for (int i = tid; i < K; i += kPinnThreads) pinn_lds[i] = a.tau2 * a.t[i];
+    __syncthreads();
+    const bool sq = a.h_kind == PINN_H_EXP_SQ, pair = sq || a.h_kind == PINN_H_EXP_SIN;
+    for (int j = blockIdx.x * 4 + wave; j < K; j += gridDim.x * 4) {
+        const float* x = a.x + (size_t)j * d;
+        float rr = 0.f;
+        for (int c = 0; c < d; ++c) rr = fmaf(x[c], x[c], rr);
+        const float ex = 2.0f * a.al * rr, y = a.V[j], y2 = y * y, Aj = a.A[j];
+        float sR = 0.f, sD = 0.f, sQ = 0.f;
+        for (int i = lane; i < K; i += 64) {
+            float R = Aj, dn = 0.f;
+            if (pair) {
+                const float arg = expf(ex + pinn_lds[i]) - y2;     // one exponential of the sum, as the reference takes it
+                if (sq) { R += arg; dn = 1.f; }
+                else { R += sinf(arg); dn = cosf(arg); }
+            }
+            sR += R;
+            sQ = fmaf(R, R, sQ);
+            sD = fmaf(R, dn, sD);
+        }
+        double q = (double)sQ;
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            sR += __shfl_xor(sR, m, 64);
+            sD += __shfl_xor(sD, m, 64);
+            q += __shfl_xor(q, m, 64);
+        }
+        if (lane == 0) {
+            a.rho[j] = a.coef * sR;
+            a.nu[j] = a.coef * (-2.0f * y) * sD;
+            a.work[j] = q;
+        }
+    }
+}
+
+// One wave: the K per-sample sums of squares in index order, in double.
+__global__ void pinn_pair_loss_kernel(const PinnPairArgs a) {
+    __shared__ double part[64];
+    const int lane = threadIdx.x, per = (a.K + 63) / 64;
+    const int lo = lane * per, hi = lo + per < a.K ? lo + per : a.K;
+    double s = 0.0;
+    for (int j = lo; j < hi; ++j) s += a.work[j];
+    part[lane] = s;
+    __syncthreads();
+    if (lane == 0) {
+        double tot = 0.0;
+        for (int l = 0; l < 64; ++l) tot += part[l];
+        a.loss[0] = (float)(a.loss_coef * tot);
     }
 }
 

@@ -2011,14 +2011,17 @@ int psp_hjb_control_eval(int32_t d, int32_t H, const float* params, const float*
 // ---- the PINN loss (pinn_kernels.h) ---------------------------------------------------------------------------------------
 namespace {
 struct PinnPlan { psp::PinnArgs a; int lds_fwd, lds_bwd; int64_t scratch_floats; };
-// every check of a psp_pinn_config (the three entry points share it) and the launch geometry
-int make_pinn_plan(const psp_pinn_config* c, PinnPlan* p) {
+// every check of a psp_pinn_config (the three entry points share it) and the launch geometry; `pairs`: the psp_pinn_pairs_* entry
+// points, which take an h that reads t
+int make_pinn_plan(const psp_pinn_config* c, PinnPlan* p, bool pairs = false) {
     if (!c) return fail(-1, "null config");
     if (c->d <= 0 || c->K <= 0) return fail(-1, "psp_pinn: d and K must be positive");
     if (c->has_time != 0 && c->has_time != 1) return fail(-1, "psp_pinn: has_time must be 0 or 1");
     if (c->sigma_kind != PSP_GENL_SIGMA_SCALED && c->sigma_kind != PSP_GENL_SIGMA_DENSE)
         return fail(-1, "psp_pinn: sigma_kind out of range");
     const bool dense = c->sigma_kind == PSP_GENL_SIGMA_DENSE;
+    if (pairs && !c->has_time) return fail(-1, "psp_pinn_pairs: the (K, K) residual needs a time input (has_time = 1)");
+    if (pairs && dense) return fail(-1, "psp_pinn_pairs: a dense sigma is not built with an h that reads t");
     if (dense && !c->dirs) return fail(-4, "psp_pinn: a dense sigma needs its direction table (dirs)");
     if (dense && (c->n_dirs < 1 || c->n_dirs > c->d)) return fail(-1, "psp_pinn: n_dirs must lie in 1 .. d");
     if (c->n_hidden < 1 || c->n_hidden > 4) return fail(-2, "psp_pinn: 1 to 4 hidden layers");
@@ -2032,7 +2035,12 @@ int make_pinn_plan(const psp_pinn_config* c, PinnPlan* p) {
         return fail(-1, "psp_pinn: drift_kind must be PSP_DRIFT_ZERO, _DIAG or _DOUBLE_WELL");
     if (c->drift_kind != PSP_DRIFT_ZERO && !c->drift) return fail(-1, "psp_pinn: this drift_kind needs the drift vector");
     if (c->h_kind < PSP_GH_ZERO || c->h_kind > PSP_GH_EXPBALL_SIN_FULL) return fail(-1, "psp_pinn: h_kind out of range");
-    if (c->h_kind >= PSP_GH_EXPBALL_LIN && c->h_par[3] != 0.f) return fail(-1, "psp_pinn: an h that reads t is not built");
+    if (!pairs && c->h_kind >= PSP_GH_EXPBALL_LIN && c->h_par[3] != 0.f) return fail(-1, "psp_pinn: an h that reads t is not built");
+    if (pairs) {
+        if (c->h_kind >= PSP_GH_EXPBALL_LIN && c->h_par[3] != 0.f && c->h_kind != PSP_GH_EXPBALL_SQ && c->h_kind != PSP_GH_EXPBALL_SIN)
+            return fail(-1, "psp_pinn_pairs: only PSP_GH_EXPBALL_SQ and PSP_GH_EXPBALL_SIN read t (h_par[3] != 0)");
+        if (c->K > psp::kPinnPairMaxK) return fail(-1, "psp_pinn_pairs: K above 16384 (K^2 pairs per iteration)");
+    }
     if (dense && c->h_kind == PSP_GH_QUAD) return fail(-1, "psp_pinn: an h that reads z = B grad V is not built for dense directions");
     // the gradient directions are dropped where nothing reads grad V: no drift, no time input, an h that does not read z
     const int n_hess = dense ? c->n_dirs : 0;
@@ -2066,6 +2074,7 @@ int make_pinn_plan(const psp_pinn_config* c, PinnPlan* p) {
     a.drift_kind = c->drift_kind; a.h_kind = c->h_kind; a.s = c->sigma_scale;
     for (int i = 0; i < 4; ++i) a.h_par[i] = c->h_par[i];
     a.drift = c->drift;
+    a.pairs = pairs ? 1 : 0;
     p->lds_fwd = psp::pinn_lds_bytes(a.AST, a.L, false);
     p->lds_bwd = psp::pinn_lds_bytes(a.AST, a.L, true);
     if (p->lds_bwd > kMaxLds) return fail(-3, "psp_pinn: the activation images exceed the LDS");
@@ -2076,6 +2085,16 @@ void pinn_scratch(PinnPlan* p, float* scratch) {
     psp::PinnArgs& a = p->a;
     const size_t K = (size_t)a.K;
     a.V = scratch; a.lap = a.V + K; a.gradV = a.lap + K * a.nblk; a.cV = a.gradV + K * a.n_grad; a.cG = a.cV + K;
+}
+int pinn_fill_sizes(const PinnPlan& p, psp_pinn_sizes* out) {
+    if (!out) return fail(-1, "null output");
+    memset(out, 0, sizeof(*out));
+    out->n_params = p.a.P;
+    out->scratch_bytes = p.scratch_floats * 4;
+    out->grad_partial_bytes = (int64_t)p.a.G * p.a.P * 4;
+    out->dir_blocks = p.a.nblk; out->tiles = p.a.ntiles; out->bwd_workgroups = p.a.G;
+    out->lds_fwd_bytes = p.lds_fwd; out->lds_bwd_bytes = p.lds_bwd;
+    return 0;
 }
 }  // namespace
 
@@ -2089,14 +2108,7 @@ int psp_pinn_query(const psp_pinn_config* cfg, psp_pinn_sizes* out) {
     PinnPlan p;
     const int rc = make_pinn_plan(cfg, &p);
     if (rc) return rc;
-    if (!out) return fail(-1, "null output");
-    memset(out, 0, sizeof(*out));
-    out->n_params = p.a.P;
-    out->scratch_bytes = p.scratch_floats * 4;
-    out->grad_partial_bytes = (int64_t)p.a.G * p.a.P * 4;
-    out->dir_blocks = p.a.nblk; out->tiles = p.a.ntiles; out->bwd_workgroups = p.a.G;
-    out->lds_fwd_bytes = p.lds_fwd; out->lds_bwd_bytes = p.lds_bwd;
-    return 0;
+    return pinn_fill_sizes(p, out);
 }
 
 int psp_pinn_residual(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, float* scratch,
@@ -2122,6 +2134,66 @@ int psp_pinn_backward(const psp_pinn_config* cfg, const float* params, const flo
     if (cfg->has_time && !t) return fail(-1, "psp_pinn_backward: a net with a time input needs t");
     pinn_scratch(&p, const_cast<float*>(scratch));
     p.a.params = params; p.a.x = x; p.a.t = t; p.a.rbar = rbar; p.a.gpart = grad_partial;
+    const hipError_t e = psp::pinn_launch_backward(p.a, p.lds_bwd, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "pinn_backward_kernel launch");
+    return PSP_LAUNCH(reduce_grad_kernel, dim3((p.a.P + 31) / 32), dim3(256), 0, stream, grad_partial, p.a.G, p.a.P, grad_out);
+}
+
+// ---- the (K, K) residual of an h that reads t (pinn_kernels.h) ---------------------------------------------------------------
+int psp_pinn_pairs_query(const psp_pinn_config* cfg, psp_pinn_sizes* sizes_out, int64_t* pair_work_bytes_out) {
+    PinnPlan p;
+    const int rc = make_pinn_plan(cfg, &p, true);
+    if (rc) return rc;
+    if (!sizes_out || !pair_work_bytes_out) return fail(-1, "null output");
+    const int rc2 = pinn_fill_sizes(p, sizes_out);
+    if (rc2) return rc2;
+    *pair_work_bytes_out = (int64_t)p.a.K * (int64_t)sizeof(double);
+    return 0;
+}
+
+int psp_pinn_pairs_residual(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, float* scratch,
+                            float* A_out, void* stream) {
+    PinnPlan p;
+    const int rc = make_pinn_plan(cfg, &p, true);
+    if (rc) return rc;
+    if (!params || !x || !t || !scratch || !A_out) return fail(-1, "null buffer passed to psp_pinn_pairs_residual");
+    pinn_scratch(&p, scratch);
+    p.a.params = params; p.a.x = x; p.a.t = t; p.a.R = A_out;
+    const hipError_t e = psp::pinn_launch_forward(p.a, p.lds_fwd, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "pinn_forward_kernel launch");
+    return 0;
+}
+
+int psp_pinn_pairs_reduce(const psp_pinn_config* cfg, const float* x, const float* t, const float* scratch, const float* A,
+                          float alpha0, void* pair_work, float* loss_out, float* rho_out, float* nu_out, void* stream) {
+    PinnPlan p;
+    const int rc = make_pinn_plan(cfg, &p, true);
+    if (rc) return rc;
+    if (!x || !t || !scratch || !A || !pair_work || !loss_out || !rho_out || !nu_out)
+        return fail(-1, "null buffer passed to psp_pinn_pairs_reduce");
+    pinn_scratch(&p, const_cast<float*>(scratch));
+    psp::PinnPairArgs a;
+    memset(&a, 0, sizeof(a));
+    const double K2 = (double)cfg->K * (double)cfg->K;
+    a.d = cfg->d; a.K = cfg->K; a.h_kind = cfg->h_kind;
+    a.al = cfg->h_par[0]; a.tau2 = 2.0f * cfg->h_par[3];
+    a.coef = (float)(2.0 * (double)alpha0 / K2); a.loss_coef = (double)alpha0 / K2;
+    a.x = x; a.t = t; a.V = p.a.V; a.A = A;
+    a.rho = rho_out; a.nu = nu_out; a.work = static_cast<double*>(pair_work); a.loss = loss_out;
+    const hipError_t e = psp::pinn_launch_pairs(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "pinn_pair_kernel launch");
+    return 0;
+}
+
+int psp_pinn_pairs_backward(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, const float* scratch,
+                            const float* rbar, const float* vadd, float* grad_partial, float* grad_out, void* stream) {
+    PinnPlan p;
+    const int rc = make_pinn_plan(cfg, &p, true);
+    if (rc) return rc;
+    if (!params || !x || !t || !scratch || !rbar || !grad_partial || !grad_out)
+        return fail(-1, "null buffer passed to psp_pinn_pairs_backward");
+    pinn_scratch(&p, const_cast<float*>(scratch));
+    p.a.params = params; p.a.x = x; p.a.t = t; p.a.rbar = rbar; p.a.vadd = vadd; p.a.gpart = grad_partial;
     const hipError_t e = psp::pinn_launch_backward(p.a, p.lds_bwd, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "pinn_backward_kernel launch");
     return PSP_LAUNCH(reduce_grad_kernel, dim3((p.a.P + 31) / 32), dim3(256), 0, stream, grad_partial, p.a.G, p.a.P, grad_out);

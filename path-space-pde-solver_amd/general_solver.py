@@ -116,7 +116,8 @@ class GeneralSolver:
                  verbose=True, approx_method='Y', sample_center=False, loss_method='diffusion',
                  loss_with_stopped=False, K_test_log=None, PINN_log_variance=False, log_loss_parts=False,
                  boundary_loss=True, full_hessian=False, uniform_square=False, solve_linear_L2_projection=False,
-                 device=None, backend='auto', noise='reference', mlp_dtype='auto', range_guard=True, test_log='reference'):
+                 device=None, backend='auto', noise='reference', mlp_dtype='auto', range_guard=True, test_log='reference',
+                 pinn_time_h='torch'):
         self.problem, self.name = problem, name
         # K_test_log: 'reference' = the reference's host code after every iteration (CPU generator, one device-to-host sync);
         # 'device' = sampled, evaluated and reduced by the native plans' own kernels into a device log that is read back once
@@ -124,6 +125,11 @@ class GeneralSolver:
         if test_log not in ('reference', 'device'):
             raise ValueError("test_log must be 'reference' or 'device'")
         self.test_log = test_log
+        # train_PINN() with an h that reads t (the (K, K) residual of solver.py:1284-1285): 'torch' = the composite plan, as ever;
+        # 'native' = the pair kernel of plan_pinn_native.py, the same numbers up to fp32 rounding.  Ignored where h does not read t.
+        if pinn_time_h not in ('torch', 'native'):
+            raise ValueError("pinn_time_h must be 'torch' or 'native'")
+        self.pinn_time_h = pinn_time_h
         # split-product kernels ('auto' / 'f16x3'): redo an iteration on the fp32-MFMA kernels when an operand left the f16 range
         # (include/psp.h: psp_gen_config.range_flag); self.range_fallback_iterations counts them after train()
         self.range_guard, self.range_fallback_iterations = bool(range_guard), 0
@@ -466,7 +472,7 @@ class GeneralSolver:
             self.plan_name, self.plan_reason = 'native', None
             plan = getattr(self, '_pinn_plan', None)
             key = self._plan_key() + (bool(self.PINN_log_variance), bool(self.boundary_loss), bool(self.full_hessian),
-                                     getattr(self, 'hessian', 'reference'))
+                                     getattr(self, 'hessian', 'reference'), getattr(self, 'pinn_time_h', 'torch'))
             if plan is None or plan.net is not self.V or plan.key != key or not _owns_parameters(plan):
                 plan = ppn.PinnNativePlan(self)
                 plan.key = key

@@ -190,7 +190,8 @@ class GenlEvalSizes(C.Structure):
 
 
 class PinnConfig(C.Structure):
-    """psp_pinn_config: the PINN residual of a dense-concat value net (psp_pinn_query / psp_pinn_residual / psp_pinn_backward)."""
+    """psp_pinn_config: the PINN residual of a dense-concat value net (psp_pinn_query / psp_pinn_residual / psp_pinn_backward, and
+    psp_pinn_pairs_* for an h that reads t)."""
     _fields_ = [("d", C.c_int32), ("K", C.c_int32), ("has_time", C.c_int32), ("n_hidden", C.c_int32), ("widths", C.c_int32 * 4),
                 ("activation", C.c_int32), ("linear_layout", C.c_int32), ("drift_kind", C.c_int32), ("h_kind", C.c_int32),
                 ("sigma_kind", C.c_int32), ("n_dirs", C.c_int32), ("sigma_scale", C.c_float), ("h_par", C.c_float * 4),
@@ -220,6 +221,10 @@ SIGNATURES = {
     "psp_pinn_query": (C.c_int, [C.POINTER(PinnConfig), C.POINTER(PinnSizes)]),
     "psp_pinn_residual": (C.c_int, [C.POINTER(PinnConfig), _P, _P, _P, _P, _P, _P]),
     "psp_pinn_backward": (C.c_int, [C.POINTER(PinnConfig), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psp_pinn_pairs_query": (C.c_int, [C.POINTER(PinnConfig), C.POINTER(PinnSizes), C.POINTER(C.c_int64)]),
+    "psp_pinn_pairs_residual": (C.c_int, [C.POINTER(PinnConfig), _P, _P, _P, _P, _P, _P]),
+    "psp_pinn_pairs_reduce": (C.c_int, [C.POINTER(PinnConfig), _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
+    "psp_pinn_pairs_backward": (C.c_int, [C.POINTER(PinnConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "psp_genl_query": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlSizes)]),
     "psp_genl_rollout_fwd": (C.c_int, [C.POINTER(GenlConfig), _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P]),

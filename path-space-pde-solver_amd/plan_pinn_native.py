@@ -16,9 +16,17 @@ the plan a configuration runs on does not change under its user).  Here B B^T is
 vectors u_j with sum_j u_j u_j^T = B B^T, and the same kernels carry the u_j as tangent rows: 1/2 sum_j u_j^T Hess V u_j.
 
 Scope: a dense-concat value net the run-time-shaped kernels take (plan_general_deep.value_net_spec: 1-4 hidden layers, widths
-<= 128, input <= 112, relu^2 / tanh / tanh^2), a catalogue problem whose h does not read t, with a scaled-identity sigma or --
+<= 128, input <= 112, relu^2 / tanh / tanh^2), a catalogue problem whose h does not read t (one that does: below), with a scaled-identity sigma or --
 EllipticSolver with full_hessian=True and hessian='directions' only -- a dense one, any domain, one rank.  ``pinn_eligibility`` names what keeps a
 configuration on the composite plan.
+
+An h that reads t (ExponentialOnSphereNonlinearParabolic): the reference hands it t_n as (K, 1), so the residual broadcasts to the
+(K, K) matrix R[i, j] = A_j + nl(exp(2 al |x_j|^2 + 2 tau t_i) - y_j^2) and the loss is its mean square.  The default,
+GeneralSolver(pinn_time_h='torch'), keeps that on the composite plan; pinn_time_h='native' runs it here: everything that passes
+through the net is per sample j, the pair part is an elementwise function of (t_i, sample j), so per iteration
+    psp_pinn_pairs_residual -> A_j;  psp_pinn_pairs_reduce -> the loss (a device scalar), rho_j = 2 a0 / K^2 sum_i R[i, j] and
+    nu_j = 2 a0 / K^2 sum_i R[i, j] nl'(..) (-2 y_j);  psp_pinn_pairs_backward(rbar = rho, vadd = nu);  psp_adam_step
+with nothing read on the host.
 """
 import ctypes as C
 import time
@@ -70,8 +78,10 @@ def pinn_eligibility(solver):
                 'operator of the problem (composite only)')
     if dense and spec['h'] == nat.GH_QUAD:
         return 'an h that reads z = B grad V is not in the PINN kernels for a dense sigma'
-    if spec['h'] >= nat.GH_EXPBALL_LIN and len(spec.get('h_par', ())) > 3 and spec['h_par'][3] != 0.0:
-        return 'h reads t: the reference hands it t_n as (K, 1) and the residual broadcasts to (K, K) (composite only)'
+    pairs = h_reads_t(spec)
+    if pairs and getattr(s, 'pinn_time_h', 'torch') != 'native':
+        return ("h reads t: the reference hands it t_n as (K, 1) and the residual broadcasts to (K, K) (composite by default; "
+                "GeneralSolver(pinn_time_h='native') runs it on the pair kernel)")
     if spec['drift'][0] not in (nat.DRIFT_ZERO, nat.DRIFT_DIAG, nat.DRIFT_DOUBLE_WELL):
         return 'a dense drift is not in the PINN kernels'
     if not nat.is_built():
@@ -79,11 +89,44 @@ def pinn_eligibility(solver):
     why = deep_eligibility(s)                                     # the net: structure, depth, widths
     if why is not None:
         return why
+    if pairs:                                                     # what psp_pinn_pairs_query refuses (no GPU needed)
+        net = value_net_spec(s.V, s.d + (0 if s.elliptic else 1))
+        cfg = pinn_config(s, net, spec, torch.device('cpu'), [])
+        if nat.load().psp_pinn_pairs_query(C.byref(cfg), C.byref(nat.PinnSizes()), C.byref(C.c_int64())) != 0:
+            return 'h reads t and the pair kernel does not take this configuration: ' + nat.last_error()
     if s.device.type != 'cuda':
         if full:
             return 'full_hessian=True runs on the direction-table kernels, which need a GPU: device is %s' % s.device
         return 'device is %s (the HIP kernels need a GPU)' % s.device
     return None
+
+
+def h_reads_t(spec):
+    return spec['h'] >= nat.GH_EXPBALL_LIN and len(spec.get('h_par', ())) > 3 and spec['h_par'][3] != 0.0
+
+
+def pinn_config(s, net, spec, dev, keep):
+    """psp_pinn_config of a solver for K_original points; the tensors its pointers name are appended to ``keep``."""
+    cfg = nat.PinnConfig()
+    cfg.d, cfg.K = s.d, s.K_original
+    cfg.has_time, cfg.n_hidden = (0 if s.elliptic else 1), len(net['dims']) - 2
+    for i, h in enumerate(net['dims'][1:-1]):
+        cfg.widths[i] = int(h)
+    cfg.activation, cfg.linear_layout = _ACT[net['act']], (1 if net['linear'] else 0)
+    cfg.drift_kind, cfg.h_kind = spec['drift'][0], spec['h']
+    if spec.get('sigma') is None:                              # (full_hessian with s I is s^2 times the Laplacian)
+        cfg.sigma_kind, cfg.sigma_scale = nat.GENL_SIGMA_SCALED, float(spec['sigma_scale'])
+    else:                                                      # trace(B B^T Hess V) as sum_j u_j^T Hess V u_j
+        dirs = direction_table(spec['sigma']).to(device=dev, dtype=torch.float32).contiguous()
+        keep.append(dirs)
+        cfg.sigma_kind, cfg.n_dirs, cfg.dirs = nat.GENL_SIGMA_DENSE, dirs.shape[0], nat.ptr(dirs)
+    for i, v in enumerate(spec.get('h_par', ())):
+        cfg.h_par[i] = float(v)
+    if spec['drift'][1] is not None:
+        t = spec['drift'][1].detach().to(device=dev, dtype=torch.float32).contiguous()
+        keep.append(t)
+        cfg.drift = nat.ptr(t)
+    return cfg
 
 
 def direction_table(B):
@@ -108,28 +151,14 @@ class PinnNativePlan:
         GeneralNativePlan._flatten(self, net['params'])          # self.params / P / flat / grad: the net's tensors become views
         spec = s.problem.general_native_spec()
         self._keep = []
-        cfg = nat.PinnConfig()
-        cfg.d, cfg.K = s.d, s.K_original
-        cfg.has_time, cfg.n_hidden = (0 if self.elliptic else 1), len(net['dims']) - 2
-        for i, h in enumerate(net['dims'][1:-1]):
-            cfg.widths[i] = int(h)
-        cfg.activation, cfg.linear_layout = _ACT[net['act']], (1 if net['linear'] else 0)
-        cfg.drift_kind, cfg.h_kind = spec['drift'][0], spec['h']
-        if spec.get('sigma') is None:                              # (full_hessian with s I is s^2 times the Laplacian)
-            cfg.sigma_kind, cfg.sigma_scale = nat.GENL_SIGMA_SCALED, float(spec['sigma_scale'])
-        else:                                                      # trace(B B^T Hess V) as sum_j u_j^T Hess V u_j
-            dirs = direction_table(spec['sigma']).to(device=self.dev, dtype=torch.float32).contiguous()
-            self._keep.append(dirs)
-            cfg.sigma_kind, cfg.n_dirs, cfg.dirs = nat.GENL_SIGMA_DENSE, dirs.shape[0], nat.ptr(dirs)
-        for i, v in enumerate(spec.get('h_par', ())):
-            cfg.h_par[i] = float(v)
-        if spec['drift'][1] is not None:
-            t = spec['drift'][1].detach().to(device=self.dev, dtype=torch.float32).contiguous()
-            self._keep.append(t)
-            cfg.drift = nat.ptr(t)
-        self.cfg = cfg
+        self.cfg = cfg = pinn_config(s, net, spec, self.dev, self._keep)
+        self.pairs = h_reads_t(spec)                               # the (K, K) residual of an h that reads t
         sz = nat.PinnSizes()                                       # sized for the largest batch an iteration can see
-        nat.check(self.lib.psp_pinn_query(C.byref(cfg), C.byref(sz)), 'psp_pinn_query')
+        if self.pairs:
+            work = C.c_int64()
+            nat.check(self.lib.psp_pinn_pairs_query(C.byref(cfg), C.byref(sz), C.byref(work)), 'psp_pinn_pairs_query')
+        else:
+            nat.check(self.lib.psp_pinn_query(C.byref(cfg), C.byref(sz)), 'psp_pinn_query')
         assert sz.n_params == self.P, (sz.n_params, self.P)
         self.sizes, self.K_cap = sz, s.K_original
         dev, f32 = self.dev, torch.float32
@@ -139,6 +168,10 @@ class PinnNativePlan:
         self.rbar = torch.empty(self.K_cap, dtype=f32, device=dev)
         self.m = torch.zeros(self.P, dtype=f32, device=dev)
         self.v = torch.zeros(self.P, dtype=f32, device=dev)
+        if self.pairs:
+            self.pair_work = torch.empty(work.value, dtype=torch.uint8, device=dev)
+            self.nu = torch.empty(self.K_cap, dtype=f32, device=dev)
+            self.loss_dev = torch.empty(1, dtype=f32, device=dev)
         self.step = 0
         self.test_log = GeneralNativePlan._device_test_log(self)
 
@@ -168,6 +201,8 @@ class PinnNativePlan:
     def residual(self, X, t):
         """R (K,) of the points X (K, d) [and times t (K,)] with the current parameters; leaves the backward's scratch."""
         K = X.shape[0]
+        if self.pairs:
+            raise RuntimeError('h reads t: the residual is a (K, K) matrix, see pairs_loss_and_grad()')
         if K <= 0 or K > self.K_cap:
             raise RuntimeError('batch of %d points outside the plan capacity %d' % (K, self.K_cap))
         self.cfg.K = K
@@ -188,6 +223,24 @@ class PinnNativePlan:
                                              nat.ptr(self.grad), st), 'psp_pinn_backward')
         return self.grad
 
+    def pairs_loss_and_grad(self, X, t, a0):
+        """An h that reads t: alpha0 mean over the (K, K) residual squared, as a device scalar, and its gradient in self.grad.
+        self.R holds A, self.rbar holds rho."""
+        K = X.shape[0]
+        if K <= 0 or K > self.K_cap:
+            raise RuntimeError('batch of %d points outside the plan capacity %d' % (K, self.K_cap))
+        self.cfg.K = K
+        self._x = X.detach().to(torch.float32).contiguous()
+        self._t = t.detach().to(torch.float32).reshape(-1).contiguous()
+        st, cfg, ptr = nat.stream_ptr(self.dev), C.byref(self.cfg), nat.ptr
+        x, tt, scratch = ptr(self._x), ptr(self._t), ptr(self.scratch)
+        nat.check(self.lib.psp_pinn_pairs_residual(cfg, ptr(self.flat), x, tt, scratch, ptr(self.R), st), 'psp_pinn_pairs_residual')
+        nat.check(self.lib.psp_pinn_pairs_reduce(cfg, x, tt, scratch, ptr(self.R), float(a0), ptr(self.pair_work),
+                                                 ptr(self.loss_dev), ptr(self.rbar), ptr(self.nu), st), 'psp_pinn_pairs_reduce')
+        nat.check(self.lib.psp_pinn_pairs_backward(cfg, ptr(self.flat), x, tt, scratch, ptr(self.rbar), ptr(self.nu),
+                                                   ptr(self.grad_partial), ptr(self.grad), st), 'psp_pinn_pairs_backward')
+        return self.loss_dev[0].clone()                          # (the buffer is the next iteration's too)
+
     def iteration(self, l):
         s, pb, dev, ell = self.s, self.s.problem, self.dev, self.elliptic
         for p in self.params:
@@ -202,16 +255,19 @@ class PinnNativePlan:
             if s.boundary_loss and s.bounded:
                 t_b = torch.rand(s.K_boundary, 1).to(dev) * pb.T
         term, res_b = self._data_terms(X, X_b, t_b)
-        R = self.residual(X, t_n)
         a0 = s.alpha[0]
-        if ell and s.PINN_log_variance:
-            loss = a0 * torch.var(R)
-            rbar = (2.0 * a0 / (K - 1)) * (R - torch.mean(R))
+        if self.pairs:                                           # the loss is a device scalar, the gradient is in self.grad
+            loss = self.pairs_loss_and_grad(X, t_n, a0)
         else:
-            loss = a0 * torch.mean(R ** 2)
-            rbar = (2.0 * a0 / K) * R
+            R = self.residual(X, t_n)
+            if ell and s.PINN_log_variance:
+                loss = a0 * torch.var(R)
+                rbar = (2.0 * a0 / (K - 1)) * (R - torch.mean(R))
+            else:
+                loss = a0 * torch.mean(R ** 2)
+                rbar = (2.0 * a0 / K) * R
+            self.backward(rbar)
         parts = (loss / a0, res_b) if s.log_loss_parts else None
-        self.backward(rbar)
         if term is not None:
             loss = loss + term
             self.grad += torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in self.params])
