@@ -751,6 +751,8 @@ def general_train(problem: OracleProblem, cfg: GeneralConfig, V=None, trace=Fals
         stopped = torch.zeros(K).bool()                              # :1084
         K_count = 0
         tr = dict(X0=X.detach().clone(), t0=t_n.clone(), xi=[]) if trace else None
+        if trace and bounded:                                        # the boundary batch and its times, for a replay of the draws
+            tr["X_boundary"], tr["t_b"] = X_boundary.clone(), t_b.clone()
         for n in range(cfg.N):
             if torch.sum(~stopped) == 0:                             # :1093-1097
                 break
@@ -779,6 +781,8 @@ def general_train(problem: OracleProblem, cfg: GeneralConfig, V=None, trace=Fals
             t_n = t_n + dt32 * act.float().unsqueeze(1)              # :1148
             X_t_n = torch.cat([X, t_n], 1)                           # :1149
             K_count = K_count + torch.sum(act)                       # :1152
+            if trace:
+                tr["steps"] = tr.get("steps", 0) + act.long()
             stopped = stopped | (~new_sel & ~stopped)                # :1154-1155
         if cfg.loss_method == "diffusion":
             loss = loss + cfg.alpha[0] * torch.mean((V(X_t_n).squeeze() - Y) ** 2)   # :1163
@@ -801,6 +805,9 @@ def general_train(problem: OracleProblem, cfg: GeneralConfig, V=None, trace=Fals
         if trace:
             tr["grads"] = [p.grad.detach().clone() for p in V.parameters()]
             tr["VN_minus_Y"] = None
+            with torch.no_grad():                                    # per-trajectory end points of the rollout
+                tr.update(Y_N=Y.detach().clone(), X_N=X.detach().clone(), t_N=t_n.detach().squeeze(1).clone(),
+                          V_N=V(X_t_n).squeeze(1).clone())
         V.optim.step()                                               # :1188
         out["loss_log"].append(loss.item())                          # :1192
         if cfg.K_test_log is not None:                               # :1193-1197
@@ -892,6 +899,8 @@ def elliptic_train(problem: OracleProblem, cfg: EllipticConfig, V=None, trace=Fa
         V_L2 = torch.zeros(K)
         K_count = 0
         tr = dict(X0=X.detach().clone(), xi=[]) if trace else None
+        if trace:
+            tr["X_boundary"] = X_boundary.clone()
         for n in range(cfg.N):
             Y_ = V(X)                                                # :733
             Y_eval = Y_.squeeze().sum()
@@ -920,6 +929,8 @@ def elliptic_train(problem: OracleProblem, cfg: EllipticConfig, V=None, trace=Fa
             X = (X * (~new_sel | stopped).float().unsqueeze(1).repeat(1, d)
                  + X_prop * act.float().unsqueeze(1).repeat(1, d))   # :780-781
             K_count = K_count + torch.sum(act)                       # :784
+            if trace:
+                tr["steps"] = tr.get("steps", 0) + act.long()
             stopped = stopped | (~new_sel & ~stopped)                # :786-787
         if cfg.loss_method == "diffusion":
             loss = loss + cfg.alpha[0] * torch.mean((V(X).squeeze() - Y) ** 2)   # :799
@@ -932,6 +943,8 @@ def elliptic_train(problem: OracleProblem, cfg: EllipticConfig, V=None, trace=Fa
         loss.backward()                                              # :814
         if trace:
             tr["grads"] = [p.grad.detach().clone() for p in V.parameters()]
+            with torch.no_grad():
+                tr.update(Y_N=Y.detach().clone(), X_N=X.detach().clone(), V_N=V(X).squeeze(1).clone())
         V.optim.step()                                               # :815
         out["loss_log"].append(loss.item())                          # :819
         out["V_L2_log"].append(torch.mean(V_L2).item())              # :820
