@@ -27,15 +27,17 @@ import torch
 try:
     from . import native as nat
     from . import sharding
+    from . import plan_common as pc
     from .function_space import Affine, Constant, Linear
-    from .plan_native import HjbNativePlan, PlanUnsupported, _overridden
-    from .plan_dense_native import DenseNativePlan, ul2_kind, ul2_reference, ul2_unsupported
+    from .plan_common import PlanUnsupported, ul2_kind, ul2_reference, ul2_unsupported
+    from .plan_native import _overridden
 except ImportError:
     import native as nat
     import sharding
+    import plan_common as pc
     from function_space import Affine, Constant, Linear
-    from plan_native import HjbNativePlan, PlanUnsupported, _overridden
-    from plan_dense_native import DenseNativePlan, ul2_kind, ul2_reference, ul2_unsupported
+    from plan_common import PlanUnsupported, ul2_kind, ul2_reference, ul2_unsupported
+    from plan_native import _overridden
 
 _LOSSES = ('log-variance', 'moment', 'variance', 'cross_entropy', 'relative_entropy')
 _CLASSES = (Linear, Affine, Constant)
@@ -201,11 +203,7 @@ class AffineNativePlan:
             raise nat.NativeLibraryError('libpsp_hip.so is not built; run __graft_entry__.build()')
         self.s, self.noise, self.lib, self.dev = s, noise, nat.load(), s.device
         dev = self.dev
-        self.dist, self.rank, self.world = sharding.dist_info()
-        try:
-            lo, hi = sharding.shard_bounds(s.K, self.rank, self.world)
-        except ValueError as e:
-            raise PlanUnsupported(str(e))
+        self.dist, self.rank, self.world, lo, hi = pc.local_shard(s.K)
         self.K_local, self.k_offset = hi - lo, lo
         self.mods = list(s.z_n)
         self.net = s.z_n
@@ -232,18 +230,7 @@ class AffineNativePlan:
         cfg.struct_bytes = C.sizeof(nat.AffConfig)
         b = cfg.base
         b.d, b.H = DB, 0
-        b.K_local, b.N, b.K_global, b.k_offset = self.K_local, N, s.K, self.k_offset
-        b.dt, b.sqrt_dt = float(s.delta_t.item()), float(s.sq_delta_t.item())
-        b.drift_kind, b.sigma_kind, b.sigma_scale = spec['drift'][0], spec['sigma'][0], float(spec['sigma'][2])
-        b.runcost_kind, b.term_kind = spec['runcost'][0], spec['term'][0]
-        b.adaptive = 1 if s.adaptive_forward_process else 0
-        b.loss_kind = {'log-variance': nat.LOSS_LOG_VARIANCE, 'moment': nat.LOSS_MOMENT,
-                       'relative_entropy': nat.LOSS_REL_ENTROPY}.get(s.loss_method, nat.LOSS_WEIGHTS)
-        self.generic_loss = b.loss_kind == nat.LOSS_WEIGHTS
-        self.relent = s.loss_method == 'relative_entropy'
-        self.attached = bool(s.adaptive_forward_process and not s.detach_forward)
-        b.noise_mode = nat.NOISE_PHILOX if noise == 'philox' else nat.NOISE_SUPPLIED
-        b.store_path = 3 if self.relent else (2 if self.attached else 1)
+        self.generic_loss, self.relent, self.attached = pc.fill_hjb_base(b, s, spec, noise, self.K_local, self.k_offset)
         b.mlp_dtype = nat.MLP_FP32
         b.drift = nat.ptr(padded(spec['drift'][1]))
         b.sigma = nat.ptr(padded(spec['sigma'][1]))
@@ -296,11 +283,9 @@ class AffineNativePlan:
             self.step = max(self.step, sharding.adam_state_import(self._params_of(mod), self.m[o:o + self.Pset],
                                                                   self.v[o:o + self.Pset], mod.optim))
         self.learn_y0 = bool(s.learn_Y_0)
-        if self.learn_y0:
-            self.y0_param = s.y_0.Y_0
-            self.y0_m = torch.zeros(1, dtype=f32, device=dev)
-            self.y0_v = torch.zeros(1, dtype=f32, device=dev)
-            self.y0_grad = torch.zeros(1, dtype=f32, device=dev)
+        if self.learn_y0:                                    # (its state is exported after training, not imported here)
+            self.y0 = pc.Y0Adam(s.y_0, dev, import_state=False)
+            self.y0_param = self.y0.param
 
     # ------------------------------------------------------------------------------------
     def _params_of(self, mod):
@@ -316,15 +301,7 @@ class AffineNativePlan:
         per = [self._params_of(m) for m in self.mods]
         self.Pset = sum(p.numel() for p in per[0])
         self.P = self.Pset * len(per)
-        flat = torch.empty(self.P, dtype=torch.float32, device=self.dev)
-        off = 0
-        for params in per:
-            for p in params:
-                n = p.numel()
-                flat[off:off + n].copy_(p.detach().reshape(-1))
-                p.data = flat[off:off + n].view(p.shape)
-                off += n
-        self.flat = flat
+        self.flat = pc.rehome_params([p for params in per for p in params], self.dev)
 
     def _stage_maps(self):
         """(M, c) of every step from the live parameters, zero padded to the bucket."""
@@ -335,20 +312,6 @@ class AffineNativePlan:
             self.Mpad[:, :d, :d].copy_(effective_map(self.G, F))
         if self.has_bias:
             self.cpad[:, :d].copy_(sets[:, self.Pset - d:])
-
-    def _reference_noise(self):
-        """The reference's per-iteration draws from the CPU generator (solver.py:367, 381) as (N+1, K_local, d_pad)."""
-        s, DB = self.s, self.d_pad
-        x0 = torch.randn(s.K, s.d) if s.random_X_0 else None
-        xi = torch.randn(s.K, s.d, s.N + 1)
-        lo, hi = self.k_offset, self.k_offset + self.K_local
-        pad = (0, DB - s.d)
-        xi_dev = torch.nn.functional.pad(xi[lo:hi].permute(2, 0, 1), pad).contiguous().to(self.dev)
-        x0_dev = torch.nn.functional.pad(x0[lo:hi], pad).contiguous().to(self.dev) if x0 is not None else None
-        return xi_dev, x0_dev
-
-    _generic_loss_weights = HjbNativePlan._generic_loss_weights
-    _adam_hyper = DenseNativePlan._adam_hyper
 
     def _gradient(self, w):
         """psp_aff_rollout_bwd, the slices of every step summed in order, the chain rule back to the modules' parameters."""
@@ -369,14 +332,7 @@ class AffineNativePlan:
         s, lib, cfg = self.s, self.lib, self.cfg
         st = nat.stream_ptr(self.dev)
         seed = int(s.seed) & 0xFFFFFFFFFFFFFFFF
-        xi = x0 = None
-        if self.noise == 'reference':
-            xi, x0 = self._reference_noise()
-        elif s.random_X_0:
-            g = torch.Generator(device=self.dev)
-            g.manual_seed(int(s.seed) * 1000003 + l)
-            x0 = torch.nn.functional.pad(torch.randn(s.K, s.d, generator=g, device=self.dev)[
-                self.k_offset:self.k_offset + self.K_local], (0, self.d_pad - s.d)).contiguous()
+        xi, x0 = pc.draw_noise(s, l, self.noise, self.k_offset, self.K_local, self.d_pad, self.dev)
         x0_t = x0 if x0 is not None else self.x0_vec
         self._stage_maps()
         nat.check(lib.psp_aff_rollout_fwd(C.byref(cfg), nat.ptr(self.Mpad), nat.ptr(self.cpad), nat.ptr(x0_t),
@@ -388,28 +344,16 @@ class AffineNativePlan:
                   'psp_aff_terminal_reduce')
         sharding.allreduce_sum_(self.sums)                        # collective 1: 16 bytes
         if self.generic_loss:
-            loss, w = self._generic_loss_weights()
+            loss, w = sharding.generic_loss_weights(s.loss_method, s.adaptive_forward_process, self.D, self.Yn, s.K, self.w)
         else:
             loss = sharding.loss_from_sums(self.sums, s.K, s.loss_method)
             w = None if self.relent else sharding.loss_weights(self.D, self.sums, s.K, s.loss_method)
         loss_out[l] = loss.to(torch.float32)
         if self.ul2 is not None and ul2_out is not None:
-            m = (self.ul2.sum() / float(s.K)).reshape(1)           # mean over the GLOBAL K, no host sync
-            sharding.allreduce_sum_(m)
-            ul2_out[l:l + 1] = m
+            pc.log_mean_ul2(self.ul2, s.K, ul2_out, l)
         if self.attached:
-            # per-trajectory weights mu = dL/dY_N, nu = dL/dZsum_N (global K and global mean: rank-independent); the sweep
-            # leaves dL/dZ_n / sqrt(dt) in the image slot of the path store
-            wT = None
-            if self.relent:
-                self.mu.zero_()
-                self.nu.fill_(1.0 / float(s.K))
-            else:
-                self.mu.copy_(w)
-                if s.loss_method == 'cross_entropy':
-                    # mean(Y exp(-g(X_N) + Y.detach())) (solver.py:183-185) also depends on X_N through exp(-g)
-                    wT = self.wT
-                    wT.copy_(-self.Yn * w)
+            # the sweep leaves dL/dZ_n / sqrt(dt) in the image slot of the path store
+            wT = pc.attached_weights(s.loss_method, self.relent, s.K, w, self.Yn, self.mu, self.nu, self.wT)
             nat.check(lib.psp_aff_adjoint_sweep(C.byref(cfg), nat.ptr(self.Mpad), nat.ptr(self.path), nat.ptr(self.XN_k),
                                                 nat.ptr(self.mu), nat.ptr(self.nu) if self.relent else None, nat.ptr(wT), st),
                       'psp_aff_adjoint_sweep')
@@ -422,15 +366,11 @@ class AffineNativePlan:
         self._gradient(self.w_bwd)
         sharding.allreduce_sum_(self.grad)                        # collective 2
         self.step += 1
-        lr, b1, b2, eps = self._adam_hyper(self.mods)
-        nat.check(lib.psp_adam_step(nat.ptr(self.flat), nat.ptr(self.grad), nat.ptr(self.m), nat.ptr(self.v),
-                                    self.P, self.step, lr, b1, b2, eps, st), 'psp_adam_step')
+        pc.adam_step(lib, self.flat, self.grad, self.m, self.v, self.P, self.step,
+                     pc.adam_hyper(self.mods, s.lr, PlanUnsupported), st)
         if self.learn_y0:
-            self.y0_grad[0] = sharding.y0_gradient(self.sums, s.K, s.loss_method, self.w if self.generic_loss else None)
-            ylr, yb1, yb2, yeps = self._adam_hyper([s.y_0])
-            nat.check(lib.psp_adam_step(nat.ptr(self.y0_param), nat.ptr(self.y0_grad), nat.ptr(self.y0_m),
-                                        nat.ptr(self.y0_v), 1, self.step, ylr, yb1, yb2, yeps, st),
-                      'psp_adam_step(Y_0)')
+            self.y0.step(lib, self.sums, s.K, s.loss_method, self.w if self.generic_loss else None, self.step,
+                         pc.adam_hyper(s.y_0, s.lr, PlanUnsupported), st)
         return loss
 
     def export_optimizer_state(self):
@@ -440,4 +380,4 @@ class AffineNativePlan:
             sharding.adam_state_export(self._params_of(mod), self.m[o:o + self.Pset], self.v[o:o + self.Pset], self.step,
                                        getattr(mod, 'optim', None))
         if self.learn_y0:
-            sharding.adam_state_export([self.y0_param], self.y0_m, self.y0_v, self.step, getattr(self.s.y_0, 'optim', None))
+            self.y0.export(self.step)

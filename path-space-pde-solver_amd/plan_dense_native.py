@@ -23,13 +23,14 @@ psp_dnet_adjoint_sweep (csrc/hjbd_kernels.h: hjbd_adj_kernel) walks the adjoint 
 Jacobian of the dense-concat net and overwrites the slot with dL/dZ_n / sqrt(dt), and the backward kernel runs with unit
 weights -- the scheme of plan_native.py / psp_hjb_adjoint_sweep.
 The u_L2 log (solver.py:471-472, 491-494; on by default whenever the problem has u_true) is accumulated per trajectory inside
-the forward kernel from a description of u* built once per plan by ul2_reference (below): a table of u*(t_n), the gains M_n of
+the forward kernel from a description of u* built once per plan by ul2_reference (plan_common.py): a table of u*(t_n), the gains M_n of
 a u* linear in x, or the double wells' grid tables with the reference's index arithmetic.
 The gradient-variance diagnostic (Solver(compute_gradient_variance=m), solver.py:234-281, 496-497) runs on the same images for
 time_approx='outer': DenseNativePlan.gradient_moments forms the first and second moments of the per-trajectory gradients from
 psp_dnet_rollout_bwd / psp_dnet_rollout_bwd_sq launches and psp_gradvar_finish instead of 2 K N backward passes.
 """
 import ctypes as C
+import os
 
 import torch
 
@@ -37,14 +38,18 @@ try:
     from . import native as nat
     from . import native_shapes as shapes
     from . import sharding
+    from . import plan_common as pc
     from .function_space import DenseNet
-    from .plan_native import HjbNativePlan, PlanUnsupported, _overridden, _u_tables
+    from .plan_common import PlanUnsupported, ul2_kind, ul2_reference, ul2_unsupported  # noqa: F401  (importable from here too)
+    from .plan_native import _overridden
 except ImportError:
     import native as nat
     import native_shapes as shapes
     import sharding
+    import plan_common as pc
     from function_space import DenseNet
-    from plan_native import HjbNativePlan, PlanUnsupported, _overridden, _u_tables
+    from plan_common import PlanUnsupported, ul2_kind, ul2_reference, ul2_unsupported  # noqa: F401
+    from plan_native import _overridden
 
 _LOSSES = ('log-variance', 'moment', 'variance', 'cross_entropy', 'relative_entropy')
 
@@ -56,87 +61,6 @@ def _nets(solver):
 def _instance_for(d, H):
     cands = [(D, Hh) for (D, Hh) in nat.dnet_instances() if D >= d and Hh >= H]
     return min(cands, key=lambda t: (t[0] * t[0] + 3 * t[0] * t[1], t[1])) if cands else None
-
-
-def ul2_kind(problem):
-    """Which description of the reference control u* the forward kernel can log u_L2 against (include/psp.h PSP_UL2_*): 2 the
-    grid tables of the double wells (problem.u_true_tables()), 0 a u* that does not depend on x, 1 a u* linear in x; None: none."""
-    if _u_tables(problem) is not None:
-        return nat.UL2_GRID
-    if getattr(problem, 'u_true_x_independent', False) is True:
-        return nat.UL2_TABLE
-    if getattr(problem, 'u_true_linear_in_x', False) is True:
-        return nat.UL2_LINEAR
-    return None
-
-
-def ul2_unsupported(problem, N, dt_np):
-    """None if the forward kernel can log u_L2 for this problem on the time grid (N steps of dt_np), else the precise reason."""
-    import numpy as np
-    kind = ul2_kind(problem)
-    if kind is None:
-        return ('u_l2_error_flag=True evaluates problem.u_true(X_n, t_n) on the host every step (reference solver.py:491-494); '
-                'the forward kernel logs u_L2 for a u_true that does not depend on x (u_true_x_independent), is linear in x '
-                '(u_true_linear_in_x) or is tabulated per coordinate (u_true_tables(), e.g. a double well after '
-                'compute_reference_solution) -- this problem has none of these; pass u_l2_error_flag=False for the native plan')
-    if kind != nat.UL2_GRID:
-        return None
-    tb = _u_tables(problem)
-    shapes = [np.shape(t) for t in tb['tables']]
-    if any(len(sh) != 2 or sh != shapes[0] for sh in shapes):
-        return ('the u_true_tables() of this problem have unequal shapes %s; the forward kernel reads tables of one '
-                '(rows, cells) shape' % shapes)
-    last = int(np.ceil((N - 1) * dt_np / tb['delta_t'])) if N > 0 else 0
-    if last >= shapes[0][0]:
-        return ('the u_true_tables() of this problem end at t = %g (%d rows of dt_ref = %g); the solver reads row %d at t = %g'
-                % ((shapes[0][0] - 1) * tb['delta_t'], shapes[0][0], tb['delta_t'], last, (N - 1) * dt_np))
-    return None
-
-
-def ul2_reference(problem, N, dt_np, d_pad, K_global, k_offset):
-    """Host-side description of u*(x, t_n), n < N, for the u_L2 log of the DenseNet-control forward kernel, padded to d_pad
-    (CPU tensors; None when the problem has no description the kernel reads -- see ul2_kind).  t_n = n * dt_np as the reference
-    forms it (solver.py:493).  Keys: 'kind', 'd', 'K_global', 'k_offset' and
-      kind 0: 'table' (N, d_pad) u*(t_n)                                     -- probed at x = 0 (plan_native.py recipe)
-      kind 1: 'gains' (N, d_pad, d_pad) M_n with u*(x, t_n) = M_n x          -- probed with the unit vectors
-      kind 2: 'tables' (G, nrows, ncols) fp32, 'group' (d_pad) int32, 'row' (N) int32 = ceil(t_n / dt_ref), 'xb', 'dx', 'xhi' =
-              fp32(xb - 2 dx) (formed in double, as the reference's clamp bound), 'nrows', 'ncols'.
-    The cell arithmetic of kind 2 (clamp, true fp32 division, the last global trajectory lowered by two, numpy wrap-around) is the
-    kernel's (csrc/hjbd_kernels.h); K_global / k_offset locate that trajectory.  Raises ValueError with ul2_unsupported's reason
-    for grid tables the kernel cannot read."""
-    import numpy as np
-    kind = ul2_kind(problem)
-    if kind is None:
-        return None
-    reason = ul2_unsupported(problem, N, dt_np)
-    if reason is not None:
-        raise ValueError(reason)
-    d = problem.d
-    out = dict(kind=kind, d=d, K_global=int(K_global), k_offset=int(k_offset))
-    if kind == nat.UL2_TABLE:
-        probe = torch.zeros(1, d)
-        rows = [torch.tensor(np.asarray(problem.u_true(probe, n * dt_np))).reshape(d, -1)[:, 0].float() for n in range(N)]
-        table = torch.zeros(N, d_pad)
-        table[:, :d] = torch.stack(rows)
-        out['table'] = table
-    elif kind == nat.UL2_LINEAR:
-        eye = torch.eye(d)
-        gains = torch.zeros(N, d_pad, d_pad)
-        for n in range(N):                                   # u_true returns (d, K): column j = M e_j
-            gains[n, :d, :d] = torch.tensor(np.asarray(problem.u_true(eye, n * dt_np))).reshape(d, d).float()
-        out['gains'] = gains
-    else:
-        tb = _u_tables(problem)
-        tabs = [np.asarray(t, dtype=np.float32) for t in tb['tables']]
-        nrows, ncols = tabs[0].shape
-        group = torch.zeros(d_pad, dtype=torch.int32)
-        group[:d] = torch.tensor(tb['group_of_dim'], dtype=torch.int32)
-        xb, dx = float(tb['xb']), float(tb['dx'])
-        out.update(tables=torch.from_numpy(np.stack(tabs)), group=group,
-                   row=torch.tensor([int(np.ceil(n * dt_np / tb['delta_t'])) for n in range(N)], dtype=torch.int32),
-                   xb=float(np.float32(xb)), dx=float(np.float32(dx)), xhi=float(np.float32(xb - 2 * dx)),
-                   nrows=int(nrows), ncols=int(ncols))
-    return out
 
 
 def dense_eligibility(solver):
@@ -184,7 +108,6 @@ def dense_eligibility(solver):
 def gradient_variance_unsupported(solver, instance, world=None):
     """None if DenseNativePlan.gradient_moments covers compute_gradient_variance > 0 for this solver on the (d, H) `instance`, else
     the precise reason (the composite plan then runs the reference's per-trajectory backward passes)."""
-    import os
     if solver.time_approx != 'outer':
         return ("compute_gradient_variance indexes one net per time step (reference solver.py:248): it needs time_approx='outer'")
     if solver.loss_method not in ('moment', 'log-variance'):
@@ -232,11 +155,7 @@ class DenseNativePlan:
         s = solver
         self.s, self.noise, self.lib, self.dev = s, noise, nat.load(), s.device
         dev = self.dev
-        self.dist, self.rank, self.world = sharding.dist_info()
-        try:
-            lo, hi = sharding.shard_bounds(s.K, self.rank, self.world)
-        except ValueError as e:
-            raise PlanUnsupported(str(e))
+        self.dist, self.rank, self.world, lo, hi = pc.local_shard(s.K)
         self.K_local, self.k_offset = hi - lo, lo
         self.outer = s.time_approx == 'outer'
         self.nets = _nets(s)
@@ -260,18 +179,7 @@ class DenseNativePlan:
         cfg = nat.DnetConfig()
         b = cfg.base
         b.d, b.H = self.d_pad, self.H_pad
-        b.K_local, b.N, b.K_global, b.k_offset = self.K_local, s.N, s.K, self.k_offset
-        b.dt, b.sqrt_dt = float(s.delta_t.item()), float(s.sq_delta_t.item())
-        b.drift_kind, b.sigma_kind, b.sigma_scale = spec['drift'][0], spec['sigma'][0], float(spec['sigma'][2])
-        b.runcost_kind, b.term_kind = spec['runcost'][0], spec['term'][0]
-        b.adaptive = 1 if s.adaptive_forward_process else 0
-        b.loss_kind = {'log-variance': nat.LOSS_LOG_VARIANCE, 'moment': nat.LOSS_MOMENT,
-                       'relative_entropy': nat.LOSS_REL_ENTROPY}.get(s.loss_method, nat.LOSS_WEIGHTS)
-        self.generic_loss = b.loss_kind == nat.LOSS_WEIGHTS
-        self.relent = s.loss_method == 'relative_entropy'
-        self.attached = bool(s.adaptive_forward_process and not s.detach_forward)
-        b.noise_mode = nat.NOISE_PHILOX if noise == 'philox' else nat.NOISE_SUPPLIED
-        b.store_path = 3 if self.relent else (2 if self.attached else 1)
+        self.generic_loss, self.relent, self.attached = pc.fill_hjb_base(b, s, spec, noise, self.K_local, self.k_offset)
         pad = self.pad
         b.drift = nat.ptr(dev_f32(pad.drift_or_sigma(spec['drift'][1]))) if spec['drift'][1] is not None else None
         b.sigma = nat.ptr(dev_f32(pad.drift_or_sigma(spec['sigma'][1]))) if spec['sigma'][1] is not None else None
@@ -328,7 +236,6 @@ class DenseNativePlan:
         self.fwd_partial = torch.empty(sizes.fwd_partial_bytes // 8, dtype=torch.float64, device=dev)
         # gradient: the hand-written kernel (csrc/hjbd_kernels.h, hjbd_bwd_kernel) where the instance is covered, else the
         # library-GEMM formulation on row-major stores (PSP_DENSE_BWD=gemm forces the latter: cross-check / timing)
-        import os
         self.kernel_bwd = bool(sizes.bwd_supported) and os.environ.get('PSP_DENSE_BWD', 'kernel') != 'gemm'
         self._gidx = None                                        # padded -> real gather index of a parameter set ('outer')
         if (self.attached or self.relent) and not self.kernel_bwd:
@@ -372,10 +279,8 @@ class DenseNativePlan:
         self._gv = None
         self.learn_y0 = bool(s.learn_Y_0)
         if self.learn_y0:
-            self.y0_param = s.y_0.Y_0
-            self.y0_m = torch.zeros(1, dtype=f32, device=dev)
-            self.y0_v = torch.zeros(1, dtype=f32, device=dev)
-            self.y0_grad = torch.zeros(1, dtype=f32, device=dev)
+            self.y0 = pc.Y0Adam(s.y_0, dev, import_state=False)
+            self.y0_param = self.y0.param
         # sample chunk of the gradient GEMMs: bounds their temporaries (~(2H + 2d) floats per sample)
         self.chunk = max(1, (1 << 21) // max(1, self.K_local)) if not self.outer else s.N
 
@@ -386,15 +291,7 @@ class DenseNativePlan:
         per = [list(net.W) for net in self.nets]                     # registration order W1,b1,W2,b2,W3,b3
         self.Pset = sum(p.numel() for p in per[0])
         self.P = self.Pset * len(per)
-        flat = torch.empty(self.P, dtype=torch.float32, device=self.dev)
-        off = 0
-        for params in per:
-            for p in params:
-                n = p.numel()
-                flat[off:off + n].copy_(p.detach().reshape(-1))
-                p.data = flat[off:off + n].view(p.shape)
-                off += n
-        self.flat = flat
+        self.flat = pc.rehome_params([p for params in per for p in params], self.dev)
         di, H, d = self.di, self.H, self.nets[0].nn_dims[3]
         o, self.off = 0, {}
         for name, shape in (('W1', (di, H)), ('b1', (H,)), ('W2', (di + H, H)), ('b2', (H,)),
@@ -410,9 +307,6 @@ class DenseNativePlan:
         o, n, shape = self.off[name]
         return buf.view(self.B, self.Pset)[:, o:o + n].reshape(self.B, *shape) if self.B == 1 else \
             buf.view(self.B, self.Pset)[:, o:o + n].unflatten(1, shape)
-
-    _reference_noise = HjbNativePlan._reference_noise
-    _generic_loss_weights = HjbNativePlan._generic_loss_weights
 
     # ------------------------------------------------------------------------------------
     def _gradient_kernel(self, w):
@@ -610,14 +504,7 @@ class DenseNativePlan:
         s, lib, cfg = self.s, self.lib, self.cfg
         st = nat.stream_ptr(self.dev)
         seed = int(s.seed) & 0xFFFFFFFFFFFFFFFF
-        xi = x0 = None
-        if self.noise == 'reference':
-            xi, x0 = self._reference_noise()
-        elif s.random_X_0:
-            g = torch.Generator(device=self.dev)
-            g.manual_seed(int(s.seed) * 1000003 + l)
-            x0 = self.pad.last_dim(torch.randn(s.K, s.d, generator=g, device=self.dev)[
-                self.k_offset:self.k_offset + self.K_local].contiguous())
+        xi, x0 = pc.draw_noise(s, l, self.noise, self.k_offset, self.K_local, self.d_pad, self.dev)
         x0_t = x0 if x0 is not None else self.x0_vec
         ev = None
         if self.events is not None:
@@ -635,15 +522,13 @@ class DenseNativePlan:
                   'psp_dnet_terminal_reduce')
         sharding.allreduce_sum_(self.sums)                        # collective 1: 16 bytes
         if self.generic_loss:
-            loss, w = self._generic_loss_weights()
+            loss, w = sharding.generic_loss_weights(s.loss_method, s.adaptive_forward_process, self.D, self.Yn, s.K, self.w)
         else:
             loss = sharding.loss_from_sums(self.sums, s.K, s.loss_method)
             w = None if self.relent else sharding.loss_weights(self.D, self.sums, s.K, s.loss_method)
         loss_out[l] = loss.to(torch.float32)
         if self.ul2 is not None and ul2_out is not None:
-            m = (self.ul2.sum() / float(s.K)).reshape(1)           # mean over the GLOBAL K, no host sync
-            sharding.allreduce_sum_(m)
-            ul2_out[l:l + 1] = m
+            pc.log_mean_ul2(self.ul2, s.K, ul2_out, l)
         if ev is not None:
             ev[2].record()
         m_gv = int(s.compute_gradient_variance)
@@ -653,18 +538,8 @@ class DenseNativePlan:
             self.gradient_moments(out=self.gv_log[self.gv_count:self.gv_count + 1])
             self.gv_count += 1
         if self.attached:
-            # per-trajectory weights mu = dL/dY_N, nu = dL/dZsum_N (global K and global mean: rank-independent), as in
-            # plan_native.py; the sweep leaves dL/dZ_n / sqrt(dt) in the xi slot of the images
-            wT = None
-            if self.relent:
-                self.mu.zero_()
-                self.nu.fill_(1.0 / float(s.K))
-            else:
-                self.mu.copy_(w)
-                if s.loss_method == 'cross_entropy':
-                    # mean(Y exp(-g(X_N) + Y.detach())) (solver.py:183-185) also depends on X_N through exp(-g)
-                    wT = self.wT
-                    wT.copy_(-self.Yn * w)
+            # the sweep leaves dL/dZ_n / sqrt(dt) in the xi slot of the images
+            wT = pc.attached_weights(s.loss_method, self.relent, s.K, w, self.Yn, self.mu, self.nu, self.wT)
             nat.check(lib.psp_dnet_adjoint_sweep(C.byref(cfg), nat.ptr(self.flat), nat.ptr(self.images), nat.ptr(self.XN_k),
                                                  nat.ptr(self.mu), nat.ptr(self.nu) if self.relent else None, nat.ptr(wT),
                                                  nat.ptr(self.tables), st), 'psp_dnet_adjoint_sweep')
@@ -680,36 +555,12 @@ class DenseNativePlan:
             self.events.append(ev)
         sharding.allreduce_sum_(self.grad)                        # collective 2
         self.step += 1
-        lr, b1, b2, eps = self._adam_hyper(self.nets)
-        nat.check(lib.psp_adam_step(nat.ptr(self.flat), nat.ptr(self.grad), nat.ptr(self.m), nat.ptr(self.v),
-                                    self.P, self.step, lr, b1, b2, eps, st), 'psp_adam_step')
+        pc.adam_step(lib, self.flat, self.grad, self.m, self.v, self.P, self.step,
+                     pc.adam_hyper(self.nets, s.lr, PlanUnsupported), st)
         if self.learn_y0:
-            self.y0_grad[0] = sharding.y0_gradient(self.sums, s.K, s.loss_method, self.w if self.generic_loss else None)
-            ylr, yb1, yb2, yeps = self._adam_hyper([s.y_0])
-            nat.check(lib.psp_adam_step(nat.ptr(self.y0_param), nat.ptr(self.y0_grad), nat.ptr(self.y0_m),
-                                        nat.ptr(self.y0_v), 1, self.step, ylr, yb1, yb2, yeps, st),
-                      'psp_adam_step(Y_0)')
+            self.y0.step(lib, self.sums, s.K, s.loss_method, self.w if self.generic_loss else None, self.step,
+                         pc.adam_hyper(s.y_0, s.lr, PlanUnsupported), st)
         return loss
 
     def range_fallbacks(self):
-        """Iterations the range guard sent to the fp32-MFMA rollout so far; one device read."""
-        return int(self.range_flag[1].item()) if self.range_flag is not None else 0
-
-    def _adam_hyper(self, nets):
-        """lr / betas / eps of the nets' OWN optimisers (function_space.py:131; solver.py:198-200 steps every Phi's Adam).  One
-        fused Adam runs over the concatenation of all parameter sets, so the sets must agree."""
-        hyp = None
-        for net in nets:
-            opt = getattr(net, 'optim', None)
-            if opt is None or not opt.param_groups:
-                h = (float(self.s.lr), 0.9, 0.999, 1e-8)
-            else:
-                g = opt.param_groups[0]
-                if g.get('weight_decay', 0) or g.get('amsgrad', False):
-                    raise PlanUnsupported('the native Adam implements weight_decay = 0, amsgrad = False (the reference default)')
-                b = g.get('betas', (0.9, 0.999))
-                h = (float(g['lr']), float(b[0]), float(b[1]), float(g.get('eps', 1e-8)))
-            if hyp is not None and h != hyp:
-                raise PlanUnsupported('the per-step nets carry different Adam settings; the fused native Adam needs one')
-            hyp = h
-        return hyp
+        return pc.range_fallbacks(self.range_flag)

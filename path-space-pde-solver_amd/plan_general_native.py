@@ -22,18 +22,21 @@ its all-stopped break; on a bounded domain that count depends on the paths, so i
 and the CPU generator is rewound and advanced by that many draws.
 """
 import ctypes as C
+import time
 
 import torch
 
 try:
     from . import native as nat
     from . import native_shapes as shapes
+    from . import plan_common as pc
     from . import sharding
     from .function_space import DenseNet
     from . import general_solver as gs
 except ImportError:
     import native as nat
     import native_shapes as shapes
+    import plan_common as pc
     import sharding
     from function_space import DenseNet
     import general_solver as gs
@@ -210,27 +213,7 @@ class GeneralNativePlan:
         self._extra_grad = None
         self.events = None   # bench.py: HIP-event pairs around the two rollout kernels
         self._batch_views()
-        self.test_log = self._device_test_log()
-
-    def _device_test_log(self):
-        """test_log='device': the K_test_log diagnostic on this plan's stream (device_test_log.py); every rank evaluates all
-        K_test_log points with its replicated parameters -- no collective, identical logs.  None: the host log."""
-        s = self.s
-        if getattr(s, 'test_log', 'reference') != 'device' or s.K_test_log is None:
-            return None
-        try:
-            from . import device_test_log as dtl
-            from .plan_general_deep import value_net_spec
-        except ImportError:
-            import device_test_log as dtl
-            from plan_general_deep import value_net_spec
-        why = dtl.eval_reason(s.problem)
-        net = getattr(self, 'net_spec', None) or value_net_spec(s.V, s.d + (0 if self.elliptic else 1))
-        if why is None and isinstance(net, str):
-            why = net
-        if why is not None:
-            raise ValueError("test_log='device' unavailable: " + why)
-        return dtl.DeviceTestLog(net, s.problem, s.K_test_log, 'elliptic' if self.elliptic else 'parabolic', self.dev, max(1, s.L))
+        self.test_log = pc.device_test_log(self.s, getattr(self, 'net_spec', None), self.elliptic, dev)
 
     def _batch_views(self):
         """Output views for this iteration's batch (K_local <= K_cap)."""
@@ -263,15 +246,8 @@ class GeneralNativePlan:
 
     def _flatten(self, params):
         self.params = params
-        self.P = sum(p.numel() for p in params)
-        flat = torch.empty(self.P, dtype=torch.float32, device=self.dev)
-        off = 0
-        for p in params:
-            n = p.numel()
-            flat[off:off + n].copy_(p.detach().reshape(-1))
-            p.data = flat[off:off + n].view(p.shape)
-            off += n
-        self.flat = flat
+        self.flat = pc.rehome_params(params, self.dev)
+        self.P = self.flat.numel()
         self.grad = torch.empty(self.P, dtype=torch.float32, device=self.dev)
 
     def _sample_domain_device(self, l):
@@ -490,9 +466,8 @@ class GeneralNativePlan:
             self._extra_grad = None
         self.last_v_l2 = self._v_l2_from_path() if self.log_v_l2 else None     # before the update, as the reference logs it
         self.step += 1
-        lr, b1, b2, eps = self._adam_hyper()
-        nat.check(lib.psp_adam_step(nat.ptr(self.flat), nat.ptr(self.grad), nat.ptr(self.m), nat.ptr(self.v),
-                                    self.P, self.step, lr, b1, b2, eps, st), 'psp_adam_step')
+        pc.adam_step(lib, self.flat, self.grad, self.m, self.v, self.P, self.step,
+                     pc.adam_hyper(self.net, s.lr, NotImplementedError), st)    # V's own optimiser (solver.py:1188 steps V.optim)
         kc = self.kcount.clone()
         sharding.allreduce_sum_(kc)
         if s.K_test_log is not None and self.test_log is not None:     # on the device: the updated parameters, no host sync
@@ -549,19 +524,7 @@ class GeneralNativePlan:
         return self.sizes.path_bytes // 4 // ((self.s.N + 1) * nt)
 
     def range_fallbacks(self):
-        """Iterations the range guard sent to the fp32-MFMA kernels so far; one device read."""
-        return int(self.range_flag[1].item()) if self.range_flag is not None else 0
-
-    def _adam_hyper(self):
-        """lr / betas / eps of V's OWN optimiser (function_space.py:131; solver.py:1188 steps V.optim)."""
-        opt = getattr(self.net, 'optim', None)
-        if opt is not None and len(opt.param_groups) > 0:
-            g = opt.param_groups[0]
-            if g.get('weight_decay', 0) or g.get('amsgrad', False):
-                raise NotImplementedError('the native Adam implements weight_decay = 0, amsgrad = False (the reference default)')
-            b = g.get('betas', (0.9, 0.999))
-            return float(g['lr']), float(b[0]), float(b[1]), float(g.get('eps', 1e-8))
-        return float(self.s.lr), 0.9, 0.999, 1e-8
+        return pc.range_fallbacks(self.range_flag)
 
     @property
     def log_v_l2(self):
@@ -594,30 +557,9 @@ class GeneralNativePlan:
         return tot[0] / float(s.K)
 
     def train(self):
-        s = self.s
-        if self.test_log is None:
-            return self._train_loop()
-        self.test_log.begin(max(1, s.L))
-        try:
-            self._train_loop()
-        except BaseException:                                        # the log of the iterations that ran; the loop's error survives
-            try:
-                self._read_test_log()
-            except Exception:
-                pass
-            raise
-        self._read_test_log()
-
-    def _read_test_log(self):
-        """The one read-back of the device test log."""
-        s = self.s
-        l2, mae, mre = self.test_log.read()
-        s.V_test_L2 += l2
-        s.V_test_abs += mae
-        s.V_test_rel_abs += mre
+        return pc.train_with_test_log(self.s, self.test_log, self._train_loop)
 
     def _train_loop(self):
-        import time
         s = self.s
         losses, counts, vl2, Ks = [], [], [], []
         t_block = time.time()

@@ -30,17 +30,15 @@ import torch
 try:
     from . import native as nat
     from . import native_shapes as shapes
+    from . import plan_common as pc
     from . import sharding
+    from .plan_common import PlanUnsupported  # noqa: F401  (re-exported: the name callers import from here)
 except ImportError:
     import native as nat
     import native_shapes as shapes
+    import plan_common as pc
     import sharding
-
-
-def _u_tables(problem):
-    """problem.u_true_tables() (the double wells' finite-difference reference control, problems.py) or None."""
-    fn = getattr(problem, 'u_true_tables', None)
-    return fn() if fn is not None else None
+    from plan_common import PlanUnsupported  # noqa: F401
 
 
 def _overridden(problem):
@@ -49,10 +47,6 @@ def _overridden(problem):
     except ImportError:
         from problems import coefficients_overridden
     return coefficients_overridden(problem)
-
-
-class PlanUnsupported(Exception):
-    """The (problem, net, loss, flags) combination is outside the native catalogue."""
 
 
 # ---- state basis (DESIGN.md section 3) -------------------------------------------------------------------------------------
@@ -156,7 +150,7 @@ def native_eligibility(solver):
     if solver.burgers_drift:
         return 'burgers_drift is not native'
     if solver.u_l2_error_flag and getattr(solver.problem, 'u_true_x_independent', False) is not True \
-            and getattr(solver.problem, 'u_true_linear_in_x', False) is not True and _u_tables(solver.problem) is None:
+            and getattr(solver.problem, 'u_true_linear_in_x', False) is not True and pc.u_tables(solver.problem) is None:
         return ('u_l2_error_flag=True evaluates problem.u_true(X_n, t_n) on the host every step '
                 '(reference solver.py:491-494); a u_true that does not depend on x (LLGC) is logged inside the kernels, one '
                 'that is linear in x (LQGC) or tabulated per coordinate (the double wells) from the path store -- pass '
@@ -215,17 +209,14 @@ class HjbNativePlan:
         self.noise = noise
         dev = solver.device
         self.dev = dev
-        self.dist, self.rank, self.world = sharding.dist_info()
         K = solver.K
-        try:
-            lo, hi = sharding.shard_bounds(K, self.rank, self.world)
-        except ValueError as e:
-            raise PlanUnsupported(str(e))
+        self.dist, self.rank, self.world, lo, hi = pc.local_shard(K)
         self.K_local, self.k_offset = hi - lo, lo
         net = solver.z_n
         self.net = net
         self.H = net.native_shape()[1]
-        self._flatten(net)
+        self.flat = pc.rehome_params(net.flat_layout(), dev)       # (psp.h layout)
+        self.P = self.flat.numel()
         spec = solver.problem.native_spec()
         self._keep = []   # device tensors referenced by raw pointer from the config
 
@@ -237,11 +228,7 @@ class HjbNativePlan:
             return t
 
         cfg = nat.HjbConfig()
-        cfg.K_local, cfg.N = self.K_local, solver.N
-        cfg.K_global, cfg.k_offset = K, self.k_offset
-        cfg.dt = float(solver.delta_t.item())
-        cfg.sqrt_dt = float(solver.sq_delta_t.item())
-        cfg.drift_kind = spec['drift'][0]
+        self.generic_loss, self.relent, self.attached = pc.fill_hjb_base(cfg, solver, spec, noise, self.K_local, self.k_offset)
         # the state basis of every launch of this plan (module comment above): under 'sigma' the kernels get identity sigma
         self.state_basis, self.state_basis_reason = state_basis_decision(solver, spec)
         if (self.state_basis == 'sigma' and getattr(solver, 'state_basis', 'auto') == 'auto' and torch.device(dev).type == 'cuda'
@@ -252,20 +239,8 @@ class HjbNativePlan:
             # hipGraph replay, which the gradient transform splits).  Conservative: at d = 100, K = 8192 an explicit 'sigma' still
             # measures 4 % faster.  state_basis='sigma' overrides.
             self.state_basis, self.state_basis_reason = 'x', 'launch-bound size (at most two 16-trajectory tiles per CU)'
-        cfg.sigma_kind = nat.SIGMA_IDENTITY if self.state_basis == 'sigma' else spec['sigma'][0]
-        cfg.sigma_scale = float(spec['sigma'][2])
-        cfg.runcost_kind = spec['runcost'][0]
-        cfg.term_kind = spec['term'][0]
-        cfg.adaptive = 1 if solver.adaptive_forward_process else 0
-        cfg.loss_kind = {'log-variance': nat.LOSS_LOG_VARIANCE, 'moment': nat.LOSS_MOMENT,
-                         'relative_entropy': nat.LOSS_REL_ENTROPY}.get(solver.loss_method, nat.LOSS_WEIGHTS)
-        self.generic_loss = cfg.loss_kind == nat.LOSS_WEIGHTS
-        self.relent = solver.loss_method == 'relative_entropy'
-        # gradients through the state path (the reference's default flags): forward with the attached-mode image in
-        # the xi slot, reverse-time adjoint sweep, then the ordinary backward with unit weights (include/psp.h)
-        self.attached = bool(solver.adaptive_forward_process and not solver.detach_forward)
-        cfg.noise_mode = nat.NOISE_PHILOX if noise == 'philox' else nat.NOISE_SUPPLIED
-        cfg.store_path = 3 if self.relent else (2 if self.attached else 1)
+        if self.state_basis == 'sigma':
+            cfg.sigma_kind = nat.SIGMA_IDENTITY
         # matrix products: 'fp32' = v_mfma_f32_16x16x4_f32; 'f16x3' = fp32-grade split products on the f16 pipe (three
         # v_mfma_f32_16x16x32_f16 per fp32 product, csrc/hjb_kernels.h gemm_Tx, csrc/hjbx_kernels.h -- same parity bounds);
         # 'auto' (the default) = 'f16x3' where those kernels exist, fit the LDS and the tile-per-wave forward would run anyway
@@ -362,11 +337,10 @@ class HjbNativePlan:
         self.ul2 = None
         self.ul2_gain = None
         self.ul2_tab = None
-        if solver.u_l2_error_flag and _u_tables(solver.problem) is not None:
+        if solver.u_l2_error_flag and pc.u_tables(solver.problem) is not None:
             # u*(x, t) tabulated per coordinate on a grid (the double wells: problems.py u_true_tables, reference problems.py:
             # 277-281, 399-404, 471-476): the tables go to the device once, the log is formed from the path store (_ul2_from_path)
-            import numpy as np
-            tb = _u_tables(solver.problem)
+            tb = pc.u_tables(solver.problem)
             self.ul2_tab = dict(tables=[torch.tensor(np.asarray(t), dtype=torch.float32, device=dev) for t in tb['tables']],
                                 group=torch.tensor(tb['group_of_dim'], dtype=torch.long, device=dev),
                                 xb=float(tb['xb']), dx=float(tb['dx']),
@@ -375,7 +349,6 @@ class HjbNativePlan:
         elif solver.u_l2_error_flag and getattr(solver.problem, 'u_true_x_independent', False) is not True:
             # u*(x, t_n) = M_n x (LQGC, problems.py:169-171): M_n once per plan by probing u_true with the unit vectors; the log
             # is then formed from the X_n and h2 images of the path store after the forward kernel (_ul2_from_path)
-            import numpy as np
             eye = torch.eye(solver.d)
             gains = [torch.tensor(np.asarray(solver.problem.u_true(eye, n * solver.delta_t_np))).reshape(solver.d, solver.d).float()
                      for n in range(solver.N)]                                       # u_true returns (d, K): column i = M e_i
@@ -384,7 +357,6 @@ class HjbNativePlan:
         elif solver.u_l2_error_flag:
             # u_L2 log (solver.py:491-494) for an x-independent reference control: u*(t_n) once per plan instead of
             # problem.u_true(X.cpu(), t_n) every step of every iteration; the kernels accumulate |-Z_n - u*(t_n)|^2 dt
-            import numpy as np
             probe = torch.zeros(1, solver.d)
             rows = [torch.tensor(np.asarray(solver.problem.u_true(probe, n * solver.delta_t_np))).reshape(solver.d, -1)[:, 0].float()
                     for n in range(solver.N)]
@@ -412,30 +384,13 @@ class HjbNativePlan:
         self._graph_iter = -1
         self._eager_done = 0
         self.graph_active = False
-        # learnable Y_0 (solver.py:372-374): tiny Adam in torch on a 1-element tensor
+        # learnable Y_0 (solver.py:372-374): a one-element Adam beside the net's; it continues the state y_0.optim carries
         self.learn_y0 = bool(solver.learn_Y_0)
         if self.learn_y0:
-            self.y0_param = solver.y_0.Y_0
-            self.y0_m = torch.zeros(1, dtype=torch.float32, device=dev)
-            self.y0_v = torch.zeros(1, dtype=torch.float32, device=dev)
-            self.y0_grad = torch.zeros(1, dtype=torch.float32, device=dev)
-            sharding.adam_state_import([self.y0_param], self.y0_m, self.y0_v, getattr(solver.y_0, 'optim', None))
+            self.y0 = pc.Y0Adam(solver.y_0, dev, import_state=True)
+            self.y0_param = self.y0.param
 
     # ------------------------------------------------------------------------------------
-    def _flatten(self, net):
-        """Re-home the net's parameters as views of one flat fp32 buffer (psp.h layout) so
-        that state_dict / save_networks / Z_n keep working on live values."""
-        params = net.flat_layout()
-        self.P = sum(p.numel() for p in params)
-        flat = torch.empty(self.P, dtype=torch.float32, device=self.dev)
-        off = 0
-        for p in params:
-            n = p.numel()
-            flat[off:off + n].copy_(p.detach().reshape(-1))
-            p.data = flat[off:off + n].view(p.shape)
-            off += n
-        self.flat = flat
-
     def _stream(self):
         return nat.stream_ptr(self.dev)
 
@@ -547,14 +502,7 @@ class HjbNativePlan:
         s, lib, cfg = self.s, self.lib, self.cfg
         st = self._stream()
         seed = int(s.seed) & 0xFFFFFFFFFFFFFFFF
-        xi_full = x0 = None
-        if self.noise == 'reference':
-            xi_full, x0 = self._reference_noise()
-        elif s.random_X_0:
-            g = torch.Generator(device=self.dev)
-            g.manual_seed(int(s.seed) * 1000003 + l)
-            x0 = self.pad.last_dim(torch.randn(s.K, s.d, generator=g, device=self.dev)[
-                self.k_offset:self.k_offset + self.K_local].contiguous())
+        xi_full, x0 = pc.draw_noise(s, l, self.noise, self.k_offset, self.K_local, self.d_pad, self.dev)
         flat_k = self._kernel_params(st)
         y0_ptr = nat.ptr(self.y0_param) if self.learn_y0 else None
         K = float(s.K)
@@ -633,22 +581,12 @@ class HjbNativePlan:
             sharding.allreduce_sum_(self.sums)           # collective 1
             w_t, use_w = self.D, False
             if self.generic_loss:
-                loss, w_t = self._generic_loss_weights()
+                loss, w_t = sharding.generic_loss_weights(s.loss_method, s.adaptive_forward_process, self.D, self.Yn, s.K, self.w)
                 use_w = True
             else:
                 loss = sharding.loss_from_sums(self.sums, s.K, s.loss_method)
             if self.attached:
-                wT = None
-                if self.relent:
-                    self.mu.zero_()
-                    self.nu.fill_(1.0 / K)
-                elif self.generic_loss:
-                    self.mu.copy_(w_t)
-                    if s.loss_method == 'cross_entropy':
-                        wT = self.wT
-                        wT.copy_(-self.Yn * w_t)
-                else:
-                    self.mu.copy_(sharding.loss_weights(self.D, self.sums, s.K, s.loss_method))
+                wT = pc.attached_weights(s.loss_method, self.relent, s.K, self._dL_dY(w_t), self.Yn, self.mu, self.nu, self.wT)
                 self.w_bwd.fill_(1.0)
                 w_t, use_w = self.w_bwd, True
             elif self.relent:
@@ -676,9 +614,7 @@ class HjbNativePlan:
             torch.sum(self.grad_rows, 0, out=self.grad_k)
         loss_out[l] = loss.to(torch.float32)
         if self.ul2 is not None and ul2_out is not None:
-            m = (self.ul2.sum() / K).reshape(1)
-            sharding.allreduce_sum_(m)
-            ul2_out[l:l + 1] = m
+            pc.log_mean_ul2(self.ul2, s.K, ul2_out, l)
         self._finish_step(st, self.w if self.generic_loss else None)
         return loss
 
@@ -724,12 +660,8 @@ class HjbNativePlan:
                                                    nat.ptr(loss_out), state, st), 'psp_hjb_terminal_reduce_loss')
         d_or_w, bcfg = self.D, cfg
         if self.attached:
-            # trajectory weights of the adjoint sweep (plain iteration: same lines), sweep, backward with unit weights (w_bwd = 1)
-            if self.relent:
-                self.mu.zero_()
-                self.nu.fill_(1.0 / float(s.K))
-            else:
-                self.mu.copy_(sharding.loss_weights(self.D, self.sums, s.K, s.loss_method))
+            # trajectory weights of the adjoint sweep (plain iteration: same call), sweep, backward with unit weights (w_bwd = 1)
+            pc.attached_weights(s.loss_method, self.relent, s.K, self._dL_dY(None), None, self.mu, self.nu, None)
             nat.check(lib.psp_hjb_adjoint_sweep(C.byref(cfg), nat.ptr(flat_k), nat.ptr(self.path), nat.ptr(self.XN_k),
                                                 nat.ptr(self.mu), nat.ptr(self.nu) if self.relent else None, None,
                                                 nat.ptr(self.fwd_partial), st), 'psp_hjb_adjoint_sweep')
@@ -753,15 +685,16 @@ class HjbNativePlan:
         nat.check(lib.psp_adam_step_dev(nat.ptr(self.flat), nat.ptr(self.grad), nat.ptr(self.m), nat.ptr(self.v), self.P,
                                         state, lr, b1, b2, eps, st), 'psp_adam_step_dev')
         if self.learn_y0:
-            self.y0_grad[0] = sharding.y0_gradient(self.sums, s.K, s.loss_method)
-            ylr = self._adam_hyper(s.y_0)[0]
-            nat.check(lib.psp_adam_step_dev(nat.ptr(self.y0_param), nat.ptr(self.y0_grad), nat.ptr(self.y0_m),
-                                            nat.ptr(self.y0_v), 1, state, ylr, b1, b2, eps, st), 'psp_adam_step_dev(Y_0)')
+            y0 = self.y0
+            y0.grad[0] = sharding.y0_gradient(self.sums, s.K, s.loss_method)
+            ylr = pc.adam_hyper(s.y_0, s.lr, PlanUnsupported)[0]
+            nat.check(lib.psp_adam_step_dev(nat.ptr(y0.param), nat.ptr(y0.grad), nat.ptr(y0.m),
+                                            nat.ptr(y0.v), 1, state, ylr, b1, b2, eps, st), 'psp_adam_step_dev(Y_0)')
         nat.check(lib.psp_iter_state_advance(state, b1, b2, st), 'psp_iter_state_advance')
 
     def _iteration_graph(self, l, loss_out):
-        hyper = self._adam_hyper()
-        if self.learn_y0 and self._adam_hyper(self.s.y_0)[1:] != hyper[1:]:
+        hyper = pc.adam_hyper(self.net, self.s.lr, PlanUnsupported)
+        if self.learn_y0 and pc.adam_hyper(self.s.y_0, self.s.lr, PlanUnsupported)[1:] != hyper[1:]:
             self.s.use_graph = False                     # different betas for Y_0: one psp_iter_state cannot serve both
             return self.iteration(l, loss_out)
         if self._eager_done < 1:
@@ -845,51 +778,26 @@ class HjbNativePlan:
         self.pad.gather_grad(self.grad_k, self.grad)    # real entries of the (possibly padded) gradient
         sharding.allreduce_sum_(self.grad)              # collective 2: p floats
         self.step += 1
-        lr, b1, b2, eps = self._adam_hyper()
-        nat.check(lib.psp_adam_step(nat.ptr(self.flat), nat.ptr(self.grad), nat.ptr(self.m), nat.ptr(self.v),
-                                    self.P, self.step, lr, b1, b2, eps, st), 'psp_adam_step')
+        pc.adam_step(lib, self.flat, self.grad, self.m, self.v, self.P, self.step, pc.adam_hyper(self.net, s.lr, PlanUnsupported), st)
         if self.learn_y0:
-            # dL/dY_0 = sum_k dL/dY_k ; log-variance: exactly 0 ; moment: (2/K) sum D (global sums) ; variance: sum of the weights
-            self.y0_grad[0] = sharding.y0_gradient(self.sums, s.K, s.loss_method, w_generic)
-            ylr, yb1, yb2, yeps = self._adam_hyper(s.y_0)
-            nat.check(lib.psp_adam_step(nat.ptr(self.y0_param), nat.ptr(self.y0_grad), nat.ptr(self.y0_m),
-                                        nat.ptr(self.y0_v), 1, self.step, ylr, yb1, yb2, yeps, st),
-                      'psp_adam_step(Y_0)')
+            self.y0.step(lib, self.sums, s.K, s.loss_method, w_generic, self.step,
+                         pc.adam_hyper(s.y_0, s.lr, PlanUnsupported), st)
 
     def range_fallbacks(self):
-        """Iterations (chunk launches) the range guard sent to the fp32-MFMA kernels so far; one device read."""
-        return int(self.range_flag[1].item()) if self.range_flag is not None else 0
+        return pc.range_fallbacks(self.range_flag)
 
     def export_optimizer_state(self):
         """Called by Solver._train_native when training returns: the nets' own optimisers see the moments this plan kept."""
         sharding.adam_state_export(self.net.flat_layout(), self.m, self.v, self.step, getattr(self.net, 'optim', None))
         if self.learn_y0:
-            sharding.adam_state_export([self.y0_param], self.y0_m, self.y0_v, self.step, getattr(self.s.y_0, 'optim', None))
+            self.y0.export(self.step)
 
-    def _adam_hyper(self, net=None):
-        """lr, betas, eps of the net's OWN optimiser (function_space.py:185: each ansatz space builds its Adam in its
-        constructor, solver.py:198-200 steps every Phi's) -- a swapped-in net keeps its learning rate."""
-        opt = getattr(net if net is not None else self.net, 'optim', None)
-        if opt is not None and len(opt.param_groups) > 0:
-            g = opt.param_groups[0]
-            if g.get('weight_decay', 0) or g.get('amsgrad', False):
-                raise PlanUnsupported('the native Adam implements weight_decay = 0, amsgrad = False (the reference default)')
-            b = g.get('betas', (0.9, 0.999))
-            return float(g['lr']), float(b[0]), float(b[1]), float(g.get('eps', 1e-8))
-        return float(self.s.lr), 0.9, 0.999, 1e-8
-
-    def _reference_noise(self):
-        """The reference's per-iteration draws from the CPU generator (solver.py:367,381),
-        re-laid-out as (N+1, K_local, d) for coalesced per-step reads."""
-        s = self.s
-        x0 = None
-        if s.random_X_0:
-            x0 = torch.randn(s.K, s.d)
-        xi = torch.randn(s.K, s.d, s.N + 1)
-        lo, hi = self.k_offset, self.k_offset + self.K_local
-        xi_dev = self.pad.last_dim(xi[lo:hi].permute(2, 0, 1).contiguous().to(self.dev))
-        x0_dev = self.pad.last_dim(x0[lo:hi].contiguous().to(self.dev)) if x0 is not None else None
-        return xi_dev, x0_dev
+    def _dL_dY(self, w_generic):
+        """dL/dY_k of this rank's trajectories, for the adjoint sweep: the weights the plan formed itself (generic losses),
+        those of the global sums (log-variance, moment), or None (relative entropy: the sweep's weights are constants)."""
+        if self.generic_loss:
+            return w_generic
+        return None if self.relent else sharding.loss_weights(self.D, self.sums, self.s.K, self.s.loss_method)
 
     def iteration(self, l, loss_out, ul2_out=None):
         """One training iteration; writes the fp32 loss into loss_out[l] (and mean u_L2 into ul2_out[l]) on the
@@ -901,14 +809,7 @@ class HjbNativePlan:
         s, lib, cfg = self.s, self.lib, self.cfg
         st = self._stream()
         seed = int(s.seed) & 0xFFFFFFFFFFFFFFFF
-        xi = x0 = None
-        if self.noise == 'reference':
-            xi, x0 = self._reference_noise()
-        elif s.random_X_0:
-            g = torch.Generator(device=self.dev)
-            g.manual_seed(int(s.seed) * 1000003 + l)
-            x0 = self.pad.last_dim(torch.randn(s.K, s.d, generator=g, device=self.dev)[
-                self.k_offset:self.k_offset + self.K_local].contiguous())
+        xi, x0 = pc.draw_noise(s, l, self.noise, self.k_offset, self.K_local, self.d_pad, self.dev)
         x0_t = x0 if x0 is not None else self.x0_vec
         x0_stride = self.d_pad if x0 is not None else 0
         flat_k = self._kernel_params(st)
@@ -934,14 +835,13 @@ class HjbNativePlan:
                       'psp_hjb_terminal_reduce')
             sharding.allreduce_sum_(self.sums)              # collective 1: 16 bytes
             if self.generic_loss:
-                loss, d_or_w = self._generic_loss_weights()
+                loss, d_or_w = sharding.generic_loss_weights(s.loss_method, s.adaptive_forward_process, self.D, self.Yn, s.K,
+                                                             self.w)
             else:
                 loss = sharding.loss_from_sums(self.sums, s.K, s.loss_method)
             loss_out[l] = loss.to(torch.float32)
         if self.ul2 is not None and ul2_out is not None:
-            m = (self.ul2.sum() / float(s.K)).reshape(1)
-            sharding.allreduce_sum_(m)
-            ul2_out[l:l + 1] = m
+            pc.log_mean_ul2(self.ul2, s.K, ul2_out, l)
         elif (self.ul2_gain is not None or self.ul2_tab is not None) and ul2_out is not None:
             m = self._ul2_from_path().reshape(1)
             sharding.allreduce_sum_(m)
@@ -949,20 +849,7 @@ class HjbNativePlan:
         if ev is not None:
             ev[2].record()
         if self.attached:
-            # per-trajectory weights mu = dL/dY_N, nu = dL/dZsum_N (global K and global mean: rank-independent)
-            wT = None
-            if self.relent:
-                self.mu.zero_()
-                self.nu.fill_(1.0 / float(s.K))
-            elif self.generic_loss:
-                self.mu.copy_(d_or_w)
-                if s.loss_method == 'cross_entropy':
-                    # mean(Y exp(-g(X_N) + Y.detach())) (solver.py:183-185) also depends on X_N through exp(-g):
-                    # lambda_N = -(Y_N exp(D) / K) grad g, while dL/dY_N = exp(D) / K
-                    wT = self.wT
-                    wT.copy_(-self.Yn * d_or_w)
-            else:
-                self.mu.copy_(sharding.loss_weights(self.D, self.sums, s.K, s.loss_method))
+            wT = pc.attached_weights(s.loss_method, self.relent, s.K, self._dL_dY(d_or_w), self.Yn, self.mu, self.nu, self.wT)
             nat.check(lib.psp_hjb_adjoint_sweep(C.byref(cfg), nat.ptr(flat_k), nat.ptr(self.path), nat.ptr(self.XN_k),
                                                 nat.ptr(self.mu), nat.ptr(self.nu) if self.relent else None, nat.ptr(wT),
                                                 nat.ptr(self.fwd_partial), st), 'psp_hjb_adjoint_sweep')
@@ -983,39 +870,14 @@ class HjbNativePlan:
         # torch's caching allocator is stream-ordered, so freeing here is safe.
         return loss
 
-    def _generic_loss_weights(self):
-        """Losses whose weights w_k = dLoss/dY_k are not affine in D (K-vector arithmetic in torch, the
-        rollout and the gradient stay in the kernels):
-          variance       var(exp(-g + Y))            (solver.py:171-172, unbiased)  w = 2 (E - mean E) E / (K - 1)
-          cross_entropy  mean(Y exp(-g + Y.detach()))  (adaptive, :185)             w = exp(D) / K
-                         mean(Y exp(-g))               (else, :186)                 w = exp(-g) / K"""
-        s, K = self.s, float(self.s.K)
-        D = self.D
-        if s.loss_method == 'variance':
-            E = torch.exp(D)
-            st = torch.stack([E.double().sum(), (E.double() ** 2).sum()])
-            sharding.allreduce_sum_(st)
-            mean = st[0] / K
-            loss = (st[1] - K * mean * mean) / (K - 1.0)
-            w = (2.0 / (K - 1.0)) * (E - mean.float()) * E
-        else:
-            Y = self.Yn
-            E = torch.exp(D) if s.adaptive_forward_process else torch.exp(D - Y)     # exp(-g) = exp(D - Y)
-            st = (Y.double() * E.double()).sum().reshape(1)
-            sharding.allreduce_sum_(st)
-            loss = st[0] / K
-            w = E / K
-        self.w.copy_(w)
-        return loss, self.w
-
     def forward_only(self, l, want_XN=False):
         """Forward rollout without the path store; returns (D, X_N or None)."""
         s, lib = self.s, self.lib
         cfg = nat.HjbConfig.from_buffer_copy(self.cfg)
         cfg.store_path = 0
         xi = x0 = None
-        if self.noise == 'reference':
-            xi, x0 = self._reference_noise()
+        if self.noise == 'reference':                    # (under 'philox' this helper starts every trajectory at the fixed X_0)
+            xi, x0 = pc.draw_noise(s, l, self.noise, self.k_offset, self.K_local, self.d_pad, self.dev)
         x0_t = x0 if x0 is not None else self.x0_vec
         XN = torch.empty(self.K_local, self.d_pad, dtype=torch.float32, device=self.dev) if want_XN else None
         flat_k = self._kernel_params(self._stream())

@@ -35,13 +35,13 @@ import torch
 
 try:
     from . import native as nat
+    from . import plan_common as pc
     from . import sharding
-    from .plan_general_native import GeneralNativePlan
     from .plan_general_deep import value_net_spec, deep_eligibility, _ACT
 except ImportError:
     import native as nat
+    import plan_common as pc
     import sharding
-    from plan_general_native import GeneralNativePlan
     from plan_general_deep import value_net_spec, deep_eligibility, _ACT
 
 
@@ -148,7 +148,10 @@ class PinnNativePlan:
         net = value_net_spec(s.V, s.d + (0 if self.elliptic else 1))
         assert not isinstance(net, str), net
         self.net_spec = net
-        GeneralNativePlan._flatten(self, net['params'])          # self.params / P / flat / grad: the net's tensors become views
+        self.params = net['params']
+        self.flat = pc.rehome_params(self.params, self.dev)       # the net's tensors become views of it
+        self.P = self.flat.numel()
+        self.grad = torch.empty(self.P, dtype=torch.float32, device=self.dev)
         spec = s.problem.general_native_spec()
         self._keep = []
         self.cfg = cfg = pinn_config(s, net, spec, self.dev, self._keep)
@@ -173,10 +176,7 @@ class PinnNativePlan:
             self.nu = torch.empty(self.K_cap, dtype=f32, device=dev)
             self.loss_dev = torch.empty(1, dtype=f32, device=dev)
         self.step = 0
-        self.test_log = GeneralNativePlan._device_test_log(self)
-
-    _adam_hyper = GeneralNativePlan._adam_hyper
-    _read_test_log = GeneralNativePlan._read_test_log
+        self.test_log = pc.device_test_log(s, net, self.elliptic, dev)
 
     def _data_terms(self, X, X_b, t_b):
         """The K_boundary-sized terms of solver.py:1288-1303 / :909-912, differentiated by autograd into p.grad.  Returns
@@ -272,10 +272,9 @@ class PinnNativePlan:
             loss = loss + term
             self.grad += torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in self.params])
         self.step += 1
-        lr, b1, b2, eps = self._adam_hyper()
         st = nat.stream_ptr(dev)
-        nat.check(self.lib.psp_adam_step(nat.ptr(self.flat), nat.ptr(self.grad), nat.ptr(self.m), nat.ptr(self.v),
-                                         self.P, self.step, lr, b1, b2, eps, st), 'psp_adam_step')
+        pc.adam_step(self.lib, self.flat, self.grad, self.m, self.v, self.P, self.step,
+                     pc.adam_hyper(self.net, s.lr, NotImplementedError), st)
         v_l2 = None
         if ell:                                                  # solver.py:919: after the step, on this iteration's points
             with torch.no_grad():
@@ -288,19 +287,7 @@ class PinnNativePlan:
         return loss, v_l2, parts
 
     def train(self):
-        s = self.s
-        if self.test_log is None:
-            return self._train_loop()
-        self.test_log.begin(max(1, s.L))
-        try:
-            self._train_loop()
-        except BaseException:
-            try:
-                self._read_test_log()
-            except Exception:
-                pass
-            raise
-        self._read_test_log()
+        return pc.train_with_test_log(self.s, self.test_log, self._train_loop)
 
     def _train_loop(self):
         s = self.s

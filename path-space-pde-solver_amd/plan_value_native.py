@@ -26,7 +26,7 @@ direction U = B^T u and f does not depend on the parameters while the state path
 
 The u_L2 log (solver.py:471-475, 491-494; on by default whenever the problem has u_true): sum_n |-Z_n - u*(X_{n+1}, n dt)|^2 dt per
 trajectory, accumulated inside the forward kernel (genl_fwd_kernel<.., LOGU>) from the description of u* that
-plan_dense_native.ul2_reference builds once per plan -- a table of u*(t_n) (LLGC), the gains of a u* linear in x (LQGC, staged
+plan_common.ul2_reference builds once per plan -- a table of u*(t_n) (LLGC), the gains of a u* linear in x (LQGC, staged
 into the table scratch once by psp_genl_ul2_stage), the double wells' grid tables -- through psp_genl_query_ul2 /
 psp_genl_rollout_fwd_ul2 with a psp_genl_ul2 beside the config and the coefficients.  Only the run-time-shaped family has log
 instances (the templated (d, H) family does not: its instance list would double), so with the flag on EVERY net runs there
@@ -50,14 +50,18 @@ try:
     from . import native as nat
     from . import native_shapes as shapes
     from . import sharding
+    from . import plan_common as pc
     from .function_space import DenseNet
-    from .plan_native import PlanUnsupported, _overridden
+    from .plan_common import PlanUnsupported
+    from .plan_native import _overridden
 except ImportError:
     import native as nat
     import native_shapes as shapes
     import sharding
+    import plan_common as pc
     from function_space import DenseNet
-    from plan_native import PlanUnsupported, _overridden
+    from plan_common import PlanUnsupported
+    from plan_native import _overridden
 
 
 def value_eligibility(solver):
@@ -80,7 +84,7 @@ def value_eligibility(solver):
         return 'per-step / per-iteration diagnostics (gradient logs, metastability, in-loop IS) are not native here'
     log = bool(s.u_l2_error_flag)
     if log:
-        reason = _pdn().ul2_unsupported(s.problem, s.N, s.delta_t_np)
+        reason = pc.ul2_unsupported(s.problem, s.N, s.delta_t_np)
         if reason is not None:
             return reason
     nets = getattr(s, 'y_n', None)
@@ -129,7 +133,7 @@ def value_eligibility(solver):
         u = None
         if log:                                           # (a query reads no pointer: any non-null value stands for the buffers)
             probe = C.addressof(_PROBE)
-            u = nat.GenlUl2(struct_bytes=C.sizeof(nat.GenlUl2), kind=_pdn().ul2_kind(s.problem), u_l2_out=probe, u_ref=probe,
+            u = nat.GenlUl2(struct_bytes=C.sizeof(nat.GenlUl2), kind=pc.ul2_kind(s.problem), u_l2_out=probe, u_ref=probe,
                             tables=probe, group=probe, row=probe, ntables=1, nrows=1, ncols=1, xb=1.0, dx=1.0, K_global=1)
         lib = nat.load()
         qr, ur = C.byref(q) if q is not None else None, C.byref(u) if u is not None else None
@@ -152,14 +156,6 @@ _PROBE = C.c_float(0.0)
 def state_path_attached(solver):
     """Whether the loss back-propagates through the state path: the control -Z in the drift stays attached (solver.py:456-469)."""
     return bool(solver.adaptive_forward_process and not solver.detach_forward)
-
-
-def _pdn():
-    try:
-        from . import plan_dense_native as pdn
-    except ImportError:
-        import plan_dense_native as pdn
-    return pdn
 
 
 def needs_lq(spec):
@@ -233,11 +229,7 @@ class ValueNativePlan:
         s = solver
         self.s, self.noise, self.lib, self.dev = s, noise, nat.load(), s.device
         dev = self.dev
-        self.dist, self.rank, self.world = sharding.dist_info()
-        try:
-            lo, hi = sharding.shard_bounds(s.K, self.rank, self.world)
-        except ValueError as e:
-            raise PlanUnsupported(str(e))
+        self.dist, self.rank, self.world, lo, hi = pc.local_shard(s.K)
         self.lo, self.hi, self.K_local = lo, hi, hi - lo
         self.net = s.y_n[0]
         self.key = None
@@ -247,7 +239,10 @@ class ValueNativePlan:
         self.attached = state_path_attached(s)            # the adjoint sweep of the state path: the run-time-shaped family as well
         self.adj = None                                   # its psp_genl_adj
         self.deep = _deep_net(s, self.net, force=needs_lq(spec) or self.log or self.attached)     # value nets of other depths / activations: csrc/genl_kernels.h
-        self._flatten(self.net if self.deep is None else self.deep['params'])
+        # registration order W1,b1,W2,b2,.. (include/psp.h)
+        self.params = list(self.net.W) if self.deep is None else list(self.deep['params'])
+        self.flat = pc.rehome_params(self.params, dev)
+        self.P = self.flat.numel()
         self._keep = []
         self.coeffs = None                                # psp_genl_coeffs (dense sigma / drift matrix / running cost), deep plans only
         self.ul2, self.ul2_cfg = None, None               # per-trajectory u_L2 (K_local) and its psp_genl_ul2, with the log on
@@ -357,14 +352,14 @@ class ValueNativePlan:
         self.events = None
 
     def _make_ul2(self):
-        """psp_genl_ul2 from plan_dense_native.ul2_reference (unpadded: the kernel reads (N, d) / (N, d, d) / (d) arrays)."""
+        """psp_genl_ul2 from plan_common.ul2_reference (unpadded: the kernel reads (N, d) / (N, d, d) / (d) arrays)."""
         s, dev = self.s, self.dev
         try:
-            ref = _pdn().ul2_reference(s.problem, s.N, s.delta_t_np, s.d, s.K, self.lo)
+            ref = pc.ul2_reference(s.problem, s.N, s.delta_t_np, s.d, s.K, self.lo)
         except ValueError as e:
             raise PlanUnsupported(str(e))
         if ref is None:
-            raise PlanUnsupported(_pdn().ul2_unsupported(s.problem, s.N, s.delta_t_np))
+            raise PlanUnsupported(pc.ul2_unsupported(s.problem, s.N, s.delta_t_np))
 
         def up(t, dtype=torch.float32):
             t = t.detach().to(device=dev, dtype=dtype).contiguous()
@@ -388,47 +383,17 @@ class ValueNativePlan:
     def _coeffs_ref(self):
         return C.byref(self.coeffs) if self.coeffs is not None else None
 
-    def _flatten(self, V):
-        params = list(V) if isinstance(V, (list, tuple)) else list(V.W)      # registration order W1,b1,W2,b2,.. (include/psp.h)
-        self.params = params
-        self.P = sum(p.numel() for p in params)
-        flat = torch.empty(self.P, dtype=torch.float32, device=self.dev)
-        off = 0
-        for p in params:
-            n = p.numel()
-            flat[off:off + n].copy_(p.detach().reshape(-1))
-            p.data = flat[off:off + n].view(p.shape)
-            off += n
-        self.flat = flat
-
-    def _adam_hyper(self):
-        opt = getattr(self.net, 'optim', None)
-        if opt is not None and len(opt.param_groups) > 0:
-            g = opt.param_groups[0]
-            if g.get('weight_decay', 0) or g.get('amsgrad', False):
-                raise PlanUnsupported('the native Adam implements weight_decay = 0, amsgrad = False (the reference default)')
-            b = g.get('betas', (0.9, 0.999))
-            return float(g['lr']), float(b[0]), float(b[1]), float(g.get('eps', 1e-8))
-        return float(self.s.lr), 0.9, 0.999, 1e-8
-
     def iteration(self, l, loss_out, ul2_out=None):
         s, lib, cfg, dev = self.s, self.lib, self.cfg, self.dev
         st = nat.stream_ptr(dev)
         K, N = float(s.K), s.N
         lo, hi = self.lo, self.hi
         # ---- initial state and noise in the reference's order (solver.py:364-382)
-        xi = None
-        if self.noise == 'reference':
-            X0 = torch.randn(s.K, s.d)[lo:hi].to(dev) if s.random_X_0 else self.x0_row.repeat(self.K_local, 1)
-            noise = torch.randn(s.K, s.d, N + 1)
-            xi = self.pad.last_dim(noise[lo:hi].permute(2, 0, 1)[1:].contiguous().to(dev))   # slot n = xi[:, :, n + 1]
-        elif s.random_X_0:
-            g = torch.Generator(device=dev)
-            g.manual_seed(int(s.seed) * 1000003 + l)
-            X0 = torch.randn(s.K, s.d, generator=g, device=dev)[lo:hi]
-        else:
-            X0 = self.x0_row.repeat(self.K_local, 1)
-        x0 = self.pad.last_dim(X0.contiguous())
+        xi, x0 = pc.draw_noise(s, l, self.noise, lo, self.K_local, self.d_pad, dev)
+        if xi is not None:
+            xi = xi[1:]                                           # the kernels' slot n = the reference's xi[:, :, n + 1]
+        if x0 is None:                                            # these kernels take one start point per trajectory
+            x0 = self.pad.last_dim(self.x0_row.repeat(self.K_local, 1))
         flat_k = self.flat if self.deep is not None else self.pad.scatter_params(self.flat, self.flat_k)
         self.kcount.zero_()
         ev = None
@@ -508,7 +473,6 @@ class ValueNativePlan:
             self.events.append(ev)
         sharding.allreduce_sum_(self.grad)                        # collective 2
         self.step += 1
-        lr, b1, b2, eps = self._adam_hyper()
-        nat.check(lib.psp_adam_step(nat.ptr(self.flat), nat.ptr(self.grad), nat.ptr(self.m), nat.ptr(self.v),
-                                    self.P, self.step, lr, b1, b2, eps, st), 'psp_adam_step')
+        pc.adam_step(lib, self.flat, self.grad, self.m, self.v, self.P, self.step,
+                     pc.adam_hyper(self.net, s.lr, PlanUnsupported), st)
         return loss

@@ -9,8 +9,11 @@ is split into contiguous blocks, one per rank.  Two collectives per iteration:
   2. SUM all-reduce of the flat parameter gradient, after which every rank applies the
      identical Adam step.
 
-The helpers below are the only place that arithmetic lives; plan_native.py uses them on the
-device (RCCL) and tests/test_sharding_gloo.py exercises them on CPU with gloo, world_size 2.
+The helpers below are where the loss arithmetic on GLOBAL sums lives (loss value, trajectory
+weights dLoss/dY_k, the Y_0 gradient, for every native loss) together with the Adam state
+hand-over; the native plans call them on the device (RCCL), plan_common.py holds the plans'
+other shared host steps, and tests/test_sharding_gloo.py exercises them on CPU with gloo,
+world_size 2.
 """
 import torch
 
@@ -84,6 +87,31 @@ def loss_weights(D_local, sums, K_global, loss_method):
     if loss_method == 'moment':
         return (2.0 / K) * D_local
     raise ValueError(loss_method)
+
+
+def generic_loss_weights(loss_method, adaptive, D, Yn, K_global, w_out):
+    """(loss, w_out) for the losses whose weights w_k = dLoss/dY_k are not affine in D (K-vector arithmetic in torch, the
+    rollout and the gradient stay in the kernels); D, Yn: this rank's D_k and Y_N (Yn unused for 'variance'); the weights are
+    written into w_out:
+      variance       var(exp(-g + Y))            (solver.py:171-172, unbiased)  w = 2 (E - mean E) E / (K - 1)
+      cross_entropy  mean(Y exp(-g + Y.detach()))  (adaptive, :185)             w = exp(D) / K
+                     mean(Y exp(-g))               (else, :186)                 w = exp(-g) / K"""
+    K = float(K_global)
+    if loss_method == 'variance':
+        E = torch.exp(D)
+        st = torch.stack([E.double().sum(), (E.double() ** 2).sum()])
+        allreduce_sum_(st)
+        mean = st[0] / K
+        loss = (st[1] - K * mean * mean) / (K - 1.0)
+        w = (2.0 / (K - 1.0)) * (E - mean.float()) * E
+    else:
+        E = torch.exp(D) if adaptive else torch.exp(D - Yn)     # exp(-g) = exp(D - Y)
+        st = (Yn.double() * E.double()).sum().reshape(1)
+        allreduce_sum_(st)
+        loss = st[0] / K
+        w = E / K
+    w_out.copy_(w)
+    return loss, w_out
 
 
 def y0_gradient(sums, K_global, loss_method, w_local=None):
