@@ -65,7 +65,9 @@ extern "C" {
  *        psp_genl_ul2 / psp_genl_query_ul2 / psp_genl_ul2_stage / psp_genl_rollout_fwd_ul2 -- the u_L2 log of
                          *        that ansatz inside the run-time-shaped forward kernel (PSP_UL2_*); its own size again;
                          *        psp_pinn_config.n_dirs (the former `reserved`) / dirs (appended) -- second-order directions of a
-                         *        dense sigma in the PINN kernels (PSP_GENL_SIGMA_DENSE, PSP_GH_EXPBALL_SIN_FULL) */
+                         *        dense sigma in the PINN kernels (PSP_GENL_SIGMA_DENSE, PSP_GH_EXPBALL_SIN_FULL);
+                         *        PSP_GH_AFFINE_EXP / _SINE_SOURCE / _SINNORM2 (the exit-time and box problems),
+                         *        psp_gen_config.dwell_form (the former `reserved`), PSP_VTRUE_LOGQ / _SINPROD / _SINSUM / _SINR2 */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
@@ -333,9 +335,20 @@ int psp_hjb_control_eval(int32_t d, int32_t H, const float* params, const float*
  * family  h = -2 al y (2 al |x|^2 + d) - e y + nl,  nl = 0 (LIN: problems.py:985, :1130 with e = 1),
  * E - y^2 (SQ: :1022), sin(E - y^2) (SIN: :1058, :1166 with e = 1 and the time term), E = exp(2 al |x|^2 + 2 tau t_n);
  * h_par = {al, d, e, tau}.  SIN_FULL (:1094, the full-Hessian problem; psp_genl_* only): SIN with (sum_i x_i)^2 = sum_ij x_i x_j
- * in place of |x|^2 in the linear term, |x|^2 kept in E */
+ * in place of |x|^2 in the linear term, |x|^2 kept in E
+ *
+ * The exit-time and box problems (problems.py:1220-1730), h_par = {p0, p1, p2, p3} with another meaning per kind:
+ *   AFFINE_EXP   h = p0 + p1 y + p2 |z|^2 + p3 exp(-y);  h_y = p1 - p3 exp(-y), -h_z = -2 p2 z (the stored tangent direction carries
+ *                (-2 p2) dt Z where PSP_GH_QUAD carries dt Z).  DoubleWell_stopping (1, 0, -1/2, 0), _stopping_linear (0, -1, 0, 0),
+ *                _expectation_hitting_time (1, 0, 0, 0), QuadraticGradient (0, 0, 1 / B_00^2, -2)
+ *   SINE_SOURCE  h = c y + s(x), sub-mode p0:  0 (Helmholtz, d >= 2): with S = sin(p1 x_0) sin(p2 x_1), c = p3 (= k^2),
+ *                h = ((c y + p1^2 S) + p2^2 S) - c S;  1 (Oscillations): c = 0, h = p1^2 sin(p1 x_0) + (p2^2 p3) sin(p2 x_0)
+ *   SINNORM2     (dense sigma: psp_genl_* only) with r2 = |x|^2, sx = sum_i x_i, al = p0, d = p1:  p2 != 0 (linear):
+ *                h = al^2 (4 pi^2 sin(pi r2) sx^2 - 2 d pi cos(pi r2));  p2 = 0: h = al^2 (4 pi^2 y sx^2 - 2 d pi cos(pi r2)
+ *                + sin(pi r2)^2 - y^2)
+ * None of the three is built for the adjoint sweep, a running cost or psp_pinn_pairs_*; SINNORM2 not for psp_gen_* */
 enum { PSP_GH_ZERO = 0, PSP_GH_QUAD = 1, PSP_GH_ALLEN_CAHN = 2, PSP_GH_EXPBALL_LIN = 3, PSP_GH_EXPBALL_SQ = 4,
-       PSP_GH_EXPBALL_SIN = 5, PSP_GH_EXPBALL_SIN_FULL = 6 };
+       PSP_GH_EXPBALL_SIN = 5, PSP_GH_EXPBALL_SIN_FULL = 6, PSP_GH_AFFINE_EXP = 7, PSP_GH_SINE_SOURCE = 8, PSP_GH_SINNORM2 = 9 };
 /* exit test of a bounded domain: a trajectory stays active while (solver.py:1119-1129; EllipticSolver :758-767)
  *   SPHERE        |X_n| < dom_a               (the state BEFORE the move, as the reference tests it)
  *   BOX           dom_a <= X_proposal <= dom_b in every coordinate
@@ -360,7 +373,8 @@ typedef struct psp_gen_config {
     int32_t domain_kind;  /* PSP_DOM_*                                                         */
     const float* drift;   /* DOUBLE_WELL: kappa (d); DIAG: a (d); else NULL                  */
     float dom_a, dom_b;   /* sphere radius (dom_a), box bounds X_l, X_r, or annulus radii r_1, r_2 */
-    float h_par[4];       /* PSP_GH_EXPBALL_*: al, d (the REAL dimension, not a padded one), e, tau */
+    float h_par[4];       /* PSP_GH_EXPBALL_*: al, d (the REAL dimension, not a padded one), e, tau; PSP_GH_AFFINE_EXP,
+                           * _SINE_SOURCE, _SINNORM2: p0 .. p3 as listed at the enum                     */
     int32_t d_real;       /* components the exit test and |x|^2 read when d is a zero-padded instance (0: all d);
                            * the padding carries device noise, which nothing else ever reads                */
     int32_t mlp_dtype;    /* PSP_MLP_FP32 (0); PSP_MLP_BF16_FWD: the value-net products of the forward rollout (V, grad_x V,
@@ -380,7 +394,9 @@ typedef struct psp_gen_config {
     int32_t per_sample_weights; /* psp_gen_rollout_bwd: 1 -> wY is (N+1, 16*ceil(K_local/16)) = weight of the TANGENT part of every
                            * sample (0 in slot N) and `ahat` holds the coefficient of grad_theta V of every sample itself
                            * (wV is ignored): losses with a term at every step.  0: per-trajectory wY, wV as described below     */
-    int32_t reserved;
+    int32_t dwell_form;   /* (the former `reserved`) PSP_DRIFT_DOUBLE_WELL rounding, as psp_is_config.dwell_form: 0 =
+                           * -(4 kappa_i) (x (x^2 - 1)) (the DoubleWell_multidim family), 1 = -((4 kappa_i) x) (x^2 - 1) (the
+                           * exit-time double wells, problems.py:1286); read by the forward rollouts only                      */
     int32_t* range_flag;  /* optional DEVICE int32[4]: range guard of PSP_MLP_F16X3 as in psp_hjb_config.range_flag -- the forward sets
                            * range_flag[0] iff V(X_N) or Y_N of any trajectory is non-finite and enqueues the fp32-MFMA forward
                            * predicated on it; psp_gen_rollout_bwd enqueues both backward kernels, predicated.  NULL: unguarded    */
@@ -877,11 +893,17 @@ int psp_hjb_basis_grad(float* grad, const float* B, int32_t d, int32_t H, void* 
  *     EXP        exp(p0 r2 + p1 t)                                          (exponential on the ball; parabolic: p1 = 1)
  *     QUAD       r2 + p0 (p1 - t)                                           (HeatEquation p0 = 2 d, p1 = T; QuadraticOnBox p0 = 0)
  *     COMMITTOR  (a^2 - r^(2-d) a^d) / (a^2 - c^(2-d) a^d), p0 = a, p1 = c, p2 = d
+ *   and, in a group of its own from 16 on, the forms the kernel also hands the coordinates x_0, x_1:
+ *     LOGQ       log((r2 + 1) / p0)                                         (QuadraticGradient, p0 = d)
+ *     SINPROD    sin(p0 x_0) sin(p1 x_1)                                    (Helmholtz, p0 = a_1 pi, p1 = a_2 pi; d >= 2)
+ *     SINSUM     sin(p0 x_0) + p2 sin(p1 x_0)                               (Oscillations, p0 = 2 pi, p1 = a pi, p2 = 0.1)
+ *     SINR2      sin(pi r2)                                                 (SinNorm2)
  * log_out[4 slot .. 4 slot + 3] = sum e^2, sum |e|, sum |e| / v_true, count over the kept points, e = v_true - V, in fp64
  * (per-workgroup partials summed in a fixed order: equal arguments give bit-identical output).
  * ------------------------------------------------------------------------------------------------ */
 enum { PSP_TSAMPLE_SUPPLIED = 0, PSP_TSAMPLE_BALL = 1, PSP_TSAMPLE_ANNULUS = 2, PSP_TSAMPLE_BOX = 3 };
-enum { PSP_VTRUE_EXP = 0, PSP_VTRUE_QUAD = 1, PSP_VTRUE_COMMITTOR = 2 };
+enum { PSP_VTRUE_EXP = 0, PSP_VTRUE_QUAD = 1, PSP_VTRUE_COMMITTOR = 2,
+       PSP_VTRUE_LOGQ = 16, PSP_VTRUE_SINPROD = 17, PSP_VTRUE_SINSUM = 18, PSP_VTRUE_SINR2 = 19 };   /* 3 .. 15 are no kind */
 
 typedef struct psp_genl_eval_config {
     int32_t d;                /* state dimension                                                                                 */
@@ -969,7 +991,9 @@ typedef struct psp_pinn_config {
     int32_t drift_kind;       /* PSP_DRIFT_ZERO, PSP_DRIFT_DIAG or PSP_DRIFT_DOUBLE_WELL                                       */
     int32_t h_kind;           /* PSP_GH_ZERO .. PSP_GH_EXPBALL_SIN_FULL, as psp_gen_config.h_kind; h must not read t
                                * (h_par[3] = 0; psp_pinn_pairs_* below take one that does); PSP_GH_EXPBALL_SIN_FULL on either
-                               * sigma_kind; no PSP_GH_QUAD with _DENSE                                                          */
+                               * sigma_kind; no PSP_GH_QUAD with _DENSE.  PSP_GH_AFFINE_EXP and PSP_GH_SINE_SOURCE (h_par = p0 ..
+                               * p3: no time term; refused by psp_pinn_pairs_*; AFFINE_EXP with p2 != 0 reads z: not with _DENSE);
+                               * PSP_GH_SINNORM2 is not built here                                                               */
     int32_t sigma_kind;       /* PSP_GENL_SIGMA_SCALED: sigma = s I, the Laplacian; PSP_GENL_SIGMA_DENSE: the table `dirs`       */
     int32_t n_dirs;           /* PSP_GENL_SIGMA_DENSE: rows of `dirs`, 1 .. d; ignored with _SCALED                             */
     float sigma_scale;        /* s (PSP_GENL_SIGMA_SCALED)                                                                      */

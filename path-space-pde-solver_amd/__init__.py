@@ -14,7 +14,10 @@ from .problems import (LLGC, LQGC, AllenCahn, DoubleWell, DoubleWell_multidim,  
                        DoubleWell_multidim_for_general_solver, HeatEquation, ExponentialOnSphere,
                        ExponentialOnBallNonlinear, ExponentialOnBallNonlinearSin,
                        ExponentialOnBallNonlinearSinHessian,
-                       ExponentialOnSphereNonlinearParabolic, QuadraticOnBox, Committor)
+                       ExponentialOnSphereNonlinearParabolic, QuadraticOnBox, Committor,
+                       ExponentialOnSphereParabolic, DoubleWell_stopping, DoubleWell_stopping_linear,
+                       DoubleWell_expectation_hitting_time, Committor_DoubleWell, QuadraticGradient, Helmholtz, Oscillations,
+                       SinNorm2)
 from .solver import Solver  # noqa: F401
 from .general_solver import GeneralSolver, EllipticSolver  # noqa: F401
 from .plan_native import PlanUnsupported  # noqa: F401
@@ -26,4 +29,6 @@ from .utilities import do_importance_sampling_me  # noqa: F401
 __all__ = ['Solver', 'GeneralSolver', 'EllipticSolver', 'ExponentialOnSphere', 'ExponentialOnBallNonlinear',
            'ExponentialOnBallNonlinearSin', 'ExponentialOnBallNonlinearSinHessian', 'ExponentialOnSphereNonlinearParabolic', 'QuadraticOnBox', 'Committor', 'LLGC', 'LQGC', 'DoubleWell', 'DoubleWell_multidim', 'DoubleWell_multidim_for_general_solver',
            'AllenCahn', 'HeatEquation', 'MySequential', 'DenseNet', 'DenseNet_tanh', 'DenseNet_tanh_2', 'SingleParam',
-           'Constant', 'Linear', 'Affine', 'PlanUnsupported', 'native']
+           'Constant', 'Linear', 'Affine', 'PlanUnsupported', 'native', 'ExponentialOnSphereParabolic', 'DoubleWell_stopping',
+           'DoubleWell_stopping_linear', 'DoubleWell_expectation_hitting_time', 'Committor_DoubleWell', 'QuadraticGradient',
+           'Helmholtz', 'Oscillations', 'SinNorm2']

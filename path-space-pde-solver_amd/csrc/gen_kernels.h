@@ -15,7 +15,34 @@
 
 namespace psp {
 
-enum { GH_ZERO = 0, GH_QUAD = 1, GH_ALLEN_CAHN = 2, GH_EXPBALL_LIN = 3, GH_EXPBALL_SQ = 4, GH_EXPBALL_SIN = 5 };
+enum { GH_ZERO = 0, GH_QUAD = 1, GH_ALLEN_CAHN = 2, GH_EXPBALL_LIN = 3, GH_EXPBALL_SQ = 4, GH_EXPBALL_SIN = 5,
+       // (6 = GH_EXPBALL_SIN_FULL, genl_kernels.h) the exit-time and box problems (include/psp.h), h_par = p0 .. p3:
+       GH_AFFINE_EXP = 7,      // h = p0 + p1 y + p2 |z|^2 + p3 exp(-y)
+       GH_SINE_SOURCE = 8,     // h = c y + s(x_0, x_1): Helmholtz (p0 = 0), Oscillations (p0 = 1)
+       GH_SINNORM2 = 9 };      // SinNorm2.h, from |x|^2 and sum_i x_i (dense sigma: genl_kernels.h only)
+// the kinds whose h reads |x|^2
+__host__ __device__ inline bool gh_reads_r2(int kind) { return kind >= GH_EXPBALL_LIN && kind != GH_AFFINE_EXP && kind != GH_SINE_SOURCE; }
+
+// GH_AFFINE_EXP (problems.py:1301, :1393, :1488, :1605): -h and h_y from y = V(X) and S = |z|^2; exp only where p3 asks for it
+__device__ inline void gh_affine_exp(const float* p, float y, float S, float& minus_h, float& hy) {
+    float e = 0.f;
+    if (p[3] != 0.f) e = p[3] * expf(-y);
+    minus_h = -(((p[2] * S + p[0]) + p[1] * y) + e);
+    hy = p[1] - e;
+}
+// GH_SINE_SOURCE (problems.py:1646-1648, :1687), the terms summed in the order written there.  A squared coefficient meets its
+// sine one factor at a time, p (p s): a product of two launch constants is loop-invariant, would be hoisted out of the time loop
+// into a register of its own and from there -- the split-product instance of d = 100 has none to spare -- into scratch
+__device__ inline void gh_sine_source(const float* p, float y, float x0, float x1, float& minus_h, float& hy) {
+    if (p[0] == 0.f) {
+        const float c = p[3], s1 = sinf(p[1] * x0), s2 = sinf(p[2] * x1);
+        minus_h = -(((c * y + (p[1] * (p[1] * s1)) * s2) + (p[2] * (p[2] * s1)) * s2) - (c * s1) * s2);
+        hy = c;
+    } else {
+        minus_h = -(p[1] * (p[1] * sinf(p[1] * x0)) + p[2] * (p[2] * (p[3] * sinf(p[2] * x0))));
+        hy = 0.f;
+    }
+}
 // exit test of a bounded domain (solver.py:1119-1129, :758-767): sphere |X_n| < a (the state BEFORE the move), boxes on the proposal,
 // annulus a < |X_n| < b ('two_spheres', :1122-1123 / :752-753; the state before the move).  'square-corner' (:759-760) tests
 // any(X_proposal <= X_r): that is DOM_BOX_UPPER_ANY
@@ -52,6 +79,8 @@ struct GenArgs {
     uint32_t seed_lo, seed_hi, iter;
     const int* cond;      // launch predicate of the guarded split-product mode (hjb_kernels.h PSP_COND_EXIT)
     int cond_want;
+    int dwell_form;       // DRIFT_DWELL rounding: 0 = -(4 kappa) (x (x^2 - 1)), 1 = -((4 kappa) x) (x^2 - 1) (psp_gen_config.dwell_form);
+                          // it sits in what was the padding behind cond_want, so every other field keeps its offset
     unsigned long long* dbg;   // diagnostic builds (-DPSP_STAMPS): per-wave cycle sums of gen_bwd2_kernel (tools/r4/gen_stamps.py)
 };
 
@@ -176,7 +205,7 @@ __global__ __launch_bounds__(512) void gen_fwd_kernel(const GenArgs a_) {
     GenArgs a = a_;
     if constexpr (SPEC) {
         a.drift_kind = SPECK & 15; a.h_kind = (SPECK >> 4) & 15; a.domain_kind = DOM_NONE; a.adaptive = 0; a.store_path = 1;
-        a.Vsteps = nullptr; a.Ysteps = nullptr;
+        a.Vsteps = nullptr; a.Ysteps = nullptr; a.dwell_form = 0;
     }
     using G = GGeo<D, H>;
     constexpr int DI = G::DI, DBI = G::DBI, KSI = G::KSI, HB = G::HB, KSH = G::KSH;
@@ -361,14 +390,16 @@ __global__ __launch_bounds__(512) void gen_fwd_kernel(const GenArgs a_) {
             auto move_block = [&](int b, const f32x4& Z, const f32x4& xi) __attribute__((always_inline)) {
                 const f32x4 cdt = a.adaptive ? (-dt) * Z : 0.f * Z;
                 f32x4 drift = 0.f * Z;
-                if (a.drift_kind == DRIFT_DWELL) drift = -(4.0f * vdr[b * 4] * (X[b] * (X[b] * X[b] - 1.0f)));
-                else if (a.drift_kind == DRIFT_DIAG) drift = vdr[b * 4] * X[b];          // b(x) = diag(a) x (problems.py:36-37 with a diagonal A)
+                if (a.drift_kind == DRIFT_DWELL) {
+                    if (a.dwell_form) drift = -(((4.0f * vdr[b * 4]) * X[b]) * (X[b] * X[b] - 1.0f));      // problems.py:1286
+                    else drift = -(4.0f * vdr[b * 4] * (X[b] * (X[b] * X[b] - 1.0f)));
+                } else if (a.drift_kind == DRIFT_DIAG) drift = vdr[b * 4] * X[b];          // b(x) = diag(a) x (problems.py:36-37 with a diagonal A)
                 const f32x4 step = (drift * dt + sig * cdt + (sig * sqdt) * xi) * alivef;
                 return step;
             };
             // ---- exit test of a bounded domain (solver.py:1119-1129; EllipticSolver :758-767) and |x|^2 for the x-dependent h
             float rr = 0.f;
-            if (a.domain_kind == DOM_SPHERE || a.domain_kind == DOM_ANNULUS || a.h_kind >= GH_EXPBALL_LIN) {
+            if (a.domain_kind == DOM_SPHERE || a.domain_kind == DOM_ANNULUS || gh_reads_r2(a.h_kind)) {
 #pragma unroll
                 for (int b = 0; b < DBI; ++b)
 #pragma unroll
@@ -402,6 +433,10 @@ __global__ __launch_bounds__(512) void gen_fwd_kernel(const GenArgs a_) {
                 n_out = qsum(n_out); n_le = qsum(n_le);
                 inside = a.domain_kind == DOM_BOX_UPPER_ANY ? n_le > 0.f : n_out == 0.f;
             }
+            // GH_SINE_SOURCE reads coordinates 0 and 1 of the state BEFORE the move: this lane's X[0][0] (lane q holds coordinate q)
+            // crosses the Euler step in rr, which the kind does not read and the exit tests above are done with -- no register of
+            // its own in the loop (two more spilled the split-product instance of d = 100)
+            if (a.h_kind == GH_SINE_SOURCE) rr = X[0][0];
             const bool in_time = inside && (t + dt) <= Tend;         // new_selection of solver.py:1119-1131 (fp32)
             const bool act = in_time && !stopped;
             const float actf = act ? 1.f : 0.f;
@@ -421,6 +456,10 @@ __global__ __launch_bounds__(512) void gen_fwd_kernel(const GenArgs a_) {
                 // tangent direction u^ = act ((-h_z + c) dt + xi sqrt(dt)),  -h_z = Z for h = -|z|^2/2
                 f32x4 u = sqdt * xi + cdt;
                 if (a.h_kind == GH_QUAD) u += dt * Z;
+                else if (a.h_kind == GH_AFFINE_EXP) {                // -h_z = -2 p2 z.  (Every product has Z in it: the coefficient
+                    const f32x4 pz = a.h_par[2] * Z;                  //  -2 p2 dt alone is loop-invariant and would sit in a register
+                    u -= dt * (pz + pz);                              //  of its own all through the time loop)
+                }
                 U[b] = (actf * sig) * u;
                 const f32x4 step = move_block(b, Z, xi);
                 f32x4 Xn;
@@ -451,6 +490,9 @@ __global__ __launch_bounds__(512) void gen_fwd_kernel(const GenArgs a_) {
             float minus_h = 0.f, hy = 0.f;
             if (a.h_kind == GH_QUAD) minus_h = 0.5f * S;
             else if (a.h_kind == GH_ALLEN_CAHN) { minus_h = -(Vnow - Vnow * Vnow * Vnow); hy = 1.0f - 3.0f * Vnow * Vnow; }
+            else if (a.h_kind == GH_AFFINE_EXP) gh_affine_exp(a.h_par, Vnow, S, minus_h, hy);
+            else if (a.h_kind == GH_SINE_SOURCE)
+                gh_sine_source(a.h_par, Vnow, qsum(q == 0 ? rr : 0.f), qsum(q == 1 ? rr : 0.f), minus_h, hy);
             else if (a.h_kind >= GH_EXPBALL_LIN) {
                 // h = -2 al y (2 al |x|^2 + d) - e y + {0, E - y^2, sin(E - y^2)},  E = exp(2 al |x|^2 + 2 t), t = n dt
                 // (problems.py:985, :1022, :1058, :1130, :1166; h sees y = V(X,t), solver.py:1141)

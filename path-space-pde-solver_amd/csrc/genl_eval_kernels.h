@@ -27,7 +27,13 @@
 namespace psp {
 
 enum { TS_SUPPLIED = 0, TS_BALL = 1, TS_ANNULUS = 2, TS_BOX = 3 };
-enum { VT_EXP = 0, VT_QUAD = 1, VT_COMMITTOR = 2 };
+enum { VT_EXP = 0, VT_QUAD = 1, VT_COMMITTOR = 2,
+       // the solutions of the exit-time and box problems (problems.py:1611, :1654, :1693, :1730), a group of its own from 16 on:
+       // the kernel hands them the coordinates x_0, x_1 beside r2
+       VT_LOGQ = 16,                   // log((r2 + 1) / p0)
+       VT_SINPROD = 17,                // sin(p0 x_0) sin(p1 x_1)
+       VT_SINSUM = 18,                 // sin(p0 x_0) + p2 sin(p1 x_0)
+       VT_SINR2 = 19 };                // sin(pi r2)
 constexpr uint32_t kTestKeyXor = 0x54455354u;
 constexpr int kEvalStats = 4;
 
@@ -133,6 +139,8 @@ __global__ __launch_bounds__(64 * NW) void genl_eval_kernel(const GenlEvalArgs e
     r2d += __shfl_xor(r2d, 32);
     const float r2 = (float)r2d;
     const bool keep = kvalid && (kind != TS_ANNULUS || sqrtf(r2) > ea->lo);
+    // coordinates 0 and 1 (lanes q = 0, 1; taken before the time joins the image: with d = 1 it is feature 1)
+    const float xc0 = qsum(q == 0 ? X[0][0] : 0.f), xc1 = qsum(q == 1 ? X[0][0] : 0.f);
 
     if (w0) {                                                        // dumps: the points as the net sees them
         if (ea->x_out && kvalid) {
@@ -173,6 +181,14 @@ __global__ __launch_bounds__(64 * NW) void genl_eval_kernel(const GenlEvalArgs e
         vt = expf(fmaf(ea->vp[0], r2, ea->vp[1] * tval));
     } else if (ea->vtrue_kind == VT_QUAD) {
         vt = r2 + ea->vp[0] * (ea->vp[1] - tval);
+    } else if (ea->vtrue_kind == VT_LOGQ) {
+        vt = logf((r2 + 1.0f) / ea->vp[0]);
+    } else if (ea->vtrue_kind == VT_SINPROD) {
+        vt = sinf(ea->vp[0] * xc0) * sinf(ea->vp[1] * xc1);
+    } else if (ea->vtrue_kind == VT_SINSUM) {
+        vt = sinf(ea->vp[0] * xc0) + ea->vp[2] * sinf(ea->vp[1] * xc0);
+    } else if (ea->vtrue_kind == VT_SINR2) {
+        vt = sinf(3.14159265358979323846f * r2);
     } else {
         const float a2 = ea->vp[0] * ea->vp[0];
         const float delta = (float)(r2d - (double)ea->vp[0] * (double)ea->vp[0]);

@@ -75,6 +75,18 @@ enum { GACT_RELU2 = 0, GACT_TANH2 = 1, GACT_TANH = 2 };
 // h of ExponentialOnBallNonlinearSinHessian (problems.py:1094): GH_EXPBALL_SIN with (sum_i x_i)^2 = sum_ij x_i x_j in the linear
 // term, |x|^2 kept in the exponent.  Served by the dense-sigma instances of the forward kernel only.
 constexpr int GH_EXPBALL_SIN_FULL = 6;
+// GH_SINNORM2 (problems.py:1721-1724; the dense-sigma instances again: they form sx = sum_i x_i), h_par = (al, d, linear, -)
+__device__ inline void gh_sinnorm2(const float* p, float y, float rr, float sx, float& minus_h, float& hy) {
+    const float pi = 3.14159265358979323846f, a2 = p[0] * p[0], fp2 = 4.0f * (pi * pi), s = sinf(pi * rr);
+    const float cs = ((2.0f * p[1]) * pi) * cosf(pi * rr);
+    if (p[2] != 0.f) {
+        minus_h = -(a2 * ((fp2 * s) * (sx * sx) - cs));
+        hy = 0.f;
+    } else {
+        minus_h = -(a2 * (((((fp2 * y) * (sx * sx)) - cs) + s * s) - y * y));
+        hy = a2 * (fp2 * (sx * sx) - 2.0f * y);
+    }
+}
 
 // per-NW register-array bounds: hidden blocks per wave (HBsum <= 32; NW = 1 only for HBsum <= 8), concatenation blocks per wave
 // (TB <= 39; NW = 1 only for TB <= 16)
@@ -522,8 +534,10 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
         auto move_block = [&](int b, const f32x4& Z, const f32x4& xi) __attribute__((always_inline)) {
             const f32x4 cdt = a->adaptive ? (-dt) * Z : 0.f * Z;
             f32x4 drift = 0.f * Z;
-            if (a->drift_kind == DRIFT_DWELL) drift = -(4.0f * drift_vec(b) * (X[b] * (X[b] * X[b] - 1.0f)));
-            else if (a->drift_kind == DRIFT_DIAG) drift = drift_vec(b) * X[b];
+            if (a->drift_kind == DRIFT_DWELL) {
+                if (a->dwell_form) drift = -(((4.0f * drift_vec(b)) * X[b]) * (X[b] * X[b] - 1.0f));       // problems.py:1286
+                else drift = -(4.0f * drift_vec(b) * (X[b] * (X[b] * X[b] - 1.0f)));
+            } else if (a->drift_kind == DRIFT_DIAG) drift = drift_vec(b) * X[b];
             if constexpr (DENSE) return (drift * dt + img_get(G, b, lane)) * alivef;      // B w: formed once per step, below
             return (drift * dt + sig * cdt + (sig * sqdt) * xi) * alivef;
         };
@@ -604,7 +618,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             if (quad || zs) BU = Zi;
         }
         float rr = 0.f, sx = 0.f;
-        if (a->domain_kind == DOM_SPHERE || a->domain_kind == DOM_ANNULUS || a->h_kind >= GH_EXPBALL_LIN) {
+        if (a->domain_kind == DOM_SPHERE || a->domain_kind == DOM_ANNULUS || gh_reads_r2(a->h_kind)) {
 #pragma unroll
             for (int b = 0; b < GENL_MAXDB; ++b)
 #pragma unroll
@@ -641,6 +655,8 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             n_out = qsum(n_out); n_le = qsum(n_le);
             inside = a->domain_kind == DOM_BOX_UPPER_ANY ? n_le > 0.f : n_out == 0.f;
         }
+        // GH_SINE_SOURCE: this lane's X[0][0] of the state before the move (lane q holds coordinate q), carried in rr (gen_kernels.h)
+        if (a->h_kind == GH_SINE_SOURCE) rr = X[0][0];
         const bool in_time = inside && (t + dt) <= Tend;             // new_selection (:1119-1131), fp32
         const bool act = in_time && !stopped;
         const float actf = act ? 1.f : 0.f;
@@ -661,6 +677,10 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
                     const f32x4 cdt = a->adaptive ? (-dt) * Z : 0.f * Z;
                     f32x4 u = sqdt * xi + cdt;                       // u^ = act ((-h_z + c) dt + xi sqrt(dt)), -h_z = Z for h = -|z|^2 / 2
                     if (a->h_kind == GH_QUAD) u += dt * Z;
+                    else if (a->h_kind == GH_AFFINE_EXP) {           // -h_z = -2 p2 z, every product with Z in it (gen_kernels.h)
+                        const f32x4 pz = a->h_par[2] * Z;
+                        u -= dt * (pz + pz);
+                    }
                     U = (actf * sig) * u;
                     step = move_block(b, Z, xi);
                     if constexpr (LOGU) Zlog = Z;
@@ -713,7 +733,12 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
         float minus_h = 0.f, hy = 0.f;                               // Y update (solver.py:1141-1142): h sees V(X, t), not the running Y
         if (a->h_kind == GH_QUAD) minus_h = 0.5f * S;
         else if (a->h_kind == GH_ALLEN_CAHN) { minus_h = -(Vnow - Vnow * Vnow * Vnow); hy = 1.0f - 3.0f * Vnow * Vnow; }
-        else if (a->h_kind >= GH_EXPBALL_LIN) {
+        else if (a->h_kind == GH_AFFINE_EXP) gh_affine_exp(a->h_par, Vnow, S, minus_h, hy);
+        else if (a->h_kind == GH_SINE_SOURCE)
+            gh_sine_source(a->h_par, Vnow, qsum(qv == 0 ? rr : 0.f), qsum(qv == 1 ? rr : 0.f), minus_h, hy);
+        else if (a->h_kind == GH_SINNORM2) {
+            if constexpr (DENSE) gh_sinnorm2(a->h_par, Vnow, rr, sx, minus_h, hy);
+        } else if (a->h_kind >= GH_EXPBALL_LIN) {
             const float al = a->h_par[0];
             float rl = rr;                                           // |x|^2, or (sum x)^2 for the full-Hessian problem
             if constexpr (DENSE) { if (a->h_kind == GH_EXPBALL_SIN_FULL) rl = sx * sx; }

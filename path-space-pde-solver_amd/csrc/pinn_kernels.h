@@ -49,7 +49,9 @@ constexpr int kPinnMaxWg = 256;        // partial gradients of the backward kern
 
 enum { PINN_DRIFT_ZERO = 0, PINN_DRIFT_DIAG = 2, PINN_DRIFT_DWELL = 3 };                      // PSP_DRIFT_*
 enum { PINN_H_ZERO = 0, PINN_H_QUAD = 1, PINN_H_ALLEN_CAHN = 2, PINN_H_EXP_LIN = 3, PINN_H_EXP_SQ = 4, PINN_H_EXP_SIN = 5,
-       PINN_H_EXP_SIN_FULL = 6 };      // PSP_GH_*; 6 = GH_EXPBALL_SIN_FULL (genl_kernels.h): (sum_i x_i)^2 in the linear part
+       PINN_H_EXP_SIN_FULL = 6,        // PSP_GH_*; 6 = GH_EXPBALL_SIN_FULL (genl_kernels.h): (sum_i x_i)^2 in the linear part
+       PINN_H_AFFINE_EXP = 7,          // h = p0 + p1 y + p2 |z|^2 + p3 exp(-y), z = s grad V
+       PINN_H_SINE_SOURCE = 8 };       // h = c y + s(x_0, x_1) (gen_kernels.h gh_sine_source, the same arithmetic)
 enum { PINN_ACT_RELU2 = 0, PINN_ACT_TANH2 = 1, PINN_ACT_TANH = 2 };                           // PSP_ACT_*
 
 struct PinnArgs {
@@ -258,12 +260,29 @@ __global__ void pinn_finish_kernel(const PinnArgs a) {
         else if (a.drift_kind == PINN_DRIFT_DIAG) bj = a.drift[j] * xj;
         bg = fmaf(bj, g[j], bg);
         g2 = fmaf(g[j], g[j], g2);
-        cg[j] = a.h_kind == PINN_H_QUAD ? bj - s * s * g[j] : bj;       // h = -|s grad V|^2 / 2
+        // dR / dg_j = b_j + 2 p2 s^2 g_j for h = .. + p2 |s grad V|^2 (PINN_H_QUAD: p2 = -1 / 2)
+        if (a.h_kind == PINN_H_QUAD) cg[j] = bj - s * s * g[j];
+        else if (a.h_kind == PINN_H_AFFINE_EXP) cg[j] = bj + (2.0f * a.h_par[2]) * (s * s) * g[j];
+        else cg[j] = bj;
     }
     float h = 0.f, hy = 0.f;
     if (a.h_kind == PINN_H_QUAD) h = -0.5f * s * s * g2;
     else if (a.h_kind == PINN_H_ALLEN_CAHN) { h = y - y * y * y; hy = 1.0f - 3.0f * y * y; }
-    else if (a.h_kind >= PINN_H_EXP_LIN) {                           // the exponential-on-the-ball family (gen_kernels.h)
+    else if (a.h_kind == PINN_H_AFFINE_EXP) {                        // (g2 = 0 with n_grad = 0: the host refuses p2 != 0 there)
+        float e = 0.f;
+        if (a.h_par[3] != 0.f) e = a.h_par[3] * expf(-y);
+        h = ((a.h_par[2] * (s * s * g2) + a.h_par[0]) + a.h_par[1] * y) + e;
+        hy = a.h_par[1] - e;
+    } else if (a.h_kind == PINN_H_SINE_SOURCE) {
+        const float* p = a.h_par;
+        if (p[0] == 0.f) {
+            const float c = p[3], s1 = sinf(p[1] * x[0]), s2 = sinf(p[2] * x[1]);
+            h = ((c * y + (p[1] * (p[1] * s1)) * s2) + (p[2] * (p[2] * s1)) * s2) - (c * s1) * s2;
+            hy = c;
+        } else {
+            h = p[1] * (p[1] * sinf(p[1] * x[0])) + p[2] * (p[2] * (p[3] * sinf(p[2] * x[0])));
+        }
+    } else if (a.h_kind >= PINN_H_EXP_LIN) {                           // the exponential-on-the-ball family (gen_kernels.h)
         const float al = a.h_par[0];
         const float rl = a.h_kind == PINN_H_EXP_SIN_FULL ? sx * sx : rr;    // the exponent keeps |x|^2
         const float lin = 2.0f * al * (2.0f * al * rl + a.h_par[1]) + a.h_par[2];

@@ -280,6 +280,16 @@ struct GenPlan {
     int ntile16, fwd_waves, fwd_grid, bwd_grid;
 };
 
+// the h kinds of the exit-time and box problems (PSP_GH_AFFINE_EXP, _SINE_SOURCE, _SINNORM2): what their h_par must hold.  d is the
+// number of real coordinates
+int check_gh_par(int32_t h_kind, const float* h_par, int32_t d) {
+    if (h_kind == PSP_GH_SINE_SOURCE) {
+        if (h_par[0] != 0.f && h_par[0] != 1.f) return fail(-1, "PSP_GH_SINE_SOURCE: the sub-mode h_par[0] is 0 (Helmholtz) or 1 (Oscillations)");
+        if (h_par[0] == 0.f && d < 2) return fail(-1, "PSP_GH_SINE_SOURCE: sub-mode 0 reads the coordinates x_0 and x_1 (d >= 2)");
+    }
+    return 0;
+}
+
 int make_gen_plan(const psp_gen_config* c, GenPlan* p) {
     if (!c) return fail(-1, "null config");
     if (c->d <= 0 || c->H <= 0 || c->K_local <= 0 || c->N <= 0) return fail(-1, "non-positive d/H/K/N");
@@ -288,9 +298,10 @@ int make_gen_plan(const psp_gen_config* c, GenPlan* p) {
         return -2;
     }
     if ((c->drift_kind != PSP_DRIFT_ZERO && c->drift_kind != PSP_DRIFT_DOUBLE_WELL && c->drift_kind != PSP_DRIFT_DIAG) || c->h_kind < 0 ||
-        c->h_kind > PSP_GH_EXPBALL_SIN || c->noise_mode < 0 || c->noise_mode > 1 || c->domain_kind < 0 ||
-        c->domain_kind > PSP_DOM_ANNULUS)
+        c->h_kind > PSP_GH_SINE_SOURCE || c->h_kind == PSP_GH_EXPBALL_SIN_FULL || c->noise_mode < 0 || c->noise_mode > 1 ||
+        c->domain_kind < 0 || c->domain_kind > PSP_DOM_ANNULUS)        // (_SIN_FULL and _SINNORM2 read sum_i x_i: psp_genl_* only)
         return fail(-1, "config enum out of range");
+    if (int rc = check_gh_par(c->h_kind, c->h_par, (c->d_real > 0 && c->d_real < c->d) ? c->d_real : c->d)) return rc;
     if (c->domain_kind == PSP_DOM_SPHERE && !(c->dom_a > 0.f)) return fail(-1, "sphere radius must be positive");
     if (c->domain_kind == PSP_DOM_BOX && !(c->dom_a < c->dom_b)) return fail(-1, "box bounds must satisfy X_l < X_r");
     if (c->domain_kind == PSP_DOM_ANNULUS && !(c->dom_a >= 0.f && c->dom_a < c->dom_b)) return fail(-1, "annulus radii must satisfy 0 <= r_1 < r_2");
@@ -326,6 +337,7 @@ void fill_gen_args(const psp_gen_config* c, const GenPlan& p, psp::GenArgs* a) {
     for (int i = 0; i < 4; ++i) a->h_par[i] = c->h_par[i];
     a->Vsteps = c->v_steps_out; a->Ysteps = c->y_steps_out; a->per_sample = c->per_sample_weights ? 1 : 0;
     a->path16 = (c->mlp_dtype == PSP_MLP_BF16) ? 1 : 0;       // both kernels on bf16 MFMA: bf16-pair path block
+    a->dwell_form = c->dwell_form ? 1 : 0;
 }
 
 // ---- small kernels -------------------------------------------------------------------
@@ -1482,9 +1494,13 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs*
     const int D0 = b.d + (c->has_time ? 1 : 0);
     if (D0 > 16 * psp::GENL_MAXDB) return fail(-2, "value net: input width above 112");
     if ((b.drift_kind != PSP_DRIFT_ZERO && b.drift_kind != PSP_DRIFT_DOUBLE_WELL && b.drift_kind != PSP_DRIFT_DIAG) || b.h_kind < 0 ||
-        b.h_kind > PSP_GH_EXPBALL_SIN_FULL || b.noise_mode < 0 || b.noise_mode > 1 || b.domain_kind < 0 || b.domain_kind > PSP_DOM_ANNULUS ||
+        b.h_kind > PSP_GH_SINNORM2 || b.noise_mode < 0 || b.noise_mode > 1 || b.domain_kind < 0 || b.domain_kind > PSP_DOM_ANNULUS ||
         c->sigma_kind < PSP_GENL_SIGMA_SCALED || c->sigma_kind > PSP_GENL_SIGMA_DENSE)
         return fail(-1, "config enum out of range");
+    if ((b.h_kind == PSP_GH_AFFINE_EXP || b.h_kind == PSP_GH_SINE_SOURCE) && (c->sigma_kind == PSP_GENL_SIGMA_DENSE || q))
+        return fail(-1, "PSP_GH_AFFINE_EXP / PSP_GH_SINE_SOURCE are built for sigma = s I without psp_genl_coeffs");
+    if (b.h_kind == PSP_GH_SINNORM2 && q) return fail(-1, "PSP_GH_SINNORM2 is not built for psp_genl_coeffs");
+    if (int rc = check_gh_par(b.h_kind, b.h_par, b.d)) return rc;
     if (c->sigma_kind == PSP_GENL_SIGMA_DENSE && !c->sigma) return fail(-1, "sigma matrix missing");
     if (c->activation < 0 || c->activation > PSP_ACT_TANH) return fail(-1, "value net: unknown activation");
     if (b.domain_kind == PSP_DOM_SPHERE && !(b.dom_a > 0.f)) return fail(-1, "sphere radius must be positive");
@@ -1525,7 +1541,7 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs*
     a.vW = tofs; tofs += (long long)blocks * 16;
     // a dense sigma -- or the h of the full-Hessian problem, whose (sum x)^2 only the dense-sigma instances of the forward kernel
     // form (with a scaled identity the tables kernel writes s I) -- adds the tables of B and B^T
-    a.dense = (c->sigma_kind == PSP_GENL_SIGMA_DENSE || b.h_kind == PSP_GH_EXPBALL_SIN_FULL) ? 1 : 0;
+    a.dense = (c->sigma_kind == PSP_GENL_SIGMA_DENSE || b.h_kind == PSP_GH_EXPBALL_SIN_FULL || b.h_kind == PSP_GH_SINNORM2) ? 1 : 0;
     a.sigmaB = c->sigma_kind == PSP_GENL_SIGMA_DENSE ? c->sigma : nullptr;
     if (q) {                                                                     // (they run on the dense path: s I through the tables)
         a.dense = 1; a.lq = 1;
@@ -1593,6 +1609,7 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs*
     g.noise_mode = b.noise_mode; g.store_path = b.store_path;
     g.domain_kind = b.domain_kind; g.dom_a = b.dom_a; g.dom_b = b.dom_b; g.d_real = b.d;
     for (int i = 0; i < 4; ++i) g.h_par[i] = b.h_par[i];
+    g.dwell_form = b.dwell_form ? 1 : 0;
     return 0;
 }
 // the step counts of the tiles live behind the (N + 1) x 16 ceil(K/16) coefficients of `ahat`
@@ -1793,8 +1810,11 @@ int make_eval_plan(const psp_genl_eval_config* c, EvalPlan* e) {
     if (c->k_offset < 0 || c->k_offset + (int64_t)c->K_points > (1LL << 32)) return fail(-1, "k_offset + K_points must stay within 2^32");
     if (c->sample_kind < PSP_TSAMPLE_SUPPLIED || c->sample_kind > PSP_TSAMPLE_BOX)
         return fail(-1, "sample_kind out of range (PSP_TSAMPLE_SUPPLIED, _BALL, _ANNULUS, _BOX)");
-    if (c->vtrue_kind < PSP_VTRUE_EXP || c->vtrue_kind > PSP_VTRUE_COMMITTOR)
-        return fail(-1, "vtrue_kind out of range (PSP_VTRUE_EXP, _QUAD, _COMMITTOR)");
+    if (c->vtrue_kind < PSP_VTRUE_EXP || c->vtrue_kind > PSP_VTRUE_SINR2 ||
+        (c->vtrue_kind > PSP_VTRUE_COMMITTOR && c->vtrue_kind < PSP_VTRUE_LOGQ))
+        return fail(-1, "vtrue_kind out of range (PSP_VTRUE_EXP, _QUAD, _COMMITTOR; _LOGQ, _SINPROD, _SINSUM, _SINR2)");
+    if (c->vtrue_kind == PSP_VTRUE_LOGQ && !(c->vtrue_par[0] > 0.f)) return fail(-1, "PSP_VTRUE_LOGQ: the divisor p0 must be positive");
+    if (c->vtrue_kind == PSP_VTRUE_SINPROD && c->d < 2) return fail(-1, "PSP_VTRUE_SINPROD reads the coordinates x_0 and x_1 (d >= 2)");
     if (c->sample_kind == PSP_TSAMPLE_BALL && !(c->bound_b > 0.f)) return fail(-1, "ball radius must be positive");
     if (c->sample_kind == PSP_TSAMPLE_ANNULUS && !(c->bound_a >= 0.f && c->bound_a < c->bound_b))
         return fail(-1, "annulus radii must satisfy 0 <= r_1 < r_2");
@@ -2034,14 +2054,19 @@ int make_pinn_plan(const psp_pinn_config* c, PinnPlan* p, bool pairs = false) {
     if (c->drift_kind != PSP_DRIFT_ZERO && c->drift_kind != PSP_DRIFT_DIAG && c->drift_kind != PSP_DRIFT_DOUBLE_WELL)
         return fail(-1, "psp_pinn: drift_kind must be PSP_DRIFT_ZERO, _DIAG or _DOUBLE_WELL");
     if (c->drift_kind != PSP_DRIFT_ZERO && !c->drift) return fail(-1, "psp_pinn: this drift_kind needs the drift vector");
-    if (c->h_kind < PSP_GH_ZERO || c->h_kind > PSP_GH_EXPBALL_SIN_FULL) return fail(-1, "psp_pinn: h_kind out of range");
-    if (!pairs && c->h_kind >= PSP_GH_EXPBALL_LIN && c->h_par[3] != 0.f) return fail(-1, "psp_pinn: an h that reads t is not built");
+    if (c->h_kind < PSP_GH_ZERO || c->h_kind > PSP_GH_SINNORM2) return fail(-1, "psp_pinn: h_kind out of range");
+    if (c->h_kind == PSP_GH_SINNORM2) return fail(-1, "psp_pinn: PSP_GH_SINNORM2 is not built in the PINN kernels");
+    const bool catalogue = c->h_kind == PSP_GH_AFFINE_EXP || c->h_kind == PSP_GH_SINE_SOURCE;      // their h_par is no (al, d, e, tau)
+    if (pairs && catalogue) return fail(-1, "psp_pinn_pairs: PSP_GH_AFFINE_EXP / PSP_GH_SINE_SOURCE do not read t; use psp_pinn_*");
+    if (int rc = check_gh_par(c->h_kind, c->h_par, c->d)) return rc;
+    if (!pairs && !catalogue && c->h_kind >= PSP_GH_EXPBALL_LIN && c->h_par[3] != 0.f) return fail(-1, "psp_pinn: an h that reads t is not built");
     if (pairs) {
         if (c->h_kind >= PSP_GH_EXPBALL_LIN && c->h_par[3] != 0.f && c->h_kind != PSP_GH_EXPBALL_SQ && c->h_kind != PSP_GH_EXPBALL_SIN)
             return fail(-1, "psp_pinn_pairs: only PSP_GH_EXPBALL_SQ and PSP_GH_EXPBALL_SIN read t (h_par[3] != 0)");
         if (c->K > psp::kPinnPairMaxK) return fail(-1, "psp_pinn_pairs: K above 16384 (K^2 pairs per iteration)");
     }
-    if (dense && c->h_kind == PSP_GH_QUAD) return fail(-1, "psp_pinn: an h that reads z = B grad V is not built for dense directions");
+    if (dense && (c->h_kind == PSP_GH_QUAD || (c->h_kind == PSP_GH_AFFINE_EXP && c->h_par[2] != 0.f)))
+        return fail(-1, "psp_pinn: an h that reads z = B grad V is not built for dense directions");
     // the gradient directions are dropped where nothing reads grad V: no drift, no time input, an h that does not read z
     const int n_hess = dense ? c->n_dirs : 0;
     const int n_grad = (dense && c->drift_kind == PSP_DRIFT_ZERO && !c->has_time) ? 0 : n_in;

@@ -37,6 +37,9 @@ def eval_reason(problem):
     """Why the device test log cannot serve this problem (its solution or its domain), else None."""
     fn = getattr(problem, 'native_vtrue_spec', None)
     if fn is None:
+        if hasattr(problem, 'psi') or hasattr(type(problem), 'compute_reference_solution'):
+            return ('problem has no native_vtrue_spec(): its v_true reads a table (compute_reference_solution()); the device '
+                    'test log has closed forms only, the table stays on the host log')
         return 'problem has no native_vtrue_spec() (no closed-form v_true in the native catalogue)'
     if coefficients_overridden(problem, names=('v_true',)) is not None:
         return 'problem.v_true is not the catalogue implementation native_vtrue_spec() describes'

@@ -25,6 +25,7 @@ ISC_NONE, ISC_TABLE, ISC_LINEAR, ISC_GRID = 0, 1, 2, 3
 IS_MAX_D = 64                     # native range of psp_is_rollout (include/psp.h)
 NOISE_SUPPLIED, NOISE_PHILOX = 0, 1
 GH_ZERO, GH_QUAD, GH_ALLEN_CAHN, GH_EXPBALL_LIN, GH_EXPBALL_SQ, GH_EXPBALL_SIN, GH_EXPBALL_SIN_FULL = 0, 1, 2, 3, 4, 5, 6
+GH_AFFINE_EXP, GH_SINE_SOURCE, GH_SINNORM2 = 7, 8, 9     # p0 + p1 y + p2 |z|^2 + p3 exp(-y); c y + s(x); SinNorm2.h (dense sigma)
 GENL_SIGMA_SCALED, GENL_SIGMA_DENSE = 0, 1      # psp_genl_config.sigma_kind
 MLP_FP32, MLP_BF16_FWD, MLP_BF16, MLP_F16X3 = 0, 1, 2, 3
 DT_F32, DT_F64 = 0, 1
@@ -33,6 +34,7 @@ DOM_NONE, DOM_SPHERE, DOM_BOX, DOM_BOX_UPPER_ALL, DOM_BOX_UPPER_ANY, DOM_ANNULUS
 ACT_RELU2, ACT_TANH2, ACT_TANH = 0, 1, 2
 TSAMPLE_SUPPLIED, TSAMPLE_BALL, TSAMPLE_ANNULUS, TSAMPLE_BOX = 0, 1, 2, 3     # psp_genl_eval_config.sample_kind
 VTRUE_EXP, VTRUE_QUAD, VTRUE_COMMITTOR = 0, 1, 2                              # psp_genl_eval_config.vtrue_kind
+VTRUE_LOGQ, VTRUE_SINPROD, VTRUE_SINSUM, VTRUE_SINR2 = 16, 17, 18, 19         # ... the group that also sees x_0, x_1
 
 
 class NativeLibraryError(RuntimeError):
@@ -83,7 +85,7 @@ class GenConfig(C.Structure):
         ("dom_a", C.c_float), ("dom_b", C.c_float), ("h_par", C.c_float * 4),
         ("d_real", C.c_int32), ("mlp_dtype", C.c_int32),
         ("v_steps_out", C.c_void_p), ("y_steps_out", C.c_void_p),
-        ("per_sample_weights", C.c_int32), ("reserved", C.c_int32),
+        ("per_sample_weights", C.c_int32), ("dwell_form", C.c_int32),
         ("range_flag", C.c_void_p),
     ]
 

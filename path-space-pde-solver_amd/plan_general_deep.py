@@ -173,6 +173,7 @@ class GeneralDeepPlan(GeneralNativePlan):
             cfg.h_par[i] = float(v)
         set_sigma(gcfg, spec, self.dev, self._keep)
         cfg.drift_kind, cfg.h_kind = spec['drift'][0], spec['h']
+        cfg.dwell_form = int(spec.get('dwell_form', 0))
         cfg.adaptive = 1 if s.adaptive_forward_process else 0
         cfg.noise_mode = nat.NOISE_PHILOX if s.noise == 'philox' else nat.NOISE_SUPPLIED
         cfg.store_path = 1

@@ -69,7 +69,10 @@ def native_eligibility(solver, deep=False):
     over = coefficients_overridden(solver.problem)
     if over is not None:
         return 'problem.%s is not the catalogue implementation general_native_spec() describes' % over
-    if not deep and spec_fn().get('sigma') is not None:
+    spec = spec_fn()
+    if spec['h'] == nat.GH_SINE_SOURCE and spec['h_par'][0] == 0.0 and solver.d < 2:
+        return 'h reads the coordinates x_0 and x_1 (PSP_GH_SINE_SOURCE, sub-mode 0: Helmholtz) and d = %d' % solver.d
+    if not deep and spec.get('sigma') is not None:
         return 'a dense sigma runs on the run-time-shaped kernels (csrc/genl_kernels.h), whatever the net'
     if not nat.is_built():
         raise nat.NativeLibraryError('libpsp_hip.so is not built; run __graft_entry__.build()')
@@ -144,6 +147,7 @@ class GeneralNativePlan:
         cfg.sigma_scale = float(spec['sigma_scale'])
         cfg.drift_kind = spec['drift'][0]
         cfg.h_kind = spec['h']
+        cfg.dwell_form = int(spec.get('dwell_form', 0))           # the rounding order of the double-well drift (include/psp.h)
         cfg.adaptive = 1 if s.adaptive_forward_process else 0
         cfg.noise_mode = nat.NOISE_PHILOX if s.noise == 'philox' else nat.NOISE_SUPPLIED
         cfg.store_path = 1

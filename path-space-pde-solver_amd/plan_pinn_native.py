@@ -76,7 +76,9 @@ def pinn_eligibility(solver):
     if dense and not full:
         return ('a dense sigma without full_hessian: the reference takes B[0,0]^2 times the Laplacian for it, which is no '
                 'operator of the problem (composite only)')
-    if dense and spec['h'] == nat.GH_QUAD:
+    if spec['h'] == nat.GH_SINNORM2:
+        return 'PSP_GH_SINNORM2 (SinNorm2.h) is built in the rollout kernels only, not in the PINN kernels'
+    if dense and (spec['h'] == nat.GH_QUAD or (spec['h'] == nat.GH_AFFINE_EXP and spec['h_par'][2] != 0.0)):
         return 'an h that reads z = B grad V is not in the PINN kernels for a dense sigma'
     pairs = h_reads_t(spec)
     if pairs and getattr(s, 'pinn_time_h', 'torch') != 'native':
@@ -102,7 +104,9 @@ def pinn_eligibility(solver):
 
 
 def h_reads_t(spec):
-    return spec['h'] >= nat.GH_EXPBALL_LIN and len(spec.get('h_par', ())) > 3 and spec['h_par'][3] != 0.0
+    """h_par = (al, d, e, tau) of the exponential-on-the-ball kinds carries the time term; the later kinds read no t."""
+    return (nat.GH_EXPBALL_LIN <= spec['h'] <= nat.GH_EXPBALL_SIN_FULL and len(spec.get('h_par', ())) > 3
+            and spec['h_par'][3] != 0.0)
 
 
 def pinn_config(s, net, spec, dev, keep):

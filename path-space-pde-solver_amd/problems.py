@@ -659,6 +659,34 @@ class ExponentialOnSphereNonlinearParabolic(_ExpBall):
         return torch.exp(self.alpha * self._r2(x) + t)
 
 
+class ExponentialOnSphereParabolic(_ExpBall):
+    """The linear parabolic problem (reference problems.py:1103-1134): h = -y (2 alpha (2 alpha |x|^2 + d) + 1), Dirichlet
+    data exp(alpha |x|^2 + t).  As in the reference the class sets no ``boundary_type``: GeneralSolver reads it from the problem,
+    and the Neumann notebook sets it on the instance.  Native: PSP_GH_EXPBALL_LIN with e = 1."""
+    _parabolic = True
+
+    def __init__(self, name='Exponential on sphere', d=2, T=1.0, alpha=1.0, device=None):
+        self._setup(name, d, alpha, None, device)
+        del self.boundary_type
+        self.T = T
+
+    def f(self, x):
+        return torch.exp(self.alpha * self._r2(x) + self.T)
+
+    def g(self, x, t):
+        return torch.exp(self.alpha * self._r2(x) + t)
+
+    def h(self, t, x, y, z):
+        return -y * (2 * self.alpha * (self.alpha * 2 * self._r2(x) + self.d) + 1)
+
+    def v_true(self, x, t):
+        return torch.exp(self.alpha * self._r2(x) + t)
+
+    def general_native_spec(self):
+        return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': float(self.B[0, 0]), 'h': _nat.GH_EXPBALL_LIN,
+                'h_par': (float(self.alpha), float(self.d), 1.0, 0.0)}
+
+
 class Committor:
     """Committor function between two concentric spheres of radius a = 1 and c = 2 (reference problems.py:1546-1579): b = 0,
     sigma = I, h = 0, boundary data 0 on the inner and 1 on the outer sphere; ``boundary = 'two_spheres'`` (EllipticSolver:
@@ -751,3 +779,372 @@ class QuadraticOnBox:
         if self.dense_B:
             return {'drift': (_nat.DRIFT_ZERO, None), 'sigma': self.B, 'h': h}
         return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': float(self.B[0, 0]), 'h': h}
+
+
+# ---------------------------------------------------------------------------------------------
+# exit-time and box-domain problems of the diffusion-loss paper (reference problems.py:1220-1730)
+# ---------------------------------------------------------------------------------------------
+class _ExitDoubleWell:
+    """One-dimensional double well V = beta (x^2 - 1)^2 started in the left well, stopped at X_r (EllipticSolver on the box
+    [X_l, X_r] with ``one_boundary``): b = -grad V, sigma = eta I.  ``compute_reference_solution()`` solves the stationary
+    problem L psi - f psi = rhs by finite differences on [-2, 2] with psi pinned on a band of grid rows right of X_r; ``v_true``
+    reads the table by the reference's index arithmetic (floor((x + 2) / dx), clamped at ``_clamp_hi``)."""
+    _f_rate = 1            # the zeroth-order coefficient of the tabulated problem
+    _rhs = 0.0             # right-hand side away from the pinned rows
+    _pinned = 1.0          # psi on the pinned rows
+
+    def _setup(self, name, d, beta, eta, device):
+        self.device = _resolve(device)
+        self.name, self.d, self.beta = name, d, beta
+        self.B = (torch.eye(d).to(self.device) if eta is None else eta * torch.eye(d).to(self.device))
+        self.X_0 = -torch.ones(d).to(self.device)
+        self.Y_0 = -torch.zeros(d).to(self.device)
+        self.boundary, self.one_boundary = 'square', True
+        self.X_l, self.X_r = -2.0, 1.0
+        if d != 1:
+            print('The double well example is only implemented for d = 1.')
+
+    def _pinned_rows(self):
+        return 300, 310
+
+    def compute_reference_solution(self):
+        f = self._f_rate
+        sigma = self.B[0, 0].cpu().numpy()
+        self.xr = [-2, 2]
+        dx = self.dx
+        Nx = int(np.ceil((self.xr[1] - self.xr[0]) / dx))
+        x_val = np.linspace(self.xr[0], self.xr[1], Nx)
+        gV = self.grad_V
+        L = np.zeros([Nx, Nx])
+        L[0, 0] = - 2 * sigma**2 / 2 / dx**2 - gV(x_val[0]) / dx - f
+        L[0, 1] = sigma**2 / dx
+        L[Nx - 1, Nx - 2] = sigma**2 / 2 / dx**2 + gV(x_val[Nx - 1]) / dx
+        L[Nx - 1, Nx - 1] = - sigma**2 / dx**2 - sigma * gV(x_val[Nx - 1]) / dx - f
+        for i in range(1, Nx - 1):
+            L[i, i - 1] = sigma**2 / 2 / dx**2 + gV(x_val[i]) / dx
+            L[i, i] = - sigma**2 / dx**2 - gV(x_val[i]) / dx - f
+            L[i, i + 1] = sigma**2 / 2 / dx**2
+        rhs = np.zeros(Nx) + self._rhs
+        lo, hi = self._pinned_rows()                       # the boundary value on several rows, for numerical stability
+        L[lo:hi, :] = 0
+        for i in range(lo, hi):
+            L[i, i] = 1
+        rhs[lo:hi] = self._pinned
+        L[0, :] = 0                                        # psi flat at both ends of the grid
+        L[0, 0], L[0, 1], rhs[0] = 1, -1, 0
+        L[Nx - 1, :] = 0
+        L[Nx - 1, Nx - 1], L[Nx - 1, Nx - 2], rhs[Nx - 1] = 1, -1, 0
+        self.psi = np.linalg.solve(L, rhs)
+        self.u = sigma * (- np.log(self.psi[:-1]) + np.log(self.psi[1:])) / dx
+
+    def V(self, x):
+        return self.beta * (x**2 - 1)**2
+
+    def grad_V(self, x):
+        return 4.0 * self.beta * x * (x**2 - 1)
+
+    def b(self, x):
+        return -self.grad_V(x)
+
+    def sigma(self, x):
+        return self.B
+
+    def _clamp_hi(self):
+        return 298
+
+    def _index(self, x):
+        return torch.clamp(torch.floor((x + self.xr[1]) / self.dx).long(), 0, self._clamp_hi()).view(-1)
+
+    def _read(self, table, x):
+        """table[i(x)] as a (1, len) float64 tensor on x's device (the reference returns the same numbers as a numpy array)."""
+        i = self._index(x.detach().squeeze())
+        return torch.as_tensor(np.asarray(table), device=x.device)[i].reshape(1, len(i))
+
+    def u_true(self, x, t):
+        i = self._index(x.detach().cpu().squeeze(0))
+        return np.array(self.u[i.numpy()]).reshape([1, len(i)])
+
+    def _spec(self, p):
+        return {'drift': (_nat.DRIFT_DOUBLE_WELL, (self.beta * torch.ones(self.d)).float().contiguous()), 'dwell_form': 1,
+                'sigma_scale': float(self.B[0, 0]), 'h': _nat.GH_AFFINE_EXP, 'h_par': p}
+
+
+class DoubleWell_stopping(_ExitDoubleWell):
+    """Exit from the left well with the quadratic control cost (reference problems.py:1220-1309): h = -|z|^2 / 2 + 1, data 0;
+    ``v_true`` = -log psi of the tabulated linear problem."""
+
+    def __init__(self, name='Double well', d=1, beta=1, device=None):
+        self._setup(name, d, beta, None, device)
+        self.dx = 0.01
+
+    def f(self, x):
+        return torch.ones(x.shape[0]).to(x.device)
+
+    def g(self, x):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def h(self, x, y, z):
+        return -0.5 * torch.sum(z**2, dim=1) + self.f(x)
+
+    def v_true(self, x):
+        return self._read(-np.log(self.psi), x)
+
+    def general_native_spec(self):
+        return self._spec((1.0, 0.0, -0.5, 0.0))
+
+
+class DoubleWell_stopping_linear(_ExitDoubleWell):
+    """The same exit problem in its linear form (reference problems.py:1312-1401): h = -y, data 1; ``v_true`` = psi."""
+
+    def __init__(self, name='Double well', d=1, beta=1, device=None):
+        self._setup(name, d, beta, None, device)
+        self.dx = 0.01
+
+    def f(self, x):
+        return torch.ones(x.shape[0]).to(x.device)
+
+    def g(self, x):
+        return torch.ones(x.shape[0]).to(x.device)
+
+    def h(self, x, y, z):
+        return -self.f(x) * y
+
+    def v_true(self, x):
+        return self._read(self.psi, x)
+
+    def general_native_spec(self):
+        return self._spec((0.0, -1.0, 0.0, 0.0))
+
+
+class DoubleWell_expectation_hitting_time(_ExitDoubleWell):
+    """Mean hitting time of X_r from the left well (reference problems.py:1404-1496): sigma = eta I, h = 1, data 0; the table
+    solves L psi = -1 with psi = 0 on the rows index_r .. 1.1 index_r, and ``v_true`` clamps its index at index_r."""
+    _f_rate, _rhs, _pinned = 0, -1.0, 0.0
+
+    def __init__(self, name='Double well', d=1, beta=1, dx=0.01, eta=2.0, device=None):
+        self._setup(name, d, beta, eta, device)
+        self.dx = dx
+
+    def _index_r(self):
+        return int((self.X_r - self.X_l) / self.dx)
+
+    def _pinned_rows(self):
+        return self._index_r(), int(self._index_r() * 1.1)
+
+    def _clamp_hi(self):
+        return self._index_r()
+
+    def f(self, x):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def g(self, x):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def h(self, x, y, z):
+        return torch.ones(y.shape[0]).to(y.device)
+
+    def u_true(self, x):
+        return x
+
+    def v_true(self, x):
+        return self._read(self.psi, x)
+
+    def general_native_spec(self):
+        return self._spec((1.0, 0.0, 0.0, 0.0))
+
+
+class Committor_DoubleWell:
+    """Committor of the one-dimensional double well between X_l and X_r = 0 (reference problems.py:1499-1543).  Ported as a class
+    only: the reference writes ``sigma(x, t)`` and ``h(x, t, y, z)``, which is the calling convention of neither GeneralSolver
+    (``sigma(x)``, ``h(t, x, y, z)``) nor EllipticSolver (``h(x, y, z)``), so no solver of the reference runs it; it has no
+    ``general_native_spec()`` and no ``native_vtrue_spec()``."""
+
+    def __init__(self, name='Double well', d=1, beta=1, dx=0.01, eta=2.0, T=1.0, device=None):
+        self.device = _resolve(device)
+        self.name, self.T, self.d, self.beta, self.dx = name, T, d, beta, dx
+        self.B = np.sqrt(eta) * torch.eye(d).to(self.device)
+        self.X_0 = -torch.ones(d).to(self.device)
+        self.Y_0 = -torch.zeros(d).to(self.device)
+        self.boundary, self.one_boundary, self.boundary_type = 'square', True, 'Dirichlet'
+        self.X_l, self.X_r = -2.0, 0.0
+        if d != 1:
+            print('The double well example is only implemented for d = 1.')
+
+    def V(self, x):
+        return self.beta * (x**2 - 1)**2
+
+    def grad_V(self, x):
+        return 4.0 * self.beta * x * (x**2 - 1)
+
+    def b(self, x):
+        return -self.grad_V(x)
+
+    def sigma(self, x, t):
+        return self.B
+
+    def f(self, x):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def g(self, x, t):
+        return torch.ones(x.shape[0]).to(x.device)
+
+    def h(self, x, t, y, z):
+        return torch.zeros(y.shape[0]).to(y.device)
+
+    def u_true(self, x, t):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def v_true(self, x, t):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+
+class _ZeroDriftElliptic:
+    """b = 0, f = 0, constant sigma, a control reference that is zero: what the four closed-form elliptic problems share."""
+
+    def _setup(self, name, d, B, device):
+        self.device = _resolve(device)
+        self.name, self.d = name, d
+        self.B = B.to(self.device)
+        self.X_0 = -torch.ones(d).to(self.device)
+        self.Y_0 = -torch.zeros(d).to(self.device)
+        self.pi = torch.tensor(np.pi)
+
+    def b(self, x):
+        return torch.zeros(x.shape).to(x.device)
+
+    def sigma(self, x):
+        return self.B
+
+    def f(self, x):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def u_true(self, x, t):
+        return torch.zeros(x.shape[0], 1).to(x.device)
+
+
+class QuadraticGradient(_ZeroDriftElliptic):
+    """v = log((|x|^2 + 1) / d) on the ball of radius r (reference problems.py:1582-1611): sigma = sqrt(2) I,
+    h = |z|^2 / B_00^2 - 2 exp(-y)."""
+
+    def __init__(self, name='Quadratic Gradient', d=1, r=1.0, device=None):
+        self._setup(name, d, torch.sqrt(torch.tensor(2.0)) * torch.eye(d), device)
+        self.boundary, self.boundary_distance = 'sphere', r
+
+    def g(self, x):
+        return torch.log((torch.sum(x**2, 1) + 1) / self.d)
+
+    def h(self, x, y, z):
+        return torch.sum(z**2, dim=1) / self.B[0, 0]**2 - 2 * torch.exp(-y)
+
+    def v_true(self, x):
+        return torch.log((torch.sum(x**2, 1) + 1) / self.d)
+
+    def general_native_spec(self):
+        return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': float(self.B[0, 0]), 'h': _nat.GH_AFFINE_EXP,
+                'h_par': (0.0, 0.0, 1.0 / float(self.B[0, 0]**2), -2.0)}
+
+    def native_vtrue_spec(self):
+        """v_true as a closed form of the device test log (include/psp.h PSP_VTRUE_LOGQ: log((|x|^2 + 1) / p0))."""
+        return {'kind': _nat.VTRUE_LOGQ, 'par': (float(self.d), 0.0, 0.0, 0.0)}
+
+
+class Helmholtz(_ZeroDriftElliptic):
+    """Helmholtz equation on the square [-1, 1]^2 with the solution sin(a_1 pi x_0) sin(a_2 pi x_1) (reference
+    problems.py:1614-1654); ``a_1``, ``a_2``, ``k`` are attributes the notebooks change on the instance."""
+
+    def __init__(self, name='Helmholtz', d=2, r=1.0, device=None):
+        self._setup(name, d, torch.sqrt(torch.tensor(2.0)) * torch.eye(d), device)
+        self.a_1, self.a_2, self.k = 1.0, 4.0, 1.0
+        self.boundary, self.one_boundary, self.X_l, self.X_r = 'square', False, -1.0, 1.0
+        if d != 2:
+            print('Only implemented for d = 2.')
+
+    def _s(self, x):
+        pi = self.pi.to(x.device)
+        return torch.sin(self.a_1 * pi * x[:, 0]) * torch.sin(self.a_2 * pi * x[:, 1])
+
+    def g(self, x):
+        return self._s(x)
+
+    def h(self, x, y, z):
+        pi = self.pi.to(x.device)
+        s1, s2 = torch.sin(self.a_1 * pi * x[:, 0]), torch.sin(self.a_2 * pi * x[:, 1])
+        return (self.k**2 * y + (self.a_1 * pi)**2 * s1 * s2 + (self.a_2 * pi)**2 * s1 * s2 - self.k**2 * s1 * s2)
+
+    def v_true(self, x):
+        return self._s(x)
+
+    def general_native_spec(self):
+        """PSP_GH_SINE_SOURCE, sub-mode 0: h_par = (0, a_1 pi, a_2 pi, k^2), the products rounded to fp32 as ``h`` forms them."""
+        return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': float(self.B[0, 0]), 'h': _nat.GH_SINE_SOURCE,
+                'h_par': (0.0, float(self.a_1 * self.pi), float(self.a_2 * self.pi), float(self.k ** 2))}
+
+    def native_vtrue_spec(self):
+        """v_true as a closed form of the device test log (include/psp.h PSP_VTRUE_SINPROD: sin(p0 x_0) sin(p1 x_1))."""
+        return {'kind': _nat.VTRUE_SINPROD, 'par': (float(self.a_1 * self.pi), float(self.a_2 * self.pi), 0.0, 0.0)}
+
+
+class Oscillations(_ZeroDriftElliptic):
+    """Two-scale oscillation on [0, 1]: v = sin(2 pi x) + 0.1 sin(a pi x), h the matching source (reference
+    problems.py:1657-1693); ``a`` is an attribute the notebooks change on the instance."""
+
+    def __init__(self, name='Oscillations', d=1, r=1.0, device=None):
+        self._setup(name, d, torch.sqrt(torch.tensor(2.0)) * torch.eye(d), device)
+        self.a = 5
+        self.boundary, self.one_boundary, self.X_l, self.X_r = 'square', False, 0.0, 1.0
+        if d != 1:
+            print('Only implemented for d = 1.')
+
+    def g(self, x):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def h(self, x, y, z):
+        pi = self.pi.to(x.device)
+        return (2 * pi)**2 * torch.sin(2 * pi * x[:, 0]) + (self.a * pi)**2 * 0.1 * torch.sin(self.a * pi * x[:, 0])
+
+    def v_true(self, x):
+        pi = self.pi.to(x.device)
+        return torch.sin(2 * pi * x[:, 0]) + 0.1 * torch.sin(self.a * pi * x[:, 0])
+
+    def general_native_spec(self):
+        """PSP_GH_SINE_SOURCE, sub-mode 1: h_par = (1, 2 pi, a pi, 0.1)."""
+        return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': float(self.B[0, 0]), 'h': _nat.GH_SINE_SOURCE,
+                'h_par': (1.0, float(2 * self.pi), float(self.a * self.pi), 0.1)}
+
+    def native_vtrue_spec(self):
+        """v_true as a closed form of the device test log (include/psp.h PSP_VTRUE_SINSUM: sin(p0 x_0) + p2 sin(p1 x_0))."""
+        return {'kind': _nat.VTRUE_SINSUM, 'par': (float(2 * self.pi), float(self.a * self.pi), 0.1, 0.0)}
+
+
+class SinNorm2(_ZeroDriftElliptic):
+    """v = sin(pi |x|^2) on the unit ball under the dense sigma = alpha sqrt(2 / d) ones(d, d) (reference problems.py:1696-1730):
+    the operator is alpha^2 sum_ij d_i d_j, so h carries (sum_i x_i)^2; ``linear`` selects the source-only h or the one that
+    reads y."""
+
+    def __init__(self, name='SinNorm2', d=1, r=1.0, linear=True, alpha=1.0, device=None):
+        self.alpha = alpha
+        self._setup(name, d, alpha * torch.sqrt(torch.tensor(2.0) / d) * torch.ones(d, d), device)
+        self.linear = linear
+        self.boundary, self.boundary_distance = 'sphere', 1.0
+
+    def g(self, x):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def h(self, x, y, z):
+        pi = self.pi.to(x.device)
+        rr, sx = torch.sum(x**2, 1), torch.sum(x, 1)
+        if self.linear:
+            return self.alpha**2 * (4 * pi**2 * torch.sin(pi * rr) * sx**2 - 2 * self.d * pi * torch.cos(pi * rr))
+        return self.alpha**2 * (4 * pi**2 * y * sx**2 - 2 * self.d * pi * torch.cos(pi * rr) + torch.sin(pi * rr)**2 - y**2)
+
+    def v_true(self, x):
+        return torch.sin(self.pi.to(x.device) * torch.sum(x**2, 1))
+
+    def general_native_spec(self):
+        """PSP_GH_SINNORM2 with the dense B (psp_genl_* only): h_par = (alpha, d, linear, 0)."""
+        return {'drift': (_nat.DRIFT_ZERO, None), 'sigma': self.B, 'h': _nat.GH_SINNORM2,
+                'h_par': (float(self.alpha), float(self.d), 1.0 if self.linear else 0.0, 0.0)}
+
+    def native_vtrue_spec(self):
+        """v_true as a closed form of the device test log (include/psp.h PSP_VTRUE_SINR2: sin(pi |x|^2))."""
+        return {'kind': _nat.VTRUE_SINR2, 'par': (0.0, 0.0, 0.0, 0.0)}
