@@ -575,6 +575,42 @@ int psp_genl_rollout_fwd_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* 
                              float* tables, float* path, float* ahat, float* VN, float* YN, float* XN, float* tN,
                              unsigned long long* kcount, void* stream);
 
+/* Eigenvalue problems on the forward rollout (appended in 0.4.0, no version bump): what EigenvalueSolver needs for the eigenpairs
+ * (lambda, V) of the diffusion-loss paper's `Eigenvalue - *.ipynb` notebooks -- Fokker-Planck and the nonlinear Schroedinger equation
+ * on the periodic box [0, 2 pi]^d, sigma = s I, uncontrolled and detached state path.  The struct travels beside psp_genl_config,
+ * which keeps its layout.  With o the net's linear output, V = relu(o) (output_relu) or o, c = 1[o > 0] (or 1), Z = c s grad_x o:
+ *   X += (b(X) dt + s xi sqrt(dt)) alive   (the boxes test the proposal, as ever),
+ *   Y += ((-h(X, V, Z) - lambda V) dt + Z . xi sqrt(dt)) act,          Y_0 = V(X_0),
+ *   s_out[k] = sum_n act_n V(X_n) dt   (= -dY_N / dlambda: dLoss/dlambda of a loss in D = V(X_N) - Y_N is sum_k dLoss/dD_k s_out[k]).
+ * lambda is read from DEVICE memory once per launch -- it is a trained scalar, and passing it by value would cost a host read
+ * per iteration.  The path store holds the gated tangent direction c act s u and `ahat` the gated coefficient
+ * c ([n = 0] - (h_y + lambda) dt act): psp_genl_rollout_bwd consumes them unchanged -- call it with the same cfg; with output_relu
+ * the CALLER multiplies wV by 1[VN > 0] (VN is V(X_N) = relu(o_N), so VN > 0 is the gate of the final point).
+ * Kinds that only these entry points accept (numbered away from the others; psp_genl_query / psp_genl_rollout_fwd refuse them):
+ *   PSP_DRIFT_EIG_FP  b_i = -cos(S) c_i sin x_i,  S = sum_j c_j cos x_j,  c = base.drift (d floats)
+ *   PSP_GH_EIG_FP     h = y (-sin(S) sum_i c_i^2 sin^2 x_i - cos(S) S), the same c (needs PSP_DRIFT_EIG_FP)
+ *   PSP_GH_EIG_NLS    h = -y^3 - y (-p0 exp((2 / p1) sum_i cos x_i) + sum_i (sin^2 x_i / p1^2 - cos x_i / p1) - 3),
+ *                     h_par = (1 / c^2, d, -, -)
+ * The state path is detached and uncontrolled (base.adaptive = 0), so the backward never differentiates the drift or the x
+ * dependence of h: it needs h_y alone.  Every other h / drift kind of the sigma = s I path runs here as well.
+ * A NULL struct means psp_genl_query / psp_genl_rollout_fwd exactly: the same plan, kernel instance and bits. */
+enum { PSP_GH_EIG_FP = 16, PSP_GH_EIG_NLS = 17 };      /* psp_gen_config.h_kind, psp_genl_*_eig only     */
+enum { PSP_DRIFT_EIG_FP = 16 };                        /* psp_gen_config.drift_kind, psp_genl_*_eig only */
+typedef struct psp_genl_eig {
+    int32_t struct_bytes;        /* sizeof(psp_genl_eig): checked by the library (this struct is not in psp_abi_struct_sizes*) */
+    int32_t output_relu;         /* 1: V = relu(net output); 0: the net as it is                                              */
+    const float* lambda;         /* DEVICE, one float, read by every psp_genl_rollout_fwd_eig call; NULL: lambda = 0          */
+    float* s_out;                /* DEVICE, K_local floats, written by every call; NULL: not wanted                           */
+} psp_genl_eig;
+/* psp_genl_query with the struct: the sizes are those of psp_genl_query.  <0 as psp_genl_query, or: wrong struct_bytes,
+ * output_relu outside {0, 1}, a dense sigma (or an h kind that runs on the dense path), base.adaptive = 1, PSP_GH_EIG_FP without
+ * PSP_DRIFT_EIG_FP, PSP_GH_EIG_NLS with h_par[1] <= 0.  No GPU needed; reads no pointer of `eig`. */
+int psp_genl_query_eig(const psp_genl_config* cfg, const psp_genl_eig* eig, psp_genl_sizes* out);
+/* psp_genl_rollout_fwd with the struct (every other argument as there). */
+int psp_genl_rollout_fwd_eig(const psp_genl_config* cfg, const psp_genl_eig* eig, const float* params, const float* x0,
+                             const float* t0, const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path,
+                             float* ahat, float* VN, float* YN, float* XN, float* tN, unsigned long long* kcount, void* stream);
+
 /* Adjoint sweep of the state path (appended in 0.4.0, no version bump; csrc/genl_adj_kernels.h): what
  * Solver(approx_method='value_function') needs with adaptive_forward_process=True and detach_forward=False (the constructor
  * defaults; reference solver.py:449-478: c = -Z stays attached, so the states carry the parameters).  At a fixed sample the loss

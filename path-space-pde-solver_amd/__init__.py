@@ -17,9 +17,10 @@ from .problems import (LLGC, LQGC, AllenCahn, DoubleWell, DoubleWell_multidim,  
                        ExponentialOnSphereNonlinearParabolic, QuadraticOnBox, Committor,
                        ExponentialOnSphereParabolic, DoubleWell_stopping, DoubleWell_stopping_linear,
                        DoubleWell_expectation_hitting_time, Committor_DoubleWell, QuadraticGradient, Helmholtz, Oscillations,
-                       SinNorm2)
+                       SinNorm2, FokkerPlanckEigenvalue, SchroedingerEigenvalue)
 from .solver import Solver  # noqa: F401
 from .general_solver import GeneralSolver, EllipticSolver  # noqa: F401
+from .eigenvalue_solver import EigenvalueSolver  # noqa: F401
 from .plan_native import PlanUnsupported  # noqa: F401
 from . import native  # noqa: F401
 from . import native_shapes  # noqa: F401
@@ -31,4 +32,4 @@ __all__ = ['Solver', 'GeneralSolver', 'EllipticSolver', 'ExponentialOnSphere', '
            'AllenCahn', 'HeatEquation', 'MySequential', 'DenseNet', 'DenseNet_tanh', 'DenseNet_tanh_2', 'SingleParam',
            'Constant', 'Linear', 'Affine', 'PlanUnsupported', 'native', 'ExponentialOnSphereParabolic', 'DoubleWell_stopping',
            'DoubleWell_stopping_linear', 'DoubleWell_expectation_hitting_time', 'Committor_DoubleWell', 'QuadraticGradient',
-           'Helmholtz', 'Oscillations', 'SinNorm2']
+           'Helmholtz', 'Oscillations', 'SinNorm2', 'FokkerPlanckEigenvalue', 'SchroedingerEigenvalue', 'EigenvalueSolver']

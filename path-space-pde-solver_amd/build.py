@@ -109,6 +109,9 @@ def _build(force, jobs, verbose, only):
     # the u_L2-log instances of that kernel (psp_genl_rollout_fwd_ul2: two shapes, three waves-per-tile variants) and the gain staging
     ulinst_src = os.path.join(CSRC, "genl_ul2_instance.hip")
     tasks.append((ulinst_src, os.path.join(OBJ, "genl_ul2_inst.o"), NOSLP, [ulinst_src, os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
+    # the eigenvalue instances of that kernel (psp_genl_rollout_fwd_eig): three waves-per-tile variants
+    eiginst_src = os.path.join(CSRC, "genl_eig_instance.hip")
+    tasks.append((eiginst_src, os.path.join(OBJ, "genl_eig_inst.o"), NOSLP, [eiginst_src, os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
     # the adjoint sweep of the state path for the value-function ansatz (psp_genl_adjoint_sweep): three waves-per-tile variants
     adjinst_src = os.path.join(CSRC, "genl_adj_instance.hip")
     tasks.append((adjinst_src, os.path.join(OBJ, "genl_adj_inst.o"), NOSLP,

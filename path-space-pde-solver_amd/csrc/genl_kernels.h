@@ -62,6 +62,14 @@
 // arithmetic of ugrid.h.  On the dense path the Z image takes B^T u before the move, so the kinds that need X_{n+1} keep Z in an
 // image of its own (ZLi, one more carve of DB0 blocks).  The sum is sequential in n, fp32, formed by every wave alike (as S and Pz
 // are) and written by one lane per trajectory.  Defined for runs that never stop (no domain, T = inf): every step is active.
+// Eigenvalue problems (genl_fwd_kernel<NW, false, false, false, true>; the three `Eigenvalue - *.ipynb` notebooks of the
+// diffusion-loss paper: an eigenpair (lambda, V) of the generator on the periodic box, sigma = s I, state path detached):
+//   Y += ((-h(X, V, Z) - lambda V) dt + Z . xi sqrt(dt)) act,   V = relu(o) for a net with linear output o (out_relu),
+// lambda read from DEVICE memory once per launch (it is trained: no host read per iteration).  With the gate c = 1[o > 0]:
+// V = c o, grad V = c grad o, dV/dtheta = c do/dtheta, so the forward stores the gated tangent direction c U and the gated
+// coefficient c a^ with a^ = [n = 0] - (h_y + lambda) dt act -- genl_bwd_kernel consumes exactly those, unchanged (the caller gates
+// the weight of V(X_N) by 1[V(X_N) > 0] itself).  One more output, S_k = sum_n act_n V(X_n) dt = -dY_N / dlambda.  Two h kinds and a
+// drift kind that need row reductions of cos x / sin x (GH_EIG_FP + DRIFT_EIG_FP, GH_EIG_NLS) live in these instances only.
 #pragma once
 #include "gen_kernels.h"
 #include "ugrid.h"
@@ -75,6 +83,11 @@ enum { GACT_RELU2 = 0, GACT_TANH2 = 1, GACT_TANH = 2 };
 // h of ExponentialOnBallNonlinearSinHessian (problems.py:1094): GH_EXPBALL_SIN with (sum_i x_i)^2 = sum_ij x_i x_j in the linear
 // term, |x|^2 kept in the exponent.  Served by the dense-sigma instances of the forward kernel only.
 constexpr int GH_EXPBALL_SIN_FULL = 6;
+// The eigenvalue problems (EIG instances of the forward kernel only; numbered away from the kinds above):
+//   GH_EIG_FP   h = y (-sin(S) sum_i c_i^2 sin^2 x_i - cos(S) S),  S = sum_j c_j cos x_j, c = the drift vector (Fokker-Planck)
+//   GH_EIG_NLS  h = -y^3 - y (-p0 exp((2 / d) sum_i cos x_i) + sum_i (sin^2 x_i / d^2 - cos x_i / d) - 3),  h_par = (1 / c^2, d, -, -)
+//   DRIFT_EIG_FP  b_i = -cos(S) c_i sin x_i
+constexpr int GH_EIG_FP = 16, GH_EIG_NLS = 17, DRIFT_EIG_FP = 16;
 // GH_SINNORM2 (problems.py:1721-1724; the dense-sigma instances again: they form sx = sum_i x_i), h_par = (al, d, linear, -)
 __device__ inline void gh_sinnorm2(const float* p, float y, float rr, float sx, float& minus_h, float& hy) {
     const float pi = 3.14159265358979323846f, a2 = p[0] * p[0], fp2 = 4.0f * (pi * pi), s = sinf(pi * rr);
@@ -151,6 +164,14 @@ struct GenlUl2Args {
     long long tUL;                  // LINEAR: float offset of the N A-operand tables of M_n (layout of tSB), behind tA
 };
 struct GenlLogArgs { GenlArgs a; GenlUl2Args u; };
+// eigenvalue problems: the arguments of the EIG instances travel BEHIND GenlArgs as well
+struct GenlEigArgs {
+    const float* lam;               // DEVICE scalar lambda, read once per launch; NULL: 0
+    float* S_out;                   // (K_local) sum_n act_n V(X_n) dt, or NULL
+    int out_relu;                   // 1: V = relu(net output)
+    int reserved;
+};
+struct GenlEigFwdArgs { GenlArgs a; GenlEigArgs e; };
 enum { GUL2_TABLE = 0, GUL2_LINEAR = 1, GUL2_GRID = 2 };      // = PSP_UL2_*
 
 // padded feature index -> real index inside the concatenation a (or -1: padding)
@@ -252,10 +273,12 @@ __global__ __launch_bounds__(256) void genl_tables_kernel(const GenlArgs a) {
 typedef const GenlArgs* KArgs;
 typedef const GenArgs* KGen;
 // argument struct of genl_fwd_kernel<.., LOGU> and its GenlArgs part
-template <bool LOGU> struct GenlFwdArgsOf { typedef GenlArgs type; };
-template <> struct GenlFwdArgsOf<true> { typedef GenlLogArgs type; };
+template <bool LOGU, bool EIG = false> struct GenlFwdArgsOf { typedef GenlArgs type; };
+template <> struct GenlFwdArgsOf<true, false> { typedef GenlLogArgs type; };
+template <> struct GenlFwdArgsOf<false, true> { typedef GenlEigFwdArgs type; };
 __device__ __forceinline__ KArgs genl_base(const GenlArgs* p) { return p; }
 __device__ __forceinline__ KArgs genl_base(const GenlLogArgs* p) { return &p->a; }
+__device__ __forceinline__ KArgs genl_base(const GenlEigFwdArgs* p) { return &p->a; }
 
 // ---- activation as functions of the stored r (relu(z) or tanh(z)); `act` is a kernel argument: uniform branches
 __device__ __forceinline__ f32x4 gact_r(int act, f32x4 z) { return act == GACT_RELU2 ? relu4(z) : tanh4(z); }
@@ -415,13 +438,19 @@ __host__ __device__ inline int genl_fwd_lds_bytes_dense_log(int TB, int DB0) { r
 // stay the code they were.  LQ (with DENSE only): the linear-quadratic coefficients of the header comment, as uniform run-time
 // branches inside instances of their own -- for the same reason.  LOGU: the u_L2 log of the header comment, the kind a uniform
 // run-time branch; instantiated as <NW, false, false, true> (TABLE, GRID) and <NW, true, true, true> (all three kinds)
-template <int NW, bool DENSE = false, bool LQ = false, bool LOGU = false>
-__global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(const typename GenlFwdArgsOf<LOGU>::type ga_) {
+// EIG: the eigenvalue problems of the header comment (lambda, the output ReLU's gate, S_k, their h / drift kinds), sigma = s I
+// only; every line of it sits behind `if constexpr (EIG)`, so the other instances stay the code they were
+template <int NW, bool DENSE = false, bool LQ = false, bool LOGU = false, bool EIG = false>
+__global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(const typename GenlFwdArgsOf<LOGU, EIG>::type ga_) {
     static_assert(DENSE || !LQ, "the linear-quadratic coefficients run on the dense-sigma path");
     static_assert(!LOGU || DENSE == LQ, "the u_L2 log: the sigma = s I instance or the linear-quadratic one");
-    if constexpr (LOGU) { PSP_COND_EXIT(ga_.a.g); } else { PSP_COND_EXIT(ga_.g); }
+    static_assert(!EIG || (!DENSE && !LQ && !LOGU), "the eigenvalue problems run on the sigma = s I path");
+    if constexpr (LOGU || EIG) { PSP_COND_EXIT(ga_.a.g); } else { PSP_COND_EXIT(ga_.g); }
     const KArgs ga = genl_base(&ga_);
     const KGen a = &ga->g;
+    [[maybe_unused]] const GenlEigArgs* eg = nullptr;
+    [[maybe_unused]] float lam = 0.f, Slam = 0.f;                    // EIG: lambda; S_k = sum_n act_n V(X_n) dt
+    if constexpr (EIG) { eg = &ga_.e; if (eg->lam) lam = *eg->lam; }
     [[maybe_unused]] const GenlUl2Args* ul = nullptr;
     if constexpr (LOGU) ul = &ga_.u;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -496,7 +525,11 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
         //  lanes; an opaque copy of q per step keeps them as one v_cmp where they are used)
         const int qv = opaque_i(q);
         put_state();
-        const float Vnow = genl_value<NW>(ga, T, A, Rr, lane, q, wave);
+        float Vnow = genl_value<NW>(ga, T, A, Rr, lane, q, wave);
+        [[maybe_unused]] float gate = 1.f, eS = 0.f, eQ = 0.f, ecS = 0.f;     // EIG: 1[o > 0]; the row reductions of its h / drift kinds
+        if constexpr (EIG) {
+            if (eg->out_relu) { gate = Vnow > 0.f ? 1.f : 0.f; Vnow = fmaxf(Vnow, 0.f); }
+        }
         if (n == 0) Y = Vnow;                                        // solver.py:1081 / :721
         if (a->Vsteps && w0 && q == 0) {                             // Solver's value-function ansatz: sum_n (Y_n(X_n) - Y)^2 (solver.py:438-440)
             a->Vsteps[(size_t)n * (a->ntile16 * 16) + k] = Vnow;
@@ -523,6 +556,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             f32x4 Z;
 #pragma unroll
             for (int r = 0; r < 4; ++r) Z[r] = ((16 * b + 4 * r + qv) < D) ? sig * gx[r] : 0.f;
+            if constexpr (EIG) Z = gate * Z;                         // grad relu(o) = 1[o > 0] grad o
             return Z;
         };
         auto drift_vec = [&](int b) __attribute__((always_inline)) {
@@ -538,6 +572,13 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
                 if (a->dwell_form) drift = -(((4.0f * drift_vec(b)) * X[b]) * (X[b] * X[b] - 1.0f));       // problems.py:1286
                 else drift = -(4.0f * drift_vec(b) * (X[b] * (X[b] * X[b] - 1.0f)));
             } else if (a->drift_kind == DRIFT_DIAG) drift = drift_vec(b) * X[b];
+            if constexpr (EIG) {
+                if (a->drift_kind == DRIFT_EIG_FP) {                 // b_i = -cos(S) c_i sin x_i
+                    const f32x4 c4 = drift_vec(b);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) drift[r] = ((-ecS) * c4[r]) * sinf(X[b][r]);
+                }
+            }
             if constexpr (DENSE) return (drift * dt + img_get(G, b, lane)) * alivef;      // B w: formed once per step, below
             return (drift * dt + sig * cdt + (sig * sqdt) * xi) * alivef;
         };
@@ -630,6 +671,25 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             rr = qsum(rr);
             if constexpr (DENSE) sx = qsum(sx);
         }
+        if constexpr (EIG) {                                         // the state BEFORE the move, as every h here
+            if (a->h_kind == GH_EIG_FP || a->h_kind == GH_EIG_NLS || a->drift_kind == DRIFT_EIG_FP) {
+                const bool fp = a->h_kind != GH_EIG_NLS;
+                const float dd = a->h_par[1];
+#pragma unroll
+                for (int b = 0; b < GENL_MAXDB; ++b)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int f = 16 * b + 4 * r + qv;
+                        if (b < DB0 && f < D) {
+                            const float sn = sinf(X[b][r]), cs = cosf(X[b][r]);
+                            if (fp) { const float c = vdr[f]; eS += c * cs; eQ += (c * c) * (sn * sn); }
+                            else { eS += cs; eQ += (sn * sn) / (dd * dd) - cs / dd; }
+                        }
+                    }
+                eS = qsum(eS); eQ = qsum(eQ);
+                ecS = cosf(eS);
+            }
+        }
         bool inside = true;
         if (a->domain_kind == DOM_SPHERE) {
             inside = sqrtf(rr) < a->dom_a;                            // the state BEFORE the move (:1121)
@@ -682,6 +742,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
                         u -= dt * (pz + pz);
                     }
                     U = (actf * sig) * u;
+                    if constexpr (EIG) U = gate * U;
                     step = move_block(b, Z, xi);
                     if constexpr (LOGU) Zlog = Z;
                 }
@@ -738,6 +799,17 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             gh_sine_source(a->h_par, Vnow, qsum(qv == 0 ? rr : 0.f), qsum(qv == 1 ? rr : 0.f), minus_h, hy);
         else if (a->h_kind == GH_SINNORM2) {
             if constexpr (DENSE) gh_sinnorm2(a->h_par, Vnow, rr, sx, minus_h, hy);
+        } else if (EIG && a->h_kind >= GH_EIG_FP) {
+            if constexpr (EIG) {
+                float coef;                                          // h = y coef(x) [- y^3]
+                if (a->h_kind == GH_EIG_FP) {
+                    coef = (-eQ) * sinf(eS) - ecS * eS;
+                    minus_h = -(Vnow * coef); hy = coef;
+                } else {
+                    coef = ((-a->h_par[0]) * expf((2.0f / a->h_par[1]) * eS) + eQ) - 3.0f;
+                    minus_h = Vnow * Vnow * Vnow + Vnow * coef; hy = -3.0f * Vnow * Vnow - coef;
+                }
+            }
         } else if (a->h_kind >= GH_EXPBALL_LIN) {
             const float al = a->h_par[0];
             float rl = rr;                                           // |x|^2, or (sum x)^2 for the full-Hessian problem
@@ -766,8 +838,11 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
             }
         }
         const float zc = a->adaptive ? -S : 0.f;
+        if constexpr (EIG) { minus_h -= lam * Vnow; hy += lam; Slam = fmaf(Vnow * actf, dt, Slam); }
         Y = Y + ((minus_h + zc) * dt + Pz * sqdt) * actf;
-        if (a->store_path && w0 && q == 0) a->ahat[(size_t)n * (a->ntile16 * 16) + k] = (n == 0 ? 1.f : 0.f) - hy * dt * actf;
+        float ahn = (n == 0 ? 1.f : 0.f) - hy * dt * actf;
+        if constexpr (EIG) ahn *= gate;                              // dV/dtheta = 1[o > 0] do/dtheta
+        if (a->store_path && w0 && q == 0) a->ahat[(size_t)n * (a->ntile16 * 16) + k] = ahn;
         t = t + dt * actf;
         put_time(t);
         if (act && q == 0) ++nact;
@@ -777,7 +852,11 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : 2) void genl_fwd_kernel(cons
     }
     // final point: V(X_N, t_N) (solver.py:1163 / :799) as an extra value-only sample
     put_state();
-    const float VN = genl_value<NW>(ga, T, A, Rr, lane, q, wave);
+    float VN = genl_value<NW>(ga, T, A, Rr, lane, q, wave);
+    if constexpr (EIG) {
+        if (eg->out_relu) VN = fmaxf(VN, 0.f);
+        if (kvalid && w0 && q == 0 && eg->S_out) eg->S_out[k] = Slam;
+    }
     if (a->store_path && w0) {
         float* pblk = a->path + ((size_t)a->N * a->ntile16 + t16) * PBL + lane;
 #pragma unroll
@@ -1007,10 +1086,10 @@ __global__ __launch_bounds__(64 * NW) void genl_bwd_kernel(const GenlArgs ga_) {
 }
 
 // host side: launches (the dynamic LDS size exceeds the 64 KiB default)
-template <int NW, bool DENSE = false, bool LQ = false, bool LOGU = false> inline hipError_t genl_launch_fwd(const typename GenlFwdArgsOf<LOGU>::type& a, int ntile16, int lds_bytes, hipStream_t st) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW, DENSE, LQ, LOGU>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+template <int NW, bool DENSE = false, bool LQ = false, bool LOGU = false, bool EIG = false> inline hipError_t genl_launch_fwd(const typename GenlFwdArgsOf<LOGU, EIG>::type& a, int ntile16, int lds_bytes, hipStream_t st) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW, DENSE, LQ, LOGU, EIG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((genl_fwd_kernel<NW, DENSE, LQ, LOGU>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
+    hipLaunchKernelGGL((genl_fwd_kernel<NW, DENSE, LQ, LOGU, EIG>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
     return hipGetLastError();
 }
 // the linear-quadratic instances <NW, true, true> are compiled in a unit of their own (genl_lq_instance.hip), so that the unit
@@ -1020,6 +1099,8 @@ hipError_t genl_lq_launch_fwd(const GenlArgs& a, int nw, int ntile16, int lds_by
 // PSP_UL2_LINEAR (N tables behind u.tUL from u.ref): a unit of their own as well (genl_ul2_instance.hip)
 hipError_t genl_ul2_launch_fwd(const GenlLogArgs& a, int nw, int ntile16, int lds_bytes, hipStream_t st);
 hipError_t genl_ul2_launch_stage(const GenlLogArgs& a, hipStream_t st);
+// the eigenvalue instances <NW, false, false, false, true>: a unit of their own (genl_eig_instance.hip)
+hipError_t genl_eig_launch_fwd(const GenlEigFwdArgs& a, int nw, int ntile16, int lds_bytes, hipStream_t st);
 template <int NW, int MS = GenlGeo<NW>::MAXSLOT> inline hipError_t genl_launch_bwd(const GenlArgs& a, int grid, int groups, int lds_bytes, hipStream_t st) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_bwd_kernel<NW, MS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;

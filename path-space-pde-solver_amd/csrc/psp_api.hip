@@ -1453,8 +1453,24 @@ struct GenlPlan { psp::GenlArgs a; psp::GenlUl2Args u; int ul2_on; int ntile16; 
 // q: the linear-quadratic coefficients of psp_genl_query_lq / psp_genl_rollout_fwd_lq (NULL or all zero: none -- the plan, the
 // table layout and the kernel instance of psp_genl_rollout_fwd)
 // u: the u_L2 log of psp_genl_query_ul2 / psp_genl_ul2_stage / psp_genl_rollout_fwd_ul2 (NULL: none -- nothing changes)
-int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs* q = nullptr, const psp_genl_ul2* u = nullptr) {
+// e: the eigenvalue problems of psp_genl_query_eig / psp_genl_rollout_fwd_eig (NULL: none -- nothing changes; with it the kinds
+// PSP_GH_EIG_* / PSP_DRIFT_EIG_FP are accepted and the forward runs the instances of genl_eig_instance.hip)
+int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs* q = nullptr, const psp_genl_ul2* u = nullptr,
+                   const psp_genl_eig* e = nullptr) {
     if (!c) return fail(-1, "null config");
+    if (e) {
+        if (e->struct_bytes != (int32_t)sizeof(psp_genl_eig)) return fail(-1, "psp_genl_eig.struct_bytes is not sizeof(psp_genl_eig)");
+        if (e->output_relu != 0 && e->output_relu != 1) return fail(-1, "psp_genl_eig.output_relu is 0 or 1");
+        if (q || u) return fail(-1, "psp_genl_eig excludes psp_genl_coeffs and psp_genl_ul2");
+        if (c->sigma_kind != PSP_GENL_SIGMA_SCALED || c->base.h_kind == PSP_GH_EXPBALL_SIN_FULL || c->base.h_kind == PSP_GH_SINNORM2)
+            return fail(-1, "psp_genl_eig is built for sigma = s I (no dense sigma, no h kind that runs on the dense path)");
+        if (c->base.adaptive) return fail(-1, "psp_genl_eig is built for base.adaptive = 0 (the detached, uncontrolled state path)");
+    }
+    const bool eig_h = c->base.h_kind == PSP_GH_EIG_FP || c->base.h_kind == PSP_GH_EIG_NLS;
+    const bool eig_b = c->base.drift_kind == PSP_DRIFT_EIG_FP;
+    if ((eig_h || eig_b) && !e) return fail(-1, "PSP_GH_EIG_FP / PSP_GH_EIG_NLS / PSP_DRIFT_EIG_FP need a psp_genl_eig (psp_genl_rollout_fwd_eig)");
+    if (c->base.h_kind == PSP_GH_EIG_FP && !eig_b) return fail(-1, "PSP_GH_EIG_FP reads the vector c of PSP_DRIFT_EIG_FP (set both)");
+    if (c->base.h_kind == PSP_GH_EIG_NLS && !(c->base.h_par[1] > 0.f)) return fail(-1, "PSP_GH_EIG_NLS: h_par = (1 / c^2, d, -, -) with d > 0");
     if (u) {
         if (u->struct_bytes != (int32_t)sizeof(psp_genl_ul2)) return fail(-1, "psp_genl_ul2.struct_bytes is not sizeof(psp_genl_ul2)");
         if (u->kind < PSP_UL2_TABLE || u->kind > PSP_UL2_GRID) return fail(-1, "psp_genl_ul2.kind out of range");
@@ -1493,8 +1509,8 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs*
     if (L < 1 || L > psp::GENL_MAXL) return fail(-2, "value net: 1 to 4 hidden layers");
     const int D0 = b.d + (c->has_time ? 1 : 0);
     if (D0 > 16 * psp::GENL_MAXDB) return fail(-2, "value net: input width above 112");
-    if ((b.drift_kind != PSP_DRIFT_ZERO && b.drift_kind != PSP_DRIFT_DOUBLE_WELL && b.drift_kind != PSP_DRIFT_DIAG) || b.h_kind < 0 ||
-        b.h_kind > PSP_GH_SINNORM2 || b.noise_mode < 0 || b.noise_mode > 1 || b.domain_kind < 0 || b.domain_kind > PSP_DOM_ANNULUS ||
+    if ((b.drift_kind != PSP_DRIFT_ZERO && b.drift_kind != PSP_DRIFT_DOUBLE_WELL && b.drift_kind != PSP_DRIFT_DIAG && !eig_b) || b.h_kind < 0 ||
+        (b.h_kind > PSP_GH_SINNORM2 && !eig_h) || b.noise_mode < 0 || b.noise_mode > 1 || b.domain_kind < 0 || b.domain_kind > PSP_DOM_ANNULUS ||
         c->sigma_kind < PSP_GENL_SIGMA_SCALED || c->sigma_kind > PSP_GENL_SIGMA_DENSE)
         return fail(-1, "config enum out of range");
     if ((b.h_kind == PSP_GH_AFFINE_EXP || b.h_kind == PSP_GH_SINE_SOURCE) && (c->sigma_kind == PSP_GENL_SIGMA_DENSE || q))
@@ -1624,10 +1640,26 @@ int psp_genl_query_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs,
     return psp_genl_query_ul2(cfg, coeffs, nullptr, out);
 }
 
+namespace {
+int genl_sizes_of(const psp_genl_config* cfg, const GenlPlan& p, psp_genl_sizes* out);
+}
+
 int psp_genl_query_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, psp_genl_sizes* out) {
     GenlPlan p;
     int rc = make_genl_plan(cfg, &p, coeffs, ul2);
     if (rc) return rc;
+    return genl_sizes_of(cfg, p, out);
+}
+
+int psp_genl_query_eig(const psp_genl_config* cfg, const psp_genl_eig* eig, psp_genl_sizes* out) {
+    GenlPlan p;
+    int rc = make_genl_plan(cfg, &p, nullptr, nullptr, eig);
+    if (rc) return rc;
+    return genl_sizes_of(cfg, p, out);
+}
+
+namespace {
+int genl_sizes_of(const psp_genl_config* cfg, const GenlPlan& p, psp_genl_sizes* out) {
     if (!out) return fail(-1, "null output");
     memset(out, 0, sizeof(*out));
     const int64_t nblk = (int64_t)(cfg->base.N + 1) * p.ntile16;
@@ -1643,6 +1675,7 @@ int psp_genl_query_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs
     for (int i = 0; i <= p.a.L; ++i) out->seg_block_offset[i] = p.a.off[i];
     return 0;
 }
+}  // namespace
 
 int psp_genl_rollout_fwd(const psp_genl_config* cfg, const float* params, const float* x0, const float* t0,
                                     const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path, float* ahat,
@@ -1670,12 +1703,33 @@ int psp_genl_ul2_stage(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs
     return 0;
 }
 
+namespace {
+int genl_rollout_fwd_any(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, const psp_genl_eig* eig,
+                         const float* params, const float* x0, const float* t0, const float* xi, uint64_t seed, uint32_t iter,
+                         float* tables, float* path, float* ahat, float* VN, float* YN, float* XN, float* tN,
+                         unsigned long long* kcount, void* stream);
+}
+
 int psp_genl_rollout_fwd_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, const float* params,
                              const float* x0, const float* t0, const float* xi, uint64_t seed, uint32_t iter, float* tables,
                              float* path, float* ahat, float* VN, float* YN, float* XN, float* tN, unsigned long long* kcount,
                              void* stream) {
+    return genl_rollout_fwd_any(cfg, coeffs, ul2, nullptr, params, x0, t0, xi, seed, iter, tables, path, ahat, VN, YN, XN, tN, kcount, stream);
+}
+
+int psp_genl_rollout_fwd_eig(const psp_genl_config* cfg, const psp_genl_eig* eig, const float* params, const float* x0, const float* t0,
+                             const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path, float* ahat, float* VN,
+                             float* YN, float* XN, float* tN, unsigned long long* kcount, void* stream) {
+    return genl_rollout_fwd_any(cfg, nullptr, nullptr, eig, params, x0, t0, xi, seed, iter, tables, path, ahat, VN, YN, XN, tN, kcount, stream);
+}
+
+namespace {
+int genl_rollout_fwd_any(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, const psp_genl_eig* eig,
+                         const float* params, const float* x0, const float* t0, const float* xi, uint64_t seed, uint32_t iter,
+                         float* tables, float* path, float* ahat, float* VN, float* YN, float* XN, float* tN,
+                         unsigned long long* kcount, void* stream) {
     GenlPlan p;
-    int rc = make_genl_plan(cfg, &p, coeffs, ul2);
+    int rc = make_genl_plan(cfg, &p, coeffs, ul2, eig);
     if (rc) return rc;
     if (!params || !x0 || !tables || !VN || !YN || !XN || !tN || !kcount || !ahat) return fail(-1, "null buffer passed to psp_genl_rollout_fwd");
     if (cfg->has_time && !t0) return fail(-1, "t0 missing");
@@ -1692,7 +1746,12 @@ int psp_genl_rollout_fwd_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* 
     hipStream_t st = (hipStream_t)stream;
     if ((rc = PSP_LAUNCH(genl_tables_kernel, dim3(128), dim3(256), 0, st, a))) return rc;
     hipError_t e;
-    if (p.ul2_on) {
+    if (eig) {
+        psp::GenlEigFwdArgs ea;
+        ea.a = p.a;
+        ea.e.lam = eig->lambda; ea.e.S_out = eig->s_out; ea.e.out_relu = eig->output_relu; ea.e.reserved = 0;
+        e = psp::genl_eig_launch_fwd(ea, p.nw_fwd, p.ntile16, p.fwd_lds, st);        // (genl_eig_instance.hip)
+    } else if (p.ul2_on) {
         const psp::GenlLogArgs la = {p.a, p.u};
         e = psp::genl_ul2_launch_fwd(la, p.nw_fwd, p.ntile16, p.fwd_lds, st);        // (genl_ul2_instance.hip)
     } else if (p.a.lq)
@@ -1706,9 +1765,17 @@ int psp_genl_rollout_fwd_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* 
     if (e != hipSuccess) return fail_hip(e, "genl_fwd_kernel launch");
     return 0;
 }
+}  // namespace
 
-int psp_genl_rollout_bwd(const psp_genl_config* cfg, const float* params, const float* tables, const float* path,
+int psp_genl_rollout_bwd(const psp_genl_config* cfg_in, const float* params, const float* tables, const float* path,
                          const float* ahat, const float* wY, const float* wV, float* grad_partial, float* grad_out, void* stream) {
+    if (!cfg_in) return fail(-1, "null config");
+    // the backward reads (x, t), U and a^ and no coefficient: a config of psp_genl_rollout_fwd_eig is planned as what it is
+    // without the kinds only that entry point accepts
+    psp_genl_config cfg_v = *cfg_in;
+    if (cfg_v.base.h_kind == PSP_GH_EIG_FP || cfg_v.base.h_kind == PSP_GH_EIG_NLS) cfg_v.base.h_kind = PSP_GH_ZERO;
+    if (cfg_v.base.drift_kind == PSP_DRIFT_EIG_FP) cfg_v.base.drift_kind = PSP_DRIFT_ZERO;
+    const psp_genl_config* cfg = &cfg_v;
     GenlPlan p;
     int rc = make_genl_plan(cfg, &p);
     if (rc) return rc;

@@ -91,22 +91,34 @@ class DenseNet(nn.Module):
     ``activation`` (not a reference argument; default = the reference's relu(.)**2) selects the
     hidden nonlinearity: 'relu2', 'tanh2' (tanh(.)**2, the net `Committor function.ipynb` defines
     in its first cell) or 'tanh'.  The parameter draws do not depend on it.
+    ``output_relu``, ``weight_scale``, ``weight_shift`` and ``bias_init`` (not reference arguments either) give the nets the
+    eigenvalue notebooks define for themselves: a ReLU on the output, weights randn * weight_scale + weight_shift and constant
+    biases (`Eigenvalue - Fokker-Planck.ipynb`: 0.1, 0, 0.8; the Schroedinger notebook at d = 10: 0.01, 0.01, 0.1).  With the
+    defaults every draw and every output is what it was.
     """
     ACTIVATIONS = ('relu2', 'tanh2', 'tanh')
 
-    def __init__(self, d_in, d_out, lr, arch=[30, 30], seed=42, activation='relu2'):
+    def __init__(self, d_in, d_out, lr, arch=[30, 30], seed=42, activation='relu2', output_relu=False, weight_scale=0.1,
+                 weight_shift=0.0, bias_init=0.0):
         super().__init__()
         if activation not in self.ACTIVATIONS:
             raise ValueError('activation must be one of %s' % (self.ACTIVATIONS,))
         self.activation = activation
+        self.output_relu = bool(output_relu)
         torch.manual_seed(seed)
         self.nn_dims = [d_in] + list(arch) + [d_out]
         self.W = []
         fan_in = 0
         for i in range(len(self.nn_dims) - 1):
             fan_in += self.nn_dims[i]
-            self.W.append(nn.Parameter(torch.randn(fan_in, self.nn_dims[i + 1], requires_grad=True) * 0.1))
-            self.W.append(nn.Parameter(torch.zeros(self.nn_dims[i + 1], requires_grad=True)))
+            w = torch.randn(fan_in, self.nn_dims[i + 1], requires_grad=True) * weight_scale
+            if weight_shift != 0.0:
+                w = w + weight_shift
+            self.W.append(nn.Parameter(w))
+            if bias_init != 0.0:
+                self.W.append(nn.Parameter(bias_init * torch.ones(self.nn_dims[i + 1], requires_grad=True)))
+            else:
+                self.W.append(nn.Parameter(torch.zeros(self.nn_dims[i + 1], requires_grad=True)))
         for i, w in enumerate(self.W):
             self.register_parameter('param %d' % i, w)
         _own_adam(self, lr)
@@ -121,7 +133,8 @@ class DenseNet(nn.Module):
         for i in range(depth - 1):
             hidden = self._hidden(torch.matmul(x, self.W[2 * i]) + self.W[2 * i + 1])
             x = torch.cat([x, hidden], dim=1)
-        return torch.matmul(x, self.W[2 * depth - 2]) + self.W[2 * depth - 1]
+        out = torch.matmul(x, self.W[2 * depth - 2]) + self.W[2 * depth - 1]
+        return torch.relu(out) if self.output_relu else out
 
 
 class DenseNet_tanh_2(DenseNet):
@@ -133,10 +146,12 @@ class DenseNet_tanh_2(DenseNet):
 
 
 class DenseNet_tanh(nn.Module):
-    """Dense-concat net with tanh and nn.Linear layers (reference function_space.py:143-158)."""
+    """Dense-concat net with tanh and nn.Linear layers (reference function_space.py:143-158).  ``output_relu`` (not a reference
+    argument): a ReLU on the output, as the d = 5 Schroedinger eigenvalue notebook's copy of the class has it."""
 
-    def __init__(self, d_in, d_out, lr, arch=[30, 30], seed=42):
+    def __init__(self, d_in, d_out, lr, arch=[30, 30], seed=42, output_relu=False):
         super().__init__()
+        self.output_relu = bool(output_relu)
         torch.manual_seed(seed)
         self.nn_dims = [d_in] + list(arch) + [d_out]
         widths = [sum(self.nn_dims[:i + 1]) for i in range(len(self.nn_dims) - 1)]
@@ -146,7 +161,8 @@ class DenseNet_tanh(nn.Module):
     def forward(self, x):
         for layer in self.layers[:-1]:
             x = torch.cat([x, torch.tanh(layer(x))], dim=1)
-        return self.layers[-1](x)
+        out = self.layers[-1](x)
+        return torch.relu(out) if self.output_relu else out
 
 
 class MySequential(nn.Module):

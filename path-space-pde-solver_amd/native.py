@@ -164,6 +164,15 @@ class GenlUl2(C.Structure):
                 ("xb", C.c_float), ("dx", C.c_float), ("xhi", C.c_float), ("K_global", C.c_int64)]
 
 
+GH_EIG_FP, GH_EIG_NLS, DRIFT_EIG_FP = 16, 17, 16      # the eigenvalue problems: psp_genl_query_eig / psp_genl_rollout_fwd_eig only
+
+
+class GenlEig(C.Structure):
+    """psp_genl_eig: a trained lambda in device memory, the output ReLU's gate and the S_k output beside a GenlConfig
+    (psp_genl_query_eig / psp_genl_rollout_fwd_eig).  The library checks ``struct_bytes`` itself."""
+    _fields_ = [("struct_bytes", C.c_int32), ("output_relu", C.c_int32), ("lambda_", C.c_void_p), ("s_out", C.c_void_p)]
+
+
 class GenlAdj(C.Structure):
     """psp_genl_adj: the adjoint sweep of the state path beside a GenlConfig, a GenlCoeffs and a GenlUl2 (psp_genl_query_adj /
     psp_genl_adjoint_sweep).  The library checks ``struct_bytes`` itself and psp_genl_query_adj writes ``drift_t_offset``."""
@@ -238,6 +247,9 @@ SIGNATURES = {
     "psp_genl_ul2_stage": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlUl2), _P, _P]),
     "psp_genl_rollout_fwd_ul2": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlUl2), _P, _P, _P, _P,
                                            C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psp_genl_query_eig": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlEig), C.POINTER(GenlSizes)]),
+    "psp_genl_rollout_fwd_eig": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlEig), _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P,
+                                           _P, _P, _P, _P, _P, _P, _P, _P]),
     "psp_genl_query_adj": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlUl2), C.POINTER(GenlAdj),
                                      C.POINTER(GenlSizes)]),
     "psp_genl_adjoint_sweep": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlCoeffs), C.POINTER(GenlAdj), _P, _P, _P, _P, _P, _P]),

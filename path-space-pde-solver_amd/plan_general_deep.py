@@ -65,19 +65,82 @@ def _dense_concat_forward(x, params, act):
     return torch.matmul(x, params[2 * n - 2]) + params[2 * n - 1]
 
 
-def value_net_spec(V, d_in):
-    """dict(dims, act, linear, params) if V is a dense-concat net (d_in -> 1) the genl kernels implement, else a reason string."""
+def _linear_layers_spec(V, dims, d_in, relu_ok):
+    """A user-defined module whose ``layers`` are nn.Linear over the growing concatenation (the eigenvalue notebooks' own copy of
+    DenseNet_tanh): dict as value_net_spec, or None if it is not that structure or its forward is not the tanh formula."""
+    layers = getattr(V, 'layers', None)
+    if not isinstance(layers, torch.nn.ModuleList) or len(layers) != len(dims) - 1:
+        return None
+    fan, params = 0, []
+    for i, layer in enumerate(layers):
+        fan += dims[i]
+        if not isinstance(layer, torch.nn.Linear) or layer.bias is None or tuple(layer.weight.shape) != (dims[i + 1], fan):
+            return None
+        params += [layer.weight, layer.bias]
+    regs = list(V.parameters())
+    if len(regs) != len(params) or any(a is not b for a, b in zip(regs, params)):
+        return None
+    g = torch.Generator().manual_seed(1234)
+    probe = torch.randn(16, d_in, generator=g).to(params[0].device)
+    with torch.no_grad():
+        try:
+            want = V(probe)
+        except Exception:                                        # pragma: no cover
+            return None
+        def fwd():
+            return _dense_concat_forward(probe, [p.t() if p.dim() == 2 else p for p in params], 'tanh')
+        relu = _probe_output_relu(V, probe, want, fwd, params[-1], relu_ok)
+    if relu is None:
+        return None
+    return dict(dims=dims, act='tanh', linear=True, params=params, output_relu=relu)
+
+
+def _probe_output_relu(V, probe, want, fwd, out_bias, relu_ok):
+    """False: V(probe) is fwd(); True: it is relu(fwd()) (accepted only where relu_ok); None: neither.  Where no output of the
+    probe batch is negative the two cannot be told apart, so the output bias is lowered until all are (and restored), and V
+    decides -- also for a caller that takes no ReLU: a clipped net whose probe outputs happen to be positive is not the plain one."""
+    got = fwd()
+    if want.shape != got.shape:
+        return None
+    close = lambda a, b: torch.allclose(a, b, rtol=1e-5, atol=1e-6)     # noqa: E731
+    if close(want, got):
+        if bool((got < 0).any()):
+            return False
+        keep = out_bias.detach().clone()
+        try:
+            out_bias -= (got.max() + 1.0)
+            want2, got2 = V(probe), fwd()
+        finally:
+            out_bias.copy_(keep)
+        if close(want2, got2):
+            return False
+        return True if (relu_ok and close(want2, torch.relu(got2))) else None
+    if relu_ok and close(want, torch.relu(got)):
+        return True
+    return None
+
+
+def value_net_spec(V, d_in, output_relu_ok=False):
+    """dict(dims, act, linear, params, output_relu) if V is a dense-concat net (d_in -> 1) the genl kernels implement, else a
+    reason string.  output_relu_ok: the caller's kernels gate a ReLU on the output (plan_eigen_native.py); every other caller
+    refuses such a net."""
     dims = getattr(V, 'nn_dims', None)
     if dims is None or len(dims) < 3 or dims[0] != d_in or dims[-1] != 1:
         return 'V is not a dense-concat net (%d -> 1) (no matching nn_dims)' % d_in
     dims = [int(v) for v in dims]
+    relu = bool(getattr(V, 'output_relu', False))
+    if isinstance(V, (DenseNet, DenseNet_tanh)) and relu and not output_relu_ok:
+        return 'V carries a ReLU on its output (output_relu=True): only EigenvalueSolver runs that on the native kernels'
     if isinstance(V, DenseNet):
-        return dict(dims=dims, act=getattr(V, 'activation', 'relu2'), linear=False, params=list(V.W))
+        return dict(dims=dims, act=getattr(V, 'activation', 'relu2'), linear=False, params=list(V.W), output_relu=relu)
     if isinstance(V, DenseNet_tanh):
         params = []
         for layer in V.layers:
             params += [layer.weight, layer.bias]
-        return dict(dims=dims, act='tanh', linear=True, params=params)
+        return dict(dims=dims, act='tanh', linear=True, params=params, output_relu=relu)
+    lin = _linear_layers_spec(V, dims, d_in, output_relu_ok)
+    if lin is not None:
+        return lin
     # a user-defined module of the same structure (the notebooks define their own variants): W = [W_1, b_1, .., W_out, b_out] with
     # (in, out) weights over the growing concatenation, registered in that order and nothing else -- and a forward that IS one
     # of the three formulas, checked on a probe batch (a private generator: the global RNG stream is the reference's)
@@ -100,9 +163,9 @@ def value_net_spec(V, d_in):
         except Exception as e:                                   # pragma: no cover
             return 'V could not be evaluated on a probe batch (%s)' % e
         for act in ('relu2', 'tanh2', 'tanh'):
-            got = _dense_concat_forward(probe, W, act)
-            if want.shape == got.shape and torch.allclose(want, got, rtol=1e-5, atol=1e-6):
-                return dict(dims=dims, act=act, linear=False, params=list(W))
+            relu = _probe_output_relu(V, probe, want, lambda: _dense_concat_forward(probe, W, act), W[-1], output_relu_ok)
+            if relu is not None:
+                return dict(dims=dims, act=act, linear=False, params=list(W), output_relu=relu)
     return "V's forward is none of the dense-concat formulas the kernels implement (relu^2, tanh^2, tanh)"
 
 
@@ -142,6 +205,12 @@ def deep_eligibility(solver):
 
 
 class GeneralDeepPlan(GeneralNativePlan):
+    output_relu_ok = False          # plan_eigen_native.EigenDeepPlan: its forward gates the output ReLU
+
+    def _query(self, gcfg, sz):
+        """The size query of this plan's forward entry point."""
+        return self.lib.psp_genl_query(C.byref(gcfg), C.byref(sz))
+
     def __init__(self, solver):
         s = solver
         self.s = s
@@ -152,7 +221,7 @@ class GeneralDeepPlan(GeneralNativePlan):
         self.net = s.V
         self.key = None
         self.elliptic = bool(s.elliptic)
-        net = value_net_spec(s.V, s.d + (0 if self.elliptic else 1))
+        net = value_net_spec(s.V, s.d + (0 if self.elliptic else 1), self.output_relu_ok)
         assert not isinstance(net, str), net
         self.net_spec = net
         self.dims = list(net['dims'])
@@ -188,7 +257,7 @@ class GeneralDeepPlan(GeneralNativePlan):
         gcfg.linear_layout = 1 if net['linear'] else 0
         self.gcfg, self.cfg = gcfg, cfg
         sz = nat.GenlSizes()
-        nat.check(self.lib.psp_genl_query(C.byref(gcfg), C.byref(sz)), 'psp_genl_query')
+        nat.check(self._query(gcfg, sz), 'psp_genl_query')
         assert sz.n_params == self.P, (sz.n_params, self.P)
         self.sizes = sz
         self.matrix_mode, self.range_flag = 'fp32', None            # fp32 MFMA only (v_mfma_f32_16x16x4_f32)
@@ -205,7 +274,7 @@ class GeneralDeepPlan(GeneralNativePlan):
 
     def _check_sizes(self):
         sz = nat.GenlSizes()
-        nat.check(self.lib.psp_genl_query(C.byref(self.gcfg), C.byref(sz)), 'psp_genl_query')
+        nat.check(self._query(self.gcfg, sz), 'psp_genl_query')
         assert sz.path_bytes <= self.path.numel() * 4 and sz.ahat_bytes <= self.ahat.numel() * 4
         if sz.grad_partial_bytes > self.grad_partial.numel() * 4:
             self.grad_partial = torch.empty(sz.grad_partial_bytes // 4, dtype=torch.float32, device=self.dev)

@@ -1148,3 +1148,78 @@ class SinNorm2(_ZeroDriftElliptic):
     def native_vtrue_spec(self):
         """v_true as a closed form of the device test log (include/psp.h PSP_VTRUE_SINR2: sin(pi |x|^2))."""
         return {'kind': _nat.VTRUE_SINR2, 'par': (0.0, 0.0, 0.0, 0.0)}
+
+
+class _EigenvalueOnBox:
+    """What the eigenvalue problems of the diffusion-loss notebooks share (`Eigenvalue - *.ipynb`): the periodic box
+    [0, 2 pi]^d, sigma = sqrt(2) I, the centre X_0 = pi 1, zero boundary data (the notebooks use periodic terms instead)."""
+
+    def _setup(self, name, d, device):
+        self.device = _resolve(device)
+        self.name, self.d = name, d
+        self.B = (torch.sqrt(torch.tensor(2.0)) * torch.eye(d)).to(self.device)
+        self.X_0 = (torch.tensor(np.pi) * torch.ones(d)).to(self.device)
+        self.Y_0 = torch.zeros(1).to(self.device)
+        self.X_l, self.X_r = 0.0, 2 * np.pi
+        self.boundary, self.one_boundary = 'square', False
+
+    def sigma(self, x):
+        return self.B
+
+    def g(self, x):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+
+class FokkerPlanckEigenvalue(_EigenvalueOnBox):
+    """The Fokker-Planck eigenvalue problem of `Eigenvalue - Fokker-Planck.ipynb`: with c = 0.1 1 and S(x) = sum_j c_j cos x_j,
+    b = -cos(S) c sin x, h = y (-sin(S) sum_i c_i^2 sin^2 x_i - cos(S) S); eigenfunction exp(-sin S), eigenvalue 0."""
+
+    def __init__(self, name='Eigenvalue', d=1, device=None):
+        self._setup(name, d, device)
+        self.c = (0.1 * torch.ones(1, d)).to(self.device)
+        self.lambda_ = 0.0
+
+    def b(self, x):
+        c = self.c.to(x.device)
+        return -torch.cos(torch.sum(c * torch.cos(x), 1)).unsqueeze(1) * c * torch.sin(x)
+
+    def h(self, x, y, z):
+        c = self.c.to(x.device)
+        S = torch.sum(c * torch.cos(x), 1)
+        return y * (-torch.sum(c**2 * torch.sin(x)**2, 1) * torch.sin(S) - torch.cos(S) * S)
+
+    def v_true(self, x):
+        return torch.exp(-torch.sin(torch.sum(self.c.to(x.device) * torch.cos(x), 1)))
+
+    def general_native_spec(self):
+        """PSP_DRIFT_EIG_FP / PSP_GH_EIG_FP (psp_genl_*_eig only): both read the vector c."""
+        return {'drift': (_nat.DRIFT_EIG_FP, self.c.reshape(-1).float().contiguous()), 'sigma_scale': float(self.B[0, 0]),
+                'h': _nat.GH_EIG_FP, 'h_par': (0.0, float(self.d), 0.0, 0.0)}
+
+
+class SchroedingerEigenvalue(_EigenvalueOnBox):
+    """The nonlinear Schroedinger eigenvalue problem of `Eigenvalue - nonlinear Schroedinger equation, d = *.ipynb`: b = 0,
+    h = -y^3 - y (-exp((2 / d) sum cos x_i) / c^2 + sum (sin^2 x_i / d^2 - cos x_i / d) - 3) with the normalising constant
+    c = sqrt((int_0^{2 pi} exp((2 / d) cos x) dx)^d / (2 pi)^d) formed by quadrature as the notebook's first cell does;
+    eigenfunction exp((1 / d) sum cos x_i) / c, eigenvalue -3."""
+
+    def __init__(self, name='Eigenvalue', d=1, device=None):
+        from scipy import integrate
+        self._setup(name, d, device)
+        self.c = float(np.sqrt(integrate.quad(lambda x: np.exp(2 / d * np.cos(x)), 0, 2 * np.pi)[0]**d / (2 * np.pi)**d))
+        self.lambda_ = -3.0
+
+    def b(self, x):
+        return torch.zeros(x.shape).to(x.device)
+
+    def h(self, x, y, z):
+        return -y**3 - y * (-1 / self.c**2 * torch.exp(2 / self.d * torch.sum(torch.cos(x), 1))
+                            + torch.sum((torch.sin(x)**2 / self.d**2 - torch.cos(x) / self.d), 1) - 3)
+
+    def v_true(self, x):
+        return 1 / self.c * torch.exp(1 / self.d * torch.sum(torch.cos(x), 1))
+
+    def general_native_spec(self):
+        """PSP_GH_EIG_NLS (psp_genl_*_eig only): h_par = (1 / c^2, d, -, -)."""
+        return {'drift': (_nat.DRIFT_ZERO, None), 'sigma_scale': float(self.B[0, 0]), 'h': _nat.GH_EIG_NLS,
+                'h_par': (1.0 / self.c**2, float(self.d), 0.0, 0.0)}
