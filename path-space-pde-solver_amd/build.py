@@ -41,9 +41,24 @@ def _digest(paths, extra=""):
     return h.hexdigest()
 
 
-def _compile(src, obj, defs, deps, force):
+def unit_deps(src):
+    """Every file a translation unit is made of: the source, then what its `#include "..."` lines name, followed recursively --
+    headers, the .def instance lists, include/psp.h.  System headers (<...>) belong to the toolchain, not to the tree."""
+    seen, todo = [], [os.path.normpath(src)]
+    while todo:
+        path = todo.pop()
+        if path in seen:
+            continue
+        seen.append(path)
+        with open(path) as fh:
+            for name in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', fh.read(), re.M):
+                todo.append(os.path.normpath(os.path.join(os.path.dirname(path), name)))
+    return seen
+
+
+def _compile(src, obj, defs, force):
     stamp = obj + ".sha"
-    dig = _digest(deps, " ".join(FLAGS + defs))
+    dig = _digest(unit_deps(src), " ".join(FLAGS + defs))
     if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig:
         return obj, False
     cmd = [HIPCC] + FLAGS + defs + ["-c", src, "-o", obj]
@@ -71,75 +86,34 @@ def build(force=False, jobs=None, verbose=True, extra_flags=(), lib_path=None, o
 
 def _build(force, jobs, verbose, only):
     os.makedirs(OBJ, exist_ok=True)
-    hdr = os.path.join(CSRC, "hjb_kernels.h")
-    inc = os.path.join(HERE, "..", "include", "psp.h")
-    idef = os.path.join(CSRC, "instances.def")
-    inst_src = os.path.join(CSRC, "hjb_instance.hip")
-    api_src = os.path.join(CSRC, "psp_api.hip")
-    ghdr = os.path.join(CSRC, "gen_kernels.h")
-    gdef = os.path.join(CSRC, "gen_instances.def")
-    ginst_src = os.path.join(CSRC, "gen_instance.hip")
-    whdr = os.path.join(CSRC, "hjbw_kernels.h")
-    wdef = os.path.join(CSRC, "wide_instances.def")
-    winst_src = os.path.join(CSRC, "hjbw_instance.hip")
-    dhdr = os.path.join(CSRC, "hjbd_kernels.h")
-    ddef = os.path.join(CSRC, "dense_instances.def")
-    dinst_src = os.path.join(CSRC, "hjbd_instance.hip")
     # The split of an fp32 operand into its f16 pair (hjb_kernels.h split8) costs two instructions per value only when the SLP
     # vectoriser leaves its two fmas alone: every translation unit but the wide family's is compiled with it off (measured, same
     # box: d = 100 forward -1.8 %, diffusion iteration -3 %, others unchanged; wide d = 500 backward +30 % from spills -- it keeps
     # the round-3 form).
     NOSLP, CLASSIC = ["-fno-slp-vectorize"], ["-DPSP_SPLIT_CLASSIC=1"]
-    ugrid = os.path.join(CSRC, "ugrid.h")
-    ehdr = os.path.join(CSRC, "hjbe_kernels.h")
-    einst_src = os.path.join(CSRC, "hjbe_instance.hip")
-    tasks = [(api_src, os.path.join(OBJ, "psp_api.o"), NOSLP, [api_src, hdr, os.path.join(CSRC, "hjb_basis_kernels.h"), ghdr, whdr, dhdr, ehdr, os.path.join(CSRC, "aff_kernels.h"), ugrid, os.path.join(CSRC, "genl_kernels.h"), os.path.join(CSRC, "genl_eval_kernels.h"), os.path.join(CSRC, "genl_adj_kernels.h"), os.path.join(CSRC, "pinn_kernels.h"), inc, idef, gdef, wdef, ddef])]
-    # the reference-control / uncontrolled evaluation rollout (psp_is_rollout): every d bucket and control kind in one unit
-    tasks.append((einst_src, os.path.join(OBJ, "hjbe_inst.o"), NOSLP, [einst_src, ehdr, ugrid, hdr]))
-    # the linear / affine / constant control kernels (psp_aff_*): the three d buckets in one unit
-    ainst_src = os.path.join(CSRC, "aff_instance.hip")
-    tasks.append((ainst_src, os.path.join(OBJ, "aff_inst.o"), NOSLP, [ainst_src, os.path.join(CSRC, "aff_kernels.h"), hdr]))
-    # the device-side K_test_log evaluation (psp_genl_test_error): both waves-per-tile instances in one unit
-    vinst_src = os.path.join(CSRC, "genl_eval_instance.hip")
-    tasks.append((vinst_src, os.path.join(OBJ, "genl_eval_inst.o"), NOSLP,
-                  [vinst_src, os.path.join(CSRC, "genl_eval_kernels.h"), os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
-    # the linear-quadratic instances of the run-time-shaped forward kernel (psp_genl_rollout_fwd_lq): three waves-per-tile variants
-    lqinst_src = os.path.join(CSRC, "genl_lq_instance.hip")
-    tasks.append((lqinst_src, os.path.join(OBJ, "genl_lq_inst.o"), NOSLP, [lqinst_src, os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
-    # the u_L2-log instances of that kernel (psp_genl_rollout_fwd_ul2: two shapes, three waves-per-tile variants) and the gain staging
-    ulinst_src = os.path.join(CSRC, "genl_ul2_instance.hip")
-    tasks.append((ulinst_src, os.path.join(OBJ, "genl_ul2_inst.o"), NOSLP, [ulinst_src, os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
-    # the eigenvalue instances of that kernel (psp_genl_rollout_fwd_eig): three waves-per-tile variants
-    eiginst_src = os.path.join(CSRC, "genl_eig_instance.hip")
-    tasks.append((eiginst_src, os.path.join(OBJ, "genl_eig_inst.o"), NOSLP, [eiginst_src, os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
-    # the adjoint sweep of the state path for the value-function ansatz (psp_genl_adjoint_sweep): three waves-per-tile variants
-    adjinst_src = os.path.join(CSRC, "genl_adj_instance.hip")
-    tasks.append((adjinst_src, os.path.join(OBJ, "genl_adj_inst.o"), NOSLP,
-                  [adjinst_src, os.path.join(CSRC, "genl_adj_kernels.h"), os.path.join(CSRC, "genl_kernels.h"), ghdr, hdr, ugrid]))
-    # the PINN loss (psp_pinn_*): forward-Laplacian residual, per-sample finish, adjoint with the weight gradients
-    pinst_src = os.path.join(CSRC, "pinn_instance.hip")
-    tasks.append((pinst_src, os.path.join(OBJ, "pinn_inst.o"), NOSLP, [pinst_src, os.path.join(CSRC, "pinn_kernels.h")]))
-    for d, H in instances("dense_instances.def"):
-        tasks.append((dinst_src, os.path.join(OBJ, "dnet_inst_%d_%d.o" % (d, H)),
-                      ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [dinst_src, dhdr, ugrid, whdr, hdr]))
-    for d, H in instances():
-        tasks.append((inst_src, os.path.join(OBJ, "inst_%d_%d.o" % (d, H)),
-                      ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [inst_src, hdr, os.path.join(CSRC, "hjbs_kernels.h"), os.path.join(CSRC, "hjba_kernels.h"),
-                       os.path.join(CSRC, "hjbq_kernels.h"), os.path.join(CSRC, "hjbx_kernels.h")]))
-    for d, H in instances("wide_instances.def"):
-        tasks.append((winst_src, os.path.join(OBJ, "wide_inst_%d_%d.o" % (d, H)),
-                      ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + CLASSIC, [winst_src, whdr, hdr, os.path.join(CSRC, "hjbc_kernels.h")]))
-    wxinst_src = os.path.join(CSRC, "hjbwx_instance.hip")
-    for d, H in instances("wide_instances.def"):
-        if d <= 256:        # the split-product role-specialised backward of these instances: its own unit, SLP vectoriser off
-            tasks.append((wxinst_src, os.path.join(OBJ, "widex_inst_%d_%d.o" % (d, H)),
-                          ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [wxinst_src, os.path.join(CSRC, "hjbwx_kernels.h"), whdr, hdr]))
-    for d, H in instances("gen_instances.def"):
-        tasks.append((ginst_src, os.path.join(OBJ, "gen_inst_%d_%d.o" % (d, H)),
-                      ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + NOSLP, [ginst_src, ghdr, hdr]))
+    # (source, object, defines and flags); what a unit depends on is read from its #include lines (unit_deps)
+    tasks = [("psp_api.hip", "psp_api.o", NOSLP),
+             ("hjbe_instance.hip", "hjbe_inst.o", NOSLP),           # psp_is_rollout: every d bucket and control kind in one unit
+             ("aff_instance.hip", "aff_inst.o", NOSLP),             # psp_aff_*: the three d buckets in one unit
+             ("genl_eval_instance.hip", "genl_eval_inst.o", NOSLP),     # psp_genl_test_error: both waves-per-tile instances
+             ("genl_lq_instance.hip", "genl_lq_inst.o", NOSLP),     # psp_genl_rollout_fwd_lq: three waves-per-tile variants
+             ("genl_ul2_instance.hip", "genl_ul2_inst.o", NOSLP),   # psp_genl_rollout_fwd_ul2 (two shapes, three variants), gain staging
+             ("genl_eig_instance.hip", "genl_eig_inst.o", NOSLP),   # psp_genl_rollout_fwd_eig: three waves-per-tile variants
+             ("genl_adj_instance.hip", "genl_adj_inst.o", NOSLP),   # psp_genl_adjoint_sweep: three waves-per-tile variants
+             ("pinn_instance.hip", "pinn_inst.o", NOSLP)]           # psp_pinn_*: residual, per-sample finish, adjoint
+    per_shape = [("hjbd_instance.hip", "dnet_inst", "dense_instances.def", NOSLP, 1 << 30),
+                 ("hjb_instance.hip", "inst", "instances.def", NOSLP, 1 << 30),
+                 ("hjbw_instance.hip", "wide_inst", "wide_instances.def", CLASSIC, 1 << 30),
+                 # the split-product role-specialised backward of the wide instances up to d = 256: its own unit, SLP vectoriser off
+                 ("hjbwx_instance.hip", "widex_inst", "wide_instances.def", NOSLP, 256),
+                 ("gen_instance.hip", "gen_inst", "gen_instances.def", NOSLP, 1 << 30)]
+    for src, stem, deffile, flags, d_max in per_shape:
+        tasks += [(src, "%s_%d_%d.o" % (stem, d, H), ["-DPSP_D=%d" % d, "-DPSP_H=%d" % H] + flags)
+                  for d, H in instances(deffile) if d <= d_max]
+    tasks = [(os.path.join(CSRC, src), os.path.join(OBJ, obj), defs) for src, obj, defs in tasks]
     jobs = jobs or min(6, os.cpu_count() or 2)
     with ThreadPoolExecutor(max_workers=jobs) as ex:
-        results = list(ex.map(lambda t: _compile(t[0], t[1], t[2], t[3], force), tasks))
+        results = list(ex.map(lambda t: _compile(t[0], t[1], t[2], force), tasks))
     objs = [r[0] for r in results]
     rebuilt = any(r[1] for r in results)
     # drop objects of instances that were removed from instances.def

@@ -80,9 +80,6 @@ constexpr int GENL_MAXL = 4;        // hidden layers
 constexpr int GENL_MAXDB = 7;       // input blocks (d + 1 <= 112)
 constexpr int GENL_MAXHB = 8;       // hidden blocks per layer (H <= 128)
 enum { GACT_RELU2 = 0, GACT_TANH2 = 1, GACT_TANH = 2 };
-// h of ExponentialOnBallNonlinearSinHessian (problems.py:1094): GH_EXPBALL_SIN with (sum_i x_i)^2 = sum_ij x_i x_j in the linear
-// term, |x|^2 kept in the exponent.  Served by the dense-sigma instances of the forward kernel only.
-constexpr int GH_EXPBALL_SIN_FULL = 6;
 // The eigenvalue problems (EIG instances of the forward kernel only; numbered away from the kinds above):
 //   GH_EIG_FP   h = y (-sin(S) sum_i c_i^2 sin^2 x_i - cos(S) S),  S = sum_j c_j cos x_j, c = the drift vector (Fokker-Planck)
 //   GH_EIG_NLS  h = -y^3 - y (-p0 exp((2 / d) sum_i cos x_i) + sum_i (sin^2 x_i / d^2 - cos x_i / d) - 3),  h_par = (1 / c^2, d, -, -)

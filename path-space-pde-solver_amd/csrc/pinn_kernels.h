@@ -39,6 +39,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gh_kinds.h"
 
 namespace psp {
 
@@ -47,11 +48,8 @@ constexpr int kPinnZS = 132;           // row stride of a layer's pre-activation
 constexpr int kPinnThreads = 256;      // four waves
 constexpr int kPinnMaxWg = 256;        // partial gradients of the backward kernel
 
+// (DRIFT_* live in hjb_kernels.h with the MFMA machinery this header does without: psp_api.hip asserts that the two agree)
 enum { PINN_DRIFT_ZERO = 0, PINN_DRIFT_DIAG = 2, PINN_DRIFT_DWELL = 3 };                      // PSP_DRIFT_*
-enum { PINN_H_ZERO = 0, PINN_H_QUAD = 1, PINN_H_ALLEN_CAHN = 2, PINN_H_EXP_LIN = 3, PINN_H_EXP_SQ = 4, PINN_H_EXP_SIN = 5,
-       PINN_H_EXP_SIN_FULL = 6,        // PSP_GH_*; 6 = GH_EXPBALL_SIN_FULL (genl_kernels.h): (sum_i x_i)^2 in the linear part
-       PINN_H_AFFINE_EXP = 7,          // h = p0 + p1 y + p2 |z|^2 + p3 exp(-y), z = s grad V
-       PINN_H_SINE_SOURCE = 8 };       // h = c y + s(x_0, x_1) (gen_kernels.h gh_sine_source, the same arithmetic)
 enum { PINN_ACT_RELU2 = 0, PINN_ACT_TANH2 = 1, PINN_ACT_TANH = 2 };                           // PSP_ACT_*
 
 struct PinnArgs {
@@ -237,7 +235,7 @@ __global__ __launch_bounds__(kPinnThreads) void pinn_forward_kernel(const PinnAr
 }
 
 // One thread per sample: the residual and what the adjoint is seeded with.  kPairs: without the pair term nl(..) of
-// PINN_H_EXP_SQ / PINN_H_EXP_SIN, which pinn_pair_kernel adds per (time, sample).
+// GH_EXPBALL_SQ / GH_EXPBALL_SIN, which pinn_pair_kernel adds per (time, sample).
 template <bool kPairs>
 __global__ void pinn_finish_kernel(const PinnArgs a) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -260,36 +258,30 @@ __global__ void pinn_finish_kernel(const PinnArgs a) {
         else if (a.drift_kind == PINN_DRIFT_DIAG) bj = a.drift[j] * xj;
         bg = fmaf(bj, g[j], bg);
         g2 = fmaf(g[j], g[j], g2);
-        // dR / dg_j = b_j + 2 p2 s^2 g_j for h = .. + p2 |s grad V|^2 (PINN_H_QUAD: p2 = -1 / 2)
-        if (a.h_kind == PINN_H_QUAD) cg[j] = bj - s * s * g[j];
-        else if (a.h_kind == PINN_H_AFFINE_EXP) cg[j] = bj + (2.0f * a.h_par[2]) * (s * s) * g[j];
+        // dR / dg_j = b_j + 2 p2 s^2 g_j for h = .. + p2 |s grad V|^2 (GH_QUAD: p2 = -1 / 2)
+        if (a.h_kind == GH_QUAD) cg[j] = bj - s * s * g[j];
+        else if (a.h_kind == GH_AFFINE_EXP) cg[j] = bj + (2.0f * a.h_par[2]) * (s * s) * g[j];
         else cg[j] = bj;
     }
     float h = 0.f, hy = 0.f;
-    if (a.h_kind == PINN_H_QUAD) h = -0.5f * s * s * g2;
-    else if (a.h_kind == PINN_H_ALLEN_CAHN) { h = y - y * y * y; hy = 1.0f - 3.0f * y * y; }
-    else if (a.h_kind == PINN_H_AFFINE_EXP) {                        // (g2 = 0 with n_grad = 0: the host refuses p2 != 0 there)
-        float e = 0.f;
-        if (a.h_par[3] != 0.f) e = a.h_par[3] * expf(-y);
-        h = ((a.h_par[2] * (s * s * g2) + a.h_par[0]) + a.h_par[1] * y) + e;
-        hy = a.h_par[1] - e;
-    } else if (a.h_kind == PINN_H_SINE_SOURCE) {
-        const float* p = a.h_par;
-        if (p[0] == 0.f) {
-            const float c = p[3], s1 = sinf(p[1] * x[0]), s2 = sinf(p[2] * x[1]);
-            h = ((c * y + (p[1] * (p[1] * s1)) * s2) + (p[2] * (p[2] * s1)) * s2) - (c * s1) * s2;
-            hy = c;
-        } else {
-            h = p[1] * (p[1] * sinf(p[1] * x[0])) + p[2] * (p[2] * (p[3] * sinf(p[2] * x[0])));
-        }
-    } else if (a.h_kind >= PINN_H_EXP_LIN) {                           // the exponential-on-the-ball family (gen_kernels.h)
+    if (a.h_kind == GH_QUAD) h = -0.5f * s * s * g2;
+    else if (a.h_kind == GH_ALLEN_CAHN) { h = y - y * y * y; hy = 1.0f - 3.0f * y * y; }
+    else if (a.h_kind == GH_AFFINE_EXP) {                        // (g2 = 0 with n_grad = 0: the host refuses p2 != 0 there)
+        float minus_h;
+        gh_affine_exp(a.h_par, y, s * s * g2, minus_h, hy);
+        h = -minus_h;
+    } else if (a.h_kind == GH_SINE_SOURCE) {                     // (sub-mode 1 reads x_0 only: d = 1 has no x[1])
+        float minus_h;
+        gh_sine_source(a.h_par, y, x[0], d > 1 ? x[1] : 0.f, minus_h, hy);
+        h = -minus_h;
+    } else if (a.h_kind >= GH_EXPBALL_LIN) {                           // the exponential-on-the-ball family (gen_kernels.h)
         const float al = a.h_par[0];
-        const float rl = a.h_kind == PINN_H_EXP_SIN_FULL ? sx * sx : rr;    // the exponent keeps |x|^2
+        const float rl = a.h_kind == GH_EXPBALL_SIN_FULL ? sx * sx : rr;    // the exponent keeps |x|^2
         const float lin = 2.0f * al * (2.0f * al * rl + a.h_par[1]) + a.h_par[2];
         float nl = 0.f, nly = 0.f;
-        if (a.h_kind != PINN_H_EXP_LIN && !(kPairs && (a.h_kind == PINN_H_EXP_SQ || a.h_kind == PINN_H_EXP_SIN))) {
+        if (a.h_kind != GH_EXPBALL_LIN && !(kPairs && (a.h_kind == GH_EXPBALL_SQ || a.h_kind == GH_EXPBALL_SIN))) {
             const float arg = expf(2.0f * al * rr) - y * y;
-            if (a.h_kind == PINN_H_EXP_SQ) { nl = arg; nly = -2.0f * y; }
+            if (a.h_kind == GH_EXPBALL_SQ) { nl = arg; nly = -2.0f * y; }
             else { nl = sinf(arg); nly = -2.0f * y * cosf(arg); }
         }
         h = nl - y * lin;
@@ -428,7 +420,7 @@ __global__ __launch_bounds__(kPinnThreads) void pinn_pair_kernel(const PinnPairA
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, K = a.K, d = a.d;
     for (int i = tid; i < K; i += kPinnThreads) pinn_lds[i] = a.tau2 * a.t[i];
     __syncthreads();
-    const bool sq = a.h_kind == PINN_H_EXP_SQ, pair = sq || a.h_kind == PINN_H_EXP_SIN;
+    const bool sq = a.h_kind == GH_EXPBALL_SQ, pair = sq || a.h_kind == GH_EXPBALL_SIN;
     for (int j = blockIdx.x * 4 + wave; j < K; j += gridDim.x * 4) {
         const float* x = a.x + (size_t)j * d;
         float rr = 0.f;

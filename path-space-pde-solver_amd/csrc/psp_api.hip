@@ -21,6 +21,24 @@
 #include "aff_kernels.h"
 #include "pinn_kernels.h"
 
+// The kernels keep the header's enums numerically (device code does not include the C header): every such numbering, tied here.
+#define PSP_SAME(a, b) static_assert(int(a) == int(b), #a " != " #b)
+PSP_SAME(psp::GH_ZERO, PSP_GH_ZERO); PSP_SAME(psp::GH_QUAD, PSP_GH_QUAD); PSP_SAME(psp::GH_ALLEN_CAHN, PSP_GH_ALLEN_CAHN);
+PSP_SAME(psp::GH_EXPBALL_LIN, PSP_GH_EXPBALL_LIN); PSP_SAME(psp::GH_EXPBALL_SQ, PSP_GH_EXPBALL_SQ);
+PSP_SAME(psp::GH_EXPBALL_SIN, PSP_GH_EXPBALL_SIN); PSP_SAME(psp::GH_EXPBALL_SIN_FULL, PSP_GH_EXPBALL_SIN_FULL);
+PSP_SAME(psp::GH_AFFINE_EXP, PSP_GH_AFFINE_EXP); PSP_SAME(psp::GH_SINE_SOURCE, PSP_GH_SINE_SOURCE);
+PSP_SAME(psp::GH_SINNORM2, PSP_GH_SINNORM2); PSP_SAME(psp::GH_EIG_FP, PSP_GH_EIG_FP); PSP_SAME(psp::GH_EIG_NLS, PSP_GH_EIG_NLS);
+PSP_SAME(psp::DOM_NONE, PSP_DOM_NONE); PSP_SAME(psp::DOM_SPHERE, PSP_DOM_SPHERE); PSP_SAME(psp::DOM_BOX, PSP_DOM_BOX);
+PSP_SAME(psp::DOM_BOX_UPPER_ALL, PSP_DOM_BOX_UPPER_ALL); PSP_SAME(psp::DOM_BOX_UPPER_ANY, PSP_DOM_BOX_UPPER_ANY);
+PSP_SAME(psp::DOM_ANNULUS, PSP_DOM_ANNULUS);
+PSP_SAME(psp::DRIFT_ZERO, PSP_DRIFT_ZERO); PSP_SAME(psp::DRIFT_DENSE, PSP_DRIFT_DENSE); PSP_SAME(psp::DRIFT_DIAG, PSP_DRIFT_DIAG);
+PSP_SAME(psp::DRIFT_DWELL, PSP_DRIFT_DOUBLE_WELL); PSP_SAME(psp::DRIFT_EIG_FP, PSP_DRIFT_EIG_FP);
+PSP_SAME(psp::PINN_DRIFT_ZERO, psp::DRIFT_ZERO); PSP_SAME(psp::PINN_DRIFT_DIAG, psp::DRIFT_DIAG);
+PSP_SAME(psp::PINN_DRIFT_DWELL, psp::DRIFT_DWELL);
+PSP_SAME(psp::GACT_RELU2, PSP_ACT_RELU2); PSP_SAME(psp::GACT_TANH2, PSP_ACT_TANH2); PSP_SAME(psp::GACT_TANH, PSP_ACT_TANH);
+PSP_SAME(psp::PINN_ACT_RELU2, PSP_ACT_RELU2); PSP_SAME(psp::PINN_ACT_TANH2, PSP_ACT_TANH2); PSP_SAME(psp::PINN_ACT_TANH, PSP_ACT_TANH);
+#undef PSP_SAME
+
 #define X(D_, H_) PSP_DECLARE_DNET_INSTANCE(D_, H_)
 #include "dense_instances.def"
 #undef X

@@ -12,13 +12,15 @@ import ctypes as C
 import torch
 
 try:
+    from . import kernel_config as kc
     from . import native as nat
     from .problems import coefficients_overridden
 except ImportError:
+    import kernel_config as kc
     import native as nat
     from problems import coefficients_overridden
 
-_ACT = {'relu2': nat.ACT_RELU2, 'tanh2': nat.ACT_TANH2, 'tanh': nat.ACT_TANH}
+_ACT = kc.ACT
 
 
 def domain_spec(problem):
@@ -49,15 +51,9 @@ def eval_reason(problem):
 
 def eval_config(net_spec, problem, K, modus, slots=1, k_offset=0):
     """psp_genl_eval_config of a value net (plan_general_deep.value_net_spec) on a problem eval_reason() accepts."""
-    dims = net_spec['dims']
     cfg = nat.GenlEvalConfig()
     cfg.d = int(problem.d)
-    cfg.has_time = 1 if modus == 'parabolic' else 0
-    cfg.n_hidden = len(dims) - 2
-    for i, h in enumerate(dims[1:-1][:4]):
-        cfg.widths[i] = int(h)
-    cfg.activation = _ACT[net_spec['act']]
-    cfg.linear_layout = 1 if net_spec['linear'] else 0
+    kc.fill_value_net(cfg, net_spec, modus == 'parabolic')
     cfg.K_points, cfg.k_offset = int(K), int(k_offset)
     cfg.sample_kind, cfg.bound_a, cfg.bound_b = domain_spec(problem)
     cfg.T = float(getattr(problem, 'T', 0.0)) if cfg.has_time else 0.0

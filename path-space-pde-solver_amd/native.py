@@ -23,6 +23,7 @@ LOSS_LOG_VARIANCE, LOSS_MOMENT, LOSS_WEIGHTS, LOSS_REL_ENTROPY = 0, 1, 2, 3
 UL2_TABLE, UL2_LINEAR, UL2_GRID = 0, 1, 2
 ISC_NONE, ISC_TABLE, ISC_LINEAR, ISC_GRID = 0, 1, 2, 3
 IS_MAX_D = 64                     # native range of psp_is_rollout (include/psp.h)
+GENL_MAX_HIDDEN_LAYERS, GENL_MAX_WIDTH, GENL_MAX_INPUT = 4, 128, 112      # the run-time-shaped value-net kernels (csrc/genl_kernels.h)
 NOISE_SUPPLIED, NOISE_PHILOX = 0, 1
 GH_ZERO, GH_QUAD, GH_ALLEN_CAHN, GH_EXPBALL_LIN, GH_EXPBALL_SQ, GH_EXPBALL_SIN, GH_EXPBALL_SIN_FULL = 0, 1, 2, 3, 4, 5, 6
 GH_AFFINE_EXP, GH_SINE_SOURCE, GH_SINNORM2 = 7, 8, 9     # p0 + p1 y + p2 |z|^2 + p3 exp(-y); c y + s(x); SinNorm2.h (dense sigma)

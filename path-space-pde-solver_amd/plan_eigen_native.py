@@ -17,16 +17,18 @@ import time
 import torch
 
 try:
+    from . import kernel_config as kc
     from . import native as nat
     from . import plan_common as pc
     from . import sharding
-    from .plan_general_deep import GeneralDeepPlan, value_net_spec
+    from .plan_general_deep import GeneralDeepPlan, deep_config, value_net_spec
     from .eigenvalue_solver import periodic_terms
 except ImportError:
+    import kernel_config as kc
     import native as nat
     import plan_common as pc
     import sharding
-    from plan_general_deep import GeneralDeepPlan, value_net_spec
+    from plan_general_deep import GeneralDeepPlan, deep_config, value_net_spec
     from eigenvalue_solver import periodic_terms
 
 
@@ -42,38 +44,18 @@ def eigen_eligibility(solver):
     net = value_net_spec(s.V, s.d, output_relu_ok=True)
     if isinstance(net, str):
         return net
-    dims = net['dims']
-    L = len(dims) - 2
-    if L < 1 or L > 4:
-        return 'V has %d hidden layers (the native value-net kernels take 1 to 4)' % L
-    if max(dims[1:-1]) > 128 or s.d > 112:
-        return 'V is wider than the native value-net kernels take (hidden <= 128, input <= 112)'
-    spec_fn = getattr(s.problem, 'general_native_spec', None)
-    if spec_fn is None:
-        return 'problem has no general_native_spec() (coefficients outside the native catalogue)'
-    try:
-        from .problems import coefficients_overridden
-    except ImportError:
-        from problems import coefficients_overridden
-    over = coefficients_overridden(s.problem, names=('b', 'sigma', 'h', 'g'))
-    if over is not None:
-        return 'problem.%s is not the catalogue implementation general_native_spec() describes' % over
-    spec = spec_fn()
+    layers, widths, _ = kc.value_net_limits_reason(net['dims'])
+    if layers or widths:
+        return layers or widths
+    spec, why = kc.catalogue_spec(s.problem, names=('b', 'sigma', 'h', 'g'))
+    if spec is None:
+        return why
     if spec.get('sigma') is not None:
         return 'a dense sigma is not built for EigenvalueSolver'
     if not nat.is_built():
         raise nat.NativeLibraryError('libpsp_hip.so is not built; run __graft_entry__.build()')
-    cfg = nat.GenlConfig()
-    cfg.base.d, cfg.base.K_local, cfg.base.N = s.d, 16, 1
-    cfg.base.h_kind, cfg.base.drift_kind = spec['h'], spec['drift'][0]
-    for i, v in enumerate(spec.get('h_par', ())):
-        cfg.base.h_par[i] = float(v)
-    keep = spec['drift'][1]
-    if keep is not None:                                          # (the query validates the pointer, it reads nothing)
-        cfg.base.drift = nat.ptr(keep)
-    cfg.has_time, cfg.n_hidden = 0, L
-    for i, h in enumerate(dims[1:-1]):
-        cfg.widths[i] = int(h)
+    keep = []                                                     # (the query validates the pointers, it reads nothing)
+    cfg = kc.probe(deep_config(s, net, spec, bool(s.elliptic), 16, 0, torch.device('cpu'), keep))
     eig = nat.GenlEig(struct_bytes=C.sizeof(nat.GenlEig), output_relu=1 if net['output_relu'] else 0)
     lib = nat.load()
     if lib.psp_genl_query_eig(C.byref(cfg), C.byref(eig), C.byref(nat.GenlSizes())) != 0:

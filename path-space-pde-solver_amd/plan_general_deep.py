@@ -22,17 +22,19 @@ import ctypes as C
 import torch
 
 try:
+    from . import kernel_config as kc
     from . import native as nat
     from . import sharding
     from .function_space import DenseNet, DenseNet_tanh
     from .plan_general_native import GeneralNativePlan, set_domain, set_sigma
 except ImportError:
+    import kernel_config as kc
     import native as nat
     import sharding
     from function_space import DenseNet, DenseNet_tanh
     from plan_general_native import GeneralNativePlan, set_domain, set_sigma
 
-_ACT = {'relu2': nat.ACT_RELU2, 'tanh2': nat.ACT_TANH2, 'tanh': nat.ACT_TANH}
+_ACT = kc.ACT
 
 
 class _IdentityPad:
@@ -180,26 +182,34 @@ def neumann_points(img_last, nexec, n_last, XN, tN):
     return torch.where(left, torch.cat([XN, tN.reshape(-1, 1)], 1), img_last)
 
 
+def deep_config(solver, net, spec, elliptic, K_local, k_offset, device, keep):
+    """The psp_genl_config of a solver, its value net (``value_net_spec``) and its problem's ``general_native_spec()``; the
+    tensors its pointers name go to ``device`` and into ``keep``.  spec None (deep_eligibility on a problem outside the catalogue,
+    which plan_general_native.native_eligibility refuses): the net's part alone."""
+    gcfg = nat.GenlConfig()
+    gcfg.base.d = solver.d
+    if spec is not None:
+        kc.fill_problem(gcfg.base, solver, spec, elliptic, K_local, k_offset, solver.noise)
+        set_sigma(gcfg, spec, device, keep)
+        if spec['drift'][1] is not None:
+            gcfg.base.drift = nat.ptr(kc.upload(spec['drift'][1], None, device, keep, 'the drift vector'))
+    kc.fill_value_net(gcfg, net, not elliptic)
+    return gcfg
+
+
 def deep_eligibility(solver):
     """None if the value net is one the genl kernels take, else a reason."""
-    d_in = solver.d + (0 if solver.elliptic else 1)
-    spec = value_net_spec(solver.V, d_in)
-    if isinstance(spec, str):
-        return spec
-    dims = spec['dims']
-    L = len(dims) - 2
-    if L < 1 or L > 4:
-        return 'V has %d hidden layers (the native value-net kernels take 1 to 4)' % L
-    if max(dims[1:-1]) > 128 or d_in > 112:
-        return 'V is wider than the native value-net kernels take (hidden <= 128, input <= 112)'
-    cfg = nat.GenlConfig()
-    cfg.base.d, cfg.base.K_local, cfg.base.N = solver.d, 16, 1
-    cfg.has_time, cfg.n_hidden = (0 if solver.elliptic else 1), L
-    for i, h in enumerate(dims[1:-1]):
-        cfg.widths[i] = int(h)
-    sizes = nat.GenlSizes()
+    elliptic = bool(solver.elliptic)
+    net = value_net_spec(solver.V, solver.d + (0 if elliptic else 1))
+    if isinstance(net, str):
+        return net
+    layers, widths, _ = kc.value_net_limits_reason(net['dims'])
+    if layers or widths:
+        return layers or widths
+    keep = []                                                     # (the query validates the pointers, it reads nothing)
+    cfg = kc.probe(deep_config(solver, net, kc.catalogue_spec(solver.problem)[0], elliptic, 16, 0, torch.device('cpu'), keep))
     lib = nat.load()
-    if lib.psp_genl_query(C.byref(cfg), C.byref(sizes)) != 0:
+    if lib.psp_genl_query(C.byref(cfg), C.byref(nat.GenlSizes())) != 0:
         return lib.psp_last_error().decode()
     return None
 
@@ -230,31 +240,8 @@ class GeneralDeepPlan(GeneralNativePlan):
         self._flatten(net['params'])
         spec = s.problem.general_native_spec()
         self._keep = []
-        gcfg = nat.GenlConfig()
+        gcfg = deep_config(s, net, spec, self.elliptic, self.K_local, self.lo, self.dev, self._keep)
         cfg = gcfg.base
-        cfg.d = s.d
-        cfg.K_local, cfg.N, cfg.k_offset = self.K_local, s.N, self.lo
-        cfg.dt, cfg.sqrt_dt = float(s.delta_t.item()), float(s.sq_delta_t.item())
-        cfg.T = float('inf') if self.elliptic else float(torch.tensor(s.problem.T, dtype=torch.float32).item())
-        set_domain(cfg, s.problem, self.elliptic)
-        cfg.d_real = s.d
-        for i, v in enumerate(spec.get('h_par', ())):
-            cfg.h_par[i] = float(v)
-        set_sigma(gcfg, spec, self.dev, self._keep)
-        cfg.drift_kind, cfg.h_kind = spec['drift'][0], spec['h']
-        cfg.dwell_form = int(spec.get('dwell_form', 0))
-        cfg.adaptive = 1 if s.adaptive_forward_process else 0
-        cfg.noise_mode = nat.NOISE_PHILOX if s.noise == 'philox' else nat.NOISE_SUPPLIED
-        cfg.store_path = 1
-        if spec['drift'][1] is not None:
-            t = spec['drift'][1].detach().to(device=self.dev, dtype=torch.float32).contiguous()
-            self._keep.append(t)
-            cfg.drift = nat.ptr(t)
-        gcfg.has_time, gcfg.n_hidden = (0 if self.elliptic else 1), self.L
-        for i, h in enumerate(self.dims[1:-1]):
-            gcfg.widths[i] = int(h)
-        gcfg.activation = _ACT[net['act']]
-        gcfg.linear_layout = 1 if net['linear'] else 0
         self.gcfg, self.cfg = gcfg, cfg
         sz = nat.GenlSizes()
         nat.check(self._query(gcfg, sz), 'psp_genl_query')

@@ -27,6 +27,7 @@ import time
 import torch
 
 try:
+    from . import kernel_config as kc
     from . import native as nat
     from . import native_shapes as shapes
     from . import plan_common as pc
@@ -34,6 +35,7 @@ try:
     from .function_space import DenseNet
     from . import general_solver as gs
 except ImportError:
+    import kernel_config as kc
     import native as nat
     import native_shapes as shapes
     import plan_common as pc
@@ -59,17 +61,9 @@ def native_eligibility(solver, deep=False):
     if not deep and (not isinstance(V, DenseNet) or dims is None or len(dims) != 4 or dims[1] != dims[2] or dims[3] != 1
                      or dims[0] != d_in or getattr(V, 'activation', 'relu2') != 'relu2'):
         return 'V is not a DenseNet(%d -> 1) with two equal hidden widths and relu^2' % d_in
-    spec_fn = getattr(solver.problem, 'general_native_spec', None)
-    if spec_fn is None:
-        return 'problem has no general_native_spec() (coefficients outside the native catalogue)'
-    try:
-        from .problems import coefficients_overridden
-    except ImportError:
-        from problems import coefficients_overridden
-    over = coefficients_overridden(solver.problem)
-    if over is not None:
-        return 'problem.%s is not the catalogue implementation general_native_spec() describes' % over
-    spec = spec_fn()
+    spec, why = kc.catalogue_spec(solver.problem)
+    if spec is None:
+        return why
     if spec['h'] == nat.GH_SINE_SOURCE and spec['h_par'][0] == 0.0 and solver.d < 2:
         return 'h reads the coordinates x_0 and x_1 (PSP_GH_SINE_SOURCE, sub-mode 0: Helmholtz) and d = %d' % solver.d
     if not deep and spec.get('sigma') is not None:
@@ -81,18 +75,7 @@ def native_eligibility(solver, deep=False):
     return None
 
 
-def set_domain(cfg, pb, elliptic):
-    """psp_gen_config.domain_kind / dom_a / dom_b from the problem's ``boundary`` (include/psp.h PSP_DOM_*)."""
-    if pb.boundary == 'sphere':
-        cfg.domain_kind, cfg.dom_a = nat.DOM_SPHERE, float(pb.boundary_distance)
-    elif pb.boundary == 'two_spheres':                            # solver.py:1122-1123 / :752-753
-        cfg.domain_kind, cfg.dom_a, cfg.dom_b = nat.DOM_ANNULUS, float(pb.boundary_distance_1), float(pb.boundary_distance_2)
-    elif pb.boundary == 'square':
-        cfg.dom_a, cfg.dom_b = float(pb.X_l), float(pb.X_r)
-        cfg.domain_kind = nat.DOM_BOX if not pb.one_boundary else \
-            (nat.DOM_BOX_UPPER_ALL if elliptic else nat.DOM_BOX_UPPER_ANY)
-    elif pb.boundary == 'square-corner':                          # solver.py:759-760: any(X_proposal <= X_r)
-        cfg.domain_kind, cfg.dom_a, cfg.dom_b = nat.DOM_BOX_UPPER_ANY, float(pb.X_l), float(pb.X_r)
+set_domain = kc.set_domain
 
 
 def set_sigma(gcfg, spec, device, keep):
@@ -105,11 +88,7 @@ def set_sigma(gcfg, spec, device, keep):
         gcfg.base.sigma_scale = float(spec['sigma_scale'])
         return
     d = int(gcfg.base.d)
-    B = torch.as_tensor(B)
-    if tuple(B.shape) != (d, d):
-        raise ValueError('general_native_spec(): sigma must be a (%d, %d) matrix, got %s' % (d, d, tuple(B.shape)))
-    t = B.detach().to(device=device, dtype=torch.float32).contiguous()
-    keep.append(t)
+    t = kc.upload(B, (d, d), device, keep, 'general_native_spec(): sigma must be a (%d, %d) matrix' % (d, d))
     gcfg.sigma_kind, gcfg.sigma = nat.GENL_SIGMA_DENSE, nat.ptr(t)
     gcfg.base.sigma_scale = 0.0
 
@@ -129,32 +108,18 @@ class GeneralNativePlan:
         spec = s.problem.general_native_spec()
         self._keep = []
         cfg = nat.GenConfig()
-        cfg.K_local, cfg.N = self.K_local, s.N
-        cfg.k_offset = self.lo
-        cfg.dt, cfg.sqrt_dt = float(s.delta_t.item()), float(s.sq_delta_t.item())
         self.elliptic = bool(s.elliptic)
-        cfg.T = float('inf') if self.elliptic else float(torch.tensor(s.problem.T, dtype=torch.float32).item())
-        pb = s.problem
-        set_domain(cfg, pb, self.elliptic)
-        cfg.d_real = s.d
+        kc.fill_problem(cfg, s, spec, self.elliptic, self.K_local, self.lo, s.noise)
         # 'f16x3': fp32-grade split products on the f16 matrix pipe in the forward rollout (csrc/hjb_kernels.h gemm_Tx; same parity
         # bounds as 'fp32'); 'auto' (the default): 'f16x3' where the instance has it and its tables fit the LDS (decided below)
         self._mlp_want = getattr(s, 'mlp_dtype', 'auto')
         cfg.mlp_dtype = {'auto': nat.MLP_FP32, 'fp32': nat.MLP_FP32, 'f16x3': nat.MLP_F16X3, 'bf16_fwd': nat.MLP_BF16_FWD,
                          'bf16': nat.MLP_BF16}[self._mlp_want]
-        for i, v in enumerate(spec.get('h_par', ())):
-            cfg.h_par[i] = float(v)
-        cfg.sigma_scale = float(spec['sigma_scale'])
-        cfg.drift_kind = spec['drift'][0]
-        cfg.h_kind = spec['h']
-        cfg.dwell_form = int(spec.get('dwell_form', 0))           # the rounding order of the double-well drift (include/psp.h)
-        cfg.adaptive = 1 if s.adaptive_forward_process else 0
-        cfg.noise_mode = nat.NOISE_PHILOX if s.noise == 'philox' else nat.NOISE_SUPPLIED
-        cfg.store_path = 1
         # kernel instance: the exact (d, H) if compiled, else the cheapest larger one (zero padding, native_shapes.py)
-        if spec['drift'][1] is not None:              # psp_gen_query validates the pointer: any device tensor will do for
-            t_probe = spec['drift'][1].detach().to(device=self.dev, dtype=torch.float32).contiguous()   # the size query
-            cfg.drift = nat.ptr(t_probe)
+        drift = spec['drift'][1]
+        unpadded = []
+        if drift is not None:                         # psp_gen_query validates the pointer: the unpadded vector will do for
+            cfg.drift = nat.ptr(kc.upload(drift, None, self.dev, unpadded, 'the drift vector'))     # the size query
         chosen, why = shapes.gen_choose(cfg, s.d, self.H)
         if chosen is None:
             raise NotImplementedError('native plan unavailable: ' + why)
@@ -174,10 +139,9 @@ class GeneralNativePlan:
             self.range_flag = torch.zeros(4, dtype=torch.int32, device=self.dev)
             cfg.range_flag = nat.ptr(self.range_flag)
         self.pad = shapes.GenParamPad(s.d, self.H, self.d_pad, self.H_pad, self.dev, time_input=not self.elliptic)
-        if spec['drift'][1] is not None:
-            t = self.pad.vec(spec['drift'][1].detach().to(device=self.dev, dtype=torch.float32)).contiguous()
-            self._keep.append(t)
-            cfg.drift = nat.ptr(t)
+        if drift is not None:
+            cfg.drift = nat.ptr(kc.upload(self.pad.vec(drift.detach().to(device=self.dev, dtype=torch.float32)), None, self.dev,
+                                          self._keep, 'the drift vector'))
         self.cfg = cfg
         assert sz.n_params == self.pad.Pp, (sz.n_params, self.pad.Pp)
         self.sizes = sz

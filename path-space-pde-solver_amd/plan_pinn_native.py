@@ -34,15 +34,17 @@ import time
 import torch
 
 try:
+    from . import kernel_config as kc
     from . import native as nat
     from . import plan_common as pc
     from . import sharding
-    from .plan_general_deep import value_net_spec, deep_eligibility, _ACT
+    from .plan_general_deep import value_net_spec, deep_eligibility
 except ImportError:
+    import kernel_config as kc
     import native as nat
     import plan_common as pc
     import sharding
-    from plan_general_deep import value_net_spec, deep_eligibility, _ACT
+    from plan_general_deep import value_net_spec, deep_eligibility
 
 
 def pinn_eligibility(solver):
@@ -61,17 +63,9 @@ def pinn_eligibility(solver):
         return "noise=%r: train_PINN draws its points from the host generator (noise='reference')" % s.noise
     if sharding.dist_info()[2] > 1:
         return 'more than one rank: the PINN kernels are single-rank'
-    spec_fn = getattr(s.problem, 'general_native_spec', None)
-    if spec_fn is None:
-        return 'problem has no general_native_spec() (coefficients outside the native catalogue)'
-    try:
-        from .problems import coefficients_overridden
-    except ImportError:
-        from problems import coefficients_overridden
-    over = coefficients_overridden(s.problem)
-    if over is not None:
-        return 'problem.%s is not the catalogue implementation general_native_spec() describes' % over
-    spec = spec_fn()
+    spec, why = kc.catalogue_spec(s.problem)
+    if spec is None:
+        return why
     dense = spec.get('sigma') is not None
     if dense and not full:
         return ('a dense sigma without full_hessian: the reference takes B[0,0]^2 times the Laplacian for it, which is no '
@@ -113,23 +107,15 @@ def pinn_config(s, net, spec, dev, keep):
     """psp_pinn_config of a solver for K_original points; the tensors its pointers name are appended to ``keep``."""
     cfg = nat.PinnConfig()
     cfg.d, cfg.K = s.d, s.K_original
-    cfg.has_time, cfg.n_hidden = (0 if s.elliptic else 1), len(net['dims']) - 2
-    for i, h in enumerate(net['dims'][1:-1]):
-        cfg.widths[i] = int(h)
-    cfg.activation, cfg.linear_layout = _ACT[net['act']], (1 if net['linear'] else 0)
-    cfg.drift_kind, cfg.h_kind = spec['drift'][0], spec['h']
+    kc.fill_value_net(cfg, net, not s.elliptic)
+    kc.fill_kinds(cfg, spec)
     if spec.get('sigma') is None:                              # (full_hessian with s I is s^2 times the Laplacian)
-        cfg.sigma_kind, cfg.sigma_scale = nat.GENL_SIGMA_SCALED, float(spec['sigma_scale'])
+        cfg.sigma_kind = nat.GENL_SIGMA_SCALED
     else:                                                      # trace(B B^T Hess V) as sum_j u_j^T Hess V u_j
-        dirs = direction_table(spec['sigma']).to(device=dev, dtype=torch.float32).contiguous()
-        keep.append(dirs)
+        dirs = kc.upload(direction_table(spec['sigma']), None, dev, keep, 'the direction table')
         cfg.sigma_kind, cfg.n_dirs, cfg.dirs = nat.GENL_SIGMA_DENSE, dirs.shape[0], nat.ptr(dirs)
-    for i, v in enumerate(spec.get('h_par', ())):
-        cfg.h_par[i] = float(v)
     if spec['drift'][1] is not None:
-        t = spec['drift'][1].detach().to(device=dev, dtype=torch.float32).contiguous()
-        keep.append(t)
-        cfg.drift = nat.ptr(t)
+        cfg.drift = nat.ptr(kc.upload(spec['drift'][1], None, dev, keep, 'the drift vector'))
     return cfg
 
 

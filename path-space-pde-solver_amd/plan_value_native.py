@@ -47,6 +47,7 @@ import ctypes as C
 import torch
 
 try:
+    from . import kernel_config as kc
     from . import native as nat
     from . import native_shapes as shapes
     from . import sharding
@@ -55,6 +56,7 @@ try:
     from .plan_common import PlanUnsupported
     from .plan_native import _overridden
 except ImportError:
+    import kernel_config as kc
     import native as nat
     import native_shapes as shapes
     import sharding
@@ -122,14 +124,10 @@ def value_eligibility(solver):
             return 'the u_L2 log (u_l2_error_flag=True) runs on the run-time-shaped value-net kernels only -- the templated ' \
                    '(d, H) kernels have no log instances --, and the value net (input %d) is %s; pass u_l2_error_flag=False ' \
                    'for the native plan' % (s.d + 1, _deep_net(s, V, why=True, force=True))
-        g = nat.GenlConfig()
-        g.base.d, g.base.K_local, g.base.N, g.base.h_kind = s.d, 16, 1, nat.GH_QUAD
-        g.base.T, g.base.domain_kind = float('inf'), nat.DOM_NONE
-        g.base.adaptive, g.base.per_sample_weights, g.base.store_path = (1 if s.adaptive_forward_process else 0), 1, 1
-        g.has_time, g.n_hidden = 1, len(net['dims']) - 2
-        for i, h in enumerate(net['dims'][1:-1]):
-            g.widths[i] = int(h)
-        q = nat.GenlCoeffs(struct_bytes=C.sizeof(nat.GenlCoeffs), z_kind=nat.GENL_Z_SIGMA) if needs_lq(spec) else None
+        keep = []                                         # (a query validates the pointers, it reads nothing)
+        g = value_config(s, spec, net)[0]
+        q = lq_coeffs(g, spec, torch.device('cpu'), keep)
+        kc.probe(g)
         u = None
         if log:                                           # (a query reads no pointer: any non-null value stands for the buffers)
             probe = C.addressof(_PROBE)
@@ -164,13 +162,27 @@ def needs_lq(spec):
             or spec['runcost'][0] == nat.RUNCOST_DIAG_QUAD)
 
 
+def value_config(s, spec, net):
+    """(psp_genl_config or None, its base / the psp_gen_config) of the ansatz for a problem's ``native_spec()``: what does not
+    depend on the batch and the step.  net: the ``_deep_net`` description (the run-time-shaped kernels) or None (the templated ones).
+    ``lq_coeffs`` adds sigma and drift of a run-time-shaped config, kernel_config.fill_run the discretisation."""
+    g = nat.GenlConfig() if net is not None else None
+    cfg = g.base if g is not None else nat.GenConfig()
+    if g is not None:
+        cfg.d = s.d
+        kc.fill_value_net(g, net, True)
+    cfg.T = float('inf')                                  # no freezing: every trajectory takes all N steps (solver.py:440)
+    cfg.d_real = s.d
+    cfg.sigma_scale = float(spec['sigma'][2])
+    cfg.drift_kind = spec['drift'][0]
+    cfg.h_kind = nat.GH_QUAD                              # h = -|z|^2 / 2 (problems.py:46, 211, 321); f(x) travels in psp_genl_coeffs
+    cfg.adaptive, cfg.store_path = (1 if s.adaptive_forward_process else 0), 1
+    cfg.domain_kind, cfg.per_sample_weights = nat.DOM_NONE, 1
+    return g, cfg
+
+
 def _upload(M, shape, device, keep, what):
-    M = torch.as_tensor(M)
-    if tuple(M.shape) != shape:
-        raise ValueError('native_spec(): %s must have shape %s, got %s' % (what, shape, tuple(M.shape)))
-    t = M.detach().to(device=device, dtype=torch.float32).contiguous()      # row-major by VALUE (a transposed view is copied)
-    keep.append(t)
-    return t
+    return kc.upload(M, shape, device, keep, 'native_spec(): %s must have shape %s' % (what, shape))
 
 
 def lq_coeffs(gcfg, spec, device, keep):
@@ -215,9 +227,9 @@ def _deep_net(solver, V, why=False, force=False):
                  and bool(shapes.gen_candidates(solver.d, dims[1])))
     if templated and not force:
         return 'the templated kernels take it' if why else None
-    L = len(dims) - 2
-    if L < 1 or L > 4 or max(dims[1:-1]) > 128 or dims[0] > 112:
-        return 'outside 1-4 hidden layers of <= 128 units, input <= 112' if why else None
+    short = kc.value_net_limits_reason(dims)[2]
+    if short is not None:
+        return short if why else None
     return 'ok' if why else spec
 
 
@@ -246,42 +258,24 @@ class ValueNativePlan:
         self._keep = []
         self.coeffs = None                                # psp_genl_coeffs (dense sigma / drift matrix / running cost), deep plans only
         self.ul2, self.ul2_cfg = None, None               # per-trajectory u_L2 (K_local) and its psp_genl_ul2, with the log on
-        if self.deep is not None:
-            self.gcfg = nat.GenlConfig()
-            cfg = self.gcfg.base
-            cfg.d = s.d
-        else:
-            cfg = nat.GenConfig()
-        cfg.K_local, cfg.N, cfg.k_offset = self.K_local, s.N, lo
-        cfg.dt, cfg.sqrt_dt = float(s.delta_t.item()), float(s.sq_delta_t.item())
-        cfg.T = float('inf')                              # no freezing: every trajectory takes all N steps (solver.py:440)
-        cfg.d_real = s.d
-        cfg.sigma_scale = float(spec['sigma'][2])
-        cfg.drift_kind = spec['drift'][0]
-        cfg.h_kind = nat.GH_QUAD                          # h = -|z|^2 / 2 (problems.py:46, 211, 321); f(x) travels in psp_genl_coeffs
-        cfg.adaptive = 1 if s.adaptive_forward_process else 0
-        cfg.noise_mode = nat.NOISE_PHILOX if noise == 'philox' else nat.NOISE_SUPPLIED
-        cfg.store_path = 1
-        cfg.domain_kind = nat.DOM_NONE
-        cfg.per_sample_weights = 1
+        gcfg, cfg = value_config(s, spec, self.deep)
+        if gcfg is not None:
+            self.gcfg = gcfg
+        kc.fill_run(cfg, s, self.K_local, lo, noise)
         drift_vec = spec['drift'][1]
         if self.deep is not None:
             self.coeffs = lq_coeffs(self.gcfg, spec, dev, self._keep)
         elif drift_vec is not None:
-            probe = drift_vec.detach().to(device=dev, dtype=torch.float32).contiguous()
-            cfg.drift = nat.ptr(probe)
+            unpadded = []                                 # (the size query validates the pointer: the unpadded vector will do)
+            cfg.drift = nat.ptr(kc.upload(drift_vec, None, dev, unpadded, 'the drift vector'))
         f32 = torch.float32
         self.Kpad = 16 * ((self.K_local + 15) // 16)
         if self.deep is not None:
             try:
-                from .plan_general_deep import _ACT, _IdentityPad
+                from .plan_general_deep import _IdentityPad
             except ImportError:
-                from plan_general_deep import _ACT, _IdentityPad
-            g, dims = self.gcfg, self.deep['dims']
-            g.has_time, g.n_hidden = 1, len(dims) - 2
-            for i, h in enumerate(dims[1:-1]):
-                g.widths[i] = int(h)
-            g.activation, g.linear_layout = _ACT[self.deep['act']], 1 if self.deep['linear'] else 0
+                from plan_general_deep import _IdentityPad
+            g = self.gcfg
             g.time_first, g.time_scale = 1, 1.0 / cfg.dt               # input [t, x], and t is the step index (solver.py:336-338, 439)
             sz = nat.GenlSizes()
             if self.log:
@@ -314,9 +308,8 @@ class ValueNativePlan:
             self.pad = shapes.GenParamPad(s.d, self.H, self.d_pad, self.H_pad, dev, time_input=True, time_first=True,
                                           time_scale=1.0 / cfg.dt)
             if drift_vec is not None:
-                t = self.pad.vec(drift_vec.detach().to(device=dev, dtype=torch.float32)).contiguous()
-                self._keep.append(t)
-                cfg.drift = nat.ptr(t)
+                cfg.drift = nat.ptr(kc.upload(self.pad.vec(drift_vec.detach().to(device=dev, dtype=torch.float32)), None, dev,
+                                              self._keep, 'the drift vector'))
             assert sz.n_params == self.pad.Pp, (sz.n_params, self.pad.Pp)
             self.flat_k = self.pad.new_padded_params()
             self.ahat = torch.zeros(s.N + 1, self.Kpad, dtype=f32, device=dev)       # written by the forward, then overwritten by AV

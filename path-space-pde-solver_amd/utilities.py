@@ -562,9 +562,11 @@ def compute_test_error_native(model, problem, K, modus='elliptic', seed=None, it
     NotImplementedError with the reason when the net, the domain or the problem is not covered."""
     try:
         from . import device_test_log as dtl
+        from . import kernel_config as kc
         from .plan_general_deep import value_net_spec
     except ImportError:
         import device_test_log as dtl
+        import kernel_config as kc
         from plan_general_deep import value_net_spec
     if modus not in ('elliptic', 'parabolic'):
         raise ValueError("modus must be 'elliptic' or 'parabolic'")
@@ -575,9 +577,9 @@ def compute_test_error_native(model, problem, K, modus='elliptic', seed=None, it
     net = value_net_spec(model.V, d + (1 if modus == 'parabolic' else 0))
     if isinstance(net, str):
         raise NotImplementedError('native test error unavailable: ' + net)
-    if len(net['dims']) - 2 > 4:
-        raise NotImplementedError('native test error unavailable: V has %d hidden layers (the native value-net kernels take 1 to 4)'
-                                  % (len(net['dims']) - 2))
+    layers = kc.value_net_limits_reason(net['dims'])[0]
+    if layers is not None:
+        raise NotImplementedError('native test error unavailable: ' + layers)
     sizes, why = dtl.eval_query(dtl.eval_config(net, problem, K, modus))
     if sizes is None:
         raise NotImplementedError('native test error unavailable: ' + why)

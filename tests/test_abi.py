@@ -157,3 +157,15 @@ def test_genl_query_without_gpu(lib):
     assert lib.psp_genl_query(C.byref(c), C.byref(sz)) != 0 and "annulus" in nat.last_error()
     rc = lib.psp_genl_rollout_bwd(C.byref(cfg(10, [20, 10])), None, None, None, None, None, None, None, None, None)
     assert rc != 0 and "null" in nat.last_error()
+
+
+def test_native_constants_match_the_header_enums():
+    """native.py numbers the h, drift, domain, activation, v_true and test-sample kinds as include/psp.h does."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "psp.h")).read(), flags=re.S)
+    header = {m.group(1) + "_" + m.group(2): int(m.group(3))
+              for m in re.finditer(r"\bPSP_(GH|DRIFT|DOM|ACT|VTRUE|TSAMPLE)_(\w+)\s*=\s*(\d+)", text)}
+    assert {k.split("_")[0] for k in header} == {"GH", "DRIFT", "DOM", "ACT", "VTRUE", "TSAMPLE"} and len(header) >= 36
+    for name, value in header.items():
+        assert getattr(nat, name) == value, name
+    mine = [n for n in vars(nat) if re.match(r"(GH|DRIFT|DOM|ACT|VTRUE|TSAMPLE)_[A-Z0-9_]+$", n)]
+    assert sorted(mine) == sorted(header)                            # and native.py names no kind the header does not have
