@@ -76,10 +76,14 @@ struct GGeo {
     // sample: both kernels of that mode are bound by the path store, not by the matrix pipe.
     static constexpr int qX = 0, qU = qX + 2 * DBI * 64, qD1 = qU + 2 * DBI * 64, qD2 = qD1 + 2 * HB * 64,
                          qZ1 = qD2 + 2 * HB * 64, qZ2 = qZ1 + 2 * HB * 64, PB16 = qZ2 + 2 * HB * 64;
-    // forward LDS carve (floats): six A-operand tables + per-feature vectors
-    static constexpr int fW1f = 0, fW2xf = fW1f + HB * KSI * 64, fW2hf = fW2xf + HB * KSI * 64,
-                         fW2hr = fW2hf + HB * KSH * 64, fW2xr = fW2hr + HB * KSH * 64,
-                         fW1r = fW2xr + DBI * KSH * 64, fVec = fW1r + DBI * KSH * 64;
+    // forward LDS carve (floats): six A-operand tables + per-feature vectors.  One table holds the fp32 image of its product (KS
+    // k-steps of 64 floats per row block, stage_aop) or the bf16 image (cdiv(INB, 2) k-steps of 64 x 16 bytes, stage_aop_bf16),
+    // so it is sized for the larger: with d + 1 <= 12 the input-side tables have KSI = 2 or 3 k-steps and their bf16 image is the
+    // larger one -- carved by KSI alone it ran 128 or 256 floats into the next table, whose staging then overwrote them
+    static constexpr int tbl(int MB, int KS, int INB) { return MB * 64 * (KS > 4 * cdiv(INB, 2) ? KS : 4 * cdiv(INB, 2)); }
+    static constexpr int fW1f = 0, fW2xf = fW1f + tbl(HB, KSI, DBI), fW2hf = fW2xf + tbl(HB, KSI, DBI),
+                         fW2hr = fW2hf + tbl(HB, KSH, HB), fW2xr = fW2hr + tbl(HB, KSH, HB),
+                         fW1r = fW2xr + tbl(DBI, KSH, HB), fVec = fW1r + tbl(DBI, KSH, HB);
     static constexpr int vb1 = fVec, vb2 = vb1 + HB * 16, vw3h1 = vb2 + HB * 16, vw3h2 = vw3h1 + HB * 16,
                          vw3x = vw3h2 + HB * 16, vdr = vw3x + DBI * 16, fRed = vdr + DBI * 16, fEnd = fRed + 64;
     static int fwd_lds_floats() { return fEnd; }

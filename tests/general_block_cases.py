@@ -14,8 +14,15 @@ the BSDE loss or loss_with_stopped here; alpha weighs the K_boundary-sized terms
 least half of it (asserted on the CPU).  `scale` multiplies the weight matrices and `bias_std` draws the biases of the dense-concat
 nets (zero at initialisation), both sides from the same seeded generator, where the initial state leaves a block under the floor.
 
-The bf16 modes (mlp_dtype 'bf16', 'bf16_fwd') stay out: their documented bound is 2e-2 (tests/test_gpu_general_variants.py), a
-hundred times the per-block bound, and a float64 judge adds nothing to what the fp32 kernels already tell about them."""
+The bf16 modes (mlp_dtype 'bf16', 'bf16_fwd') stay out of CASES: their documented bound is 2e-2 (tests/test_gpu_general_variants.py),
+a hundred times the per-block bound, and a float64 judge adds nothing to what the fp32 kernels already tell about them.
+
+PHILOX_CASES is a table of its own for tests/test_gpu_general_philox_blocks.py: the same shapes on noise='philox', where other
+compiled kernels run -- the PHILOX instances of gen_fwd_kernel, its specialised SPECK instances (unbounded, not adaptive: under
+split products and bf16 only) and the counter branch of genl_fwd_kernel.  X_0 and t_0 come from a device generator there, so the
+conditions on the reference are asserted by the GPU test itself.  Two bf16 cases are in it for the sake of their SPECK instances:
+X_N and t_N, which no bf16 product touches, pin the noise to the fp32 bound."""
+import copy
 import dataclasses
 
 import numpy as np
@@ -224,6 +231,73 @@ assert len({c["id"] for c in CASES}) == len(CASES)
 BY_ID = {c["id"]: c for c in CASES}
 
 
+# ---- cases on the kernels' own Philox noise ----------------------------------------------------------------------------------------
+SPEC_ALLEN_CAHN, SPEC_DWELL = "ZERO|ALLEN_CAHN", "DWELL|QUAD"          # the SPECK kinds of gen_fwd_kernel (GenLaunch::spec_kind)
+
+
+def _philox(c, it=0, spec=None):
+    """The case on noise='philox' (tests/test_gpu_general_philox_blocks.py): `it` is the iteration that is judged (L = it + 1 are
+    trained), route['spec'] the SPECK kind of the specialised forward instance the launch must take, or None."""
+    c = copy.deepcopy(c)
+    c["id"] = c["name"] = "philox-%s%s" % (c["id"], "-it%d" % it if it else "")
+    c["noise"], c["it"] = "philox", it
+    c["solver"]["L"] = it + 1
+    c["route"]["spec"] = spec
+    return c
+
+
+def _philox_templated():
+    """Specialised instances (unbounded, not adaptive, the path store on: split products under 'auto', and bf16), then the PHILOX
+    instances off the specialisation (fp32; split products with the adaptive shift or a bounded domain)."""
+    x3 = "f16x3"
+    gen = lambda inst, mode: dict(plan="gen", inst=inst, mode=mode)
+    ac = lambda d, T=0.045: ("general", "AllenCahn", dict(d=d, T=T, seed=42, modus="pt"))
+    dw = lambda d: ("general", "DoubleWell_multidim_for_general_solver",
+                    dict(d=d, d_1=d // 2, d_2=d - d // 2, T=0.045, eta=0.1, kappa=0.5, modus="HJB"))
+    ac10 = lambda cid, mode, **kw: _c(cid, *ac(10), _relu2(24), gen((10, 24), mode), N=3, mode=mode, scale=3.0, bias_std=0.1, **kw)
+    dw100 = lambda cid, mode, **kw: _c(cid, *dw(100), _relu2(64), gen((100, 64), mode), K=40, N=3, mode=mode, bias_std=0.1, **kw)
+    out = []
+    # ---- spec<D, H>: exact (6, 30), (10, 24) at K = 1 and 40, (100, 64); padded (16, 32) -- the time row alone in the second input
+    # block -- and (48, 48) -- three state blocks, the last with 15 zero-padded features
+    out.append(_philox(BY_ID["gen-6x30-allencahn-K257-diff-f16x3"], spec=SPEC_ALLEN_CAHN))
+    out.append(_philox(ac10("gen-10x24-allencahn-K1-bsde-plain-f16x3", x3, K=1, Kb=1), spec=SPEC_ALLEN_CAHN))
+    k40 = ac10("gen-10x24-allencahn-K40-bsde-f16x3", x3, K=40)
+    out += [_philox(k40, spec=SPEC_ALLEN_CAHN), _philox(k40, it=1, spec=SPEC_ALLEN_CAHN)]
+    out.append(_philox(_c("gen-15x20-allencahn-K40-bsde-f16x3", *ac(15), _relu2(20), gen((16, 32), x3), K=40, N=3, mode=x3, scale=2.0,
+                          bias_std=0.1), spec=SPEC_ALLEN_CAHN))
+    out += [_philox(BY_ID["gen-100x64-dwell-K40-bsde-f16x3"], spec=SPEC_DWELL),
+            _philox(BY_ID["gen-100x64-dwell-K40-bsde-f16x3"], it=1, spec=SPEC_DWELL)]
+    out.append(_philox(_c("gen-33x40-dwell-K40-bsde-f16x3", *dw(33), _relu2(40), gen((48, 48), x3), K=40, N=3, mode=x3, scale=2.0,
+                          bias_std=0.1), spec=SPEC_DWELL))
+    # ---- the same two kinds on the bf16 products (judged by the bf16 bounds; X_N and t_N never pass through a bf16 product)
+    out.append(_philox(ac10("gen-10x24-allencahn-K40-bsde-bf16", "bf16", K=40), spec=SPEC_ALLEN_CAHN))
+    out.append(_philox(dw100("gen-100x64-dwell-K40-bsde-bf16", "bf16"), spec=SPEC_DWELL))
+    # (6, 30), d + 1 = 7: two k-steps on the input side, where the bf16 image of a weight table is twice its fp32 image (GGeo::tbl)
+    out.append(_philox(_c("gen-6x30-allencahn-K257-diff-bf16", *ac(6, 0.105), _relu2(30), gen((6, 30), "bf16"), K=257, N=7,
+                          loss="diffusion", alpha=[1.0, 0.01, 1.0], Kb=10, mode="bf16", scale=3.0, bias_std=0.1), spec=SPEC_ALLEN_CAHN))
+    # ---- gen_fwd_kernel<D, H, false, true> (fp32) and <D, H, false, true, true> (split products) off the specialisation
+    for cid in ("gen-6x30-allencahn-K257-diff-fp32", "gen-7x20-expball-K16-ell-neumann-fp32", "gen-10x24-allencahn-K40-bsde-adp-f16x3",
+                "gen-33x40-sphere-K40-bsde-adp-f16x3", "gen-15x20-box-K40-diff-stopped-f16x3"):
+        out.append(_philox(BY_ID[cid]))
+    out.append(_philox(dw100("gen-100x64-dwell-K40-bsde-adp-f16x3", x3, adaptive=True)))
+    return out
+
+
+def _philox_runtime_shaped():
+    """Every run-time-shaped case, and two of them on the second iteration (iter = 1 in the counters): four waves with the adaptive
+    shift, and d = 111 -- seven noise blocks, the last with 15 features -- on eight."""
+    rt = _runtime_shaped()
+    by = {c["id"]: c for c in rt}
+    return [_philox(c) for c in rt] + [_philox(by[cid], it=1) for cid in ("genl-d16-a33x17x17-tanh2-nw4", "genl-d111-a128x4-tanh2")]
+
+
+PHILOX_CASES = _philox_templated() + _philox_runtime_shaped()
+assert len({c["id"] for c in PHILOX_CASES}) == len(PHILOX_CASES)
+PHILOX_BY_ID = {c["id"]: c for c in PHILOX_CASES}
+# the forward of rows 20 .. 39 alone (k_offset = 20, no multiple of 16): a specialised templated instance and a run-time-shaped case
+PHILOX_SHARD_IDS = ("philox-gen-10x24-allencahn-K40-bsde-f16x3", "philox-genl-d16-a33x17x17-tanh2-nw4")
+
+
 # ---- the oracle side ---------------------------------------------------------------------------------------------------------------
 def oracle_problem(c):
     """orc.make_problem of the case; a 'B' keyword (QuadraticOnBox) becomes the oracle's dense constant sigma."""
@@ -266,6 +340,24 @@ def _oracle_config(c):
     if c["family"] == "elliptic":
         return orc.EllipticConfig(alpha=tuple(s["alpha"]), boundary_type=s.get("boundary_type", "Dirichlet"), **common)
     return orc.GeneralConfig(alpha=tuple(s["alpha"]), **common)
+
+
+def reference_net(c, flat=None):
+    """(oracle problem, ref64_general.net64 of the oracle-built net after prepare_net) of a case, as runs() takes them, without an
+    oracle run.  flat: a flat parameter vector in registration order -- the package's before a later iteration -- loaded into it."""
+    oprob, cfg = oracle_problem(c), _oracle_config(c)
+    V = (orc.elliptic_build if c["family"] == "elliptic" else orc.general_build)(oprob, cfg, net=c["net"])
+    prepare_net(c, V)
+    net = r64.net64(V)
+    if flat is not None:
+        flat = flat.detach().to(device="cpu", dtype=r64.F64).reshape(-1)
+        assert flat.numel() == sum(p.numel() for p in net["params"])
+        off = 0
+        with torch.no_grad():
+            for p in net["params"]:
+                p.copy_(flat[off:off + p.numel()].view_as(p))
+                off += p.numel()
+    return oprob, net
 
 
 _RUNS = {}

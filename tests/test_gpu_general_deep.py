@@ -158,6 +158,23 @@ def test_philox_rollout_is_deterministic_and_shard_independent():
     assert torch.equal(model2._gen_plan.YN, Y1) and torch.equal(model2._gen_plan.VN, V1)
     assert model2.loss_log == model.loss_log and torch.equal(model2._gen_plan.grad, plan.grad)
     assert torch.isfinite(plan.grad).all() and float(plan.grad.abs().max()) > 0
+    # the upper half alone: a fresh solver (the initial weights: the full run's outputs precede its Adam step) with K / 2
+    # trajectories, the forward launched through the C ABI at k_offset = K / 2 on the full run's x0 and t0 of those rows
+    K = 512
+    Xfull = plan._sample_domain_device(0)
+    t0full = torch.rand(K, generator=plan._gen, device=dev()) * prob.T
+    prob3, half = build_pkg(case, device=dev(), backend="native", L=1, noise="philox", K=K // 2)
+    hp = half._choose_plan()
+    assert type(hp).__name__ == "GeneralDeepPlan" and hp.K_local == K // 2
+    hp.cfg.k_offset = K // 2
+    hp.kcount.zero_()
+    x0, t0 = Xfull[K // 2:].contiguous(), t0full[K // 2:].contiguous()
+    nat.check(nat.load().psp_genl_rollout_fwd(C.byref(hp.gcfg), nat.ptr(hp.flat), nat.ptr(x0), nat.ptr(t0), None,
+                                              int(half.seed), 0, nat.ptr(hp.tables), nat.ptr(hp.path), nat.ptr(hp.ahat),
+                                              nat.ptr(hp.VN), nat.ptr(hp.YN), nat.ptr(hp.XN_k), nat.ptr(hp.tN), nat.ptr(hp.kcount),
+                                              nat.stream_ptr(dev())), "psp_genl_rollout_fwd")
+    torch.cuda.synchronize()
+    assert torch.equal(hp.YN, Y1[K // 2:]) and torch.equal(hp.VN, V1[K // 2:])
 
 
 def test_two_hidden_layer_nets_keep_the_templated_kernels():

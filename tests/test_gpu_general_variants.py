@@ -76,7 +76,10 @@ def test_bf16_forward_products_track_the_fp32_kernels():
             assert cos >= 0.999, (name, dt, cos)
             for a, b, g in zip(res[dt][0], res["fp32"][0], rec["expected"]["loss_log"]):
                 assert math.isclose(a, b, rel_tol=2e-2) and math.isclose(a, g, rel_tol=2e-2), (name, dt, res[dt][0], res["fp32"][0])
-            assert res[dt][0] != res["fp32"][0], (name, dt)    # the bf16 path really ran
+            # the bf16 path really ran: its gradient is not the fp32 kernels'.  (The loss log does not tell: in dwgen_d10_diffusion
+            # the terminal term, which torch computes, is 1e3 and the rollout's share of a bf16 rounding is under half an ulp of it.
+            # It did differ while the bf16 weight tables of d + 1 <= 12 overran their LDS carve -- csrc/gen_kernels.h GGeo::tbl.)
+            assert not torch.equal(g16, g32), (name, dt)
         assert not torch.equal(res["bf16"][2], res["bf16_fwd"][2]), name
 
 

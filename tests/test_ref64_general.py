@@ -106,6 +106,47 @@ def test_table_covers_the_routes():
     assert all(c["solver"]["K"] <= 257 and c["solver"]["N"] <= 7 for c in C)
 
 
+def test_philox_table_covers_the_routes():
+    """PHILOX_CASES (tests/test_gpu_general_philox_blocks.py) reaches every forward instance that noise='philox' selects; no GPU
+    call.  A specialised case must satisfy, in its own description, what GenLaunch::spec_kind asks of the launch."""
+    P = gc.PHILOX_CASES
+    assert all(c["noise"] == "philox" and c["solver"]["L"] == c["it"] + 1 for c in P)
+    assert all(c["solver"]["K"] <= 257 and c["solver"]["N"] <= 7 for c in P)
+    gen = [c for c in P if c["route"]["plan"] == "gen"]
+    genl = [c for c in P if c["route"]["plan"] == "genl"]
+    spec = [c for c in gen if c["route"]["spec"] is not None]
+    off = [c for c in gen if c["route"]["spec"] is None]
+    kinds = {gc.SPEC_ALLEN_CAHN: "AllenCahn", gc.SPEC_DWELL: "DoubleWell_multidim_for_general_solver"}
+    for c in spec:                                               # unbounded, not adaptive, split products or bf16
+        assert c["problem"]["kind"] == kinds[c["route"]["spec"]] and c["family"] == "general", c["id"]
+        assert not c["solver"]["adaptive_forward_process"] and c["mode"] in ("f16x3", "bf16"), c["id"]
+    for c in off:                                                # fp32 never specialises; else adaptive, bounded or another problem
+        assert c["mode"] == "fp32" or c["solver"]["adaptive_forward_process"] or c["family"] != "general" \
+            or c["problem"]["kind"] not in kinds.values(), c["id"]
+    exact, padded = lambda c: c["route"]["inst"] in ((6, 30), (10, 24), (100, 64)), lambda c: c["route"]["inst"] in ((16, 32), (48, 48))
+    for kind in kinds:
+        x3 = [c for c in spec if c["route"]["spec"] == kind and c["mode"] == "f16x3"]
+        assert any(exact(c) for c in x3) and any(padded(c) for c in x3), kind
+        assert any(c["mode"] == "bf16" for c in spec if c["route"]["spec"] == kind), kind
+        assert any(c["it"] == 1 for c in x3), kind
+    assert {c["route"]["inst"] for c in spec if c["mode"] == "f16x3"} == {(6, 30), (10, 24), (16, 32), (48, 48), (100, 64)}
+    assert {c["solver"]["K"] for c in spec} >= {1, 40, 257}
+    assert {c["mode"] for c in off} == {"fp32", "f16x3"}
+    assert {c["route"]["inst"] for c in off if c["mode"] == "f16x3"} == {(10, 24), (16, 32), (48, 48), (100, 64)}
+    assert any(c["it"] == 1 for c in gen) and any(c["it"] == 1 for c in genl)          # iter = 1 on each plan
+    base = {c["id"] for c in gc.CASES if c["route"]["plan"] == "genl"}
+    assert {c["id"][len("philox-"):] for c in genl if c["it"] == 0} == base                # every run-time-shaped case
+    assert {c["route"]["fwd"] for c in genl} == {1, 4, 8}
+    assert sum(c["dense"] for c in genl) >= 3 and any(c["early"] for c in genl)
+    d_in = {c["problem"]["kwargs"]["d"] + (0 if c["family"] == "elliptic" else 1) for c in genl}
+    assert d_in >= {2, 16, 17, 112}, d_in
+    assert {c["it"] for c in genl if c["problem"]["kwargs"]["d"] == 111} == {0, 1}       # seven noise blocks, the last holds 15
+    for cid in gc.PHILOX_SHARD_IDS:
+        assert gc.PHILOX_BY_ID[cid]["solver"]["K"] == 40 and gc.PHILOX_BY_ID[cid]["it"] == 0
+    assert {gc.PHILOX_BY_ID[cid]["route"]["plan"] for cid in gc.PHILOX_SHARD_IDS} == {"gen", "genl"}
+    assert gc.CASES == gc._templated() + gc._runtime_shaped()    # the supplied-noise table is what it was: nothing here edits it
+
+
 # ---- c. planted errors -------------------------------------------------------------------------------------------------------------
 def views(g, c):
     """[(W_i with rows = inputs, b_i)] as writable views of the flat gradient g of the case's net."""
