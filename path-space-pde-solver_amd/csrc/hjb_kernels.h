@@ -720,9 +720,14 @@ struct Geo {
     // torch flat parameter offsets
     static constexpr int oW1 = 0, ob1 = H * (D + 1), oW2 = ob1 + H, ob2 = oW2 + H * H, oW3 = ob2 + H,
                          ob3 = oW3 + D * H, P = ob3 + D;
-    // forward LDS carve (floats)
-    static constexpr int fW1 = 0, fW2 = fW1 + HB * KSD * 64, fW3 = fW2 + HB * KSH * 64,
-                         fVec = fW3 + DB * KSH * 64;
+    // forward LDS carve (floats).  Each table holds the larger of its two images: the fp32 one (MB x KS k-steps of 64 floats)
+    // and the bf16 one of MODE 1 (stage_aop_bf16: MB x ceil(INB / 2) k-steps of 64 x 16 bytes).  The bf16 image is the larger
+    // one only where a 32-wide k-step is mostly padding: 4 ceil(INB / 2) > KS, i.e. an input of at most 12 features (the
+    // d = 2, 4, 8, 10 instances' W1); every other instance keeps the fp32 carve to the byte (static_assert below).
+    static constexpr int tbl(int MB, int KS, int INB) { return MB * (KS > 4 * ((INB + 1) / 2) ? KS : 4 * ((INB + 1) / 2)) * 64; }
+    static constexpr int fW1 = 0, fW2 = fW1 + tbl(HB, KSD, DB), fW3 = fW2 + tbl(HB, KSH, HB),
+                         fVec = fW3 + tbl(DB, KSH, HB);
+    static_assert(D <= 12 || H <= 12 || fVec == (HB * KSD + HB * KSH + DB * KSH) * 64, "only inputs of <= 12 features change the carve");
     // vectors: b1, w1t, b2 (HB*16 each), b3, driftv, runv, termv (DB*16 each)
     static constexpr int vb1 = fVec, vw1t = vb1 + HB * 16, vb2 = vw1t + HB * 16, vb3 = vb2 + HB * 16,
                          vdr = vb3 + DB * 16, vrun = vdr + DB * 16, vterm = vrun + DB * 16,

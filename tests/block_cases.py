@@ -5,10 +5,13 @@ Every case scales the initial N(0, 0.01) weights of the tanh net (default_scale 
 x 10 from d = 200 on, where x 30 saturates the hidden layers; less for the double well, whose X_0 = -1 feeds the first layer d
 inputs of size one) so that the activations are O(1): tanh' = 1 - h^2 then differs from 1 by tens of per cent and every block of the
 gradient carries signal.  The CPU test asserts exactly that of every case's float64 reference.
+
+BF16_CASES (below) is the table of tests/test_gpu_bf16_blocks.py and tests/test_ref64_bf16.py: Solver(mlp_dtype='bf16') against
+the float64 reference with bf16 operands, with the criterion both files share (bf16_errors, assert_bf16).
 """
 import torch
 
-from util_cases import make_oracle
+from util_cases import BLOCK_NAMES, block_errors, make_oracle
 
 import ref64
 
@@ -96,6 +99,47 @@ CASES = _narrow() + _wide()
 assert len({c["id"] for c in CASES}) == len(CASES)
 
 
+def _bf16():
+    """Solver(mlp_dtype='bf16'): hjb_fwd_kernel<D, H, MODE = 1, FAST = 0 | 1> -- supplied noise launches FAST = 0, Philox noise the
+    FAST = 1 instance -- followed by the fp32 backward (detached: hjb_bwd2, attached: hjb_adj).  Judged against ref64.iteration(...,
+    operands='bf16') by tests/test_gpu_bf16_blocks.py; the conditions on the table are asserted by tests/test_ref64_bf16.py.
+
+    The first four instances are those whose W1 table is larger as a bf16 image than as an fp32 one (Geo::tbl, d <= 12); each runs
+    on both noise modes, once detached and once attached."""
+    out = []
+    b = lambda route, kind, d, H, K, N, detach, exp, noise, **kw: out.append(
+        _c(route, kind, d, H, K, N, detach, "bf16", exp, noise=noise, **kw))
+    for noise, detach in (("reference", True), ("philox", False)):
+        b("bf16-d10", "LLGC", 10, 30, 65, 20, detach, (1, 10, 30), noise)
+        # (x 30: at the double well's x 15 the rounding error of W1x's block, 6e-4, is within x 3 of the fp32 block bound)
+        b("bf16-d4", "DoubleWell_multidim", 4, 30, 40, 4, detach, (1, 4, 30), noise, scale=30.0)
+    for noise, detach in (("reference", False), ("philox", True)):
+        b("bf16-d2", "LLGC", 2, 30, 48, 4, detach, (1, 2, 30), noise)
+        b("bf16-d8", "LQGC", 8, 30, 40, 4, detach, (1, 8, 30), noise)
+    # d = 5, H = 20: padded onto the cheapest instance that covers it (native_shapes.candidates), (8, 30) -- an overrunning one
+    b("bf16-pad-d5", "LLGC", 5, 20, 37, 4, True, (1, 8, 30), "philox")
+    # the two images of every table exactly equal (16 features = half a bf16 k-step, zero-filled)
+    b("bf16-16x16", "LLGC", 16, 16, 37, 4, True, (1, 16, 16), "reference")
+    b("bf16-16x16", "LLGC", 16, 16, 37, 4, False, (1, 16, 16), "philox")
+    # exact (20, 30); ragged K over 19 tiles
+    b("bf16-20x30", "LLGC", 20, 30, 299, 4, False, (1, 20, 30), "reference")
+    # odd block counts: the zero-filled half k-step of gemm_Tb on every product (48, 48), on the state only (100, 64: DB = 7)
+    b("bf16-48x48", "LLGC", 40, 48, 72, 4, True, (1, 48, 48), "reference")
+    b("bf16-48x48", "LQGC", 40, 48, 72, 4, False, (1, 48, 48), "philox")
+    b("bf16-48x64", "LQGC", 33, 50, 40, 4, False, (1, 48, 64), "reference")
+    b("bf16-100x64", "LLGC", 100, 64, 32, 5, True, (1, 100, 64), "philox")
+    b("bf16-100x64", "LLGC", 100, 64, 32, 5, False, (1, 100, 64), "reference")
+    # store_path 4: the backward regenerates xi (more than two tiles per CU, detached, Philox noise).  LQGC: over these 8208
+    # trajectories the fp32 stand-in's worst D is 0.16 of the rounding error here, 0.26 on LLGC -- past the stand-in's 1/4
+    b("bf16-store4", "LQGC", 20, 40, "cu", 3, True, (1, 32, 48), "philox", regen=True)
+    return out
+
+
+BF16_CASES = _bf16()
+assert len({c["id"] for c in BF16_CASES}) == len(BF16_CASES)
+BF16_OVERRUN = ((2, 30), (4, 30), (8, 30), (10, 30))       # instances whose bf16 W1 image exceeds the fp32 one
+
+
 def case_K(c, cus=ASSUMED_CUS):
     """'cu': one tile more than two per CU -- the smallest K at which the plan picks store_path 4."""
     return 16 * (2 * cus + 1) if c["K"] == "cu" else c["K"]
@@ -140,14 +184,46 @@ def reference_key(c, K):
 _REFS = {}
 
 
-def reference(c, K, noise):
+def reference(c, K, noise, operands="fp32", dtype=torch.float64):
     """ref64.iteration of the case, computed once per (problem, shape, flags, noise mode) -- the matrix mode and the kernel switches
-    do not enter -- and never modified.  `noise`: a callable returning (K, d, N + 1), evaluated on a miss only."""
-    key = reference_key(c, K)
+    do not enter -- and never modified.  `noise`: a callable returning (K, d, N + 1), evaluated on a miss only.  operands, dtype:
+    ref64.iteration's (the bf16-operand model and its fp32 stand-in), each kept under a key of its own."""
+    key = reference_key(c, K) + (() if (operands, dtype) == ("fp32", torch.float64) else (operands, dtype))
     if key not in _REFS:
         oprob, ocfg, z = scaled_oracle(c, K)
-        _REFS[key] = ref64.iteration(oprob, ocfg, z, noise())
+        _REFS[key] = ref64.iteration(oprob, ocfg, z, noise(), operands=operands, dtype=dtype)
     return _REFS[key]
+
+
+BF16_C = 0.5                # tests/test_gpu_bf16_blocks.py; the CPU stand-in of tests/test_ref64_bf16.py is held to half of it
+
+
+def bf16_errors(c, got, model, exact):
+    """The three-value criterion of the bf16 tests.  got / model / exact: dict(D, loss, grad) of the implementation under test, of
+    the float64 reference with bf16 operands and of the exact float64 reference.  Returns (e_kernel, e_model), each a dict with D
+    (of max(1, max |D|)), loss (relative) and blocks (util_cases.block_errors): e_kernel = |got - model|, e_model = |model - exact|.
+    For the loss e_model is max(e_model(loss), e_model(D)): one realised scalar difference can cancel by chance."""
+    def errs(a, r):
+        D, Dr = a["D"].double().cpu(), r["D"].double()
+        assert D.shape == Dr.shape and bool(torch.isfinite(D).all())
+        return dict(D=float((D - Dr).abs().max()) / max(1.0, float(Dr.abs().max())), loss=abs(a["loss"] - r["loss"]) / abs(r["loss"]),
+                    blocks=block_errors(a["grad"], r["grad"], c["d"], c["H"]))
+    ek, em = errs(got, model), errs(model, exact)
+    em["loss"] = max(em["loss"], em["D"])
+    return ek, em
+
+
+def assert_bf16(c, got, model, exact, coeff, d_tol, block_tol, tag=""):
+    """e_kernel <= coeff e_model + (the fp32 siblings' bound) for D, the loss and each of the seven blocks; prints every figure
+    before it asserts.  Returns (e_kernel, e_model)."""
+    ek, em = bf16_errors(c, got, model, exact)
+    tol_l = first_loss_tol(loss_values(c["loss"], model["D"]), model["loss"])
+    rows = [("D", ek["D"], em["D"], d_tol), ("loss", ek["loss"], em["loss"], tol_l)]
+    rows += [(n, a, b, block_tol) for n, a, b in zip(BLOCK_NAMES, ek["blocks"], em["blocks"])]
+    print("%s  " % tag + "  ".join("%s %.2e/%.2e" % r[:3] for r in rows) + "   (e_kernel/e_model)")
+    bad = [r for r in rows if not r[1] <= coeff * r[2] + r[3]]
+    assert not bad, (tag, coeff, bad)
+    return ek, em
 
 
 def loss_values(loss, D):

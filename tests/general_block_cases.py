@@ -14,8 +14,11 @@ the BSDE loss or loss_with_stopped here; alpha weighs the K_boundary-sized terms
 least half of it (asserted on the CPU).  `scale` multiplies the weight matrices and `bias_std` draws the biases of the dense-concat
 nets (zero at initialisation), both sides from the same seeded generator, where the initial state leaves a block under the floor.
 
-The bf16 modes (mlp_dtype 'bf16', 'bf16_fwd') stay out of CASES: their documented bound is 2e-2 (tests/test_gpu_general_variants.py),
-a hundred times the per-block bound, and a float64 judge adds nothing to what the fp32 kernels already tell about them.
+The bf16 modes (mlp_dtype 'bf16', 'bf16_fwd') stay out of CASES: against the exact float64 reference their documented bound is 2e-2
+(tests/test_gpu_general_variants.py), a hundred times the per-block bound -- wide enough to have passed a weight table that overran
+its LDS carve on every instance with d + 1 <= 12.  They have a table of their own, BF16_CASES, judged against the float64 reference
+with bf16 OPERANDS (ref64_general.iteration(..., operands='bf16')) by tests/test_gpu_general_bf16_blocks.py: the kernels are held to
+half the rounding error that reference predicts, on top of the fp32 bounds.
 
 PHILOX_CASES is a table of its own for tests/test_gpu_general_philox_blocks.py: the same shapes on noise='philox', where other
 compiled kernels run -- the PHILOX instances of gen_fwd_kernel, its specialised SPECK instances (unbounded, not adaptive: under
@@ -296,6 +299,102 @@ assert len({c["id"] for c in PHILOX_CASES}) == len(PHILOX_CASES)
 PHILOX_BY_ID = {c["id"]: c for c in PHILOX_CASES}
 # the forward of rows 20 .. 39 alone (k_offset = 20, no multiple of 16): a specialised templated instance and a run-time-shaped case
 PHILOX_SHARD_IDS = ("philox-gen-10x24-allencahn-K40-bsde-f16x3", "philox-genl-d16-a33x17x17-tanh2-nw4")
+
+
+# ---- the bf16 forward mode ----------------------------------------------------------------------------------------------------------
+def _bf16_cases():
+    """GeneralSolver(mlp_dtype='bf16_fwd'): gen_fwd_kernel<D, H, /*BF16*/true, ..> and the fp32 gen_bwd2_kernel behind it.  Supplied
+    noise: the three exact instances with d + 1 <= 12, whose input-side bf16 tables are larger than the fp32 ones (GGeo::tbl); the
+    exact (16, 16) -- the time row alone in the second input block, one hidden block: a zero-filled half k-step on every product;
+    d = 33, H = 40 padded onto (48, 48).  Philox noise: the two SPECK instances at (100, 64); off the specialisation the adaptive
+    shift (bf16 products move the state) and a sphere with early exits.  All on the dense-concat relu^2 net: the templated plan takes
+    no other (DenseNet_tanh runs on the genl_* kernels, which decline the bf16 modes: tests/test_gpu_general_bf16_blocks.py)."""
+    m = "bf16_fwd"
+    gen = lambda inst: dict(plan="gen", inst=inst, mode=m)
+    ac = lambda d, T=0.045: ("general", "AllenCahn", dict(d=d, T=T, seed=42, modus="pt"))
+    dw = lambda d: ("general", "DoubleWell_multidim_for_general_solver",
+                    dict(d=d, d_1=d // 2, d_2=d - d // 2, T=0.045, eta=0.1, kappa=0.5, modus="HJB"))
+    kw = dict(mode=m, bias_std=0.1)
+    sup = [_c("bf16-gen-6x30-allencahn-K257-diff", *ac(6, 0.105), _relu2(30), gen((6, 30)), K=257, N=7, loss="diffusion",
+              alpha=[1.0, 0.01, 1.0], Kb=10, scale=3.0, **kw),
+           _c("bf16-gen-10x24-allencahn-K40-bsde", *ac(10), _relu2(24), gen((10, 24)), K=40, N=3, scale=3.0, **kw),
+           _c("bf16-gen-10x32-allencahn-K37-bsde", *ac(10), _relu2(32), gen((10, 32)), K=37, N=3, scale=3.0, **kw),
+           _c("bf16-gen-16x16-allencahn-K40-bsde", *ac(16), _relu2(16), gen((16, 16)), K=40, N=3, scale=3.0, **kw),
+           _c("bf16-gen-33x40-dwell-K40-bsde", *dw(33), _relu2(40), gen((48, 48)), K=40, N=3, scale=2.0, **kw)]
+    for c in sup:
+        c["noise"], c["it"] = "reference", 0
+        c["route"]["spec"] = None
+    phx = [# (net seed 5: with 42 one relu^2 pre-activation of the oracle's draws lies within 4 fp32 roundings of zero)
+           _philox(_c("bf16-gen-100x64-allencahn-K40-bsde", *ac(100), _relu2(64, seed=5), gen((100, 64)), K=40, N=3, **kw), spec=SPEC_ALLEN_CAHN),
+           _philox(_c("bf16-gen-100x64-dwell-K40-bsde", *dw(100), _relu2(64), gen((100, 64)), K=40, N=3, **kw), spec=SPEC_DWELL),
+           _philox(_c("bf16-gen-10x24-allencahn-K40-bsde-adp", *ac(10), _relu2(24), gen((10, 24)), K=40, N=3, adaptive=True, scale=3.0, **kw)),
+           _philox(_c("bf16-gen-33x40-sphere-K40-bsde-adp", "general_bounded", "ExponentialOnSphereNonlinearParabolic",
+                      dict(d=33, T=0.0105, alpha=0.3), _relu2(40), gen((48, 48)), K=40, N=7, dt=0.001, adaptive=True, scale=2.0,
+                      early=True, **kw))]
+    return sup + phx
+
+
+def _bf16_full_cases():
+    """GeneralSolver(mlp_dtype='bf16'): the same forward instances with the bf16-pair path store, and gen_bwd2_kernel<D, H, /*BF16*/
+    true> -- every case of BF16_CASES again, and K = 299 over N = 20 steps on (10, 24): 19 tiles, the last with 11 trajectories,
+    399 sample blocks, i.e. a hundred backward rounds of four."""
+    out = []
+    for c in _bf16_cases():
+        c = copy.deepcopy(c)
+        c["id"] = c["name"] = c["id"].replace("bf16-gen", "bf16full-gen")
+        c["mode"] = c["route"]["mode"] = "bf16"
+        out.append(c)
+    c = _c("bf16full-gen-10x24-allencahn-K299-N20-bsde", "general", "AllenCahn", dict(d=10, T=0.215, seed=42, modus="pt"), _relu2(24),
+           dict(plan="gen", inst=(10, 24), mode="bf16", spec=None), K=299, N=20, mode="bf16", scale=3.0, bias_std=0.1)
+    c["noise"], c["it"] = "reference", 0
+    return out + [c]
+
+
+def bf16_reference(c, oprob, net, draws):
+    """The float64 model of the case's mode on the given draws: bf16 operands in the forward sweeps, and for the full 'bf16' mode
+    the kernel's backward with its rounding points."""
+    return r64.iteration(c, oprob, net, draws, operands="bf16", backward="bf16" if c["mode"] == "bf16" else "autograd")
+
+
+BF16_CASES = _bf16_cases()
+BF16_FULL_CASES = _bf16_full_cases()
+assert len({c["id"] for c in BF16_CASES + BF16_FULL_CASES}) == len(BF16_CASES) + len(BF16_FULL_CASES)
+BF16_C = 0.5                # tests/test_gpu_general_bf16_blocks.py; the CPU stand-in is held to half of it
+BF16_PRODUCT_BLOCKS = ("W1x", "W2x", "W2h1")        # the weight blocks of the bf16 products (W3 enters by fp32 dot products)
+
+
+def bf16_errors(c, got, model, exact):
+    """(e_kernel, e_model): dicts over YN, VN, XN, tN (of max(1, max |.|)), loss (relative) and `blocks` (names, errors), e_kernel =
+    |got - model|, e_model = |model - exact|.  For the loss e_model is max(e_model(loss), e_model(YN)): one realised scalar
+    difference can cancel by chance."""
+    lay, kw = layout(c)
+
+    def errs(a, r):
+        out = {}
+        for name in ("YN", "VN", "XN", "tN"):
+            g, want = a[name].double().cpu(), r[name].double()
+            assert g.shape == want.shape and bool(torch.isfinite(g).all()), name
+            out[name] = float((g - want).abs().max()) / max(1.0, float(want.abs().max()))
+        out["loss"] = abs(a["loss"] - r["loss"]) / abs(r["loss"])
+        out["blocks"] = general_block_errors(a["grad"], r["grad"], *lay, **kw)
+        return out
+    ek, em = errs(got, model), errs(model, exact)
+    em["loss"] = max(em["loss"], em["YN"])
+    return ek, em
+
+
+def assert_bf16(c, got, model, exact, coeff, d_tol, loss_tol, block_tol, tag=""):
+    """e_kernel <= coeff e_model + (the fp32 siblings' bound) for YN, VN, the loss and every block; X_N and t_N likewise where a bf16
+    product reaches the state (the adaptive shift) and to the plain fp32 bound where none does.  Prints every figure first."""
+    ek, em = bf16_errors(c, got, model, exact)
+    moved = c["solver"]["adaptive_forward_process"]
+    rows = [(n, ek[n], em[n], d_tol) for n in ("YN", "VN")] + [(n, ek[n], em[n] if moved else 0.0, d_tol) for n in ("XN", "tN")]
+    rows += [("loss", ek["loss"], em["loss"], loss_tol)]
+    rows += [(n, a, b, block_tol) for n, a, b in zip(ek["blocks"][0], ek["blocks"][1], em["blocks"][1])]
+    print("%s  " % tag + "  ".join("%s %.2e/%.2e" % r[:3] for r in rows) + "   (e_kernel/e_model)")
+    bad = [r for r in rows if not r[1] <= coeff * r[2] + r[3]]
+    assert not bad, (tag, coeff, bad)
+    return ek, em
 
 
 # ---- the oracle side ---------------------------------------------------------------------------------------------------------------

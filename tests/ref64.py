@@ -18,18 +18,19 @@ KINDS = ("LLGC", "LQGC", "DoubleWell_multidim")
 LOSSES = ("log-variance", "moment", "variance", "cross_entropy", "relative_entropy")
 
 
-def _coefficients(prob):
-    """(b, f, g) of the problem kind as double-precision closures over the oracle's fp32 data (pathspace_oracle.problem_*)."""
+def _coefficients(prob, dtype=F64):
+    """(b, f, g) of the problem kind as double-precision closures over the oracle's fp32 data (pathspace_oracle.problem_*);
+    dtype: the one they compute in (float64 but for the fp32 stand-in of `iteration`)."""
     ex = prob.extra
     if prob.kind == "LLGC":
-        A, alpha = ex["A"].to(F64), ex["alpha"].to(F64)
-        return (lambda x: x @ A.t()), (lambda x: torch.zeros(x.shape[0], dtype=F64)), (lambda x: (x @ alpha)[:, 0])
+        A, alpha = ex["A"].to(dtype), ex["alpha"].to(dtype)
+        return (lambda x: x @ A.t()), (lambda x: torch.zeros(x.shape[0], dtype=dtype)), (lambda x: (x @ alpha)[:, 0])
     if prob.kind == "LQGC":
-        A, P, R = ex["A"].to(F64), ex["P"].to(F64), ex["R"].to(F64)
+        A, P, R = ex["A"].to(dtype), ex["P"].to(dtype), ex["R"].to(dtype)
         return (lambda x: x @ A.t()), (lambda x: torch.sum(x * (x @ P.t()), 1)), (lambda x: torch.sum(x * (x @ R.t()), 1))
     if prob.kind == "DoubleWell_multidim":
-        eta, kappa = ex["eta_"].to(F64), ex["kappa_"].to(F64)
-        return ((lambda x: -4.0 * kappa * (x * (x ** 2 - 1.0))), (lambda x: torch.zeros(x.shape[0], dtype=F64)),
+        eta, kappa = ex["eta_"].to(dtype), ex["kappa_"].to(dtype)
+        return ((lambda x: -4.0 * kappa * (x * (x ** 2 - 1.0))), (lambda x: torch.zeros(x.shape[0], dtype=dtype)),
                 (lambda x: torch.sum(eta * (x - 1.0) ** 2, 1)))
     raise NotImplementedError(prob.kind)
 
@@ -49,8 +50,49 @@ def _loss(kind, D, Y, gX, Z_sum, adaptive):
     raise NotImplementedError(kind)
 
 
-def iteration(prob, cfg, z, noise, weights=None):
+def rb(x):
+    """Round to nearest even onto bf16, back in the dtype of x: what `(__bf16)v` does to an fp32 MFMA operand."""
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+class _Product(torch.autograd.Function):
+    """a (K, n) x W (m, n) -> a W^T (K, m) as the forward-only bf16 modes run it: both operands of the forward product are rounded to
+    bf16 (exact sums: the MFMA accumulates in fp32, which float64 stands in for); the backward is the fp32 one of those modes, on the
+    UNROUNDED a and W -- NOT the adjoint of the rounded product, which would carry rb(W) (a straight-through rounding op gets
+    exactly that wrong)."""
+
+    @staticmethod
+    def forward(ctx, a, W, rounded):
+        ctx.save_for_backward(a, W)
+        return (rb(a) @ rb(W).t()) if rounded else a @ W.t()
+
+    @staticmethod
+    def backward(ctx, g):
+        a, W = ctx.saved_tensors
+        return g @ W, g.t() @ a, None
+
+
+def product(a, W, operands="fp32"):
+    """a W^T with the operand rounding of a matrix mode ('fp32': none, 'bf16': see _Product)."""
+    assert operands in ("fp32", "bf16")
+    return _Product.apply(a, W, operands == "bf16")
+
+
+def iteration(prob, cfg, z, noise, weights=None, operands="fp32", dtype=F64):
     """One iteration in float64.
+
+    operands='bf16': the model of Solver(mlp_dtype='bf16'), hjb_fwd_kernel<D, H, MODE = 1> (csrc/hjb_kernels.h).  The rounding
+    points, all of them operands of v_mfma_f32_16x16x32_bf16 and all round-to-nearest-even:
+      W1x, W2, W3        stage_aop_bf16: `v[e] = (__bf16)src(row, ...)`, once per workgroup;
+      X_n, h1, h2        gemm_Tb: `b[e] = (__bf16)in[2 * S][e]`, per step, at the three calls `gemm_Tb<HB, DB>(h1, lds + oW1, X, ..)`,
+                         `gemm_Tb<HB, HB>(h2, lds + oW2, h1, ..)` and `gemm_Tb<DB, HB>(Z, lds + oW3, h2, ..)`.
+    Everything else is fp32 in the kernel and exact here: the accumulator starts from `vb1 + tn * vw1t` (time column and bias), the
+    biases b2, b3, tanh, drift, sigma, the state update, Y, D and the loss.  The backward kernels of this mode (hjb_bwd2 / hjb_adj)
+    run in fp32 on the stored fp32 X_n, h1, h2 and the fp32 weights: `product` returns the unrounded adjoints.
+
+    dtype=torch.float32 runs the same statements in fp32: with operands='bf16' a torch stand-in of the bf16 kernels (fp32 arithmetic
+    on bf16-rounded operands), which differs from the float64 model by fp32 rounding and by the rare operand that an fp32-sized
+    perturbation moves to the other bf16 neighbour (tests/test_ref64_bf16.py).
 
     prob: OracleProblem; cfg: HJBConfig (time_approx='inner', control ansatz, fixed X_0, no learnable Y_0); z: the fp32 TanhMLP
     (read, never modified); noise: (K, d, N + 1) as hjb_train takes it; weights: optional (K,) -- the loss is then sum_k w_k D_k
@@ -62,25 +104,25 @@ def iteration(prob, cfg, z, noise, weights=None):
     assert cfg.time_approx == "inner" and cfg.approx_method == "control" and not cfg.learn_Y_0 and not cfg.random_X_0
     assert prob.kind in KINDS and cfg.loss_method in LOSSES
     d = prob.d
-    xi = noise.detach().to(F64)
+    xi = noise.detach().to(dtype)
     K = xi.shape[0]
     N = int(np.floor(prob.T / cfg.delta_t))                            # solver.py:41
     assert xi.shape == (K, d, N + 1), (tuple(xi.shape), (K, d, N + 1))
     dt32 = torch.tensor(cfg.delta_t)                                   # solver.py:39-40: the fp32 step and its fp32 root
     dt, sq = float(dt32), float(torch.sqrt(dt32))
-    B = prob.B.to(F64)
-    b, f, g = _coefficients(prob)
-    W1, b1, W2, b2, W3, b3 = params = [p.detach().to(F64).clone().requires_grad_(True) for p in z.parameters()]
+    B = prob.B.to(dtype)
+    b, f, g = _coefficients(prob, dtype)
+    W1, b1, W2, b2, W3, b3 = params = [p.detach().to(dtype).clone().requires_grad_(True) for p in z.parameters()]
     assert W1.shape[1] == d + 1 and W3.shape[0] == d
 
     def net(t, X):                                                     # the input is [t, x]: column 0 of W1 is the time column
-        h1 = torch.tanh(t * W1[:, 0] + X @ W1[:, 1:].t() + b1)
-        h2 = torch.tanh(h1 @ W2.t() + b2)
-        return h2 @ W3.t() + b3, h1, h2
+        h1 = torch.tanh(t * W1[:, 0] + product(X, W1[:, 1:], operands) + b1)
+        h2 = torch.tanh(product(h1, W2, operands) + b2)
+        return product(h2, W3, operands) + b3, h1, h2
 
-    X = prob.X_0.to(F64).repeat(K, 1)
-    Y = torch.zeros(K, dtype=F64)
-    Z_sum = torch.zeros(K, dtype=F64)
+    X = prob.X_0.to(dtype).repeat(K, 1)
+    Y = torch.zeros(K, dtype=dtype)
+    Z_sum = torch.zeros(K, dtype=dtype)
     mid = {}
     for n in range(N):
         Z, h1, h2 = net(n * dt, X)
@@ -98,7 +140,7 @@ def iteration(prob, cfg, z, noise, weights=None):
     gX = g(X)
     D = Y - gX
     if weights is not None:
-        loss = (weights.detach().to(F64).cpu() * D).sum()
+        loss = (weights.detach().to(dtype).cpu() * D).sum()
     else:
         loss = _loss(cfg.loss_method, D, Y, gX, Z_sum, cfg.adaptive_forward_process)
     grads = torch.autograd.grad(loss, params, allow_unused=True)

@@ -16,6 +16,8 @@ The input order is [x, t] (time last); EllipticSolver's net has no time input.  
 rounding alone.  The state path carries no parameter gradient: the control is detached (the native plans take nothing else)."""
 import torch
 
+from ref64 import product
+
 F64 = torch.float64
 E32 = 2.0 ** -23
 
@@ -125,6 +127,100 @@ def value(net, a, margin=None):
         a = torch.cat([a, r if act == "tanh" else r ** 2], 1)
 
 
+# ---- the kernels' own sweeps of the two-hidden-layer relu^2 net, for the bf16 modes ----------------------------------------------------
+def _relu2_parts(net, DI):
+    assert net["act"] == "relu2" and not net["linear"] and len(net["params"]) == 6, "the templated kernels' net: DenseNet [H, H], relu^2"
+    W1, b1, W2, b2, W3, b3 = net["params"]
+    H = W1.shape[1]
+    assert W1.shape == (DI, H) and W2.shape == (DI + H, H) and W3.shape == (DI + 2 * H, 1)
+    w3 = W3[:, 0]
+    return W1, b1, W2[:DI], W2[DI:], b2, w3[:DI], w3[DI:DI + H], w3[DI + H:], b3[0]
+
+
+def up_sweep(net, a, operands):
+    """(V (K,), r1, r2 = relu(z1), relu(z2)) as net_value of gen_fwd_kernel forms them: the three products through `product` (weights
+    are stored (in, out): a W = product(a, W^T)), the output layer as fp32 dot products (dot4: exact here)."""
+    W1, b1, W2x, W2h, b2, w3x, w3h1, w3h2, b3 = _relu2_parts(net, a.shape[1])
+    r1 = torch.relu(product(a, W1.t(), operands) + b1)
+    h1 = r1 ** 2
+    r2 = torch.relu(product(a, W2x.t(), operands) + product(h1, W2h.t(), operands) + b2)
+    return a @ w3x + h1 @ w3h1 + (r2 ** 2) @ w3h2 + b3, r1, r2
+
+
+def reverse_sweep(net, r1, r2, operands):
+    """grad_a V (K, DI) by the kernel's reverse sweep over the stored relu(z1), relu(z2): g_z2 = w3h2 2 r2, g_z1 = (w3h1 + W2h g_z2) 2 r1,
+    g_a = w3x + W2x g_z2 + W1 g_z1 -- three more products."""
+    W1, b1, W2x, W2h, b2, w3x, w3h1, w3h2, b3 = _relu2_parts(net, net["params"][0].shape[0])
+    gz2 = w3h2 * (2.0 * r2)
+    gz1 = (w3h1 + product(gz2, W2h, operands)) * (2.0 * r1)
+    return w3x + product(gz2, W2x, operands) + product(gz1, W1, operands)
+
+
+def tangent_images(net, r1, r2, U, operands):
+    """(z1^, z2^) (K, H): the tangent pre-activations gen_fwd_kernel stores, z1^ = W1^T U and z2^ = W2x^T U + W2h^T (2 r1 z1^)."""
+    W1, b1, W2x, W2h, b2, w3x, w3h1, w3h2, b3 = _relu2_parts(net, U.shape[1])
+    z1t = product(U, W1.t(), operands)
+    return z1t, product(U, W2x.t(), operands) + product((2.0 * r1) * z1t, W2h.t(), operands)
+
+
+def tangent_sweep(net, r1, r2, U, operands):
+    """U . grad_a V (K,) in forward mode, as the kernel forms the images its backward differentiates, and the output layer's dot
+    products."""
+    W1, b1, W2x, W2h, b2, w3x, w3h1, w3h2, b3 = _relu2_parts(net, U.shape[1])
+    z1t, z2t = tangent_images(net, r1, r2, U, operands)
+    return U @ w3x + ((2.0 * r1) * z1t) @ w3h1 + ((2.0 * r2) * z2t) @ w3h2
+
+
+def kernel_backward(net, samples, wY, wV, rounded):
+    """The flat gradient gen_bwd2_kernel forms from the path store: grad_theta sum_samples [a V + w U . grad_x V] over the sample blocks
+    (step n < N: a = wY (dY / dV_n), w = wY; the end point: a = wV, no tangent), statement by statement as in its header comment.
+    samples: per step dict(a0 (K, DI) = [x, t], U, r1, r2, z1t, z2t, coef = dY / dV_n; fin) of detached tensors.
+
+    rounded=True is gen_bwd2_kernel<D, H, /*BF16*/true> (mlp_dtype='bf16'), whose rounding points are: the stored images, which
+    pk_bf16 rounds in the forward kernel before the backward uses them anywhere -- X, U, 2 r1, 2 r2, z1^, z2^; both operands of the
+    adjoint products on the bf16 table gW2hr (`gen_gemm<1, ..>(gz1t, lds + G::gW2hr, gz2t, ..)` and `(gz1, .., gz2, ..)`); both
+    operands of the outer products (`pack2`: the row items x, w U, h1 = (d1 / 2)^2, h1' = d1 w z1^ and the adjoint panels gz2,
+    gz2', gz1, gz1' read back from the exchange tiles).  The bias sums and the rows of dW3 are fp32 sums of unrounded registers.
+    rounded=False is the fp32 kernel, i.e. the autograd gradient to float64 rounding (tests/test_ref64_general_bf16.py)."""
+    R = (lambda v: v.to(torch.bfloat16).to(v.dtype)) if rounded else (lambda v: v)
+    W1, b1, W2x, W2h, b2, w3x, w3h1, w3h2, b3 = [p.detach() for p in _relu2_parts(net, net["params"][0].shape[0])]
+    DI, H = W1.shape
+    gW1, gW2x, gW2h = torch.zeros_like(W1), torch.zeros_like(W2x), torch.zeros_like(W2h)
+    gb1, gb2, gb3 = torch.zeros_like(b1), torch.zeros_like(b2), torch.zeros((), dtype=F64)
+    gw3x, gw3h1, gw3h2 = torch.zeros_like(w3x), torch.zeros_like(w3h1), torch.zeros_like(w3h2)
+    step2 = lambda dd: 2.0 * (dd > 0).to(F64)
+    adj = lambda g, W: R(g) @ R(W).t()                           # W g over the output side, both operands of the MFMA rounded
+    outer = lambda A, G: R(A).t() @ R(G)
+    for sm in samples:
+        X_, d1, d2 = R(sm["a0"]), R(2.0 * sm["r1"]), R(2.0 * sm["r2"])
+        if sm["fin"]:
+            w, av = torch.zeros_like(wY), wV
+            U_, z1_, z2_ = torch.zeros_like(X_), torch.zeros_like(d1), torch.zeros_like(d2)
+        else:
+            w, av = wY, wY * sm["coef"]
+            U_, z1_, z2_ = R(sm["U"]), R(sm["z1t"]), R(sm["z2t"])
+        w, av = w.unsqueeze(1), av.unsqueeze(1)
+        z2w = w * z2_
+        gz2t = w3h2 * d2
+        gz2 = av * gz2t + w3h2 * step2(d2) * z2w
+        gw3h2 += (av * (0.25 * d2 * d2) + d2 * z2w).sum(0)
+        gb3 += av.sum()
+        gh1t = w3h1 + adj(gz2t, W2h)
+        gh1 = av * w3h1 + adj(gz2, W2h)
+        z1w = w * z1_
+        gz1 = gh1 * d1 + gh1t * step2(d1) * z1w
+        gz1t = gh1t * d1
+        A0x, A1x, A0h, A1h = X_, w * U_, 0.25 * d1 * d1, d1 * z1w
+        gw3x += (av * A0x + A1x).sum(0)
+        gw3h1 += (av * A0h + A1h).sum(0)
+        gb2 += gz2.sum(0)
+        gb1 += gz1.sum(0)
+        gW2x += outer(A0x, gz2) + outer(A1x, gz2t)
+        gW1 += outer(A0x, gz1) + outer(A1x, gz1t)
+        gW2h += outer(A0h, gz2) + outer(A1h, gz2t)
+    return flat([gW1, gb1, torch.cat([gW2x, gW2h], 0), gb2, torch.cat([gw3x, gw3h1, gw3h2]), gb3.reshape(1)])
+
+
 def _inputs(x, t):
     return x if t is None else torch.cat([x, t.reshape(-1, 1)], 1)
 
@@ -174,11 +270,47 @@ def _grad(loss, params):
     return flat([g if g is not None else torch.zeros_like(p) for g, p in zip(gs, params)])
 
 
-def iteration(case, oprob, net, draws, tangent=True):
+def iteration(case, oprob, net, draws, tangent=True, operands="fp32", sweeps=None, dtype=None, backward="autograd"):
     """One iteration of the case (the layout of the golden cases: family, problem, solver) on the net `net64` returned and the
-    draws of the fp32 oracle's trace.  Returns dict(loss, grad, grad_domain, grad_boundary (flat; domain = the terms the kernels
+    draws of the fp32 oracle's trace.
+
+    operands='bf16': the model of GeneralSolver(mlp_dtype='bf16_fwd') on the templated kernels (csrc/gen_kernels.h, MODE 1: gen_stage
+    -> stage_aop_bf16 rounds every weight table, gen_gemm -> gemm_Tb rounds the register operand; both round to nearest even).  The
+    rollout then runs on the kernels' own three sweeps (`sweeps`, on by default with bf16 operands) instead of autograd:
+      up sweep       net_value: z1 = W1^T [x, t], z2 = W2x^T [x, t] + W2h^T h1 -- operands [x, t] (the TIME input sits in the state
+                     panel, put_time, and is rounded with it), h1 = relu(z1)^2 and the tables oW1f, oW2xf, oW2hf; at every step, at
+                     (X_0, t_0) for Y_0 and at (X_N, t_N) for V_N.  The output layer is fp32 (dot4) and exact here;
+      reverse sweep  g_h1 = w3h1 + W2h g_z2, g_x = w3x + W2x g_z2 + W1 g_z1 (`gen_gemm<MODE, ..>(gz1, lds + oW2hr, gz2, ..)`, `(gx, lds +
+                     oW2xr, gz2, ..)`, `(gx, lds + oW1r, gz1, ..)`): operands g_z2 = w3h2 2 r2, g_z1 = g_h1 2 r1 and the tables oW2hr,
+                     oW2xr, oW1r.  Its result is the VALUE of Z = sigma^T grad_x V in the Y update, the adaptive shift and U;
+      tangent sweep  z1^ = W1^T U, z2^ = W2x^T U + W2h^T (2 r1 z1^) (`gen_gemm<MODE, ..>(z1h, lds + oW1f, U, ..)`, `(z2h, lds + oW2xf, U,
+                     ..)`, `(z2h, lds + oW2hf, h1d, ..)`): operands U = act sigma ((-h_z + c) dt + xi sqrt(dt)), h1' and the forward
+                     tables again.  gen_bwd2_kernel differentiates U . grad_x V through THESE stored images (X, U, 2 r1, 2 r2, z1^,
+                     z2^, all fp32 in this mode) with fp32 products on the unrounded weights, which is what autograd does to the
+                     tangent sweep when `product` returns the unrounded adjoints.  So Z enters Y by the reverse sweep's value and
+                     by the tangent sweep's gradient; with exact products the two are one function and this is the plain reference.
+    The boundary terms and the Neumann residual are torch's, in fp32 on the device: exact here.  sweeps=True with operands='fp32'
+    runs the same statements unrounded (tests/test_ref64_general_bf16.py: equal to the autograd form to float64 rounding);
+    dtype=torch.float32 runs the whole iteration in fp32 -- with bf16 operands the torch stand-in of the kernels.
+    backward='fp32' | 'bf16' (with the sweeps): the domain gradient by `kernel_backward` on the recorded sample blocks instead of
+    autograd -- 'bf16' is the model of the full mlp_dtype='bf16', whose forward is the 'bf16_fwd' one.
+
+    Returns dict(loss, grad, grad_domain, grad_boundary (flat; domain = the terms the kernels
     differentiate, boundary = the K_boundary-sized terms and the BSDE loss's Neumann residual, which the plans leave to torch
     autograd), YN, VN, XN, tN, steps (active steps per trajectory), K_count, n_loop, tile_steps, margins = dict(exit, time, relu))."""
+    global F64
+    if dtype is not None and dtype != F64:                       # every statement of this module computes in F64
+        keep, F64 = F64, dtype
+        try:
+            cast = dict(net, params=[p.detach().to(dtype).requires_grad_(True) for p in net["params"]])
+            return iteration(case, oprob, cast, draws, tangent, operands, sweeps, None, backward)
+        finally:
+            F64 = keep
+    assert operands in ("fp32", "bf16")
+    sweeps = (operands == "bf16") if sweeps is None else sweeps
+    assert sweeps or operands == "fp32"
+    assert backward in ("autograd", "fp32", "bf16") and (backward == "autograd" or (sweeps and tangent))
+    samples = []
     s, ex, d = case["solver"], oprob.extra, oprob.d
     elliptic = case["family"] == "elliptic"
     assert not s.get("sample_center", False) and not s.get("uniform_square", False)
@@ -209,7 +341,7 @@ def iteration(case, oprob, net, draws, tangent=True):
             else:
                 loss_b = loss_b + a_b * _neumann(net, _inputs(Xb, tb), co["g"](Xb, tb), d)
     # ---- the rollout
-    Y = value(net, _inputs(X, t), mg)
+    Y = up_sweep(net, _inputs(X, t), operands)[0] if sweeps else value(net, _inputs(X, t), mg)
     stopped = torch.zeros(K, dtype=torch.bool)
     steps = torch.zeros(K, dtype=torch.int64)
     m_exit, m_time, n_loop, gV = float("inf"), float("inf"), 0, None
@@ -217,11 +349,17 @@ def iteration(case, oprob, net, draws, tangent=True):
         if not bool((~stopped).any()):                           # solver.py:1093-1097 / :742-744
             break
         assert n < len(draws["xi"]), "the float64 replay runs longer than the oracle's loop: a discrete decision differs"
-        x = X.clone().requires_grad_(True)
-        Vn = value(net, _inputs(x, t), mg)
-        gV, = torch.autograd.grad(Vn.sum(), x, create_graph=True)
-        Z = (gV if tangent else gV.detach()) @ B                 # sigma^T grad_x V, row form
         xi = draws["xi"][n].to(F64)
+        if sweeps:
+            Vn, r1, r2 = up_sweep(net, _inputs(X, t), operands)
+            with torch.no_grad():
+                gV = reverse_sweep(net, r1, r2, operands)[:, :d]
+            Z = gV @ B                                           # the value; its gradient comes in by the tangent sweep below
+        else:
+            x = X.clone().requires_grad_(True)
+            Vn = value(net, _inputs(x, t), mg)
+            gV, = torch.autograd.grad(Vn.sum(), x, create_graph=True)
+            Z = (gV if tangent else gV.detach()) @ B             # sigma^T grad_x V, row form
         c = -Z.detach() if adaptive else torch.zeros(K, d, dtype=F64)
         alive = (~stopped).to(F64).unsqueeze(1)
         drift = co["drift"](X) if co["drift"] is not None else 0.0
@@ -234,14 +372,33 @@ def iteration(case, oprob, net, draws, tangent=True):
             m_time = min(m_time, float(_rel(t + dt, T)[~stopped].min()))
         act = new_sel & ~stopped
         actf = act.to(F64)
-        Y = Y + ((-co["h"](n * dt, X, Vn, Z) + (Z * c).sum(1)) * dt + (Z * xi).sum(1) * sq) * actf
+        incr = lambda V_, Z_: (-co["h"](n * dt, X, V_, Z_) + (Z_ * c).sum(1)) * dt + (Z_ * xi).sum(1) * sq
+        Y = Y + incr(Vn, Z) * actf
+        if sweeps and tangent:
+            Zd = Z.clone().requires_grad_(True)
+            u, = torch.autograd.grad(incr(Vn.detach(), Zd).sum(), Zd)            # (-h_z + c) dt + xi sqrt(dt), per trajectory
+            U = torch.cat([(u @ B.t()) * actf.unsqueeze(1), torch.zeros(K, 0 if elliptic else 1, dtype=F64)], 1)
+            Tn = tangent_sweep(net, r1, r2, U, operands)
+            Y = Y + (Tn - Tn.detach())
+            if backward != "autograd":
+                Vd = Vn.detach().clone().requires_grad_(True)
+                out = (incr(Vd, Z) * actf).sum()                # (an h that does not read y: no dependence, coefficient 0)
+                coef = torch.autograd.grad(out, Vd)[0] if out.requires_grad else torch.zeros(K, dtype=F64)
+                with torch.no_grad():
+                    z1t, z2t = tangent_images(net, r1, r2, U, operands)
+                samples.append(dict(a0=_inputs(X, t), U=U, r1=r1.detach(), r2=r2.detach(), z1t=z1t, z2t=z2t,
+                                    coef=coef + (1.0 if n == 0 else 0.0), fin=False))
         X = torch.where(act.unsqueeze(1), X_prop, X).detach()
         if not elliptic:
             t = t + dt * actf
         steps += act.long()
         stopped = stopped | ~new_sel
         n_loop = n + 1
-    VN = value(net, _inputs(X, t), mg)
+    if sweeps:
+        VN, r1, r2 = up_sweep(net, _inputs(X, t), operands)
+        samples.append(dict(a0=_inputs(X, t), r1=r1.detach(), r2=r2.detach(), fin=True))
+    else:
+        VN = value(net, _inputs(X, t), mg)
     loss_d = 0.0
     if diffusion:
         loss_d = loss_d + alpha[0] * (VN - Y).pow(2).mean()
@@ -256,12 +413,19 @@ def iteration(case, oprob, net, draws, tangent=True):
         m_time = min(m_time, float(_rel(t + dt, T).min()))
         if bool(late.any()):
             loss_d = loss_d + (Y[late] - co["f"](X[late])).pow(2).mean()
+        assert not sweeps, "the BSDE-Neumann residual is torch's (fp32 autograd on the device), not the kernels' sweep"
         if int(late.sum()) < K:                                  # grad_x V of the LAST executed step against the final X
             loss_b = loss_b + ((gV * X).sum(1) - (co["g"](X, t) * X).sum(1)).pow(2).mean()
     if s.get("loss_with_stopped", False):
         target = co["g"](X) if elliptic else co["f"](X)
         loss_d = loss_d + (Y[stopped] - target[stopped]).pow(2).mean()
-    g_d, g_b = _grad(loss_d, params), _grad(loss_b, params)
+    if backward == "autograd":
+        g_d = _grad(loss_d, params)
+    else:                                                        # the weights psp_gen_rollout_bwd2 is handed: dL / dY_N, dL / dV_N
+        wY, wV = torch.autograd.grad(loss_d, [Y, VN], allow_unused=True, retain_graph=True)
+        zero = torch.zeros(K, dtype=F64)
+        g_d = kernel_backward(net, samples, zero if wY is None else wY, zero if wV is None else wV, backward == "bf16")
+    g_b = _grad(loss_b, params)
     tile = steps.clone()
     pad = (-K) % 16
     tile = torch.cat([tile, torch.full((pad,), -1, dtype=torch.int64)]).view(-1, 16).max(1).values
