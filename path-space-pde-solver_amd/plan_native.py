@@ -364,6 +364,12 @@ class HjbNativePlan:
             self.uref = dev_f32(torch.cat([table, torch.zeros(16, device=dev)]))   # 16 floats of slack: the kernels read whole blocks
             self.ul2 = torch.zeros(self.K_local, dtype=torch.float32, device=dev)
             cfg.u_ref, cfg.u_l2_out = nat.ptr(self.uref), nat.ptr(self.ul2)
+            if self.n_chunks <= 1:
+                # the sizes above were queried before u_ref was set: with it the library launches no cooperative forward (wide
+                # family, f16x3, Philox noise), so fwd_workgroups / fwd_coop_tiles described a launch that never happens.  The
+                # buffers sized from that query stay: the tile-per-wave forward needs no more workgroups than the cooperative one
+                self.sizes = nat.query(cfg)
+                assert self.sizes.fwd_partial_bytes <= sizes.fwd_partial_bytes and self.sizes.path_bytes == sizes.path_bytes
         if self.attached or self.relent:
             self.cfg_w = nat.HjbConfig.from_buffer_copy(cfg)          # backward with explicit trajectory weights
             self.cfg_w.loss_kind = nat.LOSS_WEIGHTS
@@ -731,10 +737,14 @@ class HjbNativePlan:
         return loss_out[l]
 
     def _ul2_from_path(self):
+        """This rank's share of the u_L2 log: the sum of _ul2_rows_from_path() over the GLOBAL K."""
+        return self._ul2_rows_from_path().sum() / float(self.s.K)
+
+    def _ul2_rows_from_path(self):
         """u_L2 log (solver.py:491-494) for a reference control that is linear in x (LQGC) or tabulated per coordinate (the double
-        wells): sum_k sum_n |-Z_n - u*(X_{n+1}, t_n)|^2 dt / K over this
-        rank's trajectories, from the register images the forward kernel left in the path store -- block (n, tile): X_n image at
-        float 0, h2 image behind the h1 image; image float ks * 64 + 16 q + j holds feature 4 ks + q of sample j (csrc/hjb_kernels.h
+        wells): (K_local,) values sum_n |-Z_n - u*(X_{n+1}, t_n)|^2 dt, one per trajectory of this rank, from the register images
+        the forward kernel left in the path store (the same layout in both kernel families, every matrix mode and every store_path;
+        tests/test_gpu_solver_ul2.py holds each of them to float64) -- block (n, tile): X_n image at float 0, h2 image behind the h1 image; image float ks * 64 + 16 q + j holds feature 4 ks + q of sample j (csrc/hjb_kernels.h
         Geo::pX / pH2).  Z_n = W3 h2 + b3 with the net's own parameters.  A diagnostic: K N small products in torch, skipped
         with u_l2_error_flag=False (as the timed runs do)."""
         s = self.s
@@ -759,17 +769,17 @@ class HjbNativePlan:
                 cell = torch.floor((torch.clamp(X, -tb['xb'], tb['xb'] - 2 * tb['dx']) + tb['xb']) / tb['dx']).long()
                 if self.k_offset + self.K_local == s.K:
                     cell[:, -1, :] -= 2
-                tot = torch.zeros((), dtype=torch.float32, device=self.dev)
+                tot = torch.zeros(self.K_local, dtype=torch.float32, device=self.dev)
                 for n in range(N):                                              # (per step: bounds the index tensors)
                     u_ref = torch.empty(self.K_local, s.d, device=self.dev)
                     for gi, tab in enumerate(tb['tables']):
                         dims = torch.nonzero(tb['group'] == gi).flatten()
                         if dims.numel():
                             u_ref[:, dims] = tab[tb['n_ref'][n]][cell[n][:, dims]]
-                    tot = tot + ((-Z[n] - u_ref) ** 2).sum()
-                return tot * s.delta_t / float(s.K)
-            u_ref = torch.bmm(X, self.ul2_gain.transpose(1, 2))                 # M_n X_n
-            return ((-Z - u_ref) ** 2).sum() * s.delta_t / float(s.K)
+                    tot = tot + ((-Z[n] - u_ref) ** 2).sum(1)
+                return tot * s.delta_t
+            u_ref = torch.bmm(X, self.ul2_gain.transpose(1, 2))                 # M_n X_{n+1}
+            return ((-Z - u_ref) ** 2).sum((0, 2)) * s.delta_t
 
     def _finish_step(self, st, w_generic):
         """Gather the real gradient entries, all-reduce, Adam on the net and on the learnable Y_0."""

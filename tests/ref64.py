@@ -78,7 +78,7 @@ def product(a, W, operands="fp32"):
     return _Product.apply(a, W, operands == "bf16")
 
 
-def iteration(prob, cfg, z, noise, weights=None, operands="fp32", dtype=F64):
+def iteration(prob, cfg, z, noise, weights=None, operands="fp32", dtype=F64, want_path=False):
     """One iteration in float64.
 
     operands='bf16': the model of Solver(mlp_dtype='bf16'), hjb_fwd_kernel<D, H, MODE = 1> (csrc/hjb_kernels.h).  The rounding
@@ -100,6 +100,8 @@ def iteration(prob, cfg, z, noise, weights=None, operands="fp32", dtype=F64):
 
     Returns dict(D, loss, blocks=[dW1, db1, dW2, db2, dW3, db3], grad (flat, that order), h1, h2 (K, H) at step N // 2, N);
     D is -(Zsum + g(X_N)) for the relative entropy, as the kernels define it (include/psp.h).
+    want_path: also Z (N, K, d), the net's output Z_n(X_n, t_n) of every step, and X (N + 1, K, d), the states X_0 .. X_N -- detached,
+    in `dtype` (tests/ref64_ul2.py forms the u_L2 log from them).
     """
     assert cfg.time_approx == "inner" and cfg.approx_method == "control" and not cfg.learn_Y_0 and not cfg.random_X_0
     assert prob.kind in KINDS and cfg.loss_method in LOSSES
@@ -124,6 +126,7 @@ def iteration(prob, cfg, z, noise, weights=None, operands="fp32", dtype=F64):
     Y = torch.zeros(K, dtype=dtype)
     Z_sum = torch.zeros(K, dtype=dtype)
     mid = {}
+    Zs, Xs = [], [X.detach().clone()]
     for n in range(N):
         Z, h1, h2 = net(n * dt, X)
         if n == N // 2:
@@ -137,8 +140,13 @@ def iteration(prob, cfg, z, noise, weights=None, operands="fp32", dtype=F64):
         Y = Y + (0.5 * torch.sum(Z ** 2, 1) + fX + torch.sum(Z * c, 1)) * dt + torch.sum(Z * dW, 1) * sq
         if cfg.loss_method == "relative_entropy":
             Z_sum = Z_sum + (0.5 * torch.sum(Z ** 2, 1) + fX) * dt
+        if want_path:
+            Zs.append(Z.detach().clone())
+            Xs.append(X.detach().clone())
     gX = g(X)
     D = Y - gX
+    if want_path:
+        mid.update(Z=torch.stack(Zs), X=torch.stack(Xs))
     if weights is not None:
         loss = (weights.detach().to(dtype).cpu() * D).sum()
     else:
