@@ -8,13 +8,32 @@
 // split twice:
 //   PRODUCERS (waves 0-3, one sample block each per round): G = w sqrt(dt) image, dz2 = (W3^T G)(1 - h2^2),
 //     dz1 = (W2^T dz2)(1 - h1^2) register-chained in T layout (gemm_Txp), all four bias sums (db3, db2, db1, time column), and
-//     the three panels written ONCE, already split, as f16 images (hi | lo) of the PAIR: feature-major, per feature and sample
-//     quad g the four samples of block c0 then of block c1 (ds_write_b16, conflict-free), so that
-//   CONSUMERS (waves 4-7) get an A operand (feature tile x 32 samples of the pair) as ONE 16-byte LDS read per lane, no VALU;
-//     their B operands are the feature-on-lane reads of the path store (h2 / h1 block w, X blocks w and w + 4), split on
+//     the three panels written ONCE, already split, as f16 images (hi | lo) of the PAIR, by sample rows (below), so that
+//   CONSUMERS (waves 4-7) get an A operand (feature tile x 32 samples of the pair) as two transposing LDS reads per part, no
+//     VALU; their B operands are the feature-on-lane reads of the path store (h2 / h1 block w, X blocks w and w + 4), split on
 //     arrival: 32 values per pair and wave.  Wave w owns dW3[:, w], dW2[:, w] and dW1[:, {w, w + 4}].  For dW3 and dW2 the B
 //     operand is a tanh output (|h| <= 1), so 2048 hi_h is exact in f16 and main and correction terms share ONE accumulator
 //     (2048 a.b = hi_a (2048 hi_b) + hi_a lo_b + lo_a hi_b); dW1 keeps two.
+// Exchange image.  A producer lane (j, q) holds sample j and, per 16-feature tile, the four features 4 r + q (r = 0..3) as one
+// f16x4 per part; a consumer lane (i, g) needs tile row i and eight samples.  Per pair, tile and part (hi, lo) the image keeps
+// two regions c = 0, 1 (the blocks of the pair) of 16 sample rows x 16 halves (32-byte rows, 1 KiB per tile and part).  The
+// producer stores its f16x4 with ONE 8-byte store into row j, chunk q -- column 4 q + r of a row is feature 4 r + q -- at byte
+// 512 c + 32 j + 8 (q ^ ((j >> 2) & 3)): the XOR spreads the 16 lanes of a ds_write_b64 group (fixed q) over 16 bank pairs
+// (plain 32 j + 8 q is 4-way).  28 eight-byte stores per block at (100, 64) where the feature-major image took 114 ds_write_b16.
+// The consumer's ds_read_b64_tr_b16 (lds_read_tr4) transposes on the way back: in lane group g, lane 4 q' + p supplies row
+// 4 g + q', physical chunk p ^ g, and lane i receives column i of those four rows; region c0 gives elements 0 - 3, c1 elements
+// 4 - 7: the k order k = 8 g + e above, unchanged.  A 32-lane half covers 256 contiguous bytes: no bank conflict.  The instruction
+// needs EXEC all ones: the consumers' loop is entered by wave-uniform branches only -- no lane-dependent condition around
+// pair_phase.
+// Row permutation: row i of every A tile, hence of every accumulator tile, is feature 4 (i & 3) + (i >> 2) of the tile; the
+// write-out of dW3, dW2 and dW1 rows applies it (columns come from the B operands; bias sums and the time column never pass
+// through the image).  The operand VALUES and their k order are those of the feature-major image, so the gradient is bit for bit
+// the same.
+// Tail tile: when d is no multiple of 16, the last G tile keeps only the RT = ceil((d mod 16) / 4) values of r that hold real
+// features: regions of 16 rows x 4 RT halves, column RT q + r, written with RT half-word stores per part (d = 100: RT = 1, the
+// image is 100 x 32 halves per part as before -- a full seventh tile would not fit the LDS).  Every lane of its transposing
+// reads still supplies an address inside the image (p >= RT points at chunk 0: pad, don't mask); column i < 4 RT is feature
+// 4 (i % RT) + i / RT, the duplicated rows behind are discarded at write-out.
 // Magnitudes: G (and with it dz2, dz1) carries the trajectory weights w_k ~ 1 / K -- far below the f16 normal range, where the
 // hi part would lose its bits.  Each workgroup scales G by a power of two (exact; the gradient is linear in G) and scales its
 // partial gradient back when it is written.  The scale maps  max_k |w_k| * sqrt(dt) * I  into [1, 2): max_k |w_k| from a scan of
@@ -25,7 +44,7 @@
 // range condition there: no later image entry above 3e4 x that maximum).  Below the scale the split keeps its accuracy down to
 // 2^-36 of the maximum (hi subnormal, lo still exact), i.e. weights 1e5 x smaller than the largest lose nothing that matters.
 // One barrier per round swaps the two exchange buffers, as in hjb_bwd2_kernel.  LDS: W3^T and W2^T split tables, 2 x 2 pairs
-// of (2 D + 4 * 16 HB) * 64 bytes (d = 100, H = 64: 158 736 bytes).  Reference lines: solver.py:468-472 (what carries a
+// of (2 GH + 4 * 512 HB) halves, GH = 512 (D / 16) + 128 RT = 32 D when D is a multiple of four (d = 100, H = 64: 158 736 bytes).  Reference lines: solver.py:468-472 (what carries a
 // gradient), function_space.py:190-195 (the net).
 #pragma once
 #include "hjb_kernels.h"
@@ -37,10 +56,13 @@ struct GeoX {
     using G = Geo<D, H>;
     static constexpr int DB = G::DB, HB = G::HB, KSD = G::KSD, KSH = G::KSH;
     static constexpr int T3 = 0, T2 = T3 + SplitGeo<KSD, DB>::floats(HB), EX = T2 + SplitGeo<KSH, HB>::floats(HB);   // floats
-    // exchange area of one PAIR of sample blocks, in halves: G (hi, lo: D features), dz2, dz1 (hi, lo: 16 HB features); element
-    // (feature f, block c of the pair, sample s) at f * 32 + ((s >> 2) ^ ((f >> 2) & 3)) * 8 + c * 4 + (s & 3)  (chunk swizzle: see the producers)
-    static constexpr int hG = 0, hGl = hG + D * 32, hZ2 = hGl + D * 32, hZ2l = hZ2 + HB * 512, hZ1 = hZ2l + HB * 512,
+    // exchange area of one PAIR of sample blocks, in halves: G (hi, lo), dz2, dz1 (hi, lo: HB tiles each).  A full 16-feature tile
+    // is 512 halves (two regions of 16 sample rows x 16 halves, one per block of the pair); G has DF full tiles and, when D is no
+    // multiple of 16, a compact tail tile of two regions of 16 rows x 4 RT halves (header comment)
+    static constexpr int DF = D / 16, RT = cdiv(D % 16, 4), GH = DF * 512 + RT * 128;
+    static constexpr int hG = 0, hGl = hG + GH, hZ2 = hGl + GH, hZ2l = hZ2 + HB * 512, hZ1 = hZ2l + HB * 512,
                          hZ1l = hZ1 + HB * 512, PAIRH = hZ1l + HB * 512;
+    static_assert(DF + (RT > 0) == DB && GH % 4 == 0, "G tiles; every part starts on an 8-byte boundary");
     static constexpr int RS = 16 * DB + 3 * 16 * HB;                   // bias-sum slots per producer (G | dz2 | dz1 | t dz1)
     static constexpr int NX = cdiv(DB, 4);                             // X blocks per consumer wave
     static constexpr int NT = DB + 2 * HB;                             // A tiles per pair: G, dz2, dz1
@@ -56,6 +78,35 @@ __device__ __forceinline__ void split_panel(const f32x4 (&v)[NB], f16x4 (&hi)[NB
         if ((NB & 1) && b == NB - 1) split4c(v[b], hi[b], lo[b]);       // (a trailing odd block may feed 16x16x16 MFMAs directly: hjb_kernels.h split4c)
         else split4(v[b], hi[b], lo[b]);
     }
+}
+
+// A split panel of NB tiles into the exchange image of the producer's block (header comment): `full` / `tail` = the lane's offsets
+// (halves) inside a full tile and inside the compact tail tile, which is the last of the NB when RT > 0
+template <int NB, int RT>
+__device__ __forceinline__ void put_panel(_Float16* hi, _Float16* lo, int full, int tail, const f16x4 (&vh)[NB], const f16x4 (&vl)[NB]) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        if (RT > 0 && b == NB - 1) {
+#pragma unroll
+            for (int r = 0; r < RT; ++r) {
+                hi[b * 512 + tail + r] = vh[b][r];
+                lo[b * 512 + tail + r] = vl[b][r];
+            }
+        } else {
+            *reinterpret_cast<f16x4*>(hi + b * 512 + full) = vh[b];
+            *reinterpret_cast<f16x4*>(lo + b * 512 + full) = vl[b];
+        }
+    }
+}
+
+// ds_read_b64_tr_b16: per 16-lane group, lane 4 q' + p supplies the address of row q', columns 4 p .. 4 p + 3 of a block of 4 rows
+// x 16 halves; lane i receives column i, row q' in element q'.  Needs EXEC all ones (the gather crosses lanes) and 8-byte-aligned
+// addresses.  The compiler's builtin, not inline asm (hjb_kernels.h at split4: hazards the compiler does not see in asm).
+__device__ __forceinline__ f16x4 lds_read_tr4(const _Float16* p) {
+    typedef __fp16 h16x4 __attribute__((vector_size(8)));
+    typedef __attribute__((address_space(3))) h16x4* lds_h16x4_ptr;
+    const h16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_h16x4_ptr)p);
+    return __builtin_bit_cast(f16x4, v);
 }
 
 // gemm_Tx with the input panel already split (hi / lo per 16-feature block; `last` = the fp32 value in[INB-1][0] for the exact
@@ -254,6 +305,11 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
             __syncthreads();                              // (A) pairs with the consumers' barrier behind their first loads
             g_scale(gs, ginv);
         }
+        // lane (j, q) of block c = sub & 1 of the pair, in halves.  Full tile: row j of region c, 8-byte chunk q -- XOR-swizzled
+        // with the row quad, so that the 16 lanes of one ds_write_b64 group (fixed q; bank = (byte / 4) mod 32, 32-byte rows) fall
+        // on 16 different bank pairs instead of four.  Compact tail tile: row j of 4 RT halves, column RT q + r.
+        const int pfull = (sub & 1) * 256 + j * 16 + ((q ^ ((j >> 2) & 3)) * 4);
+        const int ptail = ((sub & 1) * 64 + j * 4 + q) * X::RT;
 #ifdef PSP_STAMPS
         unsigned long long stamps[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -267,12 +323,8 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
                 const int k = t16 * 16 + j;
                 const bool kvalid = bvalid && k < a.K_local;
                 const float tn = (float)(blk / a.ntile16) * dt;
-                // exchange image: element (feature f, block c of the pair, sample s) at f * 32 + (((s >> 2) ^ ((f >> 2) & 3)) * 8
-                // + c * 4 + (s & 3): the 16-byte chunk of a sample quad is XOR-swizzled with the feature row, so that the consumers'
-                // ds_read_b128 of rows i, i + 4, i + 8, i + 12 (64 bytes apart: the same 16 banks) fall on four different bank
-                // groups (round 3: the unswizzled reads cost the kernel 27 % LDS bank-conflict cycles).  (f >> 2) & 3 = r here.
-                _Float16* ex0 = exh + ((it & 1) * 2 + (sub >> 1)) * PAIRH + (sub & 1) * 4 + (j & 3);
-                _Float16* exr[4] = {ex0 + (((j >> 2) ^ 0) * 8), ex0 + (((j >> 2) ^ 1) * 8), ex0 + (((j >> 2) ^ 2) * 8), ex0 + (((j >> 2) ^ 3) * 8)};
+                // exchange image of this round's pair (header comment): every tile, part and panel is an immediate offset from here
+                _Float16* exw = exh + ((it & 1) * 2 + (sub >> 1)) * PAIRH;
                 const float* pn = path_of(it + 1);
                 const float* pc = path_of(it);
                 const float dkc = dkn;
@@ -318,16 +370,7 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
                 PSP_ACC(0, tp1, tp0);                 // h2 loads issued, weights -> G
                 f16x4 Gh[DB], Gl[DB];
                 split_panel<DB>(Gt, Gh, Gl);
-#pragma unroll
-                for (int b = 0; b < DB; ++b)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int f = 16 * b + 4 * r + q;
-                        if (16 * b + 16 <= D || f < D) {
-                            exr[r][X::hG + f * 32] = Gh[b][r];
-                            exr[r][X::hGl + f * 32] = Gl[b][r];
-                        }
-                    }
+                put_panel<DB, X::RT>(exw + X::hG, exw + X::hGl, pfull, ptail, Gh, Gl);
                 PSP_STAMP(tp2);
                 PSP_ACC(1, tp2, tp1);                 // G split + image write
                 f32x4 dz2[HB];
@@ -365,13 +408,7 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
                 PSP_ACC(2, tp3, tp2);                 // W3^T G, tanh', h1 loads, next xi (loads or Philox)
                 f16x4 Zh[HB], Zl[HB];
                 split_panel<HB>(dz2, Zh, Zl);
-#pragma unroll
-                for (int m = 0; m < HB; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        exr[r][X::hZ2 + (16 * m + 4 * r + q) * 32] = Zh[m][r];
-                        exr[r][X::hZ2l + (16 * m + 4 * r + q) * 32] = Zl[m][r];
-                    }
+                put_panel<HB, 0>(exw + X::hZ2, exw + X::hZ2l, pfull, 0, Zh, Zl);
                 f32x4 dz1[HB];
 #pragma unroll
                 for (int m = 0; m < HB; ++m) dz1[m] = zero4;
@@ -397,13 +434,7 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
                         for (int r = 0; r < 4; ++r) h1n[m][r] = pn[G::pH1 + (4 * m + r) * 64];
                 }
                 split_panel<HB>(dz1, Zh, Zl);
-#pragma unroll
-                for (int m = 0; m < HB; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        exr[r][X::hZ1 + (16 * m + 4 * r + q) * 32] = Zh[m][r];
-                        exr[r][X::hZ1l + (16 * m + 4 * r + q) * 32] = Zl[m][r];
-                    }
+                put_panel<HB, 0>(exw + X::hZ1, exw + X::hZ1l, pfull, 0, Zh, Zl);
             }
             PSP_STAMP(tp4);
             PSP_ACC(3, tp4, tp0);                     // whole produce phase
@@ -483,14 +514,24 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
     auto pack = [&](const f32x4& u0, const f32x4& u1, f16x8& hi, f16x8& lo) __attribute__((always_inline)) {
         split8(u0, u1, hi, lo);
     };
-    // A operand of tile t of the pair (0 .. DB-1: G, then dz2, then dz1): lane (i, g) = feature 16 tile + i, samples 4 g .. 4 g + 3
-    // of block c0, then of block c1 -- one 16-byte read each for hi and lo
-    const int aofs = opaque_i((lane & 15) * 32 + (((lane >> 4) ^ ((lane >> 2) & 3)) * 8));   // (the producers' chunk swizzle)
+    // A operand of tile t of the pair (0 .. DB-1: G, then dz2, then dz1): lane (i, g) = tile row i, samples 4 g .. 4 g + 3 of block
+    // c0 (elements 0 - 3), then of block c1 (4 - 7) -- two transposing reads each for hi and lo.  In group g, lane 4 q' + p supplies
+    // sample row 4 g + q', chunk p: physical chunk p ^ g under the producers' swizzle, so a 32-lane half covers 256 contiguous
+    // bytes.  Compact tail tile: rows of RT chunks; lanes p >= RT point at chunk 0 (in the image; their columns are discarded).
+    const int aofs = opaque_i((lane >> 2) * 16 + (((lane & 3) ^ (lane >> 4)) * 4));
+    // (the tail's offset is formed where it is used, from an opaque copy of the lane: held across the loop it is one register more
+    // than the (100, 64) consumers have -- a spill)
+    auto atail = [&]() __attribute__((always_inline)) {
+        const int l = opaque_i(lane);
+        return (l >> 2) * 4 * X::RT + ((l & 3) < X::RT ? (l & 3) * 4 : 0);
+    };
     auto a_load = [&](const _Float16* e, int t, f16x8& Ah, f16x8& Al) __attribute__((always_inline)) {
         const int hi = t < DB ? X::hG + t * 512 : (t < DB + HB ? X::hZ2 + (t - DB) * 512 : X::hZ1 + (t - DB - HB) * 512);
         const int lo = t < DB ? X::hGl + t * 512 : (t < DB + HB ? X::hZ2l + (t - DB) * 512 : X::hZ1l + (t - DB - HB) * 512);
-        Ah = *reinterpret_cast<const f16x8*>(e + hi + aofs);
-        Al = *reinterpret_cast<const f16x8*>(e + lo + aofs);
+        const bool tail = X::RT > 0 && t == DB - 1;
+        const int ofs = tail ? atail() : aofs, reg = tail ? 64 * X::RT : 256;   // reg: halves per region (block of the pair)
+        Ah = __builtin_shufflevector(lds_read_tr4(e + hi + ofs), lds_read_tr4(e + hi + reg + ofs), 0, 1, 2, 3, 4, 5, 6, 7);
+        Al = __builtin_shufflevector(lds_read_tr4(e + lo + ofs), lds_read_tr4(e + lo + reg + ofs), 0, 1, 2, 3, 4, 5, 6, 7);
     };
     const f16x8 k2048 = {(_Float16)2048.f, (_Float16)2048.f, (_Float16)2048.f, (_Float16)2048.f,
                          (_Float16)2048.f, (_Float16)2048.f, (_Float16)2048.f, (_Float16)2048.f};
@@ -571,6 +612,8 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
 
     // ---- consumers write their tiles into the workgroup's partial gradient
     float* gp = a.grad_partial + (size_t)blockIdx.x * G::P;
+    // (row i = 4 qq + rr of a tile is feature 4 (i & 3) + (i >> 2) of it -- the column order of the image's rows -- and column
+    // i of the compact tail tile feature 4 (i % RT) + i / RT for i < 4 RT; the rows behind are duplicates)
     const int col = lane & 15, qq = lane >> 4;
     if (sub < HB) {
 #pragma unroll
@@ -578,8 +621,10 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
             const f32x4 v = inv2 * a3[b];
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
-                const int o3 = 16 * b + 4 * qq + rr, i3 = 16 * sub + col;
-                if (o3 < D && i3 < H) { const float gv_ = v[rr]; gp[G::oW3 + o3 * H + i3] = gv_; gchk.see(gv_); }
+                const bool tail = X::RT > 0 && b == DB - 1;
+                const int row = 4 * qq + rr, rt = X::RT > 0 ? X::RT : 1;
+                const int o3 = 16 * b + (tail ? 4 * (row % rt) + row / rt : 4 * rr + qq), i3 = 16 * sub + col;
+                if ((!tail || row < 4 * rt) && o3 < D && i3 < H) { const float gv_ = v[rr]; gp[G::oW3 + o3 * H + i3] = gv_; gchk.see(gv_); }
             }
         }
 #pragma unroll
@@ -587,7 +632,7 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
             const f32x4 v = inv2 * a2[m];
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
-                const int o2 = 16 * m + 4 * qq + rr, i2 = 16 * sub + col;
+                const int o2 = 16 * m + 4 * rr + qq, i2 = 16 * sub + col;
                 if (o2 < H && i2 < H) { const float gv_ = v[rr]; gp[G::oW2 + o2 * H + i2] = gv_; gchk.see(gv_); }
             }
         }
@@ -600,7 +645,7 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
             const int ob = sub + 4 * s;
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
-                const int o1 = 16 * m + 4 * qq + rr, i1 = 16 * ob + col;
+                const int o1 = 16 * m + 4 * rr + qq, i1 = 16 * ob + col;
                 if (ob < DB && o1 < H && i1 < D) { const float gv_ = v[rr]; gp[G::oW1 + o1 * (D + 1) + 1 + i1] = gv_; gchk.see(gv_); }
             }
         }
