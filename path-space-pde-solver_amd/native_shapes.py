@@ -39,14 +39,14 @@ def candidates(d, H, dense=True):
     return out
 
 
-def choose(cfg, d, H):
+def choose(cfg, d, H, query_rc=nat.query_rc):
     """Sets cfg.d / cfg.H to the first candidate instance psp_hjb_query accepts for this configuration (LDS budget,
     family restrictions).  Returns (d_pad, H_pad, family, sizes) or (None, reason)."""
     dense = cfg.drift_kind == nat.DRIFT_DENSE or cfg.sigma_kind == nat.SIGMA_DENSE
     last = 'no compiled kernel instance covers d=%d, H=%d (csrc/instances.def, csrc/wide_instances.def)' % (d, H)
     for D, Hh, fam in candidates(d, H, dense):
         cfg.d, cfg.H = D, Hh
-        rc, sizes, msg = nat.query_rc(cfg)
+        rc, sizes, msg = query_rc(cfg)
         if rc == 0:
             return (D, Hh, fam, sizes), None
         last = msg

@@ -23,6 +23,7 @@ The reference keeps the whole autograd graph instead (SURVEY.md 7 "Activation me
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -60,6 +61,7 @@ def _overridden(problem):
 STATE_BASIS_MAX_COND = 4.0       # fp32 rollouts of the two forms are indistinguishable against fp64 up to cond_2(B) = 4.2 and
                                  # 4x apart at 41
 STATE_BASIS_MAX_D = 112          # the narrow kernel family
+STATE_BASIS_MAX_X0_SPREAD = 100.0
 
 
 def sigma_basis_problem(A, B, alpha, x0):
@@ -89,9 +91,6 @@ def state_basis_decision(solver, spec=None):
             raise ValueError("state_basis='sigma' is not available: " + why)
         return 'x', why
     return 'sigma', 'dense drift and sigma, linear terminal cost, fixed X_0, cond_2(B) <= %g' % STATE_BASIS_MAX_COND
-
-
-STATE_BASIS_MAX_X0_SPREAD = 100.0
 
 
 def _sigma_basis_auto_obstacle(solver):
@@ -184,13 +183,14 @@ def native_eligibility(solver):
     return None
 
 
-def chunk_scratch_sizes(cfg, chunk_Ks):
+def chunk_scratch_sizes(cfg, chunk_Ks, query_rc=nat.query_rc):
     """psp_hjb_sizes that serve EVERY chunk size in `chunk_Ks`: the field-wise maximum of the per-size queries."""
     sizes = None
     for k in sorted(set(int(k) for k in chunk_Ks)):
         probe = nat.HjbConfig.from_buffer_copy(cfg)
         probe.K_local = k
-        q = nat.query(probe)
+        rc, q, _ = query_rc(probe)
+        nat.check(rc, 'psp_hjb_query')
         if sizes is None:
             sizes = q
         else:
@@ -199,129 +199,185 @@ def chunk_scratch_sizes(cfg, chunk_Ks):
     return sizes
 
 
+# ---- decide(): every selection rule of the plan is a line of it (or of state_basis_decision / _decide_chunks, which it calls) ----
+# Host arithmetic and size queries only.  tests/golden/hjb_plan_decisions.json pins its answers; a deliberate change re-records it.
+HjbDecision = namedtuple('HjbDecision', 'state_basis state_basis_reason mlp_dtype matrix_mode range_guard store_path regen_xi '
+                                        'sigma_kind d_pad H_pad family sizes alloc_sizes ul2_mode n_chunks chunk_K chunk_mode')
+QUERY_PTR = 0x1000                        # a non-null pointer for the size queries: no query dereferences one
+DEFAULT_PATH_BUDGET = 180 * 2 ** 30       # five eighths of the 288 GB of HBM3E when the device cannot be asked
+
+
+def launch_bound(K, cus):
+    """At most two 16-trajectory tiles per CU: the iteration over K trajectories is launch-bound (the regime of the small-K
+    forward kernels and of the hipGraph replay), not store- or matrix-pipe-bound.  cus = None (no device): no size rule applies."""
+    return cus is not None and (K + 15) // 16 <= 2 * cus
+
+
+def decide(solver, spec, base_cfg, K_local, world, cus, budget, query_rc=nat.query_rc):
+    """The launch configuration of an HjbNativePlan as an HjbDecision.  base_cfg: the config after plan_common.fill_hjb_base
+    (copied, not written); K_local: this rank's trajectories of the solver's K over `world` ranks; cus / budget: the device's CU
+    count and default path-store budget in bytes, None without a device (no size rule; DEFAULT_PATH_BUDGET).  Allocates
+    nothing on the device.  Raises PlanUnsupported / ValueError for what the plan refuses."""
+    cfg = nat.HjbConfig.from_buffer_copy(base_cfg)
+    H = solver.z_n.native_shape()[1]
+    # the state basis of every launch of the plan (comment above state_basis_decision): under 'sigma' the kernels get identity sigma
+    basis, basis_why = state_basis_decision(solver, spec)
+    if basis == 'sigma' and getattr(solver, 'state_basis', 'auto') == 'auto' and launch_bound(-(-solver.K // world), cus):
+        # (from the even share K / world, not this rank's K_local: every rank of a job picks the same basis)
+        # 'auto' follows the size rule of the split-product mode and of store_path 4 below: a launch-bound iteration pays for the
+        # two transform launches (and for the fused backward + Adam launch of the hipGraph replay, which the gradient transform
+        # splits).  Conservative: at d = 100, K = 8192 an explicit 'sigma' still measures 4 % faster (DESIGN.md section 4).
+        basis, basis_why = 'x', 'launch-bound size (at most two 16-trajectory tiles per CU)'
+    if basis == 'sigma':
+        cfg.sigma_kind = nat.SIGMA_IDENTITY
+    # matrix products: 'fp32' = v_mfma_f32_16x16x4_f32; 'f16x3' = fp32-grade split products on the f16 pipe (three
+    # v_mfma_f32_16x16x32_f16 per fp32 product, csrc/hjb_kernels.h gemm_Tx, csrc/hjbx_kernels.h -- same parity bounds);
+    # 'auto' (the default) = 'f16x3' where those kernels exist, fit the LDS and the tile-per-wave forward would run anyway
+    # (not launch-bound: the small-K forward kernels are fp32 only), else 'fp32'
+    want = getattr(solver, 'mlp_dtype', 'auto')
+    cfg.mlp_dtype = {'auto': nat.MLP_FP32, 'fp32': nat.MLP_FP32, 'bf16': nat.MLP_BF16_FWD, 'f16x3': nat.MLP_F16X3}[want]
+    # kernel instance: the exact (d, H) if compiled, else the cheapest larger one (zero padding, native_shapes.py)
+    chosen, why = shapes.choose(cfg, solver.d, H, query_rc)
+    if chosen is None:
+        raise PlanUnsupported(why)
+    if basis == 'sigma' and chosen[2] != 1:          # (only the narrow family has the one-product forward)
+        basis, basis_why = 'x', 'the configuration runs on the wide kernel family'
+        cfg.sigma_kind = spec['sigma'][0]
+        chosen, why = shapes.choose(cfg, solver.d, H, query_rc)
+        if chosen is None:
+            raise PlanUnsupported(why)
+    d_pad, H_pad, family, sizes = chosen
+    # (the wide family has no small-K kernels: its split-product forward serves every K)
+    if want == 'auto' and cus is not None and (family == 2 or not launch_bound(K_local, cus)):
+        cfg.mlp_dtype = nat.MLP_F16X3
+        rc, sizes_x3, _ = query_rc(cfg)
+        if rc == 0:
+            sizes = sizes_x3
+        else:
+            cfg.mlp_dtype = nat.MLP_FP32
+    # range guard of the split-product mode (include/psp.h: psp_hjb_config.range_flag): the reference is fp32 end to end
+    # (solver.py:39-40); an f16x3 operand beyond 65504 turns D_k into NaN, the forward call raises a device flag and the
+    # fp32-MFMA kernels -- enqueued behind the split ones, predicated on that flag -- redo the iteration.  No host sync.
+    guard = False
+    if cfg.mlp_dtype == nat.MLP_F16X3 and getattr(solver, 'range_guard', True):
+        cfg.range_flag = QUERY_PTR                   # (the plan puts its flag tensor here; every later query sees a guarded config)
+        guard = query_rc(cfg)[0] == 0
+        if not guard:                                # (the fp32-MFMA tables of this instance do not fit the LDS: unguarded)
+            cfg.range_flag = None
+    # store_path 4 (include/psp.h): the forward keeps X_n, h1, h2 only and the backward producers regenerate xi from the
+    # Philox counters -- where the stored image would be xi itself (detached adaptive process, on-device noise), in the
+    # narrow kernel family, on the eager iteration (psp_hjb_rollout_bwd_step of the hipGraph replay takes no seed; that
+    # regime is launch-bound, not store-bound).  Solver(path_noise='store') keeps xi.
+    regen = False
+    if (getattr(solver, 'path_noise', 'auto') != 'store' and cfg.store_path == 1 and cfg.noise_mode == nat.NOISE_PHILOX
+            and cfg.adaptive and family == 1 and getattr(solver, 'use_graph', 'auto') is not True
+            and cus is not None and not launch_bound(K_local, cus)):
+        cfg.store_path = 4
+        regen = query_rc(cfg)[0] == 0
+        if not regen:
+            cfg.store_path = 1
+    simple = base_cfg.store_path == 1 and base_cfg.loss_kind != nat.LOSS_WEIGHTS      # log-variance / moment, detached
+    n_chunks, chunk_K, chunk_mode, alloc = _decide_chunks(solver, cfg, sizes, K_local, simple, cus, budget, query_rc)
+    # the u_L2 log: tabulated per coordinate on a grid (the double wells) or linear in x (LQGC), both formed from the path store
+    # (_ul2_rows_from_path), or x-independent (LLGC), accumulated inside the kernels from a table u*(t_n)
+    ul2_mode, sizes = None, alloc
+    if solver.u_l2_error_flag:
+        x_free = getattr(solver.problem, 'u_true_x_independent', False) is True
+        ul2_mode = 'ul2_tab' if pc.u_tables(solver.problem) is not None else ('ul2' if x_free else 'ul2_gain')
+        if ul2_mode == 'ul2' and n_chunks <= 1:
+            # the sizes above were queried without u_ref: with it the library launches no cooperative forward (wide family,
+            # f16x3, Philox noise), so fwd_workgroups / fwd_coop_tiles described a launch that never happens.  The buffers
+            # sized from that query (alloc_sizes) stay: the tile-per-wave forward needs no more workgroups than the cooperative one
+            cfg.u_ref = cfg.u_l2_out = QUERY_PTR
+            rc, sizes, _ = query_rc(cfg)
+            nat.check(rc, 'psp_hjb_query')
+            assert sizes.fwd_partial_bytes <= alloc.fwd_partial_bytes and sizes.path_bytes == alloc.path_bytes
+    matrix_mode = {nat.MLP_FP32: 'fp32', nat.MLP_BF16_FWD: 'bf16', nat.MLP_F16X3: 'f16x3'}[cfg.mlp_dtype]
+    return HjbDecision(basis, basis_why, int(cfg.mlp_dtype), matrix_mode, guard, int(cfg.store_path), regen, int(cfg.sigma_kind),
+                       d_pad, H_pad, family, sizes, alloc, ul2_mode, n_chunks, chunk_K, chunk_mode)
+
+
+def _decide_chunks(solver, cfg, sizes, K_local, simple, cus, budget, query_rc):
+    """(n_chunks, chunk_K, chunk_mode, sizes): the number of trajectory chunks from the path-store budget, the trajectories per
+    chunk (a multiple of 16), 'two_gradient' | 'recompute' (None: one chunk) and the scratch sizes that serve every chunk.
+    The default budget is five eighths of the device's TOTAL memory -- a function of the device alone, so the same seed and
+    configuration give the same chunk count (hence the same summation order of the partial sums and gradients) from run to run
+    and on every rank of a job, whatever else occupies the card; a store that then does not fit fails in its allocation and says
+    so.  (A third measured worse: d = 500, K = 131 072, N = 200, a 120 GB store, paid its backward twice: 179 ms against 139 ms.)"""
+    budget = getattr(solver, 'path_budget_bytes', None) or budget or DEFAULT_PATH_BUDGET
+    forced = getattr(solver, 'path_chunks', None)
+    n = int(forced) if forced else max(1, -(-int(sizes.path_bytes) // int(budget)))
+    n = min(n, max(1, (K_local + 15) // 16))
+    if n <= 1:
+        return 1, K_local, None, sizes
+    if solver.u_l2_error_flag and getattr(solver.problem, 'u_true_x_independent', False) is not True:
+        raise PlanUnsupported('the u_L2 log of an x-dependent reference control reads the whole path store: not with K-chunking')
+    Kc = -(-K_local // n)
+    Kc = -(-Kc // 16) * 16
+    if not forced:
+        # whole launch waves: a chunk of a multiple of (16 trajectories x 4 tiles per workgroup x CUs) fills every CU the
+        # same number of times (K = 1048576 under a 32 GiB budget: 32 chunks of 32768 instead of 29 ragged ones, +24 %)
+        per_b = max(1, int(sizes.path_bytes) // max(1, K_local))          # store bytes per trajectory
+        fit = int(budget) // per_b
+        quantum = 16 * 4 * (cus if cus is not None else 256)              # (256: size queries on a machine without a GPU)
+        if fit >= quantum:
+            Kc = min(Kc if Kc % quantum == 0 else (fit // quantum) * quantum, (fit // quantum) * quantum)
+    n = -(-K_local // Kc)
+    if n <= 1:
+        return 1, K_local, None, sizes
+    # every DISTINCT chunk size is queried and each scratch buffer takes the maximum: the forward grid (hence the
+    # fp64 partials, and in the wide family the operand tables behind them) is not monotone in K_local -- a ragged
+    # last chunk can pick another forward kernel with a LARGER grid than the full chunks (K_local = 2064 in two
+    # chunks: 65 tiles -> feature-split kernel, grid 65; 64 tiles -> quad kernel, grid 256)
+    sizes = chunk_scratch_sizes(cfg, {Kc, K_local - (n - 1) * Kc}, query_rc)
+    mode = getattr(solver, 'chunk_mode', 'auto')
+    if mode == 'auto':
+        mode = 'two_gradient' if simple else 'recompute'
+    if mode == 'two_gradient' and not simple:
+        raise PlanUnsupported("chunk_mode='two_gradient' needs a detached log-variance or moment run")
+    if mode not in ('two_gradient', 'recompute'):
+        raise ValueError("chunk_mode must be 'auto', 'two_gradient' or 'recompute'")
+    return n, Kc, mode, sizes
+
+
 class HjbNativePlan:
     def __init__(self, solver, noise='reference'):
         reason = native_eligibility(solver)
         if reason is not None:
             raise PlanUnsupported(reason)
-        self.s = solver
-        self.lib = nat.load()
-        self.noise = noise
-        dev = solver.device
-        self.dev = dev
-        K = solver.K
-        self.dist, self.rank, self.world, lo, hi = pc.local_shard(K)
+        self.s, self.lib, self.noise, self.dev = solver, nat.load(), noise, solver.device
+        dev = self.dev
+        self.dist, self.rank, self.world, lo, hi = pc.local_shard(solver.K)
         self.K_local, self.k_offset = hi - lo, lo
-        net = solver.z_n
-        self.net = net
+        self.net = net = solver.z_n
         self.H = net.native_shape()[1]
         self.flat = pc.rehome_params(net.flat_layout(), dev)       # (psp.h layout)
         self.P = self.flat.numel()
         spec = solver.problem.native_spec()
         self._keep = []   # device tensors referenced by raw pointer from the config
-
-        def dev_f32(t):
-            if t is None:
-                return None
-            t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
-            self._keep.append(t)
-            return t
-
         cfg = nat.HjbConfig()
         self.generic_loss, self.relent, self.attached = pc.fill_hjb_base(cfg, solver, spec, noise, self.K_local, self.k_offset)
-        # the state basis of every launch of this plan (module comment above): under 'sigma' the kernels get identity sigma
-        self.state_basis, self.state_basis_reason = state_basis_decision(solver, spec)
-        if (self.state_basis == 'sigma' and getattr(solver, 'state_basis', 'auto') == 'auto' and torch.device(dev).type == 'cuda'
-                and (-(-K // self.world) + 15) // 16 <= 2 * torch.cuda.get_device_properties(dev).multi_processor_count):
-            # (from the even share K / world, not this rank's K_local: every rank of a job picks the same basis)
-            # 'auto' follows the size rule of the split-product mode and of store_path 4 below: at most two tiles per CU the
-            # iteration is launch-bound and pays for the two transform launches (and for the fused backward + Adam launch of the
-            # hipGraph replay, which the gradient transform splits).  Conservative: at d = 100, K = 8192 an explicit 'sigma' still
-            # measures 4 % faster.  state_basis='sigma' overrides.
-            self.state_basis, self.state_basis_reason = 'x', 'launch-bound size (at most two 16-trajectory tiles per CU)'
-        if self.state_basis == 'sigma':
-            cfg.sigma_kind = nat.SIGMA_IDENTITY
-        # matrix products: 'fp32' = v_mfma_f32_16x16x4_f32; 'f16x3' = fp32-grade split products on the f16 pipe (three
-        # v_mfma_f32_16x16x32_f16 per fp32 product, csrc/hjb_kernels.h gemm_Tx, csrc/hjbx_kernels.h -- same parity bounds);
-        # 'auto' (the default) = 'f16x3' where those kernels exist, fit the LDS and the tile-per-wave forward would run anyway
-        # (more than two 16-trajectory tiles per CU: the small-K forward kernels are fp32 only), else 'fp32'
-        want = getattr(solver, 'mlp_dtype', 'auto')
-        cfg.mlp_dtype = {'auto': nat.MLP_FP32, 'fp32': nat.MLP_FP32, 'bf16': nat.MLP_BF16_FWD, 'f16x3': nat.MLP_F16X3}[want]
-        # kernel instance: the exact (d, H) if compiled, else the cheapest larger one (zero padding, native_shapes.py)
-        chosen, why = shapes.choose(cfg, solver.d, self.H)
-        if chosen is None:
-            raise PlanUnsupported(why)
-        if self.state_basis == 'sigma' and chosen[2] != 1:          # (only the narrow family has the one-product forward)
-            self.state_basis, self.state_basis_reason = 'x', 'the configuration runs on the wide kernel family'
-            cfg.sigma_kind = spec['sigma'][0]
-            chosen, why = shapes.choose(cfg, solver.d, self.H)
-            if chosen is None:
-                raise PlanUnsupported(why)
-        self.d_pad, self.H_pad, self.family, sizes = chosen
-        if want == 'auto' and torch.device(dev).type == 'cuda':
-            cus = torch.cuda.get_device_properties(dev).multi_processor_count
-            # (the wide family has no small-K kernels: its split-product forward serves every K)
-            if self.family == 2 or (self.K_local + 15) // 16 > 2 * cus:
-                cfg.mlp_dtype = nat.MLP_F16X3
-                rc, sizes_x3, _ = nat.query_rc(cfg)
-                if rc == 0:
-                    sizes = sizes_x3
-                else:
-                    cfg.mlp_dtype = nat.MLP_FP32
-        self.matrix_mode = {nat.MLP_FP32: 'fp32', nat.MLP_BF16_FWD: 'bf16', nat.MLP_F16X3: 'f16x3'}[cfg.mlp_dtype]
-        # range guard of the split-product mode (include/psp.h: psp_hjb_config.range_flag): the reference is fp32 end to end
-        # (solver.py:39-40); an f16x3 operand beyond 65504 turns D_k into NaN, the forward call raises a device flag and the
-        # fp32-MFMA kernels -- enqueued behind the split ones, predicated on that flag -- redo the iteration.  No host sync.
-        self.range_flag = None
-        if cfg.mlp_dtype == nat.MLP_F16X3 and getattr(solver, 'range_guard', True):
-            self.range_flag = torch.zeros(4, dtype=torch.int32, device=dev)
-            cfg.range_flag = nat.ptr(self.range_flag)
-            if nat.query_rc(cfg)[0] != 0:                # (the fp32-MFMA tables of this instance do not fit the LDS: unguarded)
-                cfg.range_flag, self.range_flag = None, None
-        # store_path 4 (include/psp.h): the forward keeps X_n, h1, h2 only and the backward producers regenerate xi from the
-        # Philox counters -- where the stored image would be xi itself (detached adaptive process, on-device noise), in the
-        # narrow kernel family, on the eager iteration (psp_hjb_rollout_bwd_step of the hipGraph replay takes no seed; that
-        # regime -- at most two tiles per CU -- is launch-bound, not store-bound).  Solver(path_noise='store') keeps xi.
-        self.regen_xi = False
-        if (getattr(solver, 'path_noise', 'auto') != 'store' and cfg.store_path == 1 and cfg.noise_mode == nat.NOISE_PHILOX
-                and cfg.adaptive and self.family == 1 and torch.device(dev).type == 'cuda'
-                and getattr(solver, 'use_graph', 'auto') is not True
-                and (self.K_local + 15) // 16 > 2 * torch.cuda.get_device_properties(dev).multi_processor_count):
-            cfg.store_path = 4
-            if nat.query_rc(cfg)[0] == 0:
-                self.regen_xi = True
-            else:
-                cfg.store_path = 1
-        self.pad = shapes.ParamPad(solver.d, self.H, self.d_pad, self.H_pad, dev)
-        pad = self.pad
-        x0_plan = solver.X_0.detach().to(dev)
-        if self.state_basis == 'sigma':
-            # the transformed problem, once per plan in fp64 on the host, rounded to fp32: M = B^-1 A B, alpha' = B^T alpha,
-            # x~0 = B^-1 x0.  EVERY launch of the plan (forward, backward, the range guard's fp32 twins, chunks, ranks, the small-K
-            # forwards) takes its problem from this one config.
-            M, al, x0t = sigma_basis_problem(spec['drift'][1].detach().double().cpu().numpy(), spec['sigma'][1].detach().double().cpu().numpy(),
-                                             spec['term'][1].detach().double().cpu().numpy(), solver.X_0.detach().double().cpu().numpy())
-            self.basis_B = dev_f32(pad.mat(spec['sigma'][1]))                   # for the two per-iteration transforms
-            cfg.drift = nat.ptr(dev_f32(pad.mat(torch.from_numpy(M).to(torch.float32))))
-            cfg.sigma = None
-            cfg.term = nat.ptr(dev_f32(pad.vec(torch.from_numpy(al).to(torch.float32))))
-            x0_plan = torch.from_numpy(x0t).to(torch.float32).to(dev)
-        else:
-            self.basis_B = None
-            cfg.drift = nat.ptr(dev_f32(pad.drift_or_sigma(spec['drift'][1]))) if spec['drift'][1] is not None else None
-            cfg.sigma = nat.ptr(dev_f32(pad.drift_or_sigma(spec['sigma'][1]))) if spec['sigma'][1] is not None else None
-            cfg.term = nat.ptr(dev_f32(pad.vec(spec['term'][1])))
-        cfg.runcost = nat.ptr(dev_f32(pad.vec(spec['runcost'][1]))) if spec['runcost'][1] is not None else None
+        # the one look at the device: its CU count (the size rules) and five eighths of its memory (the path-store budget)
+        props = torch.cuda.get_device_properties(dev) if torch.device(dev).type == 'cuda' else None
+        self.cus = props.multi_processor_count if props is not None else None
+        budget = max(1 << 28, int(props.total_memory) * 5 // 8) if props is not None else None
+        self.decision = dec = decide(solver, spec, cfg, self.K_local, self.world, self.cus, budget)
+        self.state_basis, self.state_basis_reason, self.matrix_mode = dec.state_basis, dec.state_basis_reason, dec.matrix_mode
+        self.d_pad, self.H_pad, self.family, self.regen_xi = dec.d_pad, dec.H_pad, dec.family, dec.regen_xi
+        self.n_chunks, self.chunk_K, self.chunk_mode, self.sizes = dec.n_chunks, dec.chunk_K, dec.chunk_mode, dec.sizes
+        cfg.d, cfg.H, cfg.sigma_kind, cfg.mlp_dtype, cfg.store_path = dec.d_pad, dec.H_pad, dec.sigma_kind, dec.mlp_dtype, dec.store_path
+        self.range_flag = torch.zeros(4, dtype=torch.int32, device=dev) if dec.range_guard else None
+        cfg.range_flag = nat.ptr(self.range_flag)
         solver.state_basis_plan = (self.state_basis, self.state_basis_reason)
-        self.cfg = cfg
-        assert sizes.n_params == pad.Pp, (sizes.n_params, pad.Pp)
-        self._setup_chunks(solver, cfg, sizes)
         solver.path_plan = dict(n_chunks=self.n_chunks, chunk_mode=self.chunk_mode, chunk_K=self.chunk_K)   # what the budget chose
-        sizes = self.sizes
+        self.cfg = cfg
+        self.pad = pad = shapes.ParamPad(solver.d, self.H, self.d_pad, self.H_pad, dev)
+        assert dec.alloc_sizes.n_params == pad.Pp, (dec.alloc_sizes.n_params, pad.Pp)
+        x0_plan = self._upload_problem(spec)
         # kernel-side (padded) parameter and gradient vectors; identical to the real ones when nothing is padded
         # (sigma basis: always a buffer of its own -- it holds W1x B where self.flat, the nn.Parameter views, holds W1x)
+        sizes = dec.alloc_sizes
         self.flat_k = self.flat if (pad.identity and self.state_basis != 'sigma') else pad.new_padded_params()
-        self.grad_k = None
         self.path = torch.empty(sizes.path_bytes // 4, dtype=torch.float32, device=dev)
         self.fwd_partial = torch.empty(max(1, self.n_chunks) * (sizes.fwd_partial_bytes // 8), dtype=torch.float64, device=dev)
         self.grad_partial = torch.empty(sizes.grad_partial_bytes // 4, dtype=torch.float32, device=dev)
@@ -333,43 +389,8 @@ class HjbNativePlan:
         self.grad_k = self.grad if pad.identity else torch.empty(pad.Pp, dtype=torch.float32, device=dev)
         self.m = torch.zeros(self.P, dtype=torch.float32, device=dev)
         self.v = torch.zeros(self.P, dtype=torch.float32, device=dev)
-        self.x0_vec = dev_f32(pad.vec(x0_plan))
-        self.ul2 = None
-        self.ul2_gain = None
-        self.ul2_tab = None
-        if solver.u_l2_error_flag and pc.u_tables(solver.problem) is not None:
-            # u*(x, t) tabulated per coordinate on a grid (the double wells: problems.py u_true_tables, reference problems.py:
-            # 277-281, 399-404, 471-476): the tables go to the device once, the log is formed from the path store (_ul2_from_path)
-            tb = pc.u_tables(solver.problem)
-            self.ul2_tab = dict(tables=[torch.tensor(np.asarray(t), dtype=torch.float32, device=dev) for t in tb['tables']],
-                                group=torch.tensor(tb['group_of_dim'], dtype=torch.long, device=dev),
-                                xb=float(tb['xb']), dx=float(tb['dx']),
-                                n_ref=[int(np.ceil(n * solver.delta_t_np / tb['delta_t'])) for n in range(solver.N)])
-            self.XN_k = torch.empty(self.K_local, self.d_pad, dtype=torch.float32, device=dev)
-        elif solver.u_l2_error_flag and getattr(solver.problem, 'u_true_x_independent', False) is not True:
-            # u*(x, t_n) = M_n x (LQGC, problems.py:169-171): M_n once per plan by probing u_true with the unit vectors; the log
-            # is then formed from the X_n and h2 images of the path store after the forward kernel (_ul2_from_path)
-            eye = torch.eye(solver.d)
-            gains = [torch.tensor(np.asarray(solver.problem.u_true(eye, n * solver.delta_t_np))).reshape(solver.d, solver.d).float()
-                     for n in range(solver.N)]                                       # u_true returns (d, K): column i = M e_i
-            self.ul2_gain = torch.stack(gains).to(dev)                             # (N, d, d) = M_n
-            self.XN_k = torch.empty(self.K_local, self.d_pad, dtype=torch.float32, device=dev)
-        elif solver.u_l2_error_flag:
-            # u_L2 log (solver.py:491-494) for an x-independent reference control: u*(t_n) once per plan instead of
-            # problem.u_true(X.cpu(), t_n) every step of every iteration; the kernels accumulate |-Z_n - u*(t_n)|^2 dt
-            probe = torch.zeros(1, solver.d)
-            rows = [torch.tensor(np.asarray(solver.problem.u_true(probe, n * solver.delta_t_np))).reshape(solver.d, -1)[:, 0].float()
-                    for n in range(solver.N)]
-            table = pad.last_dim(torch.stack(rows).to(dev)).reshape(-1)
-            self.uref = dev_f32(torch.cat([table, torch.zeros(16, device=dev)]))   # 16 floats of slack: the kernels read whole blocks
-            self.ul2 = torch.zeros(self.K_local, dtype=torch.float32, device=dev)
-            cfg.u_ref, cfg.u_l2_out = nat.ptr(self.uref), nat.ptr(self.ul2)
-            if self.n_chunks <= 1:
-                # the sizes above were queried before u_ref was set: with it the library launches no cooperative forward (wide
-                # family, f16x3, Philox noise), so fwd_workgroups / fwd_coop_tiles described a launch that never happens.  The
-                # buffers sized from that query stay: the tile-per-wave forward needs no more workgroups than the cooperative one
-                self.sizes = nat.query(cfg)
-                assert self.sizes.fwd_partial_bytes <= sizes.fwd_partial_bytes and self.sizes.path_bytes == sizes.path_bytes
+        self.x0_vec = self._dev_f32(pad.vec(x0_plan))
+        self._alloc_ul2(dec.ul2_mode)
         if self.attached or self.relent:
             self.cfg_w = nat.HjbConfig.from_buffer_copy(cfg)          # backward with explicit trajectory weights
             self.cfg_w.loss_kind = nat.LOSS_WEIGHTS
@@ -380,23 +401,80 @@ class HjbNativePlan:
                 self.nu = torch.zeros(self.K_local, dtype=torch.float32, device=dev)
                 self.wT = torch.zeros(self.K_local, dtype=torch.float32, device=dev)
         self.step = sharding.adam_state_import(net.flat_layout(), self.m, self.v, getattr(net, 'optim', None))
-        self.events = None   # bench.py: list collecting HIP-event pairs around the two rollout kernels
-        self.pass1_events = None
+        self.events = self.pass1_events = None   # bench.py: lists collecting HIP-event pairs around the rollout kernels
         if self.n_chunks > 1:
             self._alloc_chunks()
         # hipGraph replay of the launch-bound small-K iteration (module docstring of include/psp.h: psp_iter_state)
-        self._graph = None
-        self._graph_key = None
-        self._graph_iter = -1
-        self._eager_done = 0
-        self.graph_active = False
+        self._graph, self._graph_key, self._graph_iter, self._eager_done, self.graph_active = None, None, -1, 0, False
         # learnable Y_0 (solver.py:372-374): a one-element Adam beside the net's; it continues the state y_0.optim carries
         self.learn_y0 = bool(solver.learn_Y_0)
         if self.learn_y0:
             self.y0 = pc.Y0Adam(solver.y_0, dev, import_state=True)
             self.y0_param = self.y0.param
 
-    # ------------------------------------------------------------------------------------
+    def _dev_f32(self, t):
+        """`t` as a contiguous fp32 tensor on the plan's device, kept alive for the raw pointers that reference it (None: None)."""
+        if t is None:
+            return None
+        t = t.detach().to(device=self.dev, dtype=torch.float32).contiguous()
+        self._keep.append(t)
+        return t
+
+    def _upload_problem(self, spec):
+        """The problem's coefficients on the device, padded, behind the pointers of self.cfg; returns the plan's X_0."""
+        solver, cfg, pad, dev_f32 = self.s, self.cfg, self.pad, self._dev_f32
+        x0_plan = solver.X_0.detach().to(self.dev)
+        if self.state_basis == 'sigma':
+            # the transformed problem, once per plan in fp64 on the host, rounded to fp32: M = B^-1 A B, alpha' = B^T alpha,
+            # x~0 = B^-1 x0.  EVERY launch of the plan (forward, backward, the range guard's fp32 twins, chunks, ranks, the small-K
+            # forwards) takes its problem from this one config.
+            M, al, x0t = sigma_basis_problem(spec['drift'][1].detach().double().cpu().numpy(), spec['sigma'][1].detach().double().cpu().numpy(),
+                                             spec['term'][1].detach().double().cpu().numpy(), solver.X_0.detach().double().cpu().numpy())
+            self.basis_B = dev_f32(pad.mat(spec['sigma'][1]))                   # for the two per-iteration transforms
+            cfg.drift = nat.ptr(dev_f32(pad.mat(torch.from_numpy(M).to(torch.float32))))
+            cfg.sigma = None
+            cfg.term = nat.ptr(dev_f32(pad.vec(torch.from_numpy(al).to(torch.float32))))
+            x0_plan = torch.from_numpy(x0t).to(torch.float32).to(self.dev)
+        else:
+            self.basis_B = None
+            cfg.drift = nat.ptr(dev_f32(pad.drift_or_sigma(spec['drift'][1]))) if spec['drift'][1] is not None else None
+            cfg.sigma = nat.ptr(dev_f32(pad.drift_or_sigma(spec['sigma'][1]))) if spec['sigma'][1] is not None else None
+            cfg.term = nat.ptr(dev_f32(pad.vec(spec['term'][1])))
+        cfg.runcost = nat.ptr(dev_f32(pad.vec(spec['runcost'][1]))) if spec['runcost'][1] is not None else None
+        return x0_plan
+
+    def _alloc_ul2(self, mode):
+        """The u_L2 log's reference control on the device in the form decide() chose: one of self.ul2 / ul2_gain / ul2_tab, or none."""
+        solver, dev = self.s, self.dev
+        self.ul2 = self.ul2_gain = self.ul2_tab = None
+        if mode == 'ul2_tab':
+            # u*(x, t) tabulated per coordinate on a grid (the double wells: problems.py u_true_tables, reference problems.py:
+            # 277-281, 399-404, 471-476): the tables go to the device once, the log is formed from the path store (_ul2_from_path)
+            tb = pc.u_tables(solver.problem)
+            self.ul2_tab = dict(tables=[torch.tensor(np.asarray(t), dtype=torch.float32, device=dev) for t in tb['tables']],
+                                group=torch.tensor(tb['group_of_dim'], dtype=torch.long, device=dev),
+                                xb=float(tb['xb']), dx=float(tb['dx']),
+                                n_ref=[int(np.ceil(n * solver.delta_t_np / tb['delta_t'])) for n in range(solver.N)])
+            self.XN_k = torch.empty(self.K_local, self.d_pad, dtype=torch.float32, device=dev)
+        elif mode == 'ul2_gain':
+            # u*(x, t_n) = M_n x (LQGC, problems.py:169-171): M_n once per plan by probing u_true with the unit vectors; the log
+            # is then formed from the X_n and h2 images of the path store after the forward kernel (_ul2_from_path)
+            eye = torch.eye(solver.d)
+            gains = [torch.tensor(np.asarray(solver.problem.u_true(eye, n * solver.delta_t_np))).reshape(solver.d, solver.d).float()
+                     for n in range(solver.N)]                                       # u_true returns (d, K): column i = M e_i
+            self.ul2_gain = torch.stack(gains).to(dev)                             # (N, d, d) = M_n
+            self.XN_k = torch.empty(self.K_local, self.d_pad, dtype=torch.float32, device=dev)
+        elif mode == 'ul2':
+            # u_L2 log (solver.py:491-494) for an x-independent reference control: u*(t_n) once per plan instead of
+            # problem.u_true(X.cpu(), t_n) every step of every iteration; the kernels accumulate |-Z_n - u*(t_n)|^2 dt
+            probe = torch.zeros(1, solver.d)
+            rows = [torch.tensor(np.asarray(solver.problem.u_true(probe, n * solver.delta_t_np))).reshape(solver.d, -1)[:, 0].float()
+                    for n in range(solver.N)]
+            table = self.pad.last_dim(torch.stack(rows).to(dev)).reshape(-1)
+            self.uref = self._dev_f32(torch.cat([table, torch.zeros(16, device=dev)]))   # 16 floats of slack: the kernels read whole blocks
+            self.ul2 = torch.zeros(self.K_local, dtype=torch.float32, device=dev)
+            self.cfg.u_ref, self.cfg.u_l2_out = nat.ptr(self.uref), nat.ptr(self.ul2)
+
     def _stream(self):
         return nat.stream_ptr(self.dev)
 
@@ -416,68 +494,33 @@ class HjbNativePlan:
             nat.check(self.lib.psp_hjb_basis_grad(nat.ptr(self.grad_k), nat.ptr(self.basis_B), self.d_pad, self.H_pad, st),
                       'psp_hjb_basis_grad')
 
+    # ---- the three rollout launches: the eager, chunked and captured iterations and forward_only all launch through these ----
+    def _seed(self):
+        return int(self.s.seed) & 0xFFFFFFFFFFFFFFFF
+
+    def _launch_fwd(self, cfg, flat_k, x0, xi, l, *, off=0, store=True, XN=None, Yn=None, partial_off=0, st):
+        """psp_hjb_rollout_fwd on the trajectories of `cfg`, which start `off` into this rank's.  x0: (K_local, d_pad) start points
+        or None (the plan's fixed X_0); xi: the launch's own noise or None (Philox); XN, Yn: this rank's whole output tensors, or
+        None for an output the caller does not take; partial_off: this launch's slice of the fp64 partials."""
+        x0_p, x0_stride = (nat.ptr(x0, off * self.d_pad), self.d_pad) if x0 is not None else (nat.ptr(self.x0_vec), 0)
+        nat.check(self.lib.psp_hjb_rollout_fwd(C.byref(cfg), nat.ptr(flat_k), x0_p, x0_stride,
+                                               nat.ptr(self.y0_param) if self.learn_y0 else None, nat.ptr(xi), self._seed(), l,
+                                               nat.ptr(self.path) if store else None, nat.ptr(self.D, off), nat.ptr(XN, off * self.d_pad),
+                                               nat.ptr(Yn, off), nat.ptr(self.fwd_partial, partial_off), st), 'psp_hjb_rollout_fwd')
+
+    def _launch_sweep(self, cfg, flat_k, wT, st, off=0, partial_off=0):
+        """psp_hjb_adjoint_sweep (attached forward process) over the store the forward of `cfg` left; wT: terminal weights or None."""
+        nat.check(self.lib.psp_hjb_adjoint_sweep(C.byref(cfg), nat.ptr(flat_k), nat.ptr(self.path), nat.ptr(self.XN_k, off * self.d_pad),
+                                                 nat.ptr(self.mu, off), nat.ptr(self.nu, off) if self.relent else None, nat.ptr(wT, off),
+                                                 nat.ptr(self.fwd_partial, partial_off), st), 'psp_hjb_adjoint_sweep')
+
+    def _launch_bwd(self, cfg, flat_k, xi, l, w, w_off, out, out_off, st):
+        """psp_hjb_rollout_bwd over the store: D or weights from w[w_off:], the kernel-layout gradient into out[out_off:]."""
+        nat.check(self.lib.psp_hjb_rollout_bwd(C.byref(cfg), nat.ptr(flat_k), nat.ptr(xi), self._seed(), l, nat.ptr(self.path),
+                                               nat.ptr(w, w_off), nat.ptr(self.sums), nat.ptr(self.grad_partial), nat.ptr(out, out_off),
+                                               st), 'psp_hjb_rollout_bwd')
+
     # ---- K-chunking (module docstring) -------------------------------------------------------------------------------
-    DEFAULT_PATH_BUDGET = 180 * 2 ** 30         # five eighths of the 288 GB of HBM3E when the device cannot be asked
-
-    def _default_budget(self):
-        """Five eighths of THIS device's TOTAL memory (round 4; a third before: config 5's per-GPU share -- d = 500, K = 131 072,
-        N = 200, a 120 GB store -- then ran in chunks and paid its backward twice, 179 ms, where it fits the card whole, 139 ms;
-        everything else the plan allocates is a few hundred MB) -- a function of the device alone, so the same seed and configuration give the
-        same chunk count (hence the same summation order of the partial sums and gradients) from run to run and on every rank of
-        a job, whatever else occupies the card at the moment.  (Round 3 also capped it at 80 % of the memory free right now;
-        a store that then does not fit fails in its allocation and says so -- Solver(path_budget_bytes=...) / path_chunks pick
-        another split.)  The chosen n_chunks / chunk_mode are recorded on the solver (solver.path_plan) and in bench.py's line."""
-        try:
-            return max(1 << 28, int(torch.cuda.get_device_properties(self.dev).total_memory) * 5 // 8)
-        except Exception:                                # size queries on a machine without a GPU
-            return self.DEFAULT_PATH_BUDGET
-
-    def _setup_chunks(self, solver, cfg, sizes):
-        """Decides the number of trajectory chunks from the path-store budget and re-queries the scratch sizes for one
-        chunk.  Sets self.n_chunks, self.chunk_K (trajectories per chunk, a multiple of 16), self.sizes, self.chunk_mode."""
-        budget = getattr(solver, 'path_budget_bytes', None) or self._default_budget()
-        forced = getattr(solver, 'path_chunks', None)
-        n = int(forced) if forced else max(1, -(-int(sizes.path_bytes) // int(budget)))
-        n = min(n, max(1, (self.K_local + 15) // 16))
-        self.n_chunks, self.chunk_K, self.sizes = 1, self.K_local, sizes
-        self.chunk_mode = None
-        if n <= 1:
-            return
-        if solver.u_l2_error_flag and getattr(solver.problem, 'u_true_x_independent', False) is not True:
-            raise PlanUnsupported('the u_L2 log of an x-dependent reference control reads the whole path store: not with K-chunking')
-        Kc = -(-self.K_local // n)
-        Kc = -(-Kc // 16) * 16
-        if not forced:
-            # whole launch waves: a chunk of a multiple of (16 trajectories x 4 tiles per workgroup x CUs) fills every CU the
-            # same number of times (K = 1048576 under a 32 GiB budget: 32 chunks of 32768 instead of 29 ragged ones, +24 %)
-            per_b = max(1, int(sizes.path_bytes) // max(1, self.K_local))          # store bytes per trajectory
-            fit = int(budget) // per_b
-            try:
-                cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
-            except Exception:                                                    # (size queries on a machine without a GPU)
-                cus = 256
-            quantum = 16 * 4 * cus
-            if fit >= quantum:
-                Kc = min(Kc if Kc % quantum == 0 else (fit // quantum) * quantum, (fit // quantum) * quantum)
-        n = -(-self.K_local // Kc)
-        if n <= 1:
-            return
-        # every DISTINCT chunk size is queried and each scratch buffer takes the maximum: the forward grid (hence the
-        # fp64 partials, and in the wide family the operand tables behind them) is not monotone in K_local -- a ragged
-        # last chunk can pick another forward kernel with a LARGER grid than the full chunks (K_local = 2064 in two
-        # chunks: 65 tiles -> feature-split kernel, grid 65; 64 tiles -> quad kernel, grid 256)
-        self.sizes = chunk_scratch_sizes(cfg, {Kc, self.K_local - (n - 1) * Kc})
-        self.n_chunks, self.chunk_K = n, Kc
-        mode = getattr(solver, 'chunk_mode', 'auto')
-        simple = (not self.attached and not self.relent and not self.generic_loss)      # log-variance / moment, detached
-        if mode == 'auto':
-            mode = 'two_gradient' if simple else 'recompute'
-        if mode == 'two_gradient' and not simple:
-            raise PlanUnsupported("chunk_mode='two_gradient' needs a detached log-variance or moment run")
-        if mode not in ('two_gradient', 'recompute'):
-            raise ValueError("chunk_mode must be 'auto', 'two_gradient' or 'recompute'")
-        self.chunk_mode = mode
-
     def _alloc_chunks(self):
         """Per-chunk configs (K_local, k_offset and the per-trajectory output pointers moved to the chunk) and the small
         per-chunk result rows; the big scratch buffers (path store, partial gradients) are shared by all chunks."""
@@ -505,36 +548,25 @@ class HjbNativePlan:
         self.fp_stride = self.sizes.fwd_partial_bytes // 8
 
     def _iteration_chunked(self, l, loss_out, ul2_out=None):
-        s, lib, cfg = self.s, self.lib, self.cfg
-        st = self._stream()
-        seed = int(s.seed) & 0xFFFFFFFFFFFFFFFF
+        s, lib, cfg, st = self.s, self.lib, self.cfg, self._stream()
         xi_full, x0 = pc.draw_noise(s, l, self.noise, self.k_offset, self.K_local, self.d_pad, self.dev)
         flat_k = self._kernel_params(st)
-        y0_ptr = nat.ptr(self.y0_param) if self.learn_y0 else None
         K = float(s.K)
 
         def fwd(i, c, store):
             off, k = self.chunks[i][0], self.chunks[i][1]
             xi = xi_full[:, off:off + k].contiguous() if xi_full is not None else None
-            x0_p, x0_stride = (nat.ptr(x0, off * self.d_pad), self.d_pad) if x0 is not None else (nat.ptr(self.x0_vec), 0)
-            nat.check(lib.psp_hjb_rollout_fwd(C.byref(c), nat.ptr(flat_k), x0_p, x0_stride, y0_ptr, nat.ptr(xi), seed, l,
-                                              nat.ptr(self.path) if store else None, nat.ptr(self.D, off),
-                                              nat.ptr(self.XN_k, off * self.d_pad) if (self.attached and store) else None,
-                                              nat.ptr(self.Yn, off) if self.Yn is not None else None,
-                                              nat.ptr(self.fwd_partial, i * self.fp_stride), st), 'psp_hjb_rollout_fwd')
+            self._launch_fwd(c, flat_k, x0, xi, l, off=off, store=store, XN=self.XN_k if (self.attached and store) else None,
+                             Yn=self.Yn, partial_off=i * self.fp_stride, st=st)
             nat.check(lib.psp_hjb_terminal_reduce(C.byref(c), nat.ptr(self.fwd_partial, i * self.fp_stride),
                                                   nat.ptr(self.sums_c, 2 * i), st), 'psp_hjb_terminal_reduce')
             return xi
 
         def bwd(i, c, w_t, w_off, out_rows, xi):
-            nat.check(lib.psp_hjb_rollout_bwd(C.byref(c), nat.ptr(flat_k), nat.ptr(xi), seed, l, nat.ptr(self.path),
-                                              nat.ptr(w_t, w_off), nat.ptr(self.sums), nat.ptr(self.grad_partial),
-                                              nat.ptr(out_rows, i * self.pad.Pp), st), 'psp_hjb_rollout_bwd')
+            self._launch_bwd(c, flat_k, xi, l, w_t, w_off, out_rows, i * self.pad.Pp, st)
 
         def events():
-            if self.events is None:
-                return None
-            return [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            return [torch.cuda.Event(enable_timing=True) for _ in range(4)] if self.events is not None else None
 
         if self.chunk_mode == 'two_gradient':
             logvar = s.loss_method == 'log-variance'
@@ -608,11 +640,7 @@ class HjbNativePlan:
                     ev[1].record()
                     ev[2].record()
                 if self.attached:
-                    nat.check(lib.psp_hjb_adjoint_sweep(C.byref(c), nat.ptr(flat_k), nat.ptr(self.path),
-                                                        nat.ptr(self.XN_k, off * self.d_pad), nat.ptr(self.mu, off),
-                                                        nat.ptr(self.nu, off) if self.relent else None,
-                                                        nat.ptr(wT, off) if wT is not None else None,
-                                                        nat.ptr(self.fwd_partial, i * self.fp_stride), st), 'psp_hjb_adjoint_sweep')
+                    self._launch_sweep(c, flat_k, wT, st, off=off, partial_off=i * self.fp_stride)
                 bwd(i, cw if use_w else c, w_t, off, self.grad_rows, xi)
                 if ev:
                     ev[3].record()
@@ -632,16 +660,11 @@ class HjbNativePlan:
         trajectory weights are device arithmetic on D and the sums), one rank, no u_L2 log.  Solver(use_graph=True / False) overrides
         the size rule (never the eligibility)."""
         want = getattr(self.s, 'use_graph', 'auto')
-        if want is False:
-            return False
         ok = (self.world == 1 and self.noise == 'philox' and not self.s.random_X_0 and not self.generic_loss
               and self.ul2 is None and self.ul2_gain is None and self.ul2_tab is None and self.n_chunks == 1)
-        if not ok:
+        if want is False or not ok:
             return False
-        if want is True:
-            return True
-        cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
-        return (self.K_local + 15) // 16 <= 2 * cus
+        return want is True or launch_bound(self.K_local, self.cus)
 
     def _graph_state_upload(self, l):
         b = self._graph_hyper
@@ -653,24 +676,17 @@ class HjbNativePlan:
 
     def _graph_body(self, loss_out):
         """The launches of one iteration with every per-iteration quantity read from the device psp_iter_state."""
-        s, lib, cfg = self.s, self.lib, self._gcfg
-        st = self._stream()
+        s, lib, cfg, st = self.s, self.lib, self._gcfg, self._stream()
         state = nat.ptr(self._gstate)
         flat_k = self._kernel_params(st)
-        y0_ptr = nat.ptr(self.y0_param) if self.learn_y0 else None
-        seed = int(s.seed) & 0xFFFFFFFFFFFFFFFF
-        nat.check(lib.psp_hjb_rollout_fwd(C.byref(cfg), nat.ptr(flat_k), nat.ptr(self.x0_vec), 0, y0_ptr, None, seed, 0,
-                                          nat.ptr(self.path), nat.ptr(self.D), nat.ptr(self.XN_k) if self.attached else None,
-                                          None, nat.ptr(self.fwd_partial), st), 'psp_hjb_rollout_fwd')
+        self._launch_fwd(cfg, flat_k, None, None, 0, XN=self.XN_k if self.attached else None, st=st)
         nat.check(lib.psp_hjb_terminal_reduce_loss(C.byref(cfg), nat.ptr(self.fwd_partial), nat.ptr(self.sums),
                                                    nat.ptr(loss_out), state, st), 'psp_hjb_terminal_reduce_loss')
         d_or_w, bcfg = self.D, cfg
         if self.attached:
             # trajectory weights of the adjoint sweep (plain iteration: same call), sweep, backward with unit weights (w_bwd = 1)
             pc.attached_weights(s.loss_method, self.relent, s.K, self._dL_dY(None), None, self.mu, self.nu, None)
-            nat.check(lib.psp_hjb_adjoint_sweep(C.byref(cfg), nat.ptr(flat_k), nat.ptr(self.path), nat.ptr(self.XN_k),
-                                                nat.ptr(self.mu), nat.ptr(self.nu) if self.relent else None, None,
-                                                nat.ptr(self.fwd_partial), st), 'psp_hjb_adjoint_sweep')
+            self._launch_sweep(cfg, flat_k, None, st)
             d_or_w, bcfg = self.w_bwd, self._gcfg_w
         elif self.relent:                                # detached relative entropy: weight sqrt(dt) / K on the Z image
             d_or_w, bcfg = self.w_bwd, self._gcfg_w
@@ -683,9 +699,7 @@ class HjbNativePlan:
                                                    nat.ptr(self.m), nat.ptr(self.v), state, nat.ptr(self._gticket),
                                                    lr, b1, b2, eps, st), 'psp_hjb_rollout_bwd_step')
             return
-        nat.check(lib.psp_hjb_rollout_bwd(C.byref(bcfg), nat.ptr(flat_k), None, seed, 0, nat.ptr(self.path),
-                                          nat.ptr(d_or_w), nat.ptr(self.sums), nat.ptr(self.grad_partial),
-                                          nat.ptr(self.grad_k), st), 'psp_hjb_rollout_bwd')
+        self._launch_bwd(bcfg, flat_k, None, 0, d_or_w, 0, self.grad_k, 0, st)
         self._grad_to_x_basis(st)
         self.pad.gather_grad(self.grad_k, self.grad)
         nat.check(lib.psp_adam_step_dev(nat.ptr(self.flat), nat.ptr(self.grad), nat.ptr(self.m), nat.ptr(self.v), self.P,
@@ -816,22 +830,15 @@ class HjbNativePlan:
             return self._iteration_chunked(l, loss_out, ul2_out)
         if self._graph_wanted() and self.events is None:
             return self._iteration_graph(l, loss_out)
-        s, lib, cfg = self.s, self.lib, self.cfg
-        st = self._stream()
-        seed = int(s.seed) & 0xFFFFFFFFFFFFFFFF
+        s, lib, cfg, st = self.s, self.lib, self.cfg, self._stream()
         xi, x0 = pc.draw_noise(s, l, self.noise, self.k_offset, self.K_local, self.d_pad, self.dev)
-        x0_t = x0 if x0 is not None else self.x0_vec
-        x0_stride = self.d_pad if x0 is not None else 0
         flat_k = self._kernel_params(st)
-        y0_ptr = nat.ptr(self.y0_param) if self.learn_y0 else None
         ev = None
         if self.events is not None:      # events go on torch's current stream = the launch stream
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             ev[0].record()
-        nat.check(lib.psp_hjb_rollout_fwd(C.byref(cfg), nat.ptr(flat_k), nat.ptr(x0_t), x0_stride, y0_ptr,
-                                          nat.ptr(xi), seed, l, nat.ptr(self.path), nat.ptr(self.D),
-                                          nat.ptr(self.XN_k) if (self.attached or self.ul2_gain is not None or self.ul2_tab is not None) else None,
-                                          nat.ptr(self.Yn), nat.ptr(self.fwd_partial), st), 'psp_hjb_rollout_fwd')
+        want_XN = self.attached or self.ul2_gain is not None or self.ul2_tab is not None
+        self._launch_fwd(cfg, flat_k, x0, xi, l, XN=self.XN_k if want_XN else None, Yn=self.Yn, st=st)
         if ev is not None:
             ev[1].record()
         d_or_w, bcfg = self.D, cfg
@@ -860,18 +867,14 @@ class HjbNativePlan:
             ev[2].record()
         if self.attached:
             wT = pc.attached_weights(s.loss_method, self.relent, s.K, self._dL_dY(d_or_w), self.Yn, self.mu, self.nu, self.wT)
-            nat.check(lib.psp_hjb_adjoint_sweep(C.byref(cfg), nat.ptr(flat_k), nat.ptr(self.path), nat.ptr(self.XN_k),
-                                                nat.ptr(self.mu), nat.ptr(self.nu) if self.relent else None, nat.ptr(wT),
-                                                nat.ptr(self.fwd_partial), st), 'psp_hjb_adjoint_sweep')
+            self._launch_sweep(cfg, flat_k, wT, st)
             self.w_bwd.fill_(1.0)                       # the sweep left dL/dZ_n / sqrt(dt) in the xi slot
             d_or_w, bcfg = self.w_bwd, self.cfg_w
         elif self.relent:
             # detached relative entropy: dL/dZ_n = Z_n dt / K, and the xi slot holds Z_n  ->  weight sqrt(dt) / K
             self.w_bwd.fill_(float(cfg.sqrt_dt) / float(s.K))
             d_or_w, bcfg = self.w_bwd, self.cfg_w
-        nat.check(lib.psp_hjb_rollout_bwd(C.byref(bcfg), nat.ptr(flat_k), nat.ptr(xi), seed, l, nat.ptr(self.path),
-                                          nat.ptr(d_or_w), nat.ptr(self.sums), nat.ptr(self.grad_partial),
-                                          nat.ptr(self.grad_k), st), 'psp_hjb_rollout_bwd')
+        self._launch_bwd(bcfg, flat_k, xi, l, d_or_w, 0, self.grad_k, 0, st)
         if ev is not None:
             ev[3].record()
             self.events.append(ev)
@@ -882,19 +885,15 @@ class HjbNativePlan:
 
     def forward_only(self, l, want_XN=False):
         """Forward rollout without the path store; returns (D, X_N or None)."""
-        s, lib = self.s, self.lib
+        s = self.s
         cfg = nat.HjbConfig.from_buffer_copy(self.cfg)
         cfg.store_path = 0
         xi = x0 = None
         if self.noise == 'reference':                    # (under 'philox' this helper starts every trajectory at the fixed X_0)
             xi, x0 = pc.draw_noise(s, l, self.noise, self.k_offset, self.K_local, self.d_pad, self.dev)
-        x0_t = x0 if x0 is not None else self.x0_vec
         XN = torch.empty(self.K_local, self.d_pad, dtype=torch.float32, device=self.dev) if want_XN else None
         flat_k = self._kernel_params(self._stream())
-        nat.check(lib.psp_hjb_rollout_fwd(C.byref(cfg), nat.ptr(flat_k), nat.ptr(x0_t), self.d_pad if x0 is not None else 0,
-                                          nat.ptr(self.y0_param) if self.learn_y0 else None, nat.ptr(xi),
-                                          int(s.seed), l, None, nat.ptr(self.D), nat.ptr(XN), None,
-                                          nat.ptr(self.fwd_partial), self._stream()), 'psp_hjb_rollout_fwd')
+        self._launch_fwd(cfg, flat_k, x0, xi, l, store=False, XN=XN, st=self._stream())
         if XN is not None and self.state_basis == 'sigma':
             XN = XN @ self.basis_B.t()                   # the kernel left X~_N; X_N = B X~_N (an evaluation helper, not the hot path)
         return self.D, (XN[:, :s.d] if XN is not None else None)

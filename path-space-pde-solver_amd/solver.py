@@ -363,60 +363,45 @@ class Solver:
             self._native_plan = None
             return None
 
+    def _native_plan_of(self, cls):
+        """The solver's plan of class `cls`: the cached one if it was built for the present configuration, else a new one."""
+        self.plan_name, self.plan_reason = 'native', None
+        plan = getattr(self, '_native_plan', None)
+        if plan is None or not isinstance(plan, cls) or getattr(plan, 'key', None) != self._plan_key():
+            plan = cls(self, noise=self.noise)
+            plan.key = self._plan_key()
+            self._native_plan = plan
+        if cls is HjbNativePlan:
+            self.plan_reason = 'state basis %s: %s' % (plan.state_basis, plan.state_basis_reason)
+        return plan
+
     def _choose_plan_checked(self):
         if self.backend == 'torch':
             self.plan_name, self.plan_reason = 'torch', "backend='torch' requested"
             return None
-        if self.approx_method == 'value_function':
-            # value-net ansatz (solver.py:93-97, 334-339, 438-440): the GeneralSolver kernels with per-sample weights
-            reason = value_eligibility(self)
-            if reason is None:
-                self.plan_name, self.plan_reason = 'native', None
-                plan = getattr(self, '_native_plan', None)
-                if plan is None or not isinstance(plan, ValueNativePlan) or plan.key != self._plan_key():
-                    plan = ValueNativePlan(self, noise=self.noise)
-                    plan.key = self._plan_key()
-                    self._native_plan = plan
-                return plan
-            if self.backend == 'native':
-                raise PlanUnsupported('native plan unavailable: ' + reason)
-            if self.device.type == 'cuda':
-                warnings.warn('path-space solver: running the composite torch plan (%s)' % reason)
-            self.plan_name, self.plan_reason = 'torch', reason
-            return None
-        reason = native_eligibility(self)      # raises NativeLibraryError if the .so is missing on a GPU run
-        if reason is None:
-            self.plan_name, self.plan_reason = 'native', None
-            plan = getattr(self, '_native_plan', None)
-            if plan is None or not isinstance(plan, HjbNativePlan) or getattr(plan, 'key', None) != self._plan_key():
-                plan = HjbNativePlan(self, noise=self.noise)     # owns the flat parameters and Adam moments
-                plan.key = self._plan_key()
-                self._native_plan = plan
-            self.plan_reason = 'state basis %s: %s' % (plan.state_basis, plan.state_basis_reason)
-            return plan
-        dense_reason = dense_eligibility(self)  # DenseNet controls: time_approx='outer', DenseNet swapped into z_n
-        if dense_reason is None:
-            self.plan_name, self.plan_reason = 'native', None
-            plan = getattr(self, '_native_plan', None)
-            if plan is None or not isinstance(plan, DenseNativePlan) or getattr(plan, 'key', None) != self._plan_key():
-                plan = DenseNativePlan(self, noise=self.noise)
-                plan.key = self._plan_key()
-                self._native_plan = plan
-            return plan
         z = getattr(self, 'z_n', None)                  # (approx_method='value_function' has y_n instead)
-        if control_class(z) is not None:                # a list of Linear / Affine / Constant modules, one per time step
-            affine_reason = affine_eligibility(self)
-            if affine_reason is None:
-                self.plan_name, self.plan_reason = 'native', None
-                plan = getattr(self, '_native_plan', None)
-                if plan is None or not isinstance(plan, AffineNativePlan) or getattr(plan, 'key', None) != self._plan_key():
-                    plan = AffineNativePlan(self, noise=self.noise)
-                    plan.key = self._plan_key()
-                    self._native_plan = plan
-                return plan
-            reason = affine_reason
-        elif isinstance(z, list) or isinstance(z, DenseNet):
-            reason = dense_reason
+        value = self.approx_method == 'value_function'
+        # the native plans in the order they are asked: (eligibility, plan class, is this configuration asked about it at all)
+        chain = (
+            # value-net ansatz (solver.py:93-97, 334-339, 438-440): the GeneralSolver kernels with per-sample weights
+            (value_eligibility, ValueNativePlan, value),
+            # (raises NativeLibraryError if the .so is missing on a GPU run; the plan owns the flat parameters and Adam moments)
+            (native_eligibility, HjbNativePlan, not value),
+            # DenseNet controls: time_approx='outer', DenseNet swapped into z_n
+            (dense_eligibility, DenseNativePlan, not value),
+            # a list of Linear / Affine / Constant modules, one per time step
+            (affine_eligibility, AffineNativePlan, not value and control_class(z) is not None),
+        )
+        reason = None
+        for eligibility, cls, asked in chain:
+            if not asked:
+                continue
+            why = eligibility(self)
+            if why is None:
+                return self._native_plan_of(cls)
+            # the reason reported is that of the last class asked, except that the DenseNet plan speaks only for a list or a DenseNet
+            if cls is not DenseNativePlan or isinstance(z, list) or isinstance(z, DenseNet):
+                reason = why
         if self.backend == 'native':
             raise PlanUnsupported('native plan unavailable: ' + reason)
         if self.device.type == 'cuda':
