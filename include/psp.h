@@ -67,16 +67,32 @@ extern "C" {
                          *        psp_pinn_config.n_dirs (the former `reserved`) / dirs (appended) -- second-order directions of a
                          *        dense sigma in the PINN kernels (PSP_GENL_SIGMA_DENSE, PSP_GH_EXPBALL_SIN_FULL);
                          *        PSP_GH_AFFINE_EXP / _SINE_SOURCE / _SINNORM2 (the exit-time and box problems),
-                         *        psp_gen_config.dwell_form (the former `reserved`), PSP_VTRUE_LOGQ / _SINPROD / _SINSUM / _SINR2 */
+                         *        psp_gen_config.dwell_form (the former `reserved`), PSP_VTRUE_LOGQ / _SINPROD / _SINSUM / _SINR2;
+                         *        PSP_DRIFT_WELL_DIAG / _RADIAL_WELL, PSP_TERM_QUAD_LINEAR / _RADIAL_QUAD and psp_hjb_config.coord_split
+                         *        (the former `reserved`) -- psp_dnet_* only */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
+/* DenseNet-control family only (psp_dnet_*; every other entry point answers -1 to them, as to any unknown kind):
+ *   PSP_DRIFT_WELL_DIAG    per-coordinate kinds (DoubleWell_OU, problems.py:865-866): coordinates i < coord_split are wells,
+ *                          b_i = -((4 kappa_i) x_i) (x_i^2 - 1) with kappa_i = drift[i]; the others are linear, b_i = a_i x_i
+ *                          with a_i = drift[i].  b'_i = -4 kappa_i (3 x_i^2 - 1) / a_i.
+ *   PSP_DRIFT_RADIAL_WELL  b = -(phi(r) / r) x,  r = |x|,  phi(r) = 4 kappa (r - r0) ((r - r0)^2 - w),  drift = {kappa, r0, w}
+ *                          (DoubleWell_multidim_2, problems.py:705-709: r0 = 3, w = 1).  The Jacobian is symmetric:
+ *                          b'^T l = -(phi / r) l - ((phi' - phi / r) / r^2) (x . l) x,  phi' = 4 kappa (3 (r - r0)^2 - w). */
+enum { PSP_DRIFT_WELL_DIAG = 8, PSP_DRIFT_RADIAL_WELL = 9 };
 /* sigma(x) = B constant: problems.py:39-40,157-158,317-318 */
 enum { PSP_SIGMA_IDENTITY = 0, PSP_SIGMA_DENSE = 1, PSP_SIGMA_SCALED_IDENTITY = 2 };
 /* running cost f(x) inside h = -0.5|z|^2 - f(x): problems.py:46 (zero), :161,167 (x'Px, diagonal P) */
 enum { PSP_RUNCOST_ZERO = 0, PSP_RUNCOST_DIAG_QUAD = 1 };
 /* terminal cost g(x): problems.py:49 (alpha.x), :164 (x'Rx, diagonal R), :334 (sum eta_j (x_j-1)^2) */
 enum { PSP_TERM_LINEAR = 0, PSP_TERM_DIAG_QUAD = 1, PSP_TERM_SHIFTED_QUAD = 2 };
+/* DenseNet-control family only (psp_dnet_*), like the two drift kinds above:
+ *   PSP_TERM_QUAD_LINEAR   g = sum_{i < coord_split} term[i] (x_i - 1)^2 + sum_{i >= coord_split} term[i] x_i
+ *                          (DoubleWell_OU, problems.py:880-881)
+ *   PSP_TERM_RADIAL_QUAD   g = alpha (r - rho)^2,  r = |x|,  term = {alpha, rho};  grad g = 2 alpha (r - rho) x / r
+ *                          (DoubleWell_multidim_2, problems.py:720-721: rho = 2) */
+enum { PSP_TERM_QUAD_LINEAR = 8, PSP_TERM_RADIAL_QUAD = 9 };
 /* loss: solver.py:167-168 (log-variance), :165-166 (moment) */
 /* PSP_LOSS_WEIGHTS: psp_hjb_rollout_bwd takes w_k = dLoss/dY_k itself in its D argument (losses whose
  * weights are not affine in D: variance :171-172, cross_entropy :183-186) */
@@ -113,11 +129,14 @@ typedef struct psp_hjb_config {
                            *    adaptive = 1 (the image of mode 1 is then xi itself); the block layout is that of mode 1
                            *    with the xi slot unused (same path_bytes).  Not for psp_hjb_rollout_bwd_step.        */
     float sigma_scale;    /* PSP_SIGMA_SCALED_IDENTITY                            */
-    int32_t reserved;
-    const float* drift;   /* DENSE: A (d*d row-major); DIAG: a (d); DOUBLE_WELL: kappa (d) */
+    int32_t coord_split;  /* (the former `reserved`) PSP_DRIFT_WELL_DIAG / PSP_TERM_QUAD_LINEAR: the first coord_split coordinates
+                           * take the first formula of the kind, the others the second; in [0, d_real].  Read by psp_dnet_* only,
+                           * and only with one of these two kinds                   */
+    const float* drift;   /* DENSE: A (d*d row-major); DIAG: a (d); DOUBLE_WELL: kappa (d); WELL_DIAG: kappa_i / a_i (d);
+                           * RADIAL_WELL: {kappa, r0, w} (the buffer still holds d floats) */
     const float* sigma;   /* DENSE: B (d*d row-major); else NULL                  */
     const float* runcost; /* DIAG_QUAD: p (d); else NULL                          */
-    const float* term;    /* alpha / r / eta (d)                                  */
+    const float* term;    /* alpha / r / eta (d); QUAD_LINEAR: eta_i / alpha_i (d); RADIAL_QUAD: {alpha, rho} (d floats) */
     const float* u_ref;   /* optional (N, d) + 16 floats of slack: reference control u*(t_n) of a solution that does not depend on x
                            * (LLGC, problems.py:51-53); enables the u_L2 log of solver.py:491-494 inside the
                            * forward kernels.  NULL: no logging                                             */

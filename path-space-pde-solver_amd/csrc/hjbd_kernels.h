@@ -22,6 +22,19 @@
 
 namespace psp {
 
+// coefficient kinds of this family alone (include/psp.h: PSP_DRIFT_WELL_DIAG / _RADIAL_WELL, PSP_TERM_QUAD_LINEAR / _RADIAL_QUAD)
+enum { DRIFT_WELL_DIAG = 8, DRIFT_RADIAL = 9 };
+enum { TERM_QUADLIN = 8, TERM_RADIAL = 9 };
+
+// Where the kinds are NOT compiled in, because they would cost that kernel scratch (measured against the kernels without them,
+// -Rpass-analysis=kernel-resource-usage): the split-product adjoint sweep of the (128, 64) instance (255 VGPRs, no scratch without
+// them; 52 bytes with), and the forward with the u_L2 log of an x-independent u* (LOGU = 1; (112, 64): 12 -> 16 bytes), which no
+// problem with these kinds asks for.  The radial drift alone is left out of the split-product adjoint sweep of (16, 32): with it that
+// kernel takes 83 instead of 79 VGPRs and drops from 6 to 5 waves per SIMD (80 with the per-coordinate kind, which stays).  The C ABI
+// answers -3 there.
+constexpr bool dnet_adj_x3_has_kinds(int d, int h) { return !(d == 128 && h == 64); }
+constexpr bool dnet_adj_x3_has_radial(int d, int h) { return dnet_adj_x3_has_kinds(d, h) && !(d == 16 && h == 32); }
+
 struct DnetArgs {
     HjbArgs h;                 // problem, noise, outputs (params = the first parameter set; path / tables unused here)
     float* tbl;                // table region (DGeo::table_floats(...) floats)
@@ -41,12 +54,33 @@ struct DnetArgs {
     // reference data of the kind (non-null: the log is on): 0 the (N, D) table u*(t_n); 1 the (N, D, D) gains M_n (u* = M_n x); 2 the
     // (G, ul2_nrows, ul2_ncols) grid tables (u*_i = table_{group[i]}[row[n], cell(x_i)], reference problems.py:254-260)
     int ul2_kind;
+    int coord_split;           // DRIFT_WELL_DIAG / TERM_QUADLIN: coordinates below it take the well / shifted-square formula (sits in
+                               // what was padding: the argument block keeps its size)
     const int* ul2_group;      // kind 2: (D) table of every coordinate
     const int* ul2_row;        // kind 2: (N) table row of step n, ceil(t_n / dt_ref)
     int ul2_ntables, ul2_nrows, ul2_ncols;
     float ul2_xb, ul2_dx, ul2_xhi;   // kind 2: cell = floor((clamp(x, -xb, xhi) + xb) / dx), xhi = fp32(xb - 2 dx)
     long long ul2_gofs;        // kind 1: float offset of the gain tables (N x DGeo::GAINF) in tbl, behind the rollout's tables
 };
+
+// Radial double well (DRIFT_RADIAL): b = -(phi(r) / r) x with phi = 4 kappa s (s^2 - w), s = r - r0, from r^2 = |x|^2 of one
+// trajectory (summed over its four q-lanes by the caller).  Returns phi / r and, for the adjoint sweep, (phi' - phi / r) / r^2 with
+// phi' = 4 kappa (3 s^2 - w):  b'^T l = -(phi / r) l - ((phi' - phi / r) / r^2) (x . l) x.  The lanes of trajectories past K_local
+// start from a zero state (and move with the net's biases from step 1 on): they write images, which the backward kernel multiplies
+// by zero weights, so every value they form must stay finite.  r^2 <= 1e-30 therefore gives 0 for both coefficients -- no 0 / 0 at
+// r = 0, and no overflow of the division by a denormal r^2 (the numerator is O(100 kappa)).
+__device__ __forceinline__ float radial_coef(float r2, float kappa, float r0, float w, float* jac = nullptr) {
+    const float r = sqrtf(r2), s = r - r0;
+    const float phi = (4.0f * kappa * s) * (s * s - w);
+    const bool ok = r2 > 1e-30f;
+    const float c = ok ? phi / r : 0.f;
+    if (jac) *jac = ok ? (4.0f * kappa * (3.0f * s * s - w) - c) / r2 : 0.f;
+    return c;
+}
+// The scalars of these kinds are read from the LDS inside the time loop, not held in SGPRs across it (the kernels run at the SGPR
+// limit: every scalar that lives through the loop is spilled into a VGPR lane).  Staged vectors are in T-layout order [block][q][r]:
+// feature f < 4 sits at float 4 f.  coord_split rides behind the reduction scratch.
+__device__ __forceinline__ float staged(const float* vec, int f) { return opaque(vec)[4 * f]; }
 
 __device__ __forceinline__ f32x4 relu4d(f32x4 v) {
     f32x4 o;
@@ -85,7 +119,10 @@ struct DGeo {
     }
     // LDS (floats): problem vectors, reduction scratch, two images per wave (X_n and the increment panel v)
     static constexpr int vdr = 0, vrun = vdr + DB * 16, vterm = vrun + DB * 16, fRed = vterm + DB * 16,
+                         // coord_split (an int) rides in the reduction scratch, behind the 2 doubles per wave the forward writes there
+                         iSplit = 32,
                          fImg = fRed + 64, IMG = KP * 64, lds_floats = fImg + 4 * 2 * IMG, lds_floats_x3 = fImg + 4 * 2 * IMGX;
+    static_assert(iSplit >= 2 * 2 * 4 && iSplit < 64, "coord_split sits behind the 4 waves' (sum D, sum D^2) doubles, inside the 64 floats");
     // (Round 3 tried the wide family's shared table stream -- gemm_img_x3s: each 8 KiB chunk of a step's table fetched once per
     //  workgroup -- for the two long products of the split forward at d <= 128, with the increment image aliased onto the X image
     //  so that two workgroups and their stages still fit a CU: correct on all 44 dense-control tests, but the stage's operand
@@ -324,6 +361,7 @@ template <int D, int H, bool X3 = false, bool SPEC = false, int LOGU = 0>
 __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const DnetArgs da) {   // d <= 128: two workgroups per CU
     static_assert(!(SPEC && LOGU) && LOGU >= 0 && LOGU <= 3, "the SPEC instance has no u_L2 log");
     constexpr int ukind = LOGU - 1;
+    constexpr bool KINDS = LOGU != 1;                  // (dnet_adj_x3_has_kinds: where the family's own kinds are compiled in)
     PSP_COND_EXIT(da.h);
     using W = DGeo<D, H>;
     constexpr int DB = W::DB, HB = W::HB, KP = W::KP;
@@ -342,7 +380,8 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const
     const int dr = da.d_real;
 
     stage_vec(lds + W::vdr, DB, tid, nthr, [&](int f) {
-        return (f < D && (k_drift == DRIFT_DIAG || k_drift == DRIFT_DWELL)) ? a.drift[f] : 0.f; });
+        return (f < D && (k_drift == DRIFT_DIAG || k_drift == DRIFT_DWELL || (KINDS && k_drift >= DRIFT_WELL_DIAG))) ? a.drift[f] : 0.f; });
+    if (KINDS && tid == 0) reinterpret_cast<int*>(lds + W::fRed)[W::iSplit] = da.coord_split;
     stage_vec(lds + W::vrun, DB, tid, nthr, [&](int f) {
         return (f < D && k_run == RUN_DIAGQ) ? a.runcost[f] : 0.f; });
     stage_vec(lds + W::vterm, DB, tid, nthr, [&](int f) { return f < D ? a.term[f] : 0.f; });
@@ -463,6 +502,32 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const
             } else if (k_drift == DRIFT_DWELL) {
 #pragma unroll
                 for (int b = 0; b < DB; ++b) Xn[b] -= dt * (4.0f * vdr[b * 4] * (X[b] * (X[b] * X[b] - 1.0f)));
+            } else if (KINDS && k_drift == DRIFT_WELL_DIAG) {       // wells below coord_split, linear from it on (whole blocks: wave-uniform tests)
+                const int split = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(opaque(lds + W::fRed))[W::iSplit]);
+#pragma unroll
+                for (int b = 0; b < DB; ++b) {
+                    const f32x4 c = vdr[b * 4];
+                    if (16 * b + 16 <= split) Xn[b] -= dt * (((4.0f * c) * X[b]) * (X[b] * X[b] - 1.0f));
+                    else if (16 * b >= split) Xn[b] += dt * (c * X[b]);
+                    else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {      // (qn, not q: the masks are not hoisted out of the time loop)
+                            const float x = X[b][r];
+                            const float bx = (16 * b + 4 * r + qn < split) ? -(((4.0f * c[r]) * x) * (x * x - 1.0f)) : c[r] * x;
+                            Xn[b][r] += dt * bx;
+                        }
+                    }
+                }
+            } else if (KINDS && k_drift == DRIFT_RADIAL) {          // one reduction per trajectory: r^2 over its four q-lanes (padding is zero)
+                float r2 = 0.f;
+#pragma unroll
+                for (int b = 0; b < DB; ++b)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) r2 = fmaf(X[b][r], X[b][r], r2);
+                const float* pv = lds + W::vdr;
+                const float c = radial_coef(qsum(r2), staged(pv, 0), staged(pv, 1), staged(pv, 2));
+#pragma unroll
+                for (int b = 0; b < DB; ++b) Xn[b] -= dt * (c * X[b]);
             }
             f32x4 h1[HB], h2[HB];
             const bool store_r = store && da.pr1 != nullptr && !store_img;
@@ -676,18 +741,38 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_fwd_kernel(const
 
         // ---- terminal cost g(X_N) and D = Y - g  (problems.py:49,164,334; solver.py:167-168)
         float g = 0.f;
+        if (!KINDS || a.term_kind < TERM_QUADLIN) {
 #pragma unroll
-        for (int b = 0; b < DB; ++b) {
-            const f32x4 tv = vterm[b * 4];
+            for (int b = 0; b < DB; ++b) {
+                const f32x4 tv = vterm[b * 4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float x = X[b][r];
-                if (a.term_kind == TERM_LINEAR) g = fmaf(tv[r], x, g);
-                else if (a.term_kind == TERM_DIAGQ) g = fmaf(tv[r] * x, x, g);
-                else g = fmaf(tv[r] * (x - 1.0f), (x - 1.0f), g);
+                for (int r = 0; r < 4; ++r) {
+                    const float x = X[b][r];
+                    if (a.term_kind == TERM_LINEAR) g = fmaf(tv[r], x, g);
+                    else if (a.term_kind == TERM_DIAGQ) g = fmaf(tv[r] * x, x, g);
+                    else g = fmaf(tv[r] * (x - 1.0f), (x - 1.0f), g);
+                }
+            }
+            g = qsum(g);
+        } else {                                           // the kinds of this family alone, kept apart from the loop above
+            const f32x4* vt = opaque(vecs0) + W::vterm / 4;
+            const int qt = opaque_i(q), split = reinterpret_cast<const int*>(opaque(lds + W::fRed))[W::iSplit];
+#pragma unroll
+            for (int b = 0; b < DB; ++b) {
+                const f32x4 tv = vt[b * 4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float x = X[b][r];
+                    if (a.term_kind == TERM_RADIAL) g = fmaf(x, x, g);           // r^2 (padding is zero)
+                    else g = (16 * b + 4 * r + qt < split) ? fmaf(tv[r] * (x - 1.0f), (x - 1.0f), g) : fmaf(tv[r], x, g);
+                }
+            }
+            g = qsum(g);
+            if (a.term_kind == TERM_RADIAL) {              // g = alpha (r - rho)^2, term = {alpha, rho}
+                const float s = sqrtf(g) - staged(lds + W::vterm, 1);
+                g = staged(lds + W::vterm, 0) * (s * s);
             }
         }
-        g = qsum(g);
         const float Dk = Y - g;
         if (kvalid && q == 0) a.D[k] = Dk;
         if (a.Fint && kvalid && q == 0) a.Fint[k] = Fsum;
@@ -739,6 +824,7 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_adj_kernel(const
     PSP_COND_EXIT(da.h);
     using W = DGeo<D, H>;
     constexpr int DB = W::DB, HB = W::HB, KP = W::KP;
+    constexpr bool KINDS = !X3 || dnet_adj_x3_has_kinds(D, H), RADIAL = !X3 || dnet_adj_x3_has_radial(D, H);
     const HjbArgs& a = da.h;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, nthr = blockDim.x;
@@ -747,7 +833,8 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_adj_kernel(const
     const float* __restrict__ T = da.tbl;
 
     stage_vec(lds + W::vdr, DB, tid, nthr, [&](int f) {
-        return (f < D && (a.drift_kind == DRIFT_DIAG || a.drift_kind == DRIFT_DWELL)) ? a.drift[f] : 0.f; });
+        return (f < D && (a.drift_kind == DRIFT_DIAG || a.drift_kind == DRIFT_DWELL || (KINDS && a.drift_kind >= DRIFT_WELL_DIAG))) ? a.drift[f] : 0.f; });
+    if (KINDS && tid == 0) reinterpret_cast<int*>(lds + W::fRed)[W::iSplit] = da.coord_split;
     stage_vec(lds + W::vrun, DB, tid, nthr, [&](int f) {
         return (f < D && a.runcost_kind == RUN_DIAGQ) ? a.runcost[f] : 0.f; });
     stage_vec(lds + W::vterm, DB, tid, nthr, [&](int f) { return f < D ? a.term[f] : 0.f; });
@@ -789,6 +876,22 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_adj_kernel(const
     f32x4 lam[DB];                                     // lambda_N = wT grad g(X_N)
     {
         const f32x4* vterm = vecs0 + W::vterm / 4;
+        const int split_N = reinterpret_cast<const int*>(lds + W::fRed)[W::iSplit];
+        float grad_r = 0.f;                            // TERM_RADIAL: grad g = (2 alpha (r - rho) / r) x
+        if (KINDS && a.term_kind == TERM_RADIAL) {
+            float r2 = 0.f;
+#pragma unroll
+            for (int b = 0; b < DB; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int f = 16 * b + 4 * r + q;
+                    const float x = (f < D && kvalid) ? a.XN[(size_t)k * D + f] : 0.f;
+                    r2 = fmaf(x, x, r2);
+                }
+            r2 = qsum(r2);
+            const float rr = sqrtf(r2);
+            grad_r = r2 > 0.f ? 2.0f * staged(lds + W::vterm, 0) * (rr - staged(lds + W::vterm, 1)) / rr : 0.f;
+        }
 #pragma unroll
         for (int b = 0; b < DB; ++b) {
             const f32x4 tv = vterm[b * 4];
@@ -799,6 +902,8 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_adj_kernel(const
                 float gg;
                 if (a.term_kind == TERM_LINEAR) gg = tv[r];
                 else if (a.term_kind == TERM_DIAGQ) gg = 2.0f * tv[r] * x;
+                else if (KINDS && a.term_kind == TERM_QUADLIN) gg = (f < split_N) ? 2.0f * tv[r] * (x - 1.0f) : tv[r];
+                else if (KINDS && a.term_kind == TERM_RADIAL) gg = grad_r * x;
                 else gg = 2.0f * tv[r] * (x - 1.0f);
                 lam[b][r] = wT * gg;
             }
@@ -871,6 +976,43 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void hjbd_adj_kernel(const
 #pragma unroll
                 for (int r = 0; r < 4; ++r) x[r] = px[r * 64 + ul];
                 lam[b] -= dt * (4.0f * vdr[b * 4] * ((3.0f * x * x - 1.0f) * lam[b]));
+            }
+        } else if (KINDS && a.drift_kind == DRIFT_WELL_DIAG) {      // b'_i = -4 kappa_i (3 x_i^2 - 1) below coord_split, a_i from it on
+            const int split = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(opaque(lds + W::fRed))[W::iSplit]);
+            const int qn = opaque_i(q);
+#pragma unroll
+            for (int b = 0; b < DB; ++b) {
+                if (16 * b >= split) { lam[b] += dt * (vdr[b * 4] * lam[b]); continue; }
+                gwptr_t px = pbase(n, W::pX + b * 256);
+                const f32x4 c = vdr[b * 4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float x = px[r * 64 + ul], l = lam[b][r];
+                    const float jl = (16 * b + 4 * r + qn < split) ? -(4.0f * c[r] * ((3.0f * x * x - 1.0f) * l)) : c[r] * l;
+                    lam[b][r] = l + dt * jl;
+                }
+            }
+        } else if (RADIAL && a.drift_kind == DRIFT_RADIAL) {        // symmetric Jacobian: two reductions per trajectory, then element-wise
+            float r2 = 0.f, xl = 0.f;
+#pragma unroll
+            for (int b = 0; b < DB; ++b) {
+                gwptr_t px = pbase(n, W::pX + b * 256);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float x = px[r * 64 + ul];
+                    r2 = fmaf(x, x, r2);
+                    xl = fmaf(x, lam[b][r], xl);
+                }
+            }
+            float jac;
+            const float* pv = lds + W::vdr;
+            const float c = radial_coef(qsum(r2), staged(pv, 0), staged(pv, 1), staged(pv, 2), &jac);
+            const float e = jac * qsum(xl);
+#pragma unroll
+            for (int b = 0; b < DB; ++b) {
+                gwptr_t px = pbase(n, W::pX + b * 256);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) lam[b][r] -= dt * (c * lam[b][r] + e * px[r * 64 + ul]);
             }
         }
         // gZ_n: back into the xi slot (as gZ / sqrt(dt)) and into the image (B operand of the transposed products)

@@ -35,6 +35,8 @@ PSP_SAME(psp::DRIFT_ZERO, PSP_DRIFT_ZERO); PSP_SAME(psp::DRIFT_DENSE, PSP_DRIFT_
 PSP_SAME(psp::DRIFT_DWELL, PSP_DRIFT_DOUBLE_WELL); PSP_SAME(psp::DRIFT_EIG_FP, PSP_DRIFT_EIG_FP);
 PSP_SAME(psp::PINN_DRIFT_ZERO, psp::DRIFT_ZERO); PSP_SAME(psp::PINN_DRIFT_DIAG, psp::DRIFT_DIAG);
 PSP_SAME(psp::PINN_DRIFT_DWELL, psp::DRIFT_DWELL);
+PSP_SAME(psp::DRIFT_WELL_DIAG, PSP_DRIFT_WELL_DIAG); PSP_SAME(psp::DRIFT_RADIAL, PSP_DRIFT_RADIAL_WELL);
+PSP_SAME(psp::TERM_QUADLIN, PSP_TERM_QUAD_LINEAR); PSP_SAME(psp::TERM_RADIAL, PSP_TERM_RADIAL_QUAD);
 PSP_SAME(psp::GACT_RELU2, PSP_ACT_RELU2); PSP_SAME(psp::GACT_TANH2, PSP_ACT_TANH2); PSP_SAME(psp::GACT_TANH, PSP_ACT_TANH);
 PSP_SAME(psp::PINN_ACT_RELU2, PSP_ACT_RELU2); PSP_SAME(psp::PINN_ACT_TANH2, PSP_ACT_TANH2); PSP_SAME(psp::PINN_ACT_TANH, PSP_ACT_TANH);
 #undef PSP_SAME
@@ -679,6 +681,14 @@ int psp_is_rollout(const psp_is_config* c, const float* xi, uint64_t seed, uint3
 
 // ---- DenseNet control (hjbd_kernels.h): time_approx='outer' and DenseNet(d+1 -> d) controls ---------------------
 namespace {
+// The DenseNet-control family takes four coefficient kinds more than the families that share coeff_kinds_ok (include/psp.h:
+// PSP_DRIFT_WELL_DIAG / _RADIAL_WELL, PSP_TERM_QUAD_LINEAR / _RADIAL_QUAD): they are mapped onto kinds of the shared check here
+bool dnet_kinds_ok(const psp_hjb_config& b) {
+    psp_hjb_config c = b;
+    if (c.drift_kind == PSP_DRIFT_WELL_DIAG || c.drift_kind == PSP_DRIFT_RADIAL_WELL) c.drift_kind = PSP_DRIFT_DIAG;
+    if (c.term_kind == PSP_TERM_QUAD_LINEAR || c.term_kind == PSP_TERM_RADIAL_QUAD) c.term_kind = PSP_TERM_LINEAR;
+    return coeff_kinds_ok(c);
+}
 struct DnetPlan { psp::DnetInstance inst; int ntile16, grid; long long table_floats, n_params; int slices, bwd_grid, bwd_ok; bool ul2;
                   long long ul2_gofs; };
 int make_dnet_plan(const psp_dnet_config* c, DnetPlan* p) {
@@ -691,8 +701,19 @@ int make_dnet_plan(const psp_dnet_config* c, DnetPlan* p) {
     }
     if (c->d_real <= 0 || c->d_real > b.d || c->H_real <= 0 || c->H_real > b.H)
         return fail(-1, "d_real / H_real must lie in [1, d] / [1, H] of the instance");
-    if (!coeff_kinds_ok(b) || b.store_path < 0 || b.store_path > 3 || b.loss_kind < 0 || b.loss_kind > 3)
+    if (!dnet_kinds_ok(b) || b.store_path < 0 || b.store_path > 3 || b.loss_kind < 0 || b.loss_kind > 3)
         return fail(-1, "config enum out of range");
+    if ((b.drift_kind == PSP_DRIFT_WELL_DIAG || b.term_kind == PSP_TERM_QUAD_LINEAR) && (b.coord_split < 0 || b.coord_split > c->d_real))
+        return fail(-1, "coord_split must lie in [0, d_real] (PSP_DRIFT_WELL_DIAG / PSP_TERM_QUAD_LINEAR)");
+    const bool own_kinds = b.drift_kind >= PSP_DRIFT_WELL_DIAG || b.term_kind >= PSP_TERM_QUAD_LINEAR;
+    if (own_kinds && b.mlp_dtype == PSP_MLP_F16X3 && b.store_path >= 2 && !psp::dnet_adj_x3_has_kinds(b.d, b.H))
+        return fail(-3, "the split-product adjoint sweep of this instance does not carry the per-coordinate / radial kinds (they would "
+                        "cost it scratch registers): use PSP_MLP_FP32");
+    if (b.drift_kind == PSP_DRIFT_RADIAL_WELL && b.mlp_dtype == PSP_MLP_F16X3 && b.store_path >= 2 && !psp::dnet_adj_x3_has_radial(b.d, b.H))
+        return fail(-3, "the split-product adjoint sweep of this instance does not carry the radial drift (it would cost it occupancy): "
+                        "use PSP_MLP_FP32");
+    if (own_kinds && c->ul2_kind == PSP_UL2_TABLE && b.u_ref)
+        return fail(-3, "the u_L2 log of an x-independent u* (PSP_UL2_TABLE) is not built for the per-coordinate / radial kinds");
     if (p->inst.lds_bytes > kMaxLds) return fail(-3, "DenseNet-control kernel images do not fit the 160 KiB LDS");
     if (b.mlp_dtype == PSP_MLP_F16X3 && (!p->inst.launch_fwd_x3 || p->inst.lds_bytes_x3 > kMaxLds))
         return fail(-3, "split-product forward images do not fit the 160 KiB LDS for this (d,H)");
@@ -914,6 +935,7 @@ extern "C" int psp_dnet_adjoint_sweep(const psp_dnet_config* cfg, const float* p
     h.params = params; h.XN = const_cast<float*>(XN); h.adj_mu = mu; h.adj_nu = nu; h.adj_wT = wT;
     a.tbl = tables; a.pimg = images;
     a.d_real = cfg->d_real; a.h_real = cfg->H_real; a.time_input = cfg->time_input ? 1 : 0; a.per_step = cfg->per_step ? 1 : 0;
+    a.coord_split = b->coord_split;
     const bool x3 = b->mlp_dtype == PSP_MLP_F16X3 && p.inst.launch_adj_x3 && p.inst.lds_bytes_x3 <= kMaxLds;
     auto fp32 = [&]() { return p.inst.launch_adj(a, p.grid, (hipStream_t)stream); };
     const hipError_t e = !x3 ? fp32() : launch_either(b->range_flag, h.cond, h.cond_want,           // range guard: both sweeps, predicated
@@ -964,6 +986,7 @@ extern "C" int psp_dnet_rollout_fwd(const psp_dnet_config* cfg, const float* par
     if ((cfg->r1_out == nullptr) != (cfg->r2_out == nullptr)) return fail(-1, "r1_out and r2_out go together");
     a.pr1 = cfg->r1_out; a.pr2 = cfg->r2_out; a.pimg = cfg->images_out;
     a.d_real = cfg->d_real; a.h_real = cfg->H_real; a.time_input = cfg->time_input ? 1 : 0; a.per_step = cfg->per_step ? 1 : 0;
+    a.coord_split = b->coord_split;
     if (p.ul2) {                               // u_L2 log: h.uref = the kind's reference data (non-null selects the LOGU kernels)
         h.uref = cfg->ul2_kind == PSP_UL2_TABLE ? b->u_ref : cfg->ul2_tables;
         h.ul2 = b->u_l2_out;

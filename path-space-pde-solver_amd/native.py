@@ -16,9 +16,22 @@ LIB_PATH = os.environ.get("PSP_LIB_PATH", os.path.join(HERE, "csrc", "libpsp_hip
 
 # enums (include/psp.h)
 DRIFT_ZERO, DRIFT_DENSE, DRIFT_DIAG, DRIFT_DOUBLE_WELL = 0, 1, 2, 3
+DRIFT_WELL_DIAG, DRIFT_RADIAL_WELL = 8, 9             # DenseNet-control family (psp_dnet_*) only
 SIGMA_IDENTITY, SIGMA_DENSE, SIGMA_SCALED_IDENTITY = 0, 1, 2
 RUNCOST_ZERO, RUNCOST_DIAG_QUAD = 0, 1
 TERM_LINEAR, TERM_DIAG_QUAD, TERM_SHIFTED_QUAD = 0, 1, 2
+TERM_QUAD_LINEAR, TERM_RADIAL_QUAD = 8, 9              # DenseNet-control family (psp_dnet_*) only
+DNET_ONLY_KINDS = {'drift': (DRIFT_WELL_DIAG, DRIFT_RADIAL_WELL), 'term': (TERM_QUAD_LINEAR, TERM_RADIAL_QUAD)}
+
+
+def dnet_only_kind(spec):
+    """Why a native_spec() can run on the DenseNet-control kernels alone (csrc/hjbd_kernels.h), or None: the per-coordinate and
+    radial drift / terminal kinds of DoubleWell_OU and DoubleWell_multidim_2 exist in that family only."""
+    for key in ('drift', 'term'):
+        if spec is not None and spec.get(key) is not None and spec[key][0] in DNET_ONLY_KINDS[key]:
+            return ('the %s kind %d of this problem (per-coordinate / radial double well) exists in the DenseNet-control kernel '
+                    'family only (psp_dnet_*: Solver with DenseNet controls)' % (key, spec[key][0]))
+    return None
 LOSS_LOG_VARIANCE, LOSS_MOMENT, LOSS_WEIGHTS, LOSS_REL_ENTROPY = 0, 1, 2, 3
 UL2_TABLE, UL2_LINEAR, UL2_GRID = 0, 1, 2
 ISC_NONE, ISC_TABLE, ISC_LINEAR, ISC_GRID = 0, 1, 2, 3
@@ -54,7 +67,7 @@ class HjbConfig(C.Structure):
         ("drift_kind", C.c_int32), ("sigma_kind", C.c_int32), ("runcost_kind", C.c_int32),
         ("term_kind", C.c_int32), ("adaptive", C.c_int32), ("loss_kind", C.c_int32),
         ("noise_mode", C.c_int32), ("store_path", C.c_int32),
-        ("sigma_scale", C.c_float), ("reserved", C.c_int32),
+        ("sigma_scale", C.c_float), ("coord_split", C.c_int32),
         ("drift", C.c_void_p), ("sigma", C.c_void_p), ("runcost", C.c_void_p), ("term", C.c_void_p),
         ("u_ref", C.c_void_p), ("u_l2_out", C.c_void_p),
         ("mlp_dtype", C.c_int32), ("reserved2", C.c_int32),

@@ -116,6 +116,8 @@ def affine_configuration_reason(s):
     spec_fn = getattr(s.problem, 'native_spec', None)
     if spec_fn is None or spec_fn() is None:
         return 'problem has no native_spec() (coefficients outside the native catalogue)'
+    if nat.dnet_only_kind(spec_fn()) is not None:
+        return nat.dnet_only_kind(spec_fn())
     over = _overridden(s.problem)
     if over is not None:
         return 'problem.%s is not the catalogue implementation native_spec() describes' % over

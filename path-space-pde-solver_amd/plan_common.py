@@ -116,6 +116,7 @@ def fill_hjb_base(cfg, solver, spec, noise, K_local, k_offset):
     cfg.dt, cfg.sqrt_dt = float(s.delta_t.item()), float(s.sq_delta_t.item())
     cfg.drift_kind, cfg.sigma_kind, cfg.sigma_scale = spec['drift'][0], spec['sigma'][0], float(spec['sigma'][2])
     cfg.runcost_kind, cfg.term_kind = spec['runcost'][0], spec['term'][0]
+    cfg.coord_split = int(spec.get('split', 0))           # per-coordinate kinds (DoubleWell_OU): DenseNet-control family only
     cfg.adaptive = 1 if s.adaptive_forward_process else 0
     cfg.loss_kind = {'log-variance': nat.LOSS_LOG_VARIANCE, 'moment': nat.LOSS_MOMENT,
                      'relative_entropy': nat.LOSS_REL_ENTROPY}.get(s.loss_method, nat.LOSS_WEIGHTS)
@@ -125,6 +126,16 @@ def fill_hjb_base(cfg, solver, spec, noise, K_local, k_offset):
     cfg.noise_mode = nat.NOISE_PHILOX if noise == 'philox' else nat.NOISE_SUPPLIED
     cfg.store_path = 3 if relent else (2 if attached else 1)
     return generic_loss, relent, attached
+
+
+def pad_coeff(pad, t):
+    """A coefficient of a ``native_spec()`` for a kernel instance of width pad.dp: matrices and per-coordinate vectors zero padded;
+    a parameter vector shorter than d (the radial kinds' {kappa, r0, w} / {alpha, rho}) likewise -- the kernels stage dp floats."""
+    if t is None or t.dim() == 2 or t.numel() == pad.d:
+        return pad.drift_or_sigma(t)
+    out = torch.zeros(max(pad.dp, t.numel()), dtype=t.dtype, device=t.device)
+    out[:t.numel()] = t
+    return out
 
 
 def draw_noise(solver, l, noise, k_offset, K_local, d_pad, device):
@@ -260,8 +271,23 @@ def ul2_reference(problem, N, dt_np, d_pad, K_global, k_offset):
         group = torch.zeros(d_pad, dtype=torch.int32)
         group[:d] = torch.tensor(tb['group_of_dim'], dtype=torch.int32)
         xb, dx = float(tb['xb']), float(tb['dx'])
-        out.update(tables=torch.from_numpy(np.stack(tabs)), group=group,
-                   row=torch.tensor([int(np.ceil(n * dt_np / tb['delta_t'])) for n in range(N)], dtype=torch.int32),
+        rows = [int(np.ceil(n * dt_np / tb['delta_t'])) for n in range(N)]
+        const = tb.get('constant')
+        if const:
+            # coordinates whose u* does not depend on x (DoubleWell_OU): per-STEP tables with row[n] = n -- the grid tables
+            # gathered at their rows, and one table per distinct u*_i(t_n) that is constant along the cell axis
+            tabs = [t[rows] for t in tabs]
+            vals, index = [], {}
+            for i in sorted(const):
+                v = tuple(float(np.float32(const[i](n * dt_np))) for n in range(N))
+                if v not in index:
+                    index[v] = len(tabs) + len(vals)
+                    vals.append(v)
+                group[i] = index[v]
+            tabs += [np.repeat(np.asarray(v, dtype=np.float32).reshape(N, 1), ncols, 1) for v in vals]
+            rows, nrows = list(range(N)), N
+        out.update(tables=torch.from_numpy(np.ascontiguousarray(np.stack(tabs))), group=group,
+                   row=torch.tensor(rows, dtype=torch.int32),
                    xb=float(np.float32(xb)), dx=float(np.float32(dx)), xhi=float(np.float32(xb - 2 * dx)),
                    nrows=int(nrows), ncols=int(ncols))
     return out

@@ -92,7 +92,8 @@ def dense_eligibility(solver):
             return 'control is not a DenseNet(%d -> %d) with two equal hidden widths' % (d_in, solver.d)
     spec_fn = getattr(solver.problem, 'native_spec', None)
     if spec_fn is None or spec_fn() is None:
-        return 'problem has no native_spec() (coefficients outside the native catalogue)'
+        return getattr(solver.problem, 'native_plan_reason', None) or \
+            'problem has no native_spec() (coefficients outside the native catalogue)'
     over = _overridden(solver.problem)
     if over is not None:
         return 'problem.%s is not the catalogue implementation native_spec() describes' % over
@@ -101,6 +102,9 @@ def dense_eligibility(solver):
     if _instance_for(solver.d, dims0[1]) is None:
         return 'no compiled DenseNet-control instance covers d=%d, H=%d (csrc/dense_instances.def)' % (solver.d, dims0[1])
     if solver.compute_gradient_variance > 0:
+        if nat.dnet_only_kind(spec_fn()) is not None:
+            return ('compute_gradient_variance is not native for the per-coordinate / radial double-well kinds (the squared '
+                    "backward's terminal term is not extended to them)")
         return gradient_variance_unsupported(solver, _instance_for(solver.d, dims0[1]))
     return None
 
@@ -181,10 +185,10 @@ class DenseNativePlan:
         b.d, b.H = self.d_pad, self.H_pad
         self.generic_loss, self.relent, self.attached = pc.fill_hjb_base(b, s, spec, noise, self.K_local, self.k_offset)
         pad = self.pad
-        b.drift = nat.ptr(dev_f32(pad.drift_or_sigma(spec['drift'][1]))) if spec['drift'][1] is not None else None
+        b.drift = nat.ptr(dev_f32(pc.pad_coeff(pad, spec['drift'][1]))) if spec['drift'][1] is not None else None
         b.sigma = nat.ptr(dev_f32(pad.drift_or_sigma(spec['sigma'][1]))) if spec['sigma'][1] is not None else None
         b.runcost = nat.ptr(dev_f32(pad.vec(spec['runcost'][1]))) if spec['runcost'][1] is not None else None
-        b.term = nat.ptr(dev_f32(pad.vec(spec['term'][1])))
+        b.term = nat.ptr(dev_f32(pc.pad_coeff(pad, spec['term'][1])))
         cfg.d_real, cfg.H_real = s.d, self.H
         cfg.time_input, cfg.per_step = (0 if self.outer else 1), (1 if self.outer else 0)
         self.cfg = cfg

@@ -165,7 +165,10 @@ def native_eligibility(solver):
     spec_fn = getattr(solver.problem, 'native_spec', None)
     spec = spec_fn() if spec_fn is not None else None
     if spec is None:
-        return 'problem has no native_spec() (coefficients outside the native catalogue)'
+        return getattr(solver.problem, 'native_plan_reason', None) or \
+            'problem has no native_spec() (coefficients outside the native catalogue)'
+    if nat.dnet_only_kind(spec) is not None:
+        return nat.dnet_only_kind(spec)
     over = _overridden(solver.problem)
     if over is not None:
         return 'problem.%s is not the catalogue implementation native_spec() describes' % over

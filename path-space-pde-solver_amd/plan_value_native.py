@@ -103,6 +103,8 @@ def value_eligibility(solver):
     spec = spec_fn() if spec_fn is not None else None
     if spec is None:
         return 'problem has no native_spec() (coefficients outside the native catalogue)'
+    if nat.dnet_only_kind(spec) is not None:
+        return nat.dnet_only_kind(spec)
     over = _overridden(s.problem)
     if over is not None:
         return 'problem.%s is not the catalogue implementation native_spec() describes' % over

@@ -424,6 +424,192 @@ class DoubleWell_multidim(_DoubleWellBase):
         }
 
 
+class DoubleWell_multidim_3(_DoubleWellBase):
+    """DoubleWell_multidim with one (kappa, eta) for every coordinate (reference problems.py:730-840): one table for all."""
+
+    def __init__(self, name='Double well', d=1, T=1, eta=1, kappa=1, device=None):
+        self.device = _resolve(device)
+        self.name, self.T = name, T
+        self._setup(d, d, 0, eta, kappa)
+
+    def grad_V(self, x):
+        return 4.0 * self.kappa * (x * (x ** 2 - torch.ones(self.d).to(x.device)))
+
+    def h(self, t, x, y, z):
+        return -0.5 * torch.sum(z ** 2, dim=1)
+
+    def f(self, x, t):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def g(self, x):
+        return (self.eta * (torch.sum((x - torch.ones(self.d).to(x.device)) ** 2, 1))).squeeze()
+
+    def v_true(self, x, t):
+        return None                                                      # problems.py:836-837
+
+    def native_spec(self):
+        return {
+            'drift': (_nat.DRIFT_DOUBLE_WELL, self.kappa_.float().contiguous()),
+            'sigma': (_nat.SIGMA_IDENTITY, None, 1.0),
+            'runcost': (_nat.RUNCOST_ZERO, None),
+            'term': (_nat.TERM_SHIFTED_QUAD, self.eta_.float().contiguous()),
+        }
+
+
+class DoubleWell_OU(_DoubleWellBase):
+    """A double well in coordinate 0, Ornstein-Uhlenbeck in the others (reference problems.py:843-959):
+    b = -[(4 kappa x_0)(x_0^2 - 1), a x_1, ..], a = 5;  g = alpha (x_0 - 1)^2 + gamma . x_{1:}.
+    ``compute_reference_solution_x_1()`` tabulates the control of coordinate 0; the others have u*_i = -exp(a (t - T)) gamma_i."""
+
+    def __init__(self, name='Double well', d=1, T=1, alpha=1, kappa=1, device=None):
+        self.device = _resolve(device)
+        self.name, self.d, self.T = name, d, T
+        self.alpha, self.kappa = alpha, kappa
+        self.gamma = torch.ones(d - 1, 1).to(self.device) * 1
+        self.a = 5
+        self.B = torch.eye(d).to(self.device)
+        self.X_0 = torch.tensor([-1.0] + [0.0] * (d - 1)).to(self.device)
+        self.ref_sol_is_defined = False
+
+    def grad_V_1(self, x):
+        return 4.0 * self.kappa * x * (x ** 2 - 1)
+
+    def b(self, x):
+        return -torch.cat([self.grad_V_1(x[:, 0]).unsqueeze(1), self.a * x[:, 1:]], 1)
+
+    def f(self, x, t):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def h(self, t, x, y, z):
+        return -0.5 * torch.sum(z ** 2, dim=1)
+
+    def g_1(self, x_1):
+        return self.alpha * (x_1 - 1) ** 2
+
+    def g(self, x):
+        return self.alpha * (x[:, 0] - 1) ** 2 + torch.mm(x[:, 1:], self.gamma)[:, 0]
+
+    def compute_reference_solution_x_1(self, delta_t=0.005, xb=2.5, nx=1000):
+        grid, self.psi, self.u = self._fd_reference(self.V, self.g_1, delta_t, xb, nx)
+        self._take_grid(grid)
+        self.ref_sol_is_defined = True
+        self.u_true = self._u_true
+
+    def v_true_1(self, x, t):
+        return self._table_read(self.psi, self._value_index(x), t, lambda p: -np.log(p))
+
+    def v_true(self, x, t):
+        return None                                                      # problems.py:954-955
+
+    # (like DoubleWell_multidim: ``u_true`` appears with the table, so a run without it logs no u_L2 instead of raising)
+    def _u_true(self, x, t):
+        u_ou = -np.exp(self.a * (t - self.T)) * np.ones(x[:, 1:].shape) * self.gamma.cpu().numpy().T
+        return np.concatenate([self.u_true_1(x[:, 0], t).T, u_ou], 1).T
+
+    def u_true_tables(self):
+        """The grid table of coordinate 0 plus, for the native plan's device-side u_L2 log, the coordinates whose u* does not depend
+        on x: ``constant`` maps such a coordinate to a function t -> u*_i(t) (plan_common.ul2_reference tabulates it per step as a
+        table that is constant along the cell axis)."""
+        if not self.ref_sol_is_defined:
+            return None
+        gam = self.gamma.cpu().numpy()
+        const = {i: (lambda t, i=i: (-np.exp(self.a * (t - self.T)) * np.ones((1, 1)) * gam[i - 1:i].T)[0, 0]) for i in range(1, self.d)}
+        return dict(tables=[self.u], group_of_dim=[0] * self.d, xb=self.xb, dx=self.dx, delta_t=self.delta_t, constant=const)
+
+    def native_spec(self):
+        d = self.d
+        return {
+            'drift': (_nat.DRIFT_WELL_DIAG, torch.tensor([float(self.kappa)] + [-float(self.a)] * (d - 1))),
+            'sigma': (_nat.SIGMA_IDENTITY, None, 1.0),
+            'runcost': (_nat.RUNCOST_ZERO, None),
+            'term': (_nat.TERM_QUAD_LINEAR, torch.cat([torch.tensor([float(self.alpha)]), self.gamma[:, 0].detach().cpu().float()])),
+            'split': 1,
+        }
+
+
+class DoubleWell_multidim_2:
+    """Radial double well (reference problems.py:691-727): b = -phi(r) x / r with r = |x|, phi = 4 kappa (r - 3)((r - 3)^2 - 1);
+    g = alpha (r - 2)^2; X_0 = 1 / sqrt(d).  Its ``u_true`` returns zeros(x.shape), which the solver's u_L2 line cannot broadcast
+    against the (d, K) control unless K = d -- as in the reference; pass u_l2_error_flag=False."""
+
+    def __init__(self, name='Double well', d=1, T=1, alpha=1, kappa=1, device=None):
+        self.device = _resolve(device)
+        self.name, self.d, self.T = name, d, T
+        self.alpha, self.kappa = alpha, kappa
+        self.B = torch.eye(d).to(self.device)
+        self.X_0 = (torch.ones(d) / torch.sqrt((torch.tensor(d).float()))).to(self.device)
+        self.ref_sol_is_defined = False
+
+    def V(self, x):
+        return self.kappa * ((torch.sum(x ** 2, 1) - 3) ** 2 - 1) ** 2
+
+    def grad_V(self, x):
+        r = torch.sqrt(torch.sum(x ** 2, 1))
+        return 4.0 * self.kappa * (r - 3).unsqueeze(1) * ((r - 3).unsqueeze(1) ** 2 - 1) * x / r.unsqueeze(1)
+
+    def b(self, x):
+        return -self.grad_V(x)
+
+    def sigma(self, x):
+        return self.B
+
+    def h(self, t, x, y, z):
+        return -0.5 * torch.sum(z ** 2, dim=1)
+
+    def f(self, x, t):
+        return torch.zeros(x.shape[0]).to(x.device)
+
+    def g(self, x):
+        return (self.alpha * (torch.sqrt(torch.sum(x ** 2, 1)) - 2) ** 2).squeeze()
+
+    def v_true(self, x, t):
+        return torch.zeros(x.shape)
+
+    def u_true(self, x, t):
+        return torch.zeros(x.shape)
+
+    def native_spec(self):
+        return {
+            'drift': (_nat.DRIFT_RADIAL_WELL, torch.tensor([float(self.kappa), 3.0, 1.0])),
+            'sigma': (_nat.SIGMA_IDENTITY, None, 1.0),
+            'runcost': (_nat.RUNCOST_ZERO, None),
+            'term': (_nat.TERM_RADIAL_QUAD, torch.tensor([float(self.alpha), 2.0])),
+        }
+
+
+class LLGC_general_f(_LinearDriftMixin):
+    """LLGC dynamics with A = 0 and a running cost that is not quadratic in the control (reference problems.py:68-115):
+    h = -(0.8 |z|^1.25 + x exp(T - t) - 0.8 exp(1.25 (T - t)))[:, 0].  No ``native_spec()``: the kernels' h is -|z|^2 / 2, so it
+    runs on the composite plan.  (|z|^1.25 has no gradient at z = 0, where the reference's nets start: its own training is NaN
+    from the second iteration.)"""
+
+    def __init__(self, name='LLGC', d=1, off_diag=0, T=5, seed=42, device=None):
+        self.device = _resolve(device)
+        torch.manual_seed(seed)
+        self.name, self.d, self.T = name, d, T
+        self.A = 0 * (-torch.eye(d) + off_diag * torch.randn(d, d)).to(self.device)
+        self.B = (torch.eye(d) + off_diag * torch.randn(d, d)).to(self.device)
+        self.alpha = -torch.ones(d, 1).to(self.device)
+        self.X_0 = torch.zeros(d).to(self.device)
+        if not np.all(np.linalg.eigvals(self.A.cpu().numpy()) < 0):
+            print('not all EV of A are negative')
+
+    def f(self, x, t):
+        return torch.zeros(x.shape[0])
+
+    def h(self, t, x, y, z):
+        return -(0.8 * ((- z) ** 2) ** (0.625) + x * torch.exp(self.T - t) - 0.8 * torch.exp(1.25 * (self.T - t)))[:, 0]
+
+    def g(self, x):
+        return torch.mm(x, self.alpha)[:, 0]
+
+    def u_true(self, x, t):
+        return -self.sigma(x).cpu().numpy().T.dot(expm(1 * self.B.cpu().numpy().T * (self.T - t)).dot(
+            self.alpha.cpu().numpy()) * np.ones(x.shape).T)
+
+    native_plan_reason = 'LLGC_general_f: h is not -|z|^2 / 2 (the running cost 0.8 |z|^1.25 is outside the native catalogue)'
+
+
 class DoubleWell_multidim_for_general_solver(_DoubleWellBase):
     """Same dynamics posed as a parabolic terminal-value problem for GeneralSolver
     (reference problems.py:479-534): ``f(x)`` is the terminal condition."""

@@ -141,8 +141,10 @@ def _is_dense_native(problem, model, K, delta_t, logw_only=False):
     (inner) or the per-step net (outer); here that index selects the time-feature entry or the parameter set."""
     try:
         from .plan_dense_native import _instance_for, _nets
+        from .plan_common import pad_coeff
     except ImportError:
         from plan_dense_native import _instance_for, _nets
+        from plan_common import pad_coeff
     dev = model.device
     lib = nat.load()
     N = int(np.ceil(problem.T / delta_t))
@@ -166,13 +168,14 @@ def _is_dense_native(problem, model, K, delta_t, logw_only=False):
     b.sqrt_dt = float(torch.tensor(np.sqrt(delta_t), dtype=torch.float32).item())
     b.drift_kind, b.sigma_kind, b.sigma_scale = spec['drift'][0], spec['sigma'][0], float(spec['sigma'][2])
     b.runcost_kind, b.term_kind = spec['runcost'][0], spec['term'][0]
+    b.coord_split = int(spec.get('split', 0))
     b.adaptive, b.loss_kind, b.store_path = 1, nat.LOSS_LOG_VARIANCE, 0
     philox = getattr(model, 'noise', 'reference') == 'philox'
     b.noise_mode = nat.NOISE_PHILOX if philox else nat.NOISE_SUPPLIED
-    b.drift = nat.ptr(dev_f32(pad.drift_or_sigma(spec['drift'][1]))) if spec['drift'][1] is not None else None
+    b.drift = nat.ptr(dev_f32(pad_coeff(pad, spec['drift'][1]))) if spec['drift'][1] is not None else None
     b.sigma = nat.ptr(dev_f32(pad.drift_or_sigma(spec['sigma'][1]))) if spec['sigma'][1] is not None else None
     b.runcost = nat.ptr(dev_f32(pad.vec(spec['runcost'][1]))) if spec['runcost'][1] is not None else None
-    b.term = nat.ptr(dev_f32(pad.vec(spec['term'][1])))
+    b.term = nat.ptr(dev_f32(pad_coeff(pad, spec['term'][1])))
     cfg.d_real, cfg.H_real = model.d, H
     cfg.time_input, cfg.per_step = (0 if outer else 1), (1 if outer else 0)
     sets = [torch.cat([p.detach().reshape(-1) for p in net.W]).to(dev) for net in nets]
@@ -323,6 +326,8 @@ def _coeff_reason(problem, model):
         return "backend='torch' requested"
     if not hasattr(problem, 'native_spec') or problem.native_spec() is None:
         return 'the problem has no catalogue description of its coefficients (native_spec)'
+    if nat.dnet_only_kind(problem.native_spec()) is not None:
+        return nat.dnet_only_kind(problem.native_spec())
     over = coefficients_overridden(problem)
     if over is not None:
         return 'problem.%s is not the catalogue implementation' % over
