@@ -163,7 +163,10 @@ typedef struct psp_hjb_config {
                            * mode.  The reference computes in fp32 (solver.py:39-40); an f16x3 operand beyond 65504 has hi = +inf and
                            * lo = -inf, so main and correction chains of every product it enters meet as inf - inf: every output of
                            * that trajectory is NaN from that step on and D_k is NaN -- an overflow can never go unnoticed, and it
-                           * costs nothing to detect.  With range_flag set,
+                           * costs nothing to detect.  The narrow family's forward (hjb_fwd_kernel) keeps its products on ONE accumulator
+                           * with both operands scaled by a power of two (csrc/hjb_kernels.h, split_tab); there the scaled hi part
+                           * overflows sooner and hi = +inf, lo = -inf meet in that accumulator -- the same NaN.  Its thresholds:
+                           * |weight| (net, dt A, sigma) < 1023 and |state|, |activation| < 2047.  With range_flag set,
                            *   psp_hjb_rollout_fwd / psp_dnet_rollout_fwd run the split kernel, set range_flag[0] = 1 iff a per-workgroup
                            *     partial of (sum D, sum D^2) is non-finite (else 0; range_flag[1] counts the 1s), and enqueue the
                            *     fp32-MFMA kernel of the same launch PREDICATED on range_flag[0] (its workgroups return at once when it

@@ -398,6 +398,38 @@ __device__ __forceinline__ void split_f16(float v, _Float16& hi, _Float16& lo) {
     hi = (_Float16)v;
     lo = (_Float16)((v - (float)hi) * kSplitScale);
 }
+// One-accumulator form (the narrow split forward, hjb_fwd_kernel MODE 2).  The correction chain exists only
+// because the lo parts sit on another scale than the hi parts.  Scale instead the A operand by 2^p and the B operand by 2^q, hi
+// and lo alike, p + q = 11:
+//     A = 2^p a = Ah + Al,   B = 2^q b = Bh + Bl   (hi = f16(.), lo = f16(. - hi): UNSCALED residuals)
+//     Ah Bh + Ah Bl + Al Bh = 2048 a b - Al Bl,    |Al Bl| <= 2^-22 |A B|
+// -- all three terms on one scale, one accumulator, no merge fma and no second register set.  The caller initialises the
+// accumulator with 2048 x its bias and takes the 2048 out where a multiplication already stands (tanh's argument scale, the
+// row sums' per-lane finish, the coefficient of the state update).
+// A lo part is a residual of magnitude <= 2^-11 |hi|; below the f16 normal range (2^-14) it keeps an absolute quantum of 2^-24,
+// so a scaled operand S keeps all 22 bits while |S| >= 2^-3 and loses them one by one below.
+// Choice of p, q, every product: tables 2^6 (kLgFwdA), operands 2^5 (kLgFwdB).  At the headline's magnitudes: weights ~ 0.1 -> 6,
+// lo ~ 2^-9; entries of dt M ~ 1e-2 -> 0.6, lo ~ 2^-12; states and activations 0.1 .. 3 -> 3 .. 100, lo ~ 2^-9 .. 2^-5: every part a
+// normal f16.  (All 11 bits on the tables, p = 11, q = 0, would leave the lo part of an activation of 0.1 at 2^-15: subnormal.)
+// Range: |weight| < 65504 / 64 ~ 1023, |input| < 65504 / 32 ~ 2047.
+// hjb_bwd3_kernel was measured in this form too (panels 2^8, tables and stored activations 2^3, one chain for dW1): 5 % fewer VALU
+// instructions and 4 % MORE wave cycles per launch, +0.05 ms -- it keeps its two chains (profiles/one_accumulator_ab.json).
+// Beyond the range the scaled hi part is +inf and lo = f16(S - inf) = -inf; they meet in the SAME accumulator: NaN, which is what
+// the range guard (include/psp.h: range_flag) looks for.
+constexpr int kLgFwdA = 6, kLgFwdB = 5;
+static_assert(kLgFwdA + kLgFwdB == 11, "p + q = 11: the accumulators hold 2048 a b");
+__host__ __device__ constexpr float pow2f(int e) { return e >= 0 ? (float)(1 << e) : 1.0f / (float)(1 << -e); }
+// one table entry: LG < 0 the two-chain form above, else the one-accumulator form with scale 2^LG
+template <int LG>
+__device__ __forceinline__ void split_tab(float v, _Float16& hi, _Float16& lo) {
+    if constexpr (LG >= 0) {
+        const float s = pow2f(LG) * v;
+        hi = (_Float16)s;
+        lo = (_Float16)(s - (float)hi);
+    } else {
+        split_f16(v, hi, lo);
+    }
+}
 // Packs of four / eight values (two 16-feature blocks of the T layout side by side).  Plain C on purpose.  Round 3 tried the
 // split as inline asm -- v_cvt_pk_f16_f32, one packed multiply and v_fma_mixlo/hi_f16 (lo = f16(fma(hi, -2048, 2048 x)), bit-identical,
 // two instructions per value instead of the compiler's three) -- and took it out again: the hazard recogniser does not look into
@@ -495,7 +527,42 @@ __device__ __forceinline__ void split8u(const f32x4& u0, const f32x4& u1, f16x8&
     split_pair_u(u1[0], u1[1], h, l); hi[4] = h[0]; hi[5] = h[1]; lo[4] = l[0]; lo[5] = l[1];
     split_pair_u(u1[2], u1[3], h, l); hi[6] = h[0]; hi[7] = h[1]; lo[6] = l[0]; lo[7] = l[1];
 }
-template <int KS, int INB, class F>
+// ... and of the one-accumulator form: hi = f16(c x), lo = f16(c x - hi), c a power of two.  The multiply is the one split_pair
+// has already (only its constant changes; c = 1 folds it away), the residual one v_fma_mixlo/hi_f16 as in split_pair_u.
+// (The -1 is handed in through a register the optimiser cannot see into: fma(hi, -1.0, s) is canonicalised to a subtraction,
+// which is then selected as convert back, subtract, convert -- three instructions per value.)
+__device__ __forceinline__ void split_pair_s(float a, float b, float c, f16x2& hi, f16x2& lo) {
+    const f32x2 s = f32x2{a, b} * c;
+    hi = __builtin_convertvector(s, f16x2);
+    float m1 = -1.0f;
+    asm("" : "+s"(m1));
+    lo[0] = (_Float16)__builtin_fmaf((float)hi[0], m1, s[0]);
+    lo[1] = (_Float16)__builtin_fmaf((float)hi[1], m1, s[1]);
+}
+__device__ __forceinline__ void split4s(const f32x4& u, float c, f16x4& hi, f16x4& lo) {
+    f16x2 h, l;
+    split_pair_s(u[0], u[1], c, h, l); hi[0] = h[0]; hi[1] = h[1]; lo[0] = l[0]; lo[1] = l[1];
+    split_pair_s(u[2], u[3], c, h, l); hi[2] = h[0]; hi[3] = h[1]; lo[2] = l[0]; lo[3] = l[1];
+}
+__device__ __forceinline__ void split8s(const f32x4& u0, const f32x4& u1, float c, f16x8& hi, f16x8& lo) {
+    f16x4 h0, l0, h1, l1;
+    split4s(u0, c, h0, l0);
+    split4s(u1, c, h1, l1);
+    hi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+    lo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// (the classic form for packs that feed v_mfma_f32_16x16x16f16 directly: see split4c)
+__device__ __forceinline__ void split4cs(const f32x4& u, float c, f16x4& hi, f16x4& lo) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float s = c * u[e];
+        const _Float16 h = (_Float16)s;
+        hi[e] = h; lo[e] = (_Float16)(s - (float)h);
+    }
+}
+// LG >= 0: the table of the one-accumulator form (split_tab: entries scaled by 2^LG, unscaled residuals; the fp32 k-step's
+// entries scaled too)
+template <int KS, int INB, int LG = -1, class F>
 __device__ __forceinline__ void stage_aop_x3(float* dstf, int MB, int tid, int nthr, F src) {
     using SG = SplitGeo<KS, INB>;
     if constexpr (SG::NS > 0) {
@@ -508,7 +575,7 @@ __device__ __forceinline__ void stage_aop_x3(float* dstf, int MB, int tid, int n
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 _Float16 h, l;
-                split_f16(src(row, 32 * S + (e < 4 ? 4 * e : 16 + 4 * (e - 4)) + g), h, l);
+                split_tab<LG>(src(row, 32 * S + (e < 4 ? 4 * e : 16 + 4 * (e - 4)) + g), h, l);
                 hi[e] = h; lo[e] = l;
             }
             f16x8* p = reinterpret_cast<f16x8*>(dstf + mb * SG::per_mb + S * 512);
@@ -521,13 +588,13 @@ __device__ __forceinline__ void stage_aop_x3(float* dstf, int MB, int tid, int n
             const int i = lane & 15, g = lane >> 4;
             const int row = 16 * mb + 4 * (i & 3) + (i >> 2);
             if constexpr (SG::ODD_F32) {
-                dstf[mb * SG::per_mb + SG::NS * 512 + lane] = src(row, 32 * SG::NS + g);
+                dstf[mb * SG::per_mb + SG::NS * 512 + lane] = (LG >= 0 ? pow2f(LG) : 1.0f) * src(row, 32 * SG::NS + g);
             } else {
                 f16x4 hi, lo;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     _Float16 h, l;
-                    split_f16(src(row, 32 * SG::NS + 4 * e + g), h, l);
+                    split_tab<LG>(src(row, 32 * SG::NS + 4 * e + g), h, l);
                     hi[e] = h; lo[e] = l;
                 }
                 f16x4* p = reinterpret_cast<f16x4*>(dstf + mb * SG::per_mb + SG::NS * 512);
@@ -543,16 +610,20 @@ struct NoBetween { __device__ __forceinline__ void operator()(int) const {} };
 // portions so that they stand BETWEEN the MFMAs (the scheduler clusters them into bursts of 28 - 32 otherwise, and a burst
 // blocks the in-order wave while the store path drains at 16 B/clk per CU), and the slices of their Philox calls so that they
 // run in the MFMAs' shadow; fences with a functor let nothing cross.
-template <int MB, int KS, int INB, int CU = 2, class BT = NoBetween>
+// ONE (split_tab): acc += 2048 W . in^T on the caller's accumulator alone -- table staged with stage_aop_x3<.., kLgFwdA>, the operand
+// split with 2^kLgFwdB here; the two lower-order products follow the main one into acc[mb]: no correction set, no merge.
+template <int MB, int KS, int INB, int CU = 2, bool ONE = false, class BT = NoBetween>
 __device__ __forceinline__ void gemm_Tx(f32x4 (&acc)[MB], const float* wlds, const f32x4 (&in)[INB], int lane, BT between = BT()) {
     constexpr int kFence = std::is_same<BT, NoBetween>::value ? kFenceMask : 0;      // (with a functor: nothing crosses a unit's fence)
     using SG = SplitGeo<KS, INB>;
     constexpr int NS = SG::NS;
     static_assert(MB * SG::per_mb * 4 <= 65536, "table exceeds the 16-bit ds_read immediate offset");
     lane = opaque_i(lane);
-    f32x4 corr[MB];
+    [[maybe_unused]] f32x4 corr[ONE ? 1 : MB];                                       // (ONE: unused)
+    if constexpr (!ONE) {
 #pragma unroll
-    for (int mb = 0; mb < MB; ++mb) corr[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int mb = 0; mb < MB; ++mb) corr[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     if constexpr (NS > 0) {
         // units u = S * MB + mb in a ring of R = 2 CU operand slots, each unit's pair of 16-byte reads issued R - 1 units
         // (3 (R - 1) MFMAs) before its products: with CU = 2 that is 9 MFMAs of distance for the 32 registers a double-buffered
@@ -575,41 +646,58 @@ __device__ __forceinline__ void gemm_Tx(f32x4 (&acc)[MB], const float* wlds, con
                 al[v % R] = tbl[((v % MB) * SG::per_mb + (v / MB) * 512) / 4 + 64];
             }
             const int S = u / MB, mb = u % MB;
-            if (mb == 0) split8(in[2 * S], in[2 * S + 1], bh, bl);
+            if (mb == 0) {
+                if constexpr (ONE) split8s(in[2 * S], in[2 * S + 1], pow2f(kLgFwdB), bh, bl);
+                else split8(in[2 * S], in[2 * S + 1], bh, bl);
+            }
             acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[u % R], bh, acc[mb], 0, 0, 0);
-            corr[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[u % R], bl, corr[mb], 0, 0, 0);
-            corr[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[u % R], bh, corr[mb], 0, 0, 0);
+            if constexpr (ONE) {
+                acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[u % R], bl, acc[mb], 0, 0, 0);
+                acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[u % R], bh, acc[mb], 0, 0, 0);
+            } else {
+                corr[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[u % R], bl, corr[mb], 0, 0, 0);
+                corr[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[u % R], bh, corr[mb], 0, 0, 0);
+            }
             between(u);
             __builtin_amdgcn_sched_barrier(kFence);
         }
     }
     if constexpr (SG::ODD_F32) {
-        const float bop = in[INB - 1][0];
+        const float bop = (ONE ? pow2f(kLgFwdB) : 1.0f) * in[INB - 1][0];
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb) acc[mb] = mfma16(wlds[mb * SG::per_mb + NS * 512 + lane], bop, acc[mb]);
     }
     if constexpr (SG::ODD_H16) {
         f16x4 bh, bl;
-        split4c(in[INB - 1], bh, bl);
+        if constexpr (ONE) split4cs(in[INB - 1], pow2f(kLgFwdB), bh, bl);
+        else split4c(in[INB - 1], bh, bl);
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb) {
             const f16x4* p = reinterpret_cast<const f16x4*>(wlds + mb * SG::per_mb + NS * 512) + lane;
             const f16x4 a_hi = p[0], a_lo = p[64];
             acc[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, bh, acc[mb], 0, 0, 0);
-            corr[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, bl, corr[mb], 0, 0, 0);
-            corr[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_lo, bh, corr[mb], 0, 0, 0);
+            if constexpr (ONE) {
+                acc[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, bl, acc[mb], 0, 0, 0);
+                acc[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_lo, bh, acc[mb], 0, 0, 0);
+            } else {
+                corr[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, bl, corr[mb], 0, 0, 0);
+                corr[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_lo, bh, corr[mb], 0, 0, 0);
+            }
         }
     }
+    if constexpr (!ONE) {
 #pragma unroll
-    for (int mb = 0; mb < MB; ++mb) acc[mb] = acc[mb] + kSplitInv * corr[mb];
+        for (int mb = 0; mb < MB; ++mb) acc[mb] = acc[mb] + kSplitInv * corr[mb];
+    }
 }
 
-// gemm_Tx for an input panel that feeds TWO products (the state: W1 x and (dt A) x of the same step): the panel is split once
-// by split_panel8 and both products read the packs.
+// The one-accumulator gemm_Tx for an input panel that feeds TWO products (the state: W1 x and (dt A) x of the same step): the
+// panel is split once by split_panel8 (2^kLgFwdB) and both products read the packs; `last` = the panel's trailing block, unsplit.
+// One-accumulator only: the table MUST be one staged with stage_aop_x3<.., kLgFwdA>.
 template <int INB>
 __device__ __forceinline__ void split_panel8(const f32x4 (&in)[INB], f16x8 (&bh)[INB / 2 > 0 ? INB / 2 : 1], f16x8 (&bl)[INB / 2 > 0 ? INB / 2 : 1]) {
 #pragma unroll
-    for (int S = 0; S < INB / 2; ++S) split8(in[2 * S], in[2 * S + 1], bh[S], bl[S]);
+    for (int S = 0; S < INB / 2; ++S) split8s(in[2 * S], in[2 * S + 1], pow2f(kLgFwdB), bh[S], bl[S]);
 }
 template <int MB, int KS, int INB, int CU = 2, class BT = NoBetween>
 __device__ __forceinline__ void gemm_Txs(f32x4 (&acc)[MB], const float* wlds, const f16x8 (&bh)[INB / 2 > 0 ? INB / 2 : 1],
@@ -618,9 +706,6 @@ __device__ __forceinline__ void gemm_Txs(f32x4 (&acc)[MB], const float* wlds, co
     using SG = SplitGeo<KS, INB>;
     constexpr int NS = SG::NS;
     lane = opaque_i(lane);
-    f32x4 corr[MB];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb) corr[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (NS > 0) {
         const f16x8* tbl = reinterpret_cast<const f16x8*>(wlds) + lane;
         constexpr int NU = NS * MB, R = 2 * CU, PF = R - 1;
@@ -640,31 +725,29 @@ __device__ __forceinline__ void gemm_Txs(f32x4 (&acc)[MB], const float* wlds, co
             }
             const int S = u / MB, mb = u % MB;
             acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[u % R], bh[S], acc[mb], 0, 0, 0);
-            corr[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[u % R], bl[S], corr[mb], 0, 0, 0);
-            corr[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[u % R], bh[S], corr[mb], 0, 0, 0);
+            acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[u % R], bl[S], acc[mb], 0, 0, 0);
+            acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[u % R], bh[S], acc[mb], 0, 0, 0);
             between(u);
             __builtin_amdgcn_sched_barrier(kFence);
         }
     }
     if constexpr (SG::ODD_F32) {
-        const float bop = last[0];
+        const float bop = pow2f(kLgFwdB) * last[0];
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb) acc[mb] = mfma16(wlds[mb * SG::per_mb + NS * 512 + lane], bop, acc[mb]);
     }
     if constexpr (SG::ODD_H16) {
         f16x4 b4h, b4l;
-        split4c(last, b4h, b4l);
+        split4cs(last, pow2f(kLgFwdB), b4h, b4l);
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb) {
             const f16x4* p = reinterpret_cast<const f16x4*>(wlds + mb * SG::per_mb + NS * 512) + lane;
             const f16x4 a_hi = p[0], a_lo = p[64];
             acc[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, b4h, acc[mb], 0, 0, 0);
-            corr[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, b4l, corr[mb], 0, 0, 0);
-            corr[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_lo, b4h, corr[mb], 0, 0, 0);
+            acc[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_hi, b4l, acc[mb], 0, 0, 0);
+            acc[mb] = __builtin_amdgcn_mfma_f32_16x16x16f16(a_lo, b4h, acc[mb], 0, 0, 0);
         }
     }
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb) acc[mb] = acc[mb] + kSplitInv * corr[mb];
 }
 
 __device__ __forceinline__ float qsum(float v) {  // sum over the 4 q-lanes of a trajectory
@@ -692,14 +775,18 @@ __device__ __forceinline__ double jsum(double v) {  // sum over the 16 trajector
 //   two quarter-rate VALU ops.  Absolute error <= 2e-7 everywhere (the subtraction cancels for small |x|, so the RELATIVE
 //   error grows like 1e-7 / |x|; the forward kernels are VALU-limited next to fp32 MFMA -- DESIGN.md section 4 -- and the
 //   Taylor branch that kept 3e-7 relative accuracy below |x| = 0.35 cost 3.5 % of the forward kernel).
+// X2048: the argument is 2048 x (the accumulator of a one-accumulator split product, gemm_Tx ONE): the power of two goes into
+// the constant -- the same product bit for bit -- and copysign sees the same sign.
+template <bool X2048 = false>
 __device__ __forceinline__ float tanh_f32(float x) {
-    const float e = __builtin_amdgcn_exp2f(fabsf(x) * 2.8853900817779268f);  // exp(2|x|)
+    const float e = __builtin_amdgcn_exp2f(fabsf(x) * (X2048 ? 2.8853900817779268f * kSplitInv : 2.8853900817779268f));  // exp(2|x|)
     const float big = fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);    // saturates to 1 for large |x|
     return copysignf(big, x);
 }
+template <bool X2048 = false>
 __device__ __forceinline__ f32x4 tanh4(f32x4 v) {
     f32x4 o;
-    o[0] = tanh_f32(v[0]); o[1] = tanh_f32(v[1]); o[2] = tanh_f32(v[2]); o[3] = tanh_f32(v[3]);
+    o[0] = tanh_f32<X2048>(v[0]); o[1] = tanh_f32<X2048>(v[1]); o[2] = tanh_f32<X2048>(v[2]); o[3] = tanh_f32<X2048>(v[3]);
     return o;
 }
 
@@ -817,9 +904,9 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
     auto w2src = [&](int row, int col) { return (row < H && col < H) ? P[G::oW2 + row * H + col] : 0.f; };
     auto w3src = [&](int row, int col) { return (row < D && col < H) ? P[G::oW3 + row * H + col] : 0.f; };
     if constexpr (X3) {
-        stage_aop_x3<KSD, DB>(lds + oW1, HB, tid, nthr, w1src);
-        stage_aop_x3<KSH, HB>(lds + oW2, HB, tid, nthr, w2src);
-        stage_aop_x3<KSH, HB>(lds + oW3, DB, tid, nthr, w3src);
+        stage_aop_x3<KSD, DB, kLgFwdA>(lds + oW1, HB, tid, nthr, w1src);
+        stage_aop_x3<KSH, HB, kLgFwdA>(lds + oW2, HB, tid, nthr, w2src);
+        stage_aop_x3<KSH, HB, kLgFwdA>(lds + oW3, DB, tid, nthr, w3src);
     } else {
         stage_net(lds + oW1, HB, KSD, DB, w1src);
         stage_net(lds + oW2, HB, KSH, HB, w2src);
@@ -831,19 +918,22 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
         const float dt = a.dt;
         const float* __restrict__ A = a.drift;
         auto asrc = [&](int row, int col) { return (row < D && col < D) ? dt * A[row * D + col] : 0.f; };
-        if constexpr (X3) stage_aop_x3<KSD, DB>(ldsA, DB, tid, nthr, asrc);
+        if constexpr (X3) stage_aop_x3<KSD, DB, kLgFwdA>(ldsA, DB, tid, nthr, asrc);
         else stage_aop(ldsA, DB, KSD, tid, nthr, asrc);
     }
     if (k_sigma == SIGMA_DENSE) {
         const float* __restrict__ B = a.sigma;
         auto bsrc = [&](int row, int col) { return (row < D && col < D) ? B[row * D + col] : 0.f; };
-        if constexpr (X3) stage_aop_x3<KSD, DB>(ldsB, DB, tid, nthr, bsrc);
+        if constexpr (X3) stage_aop_x3<KSD, DB, kLgFwdA>(ldsB, DB, tid, nthr, bsrc);
         else stage_aop(ldsB, DB, KSD, tid, nthr, bsrc);
     }
-    stage_vec(lds + VSH + G::vb1, HB, tid, nthr, [&](int f) { return f < H ? P[G::ob1 + f] : 0.f; });
-    stage_vec(lds + VSH + G::vw1t, HB, tid, nthr, [&](int f) { return f < H ? P[G::oW1 + f * (D + 1)] : 0.f; });
-    stage_vec(lds + VSH + G::vb2, HB, tid, nthr, [&](int f) { return f < H ? P[G::ob2 + f] : 0.f; });
-    stage_vec(lds + VSH + G::vb3, DB, tid, nthr, [&](int f) { return f < D ? P[G::ob3 + f] : 0.f; });
+    // X3: the products are one-accumulator split products (gemm_Tx ONE) -- every accumulator of the control net holds 2048 x its
+    // value, so the vectors that initialise them are staged times 2048 (exact)
+    constexpr float kAcc = X3 ? kSplitScale : 1.0f, kAccInv = X3 ? kSplitInv : 1.0f;
+    stage_vec(lds + VSH + G::vb1, HB, tid, nthr, [&](int f) { return f < H ? kAcc * P[G::ob1 + f] : 0.f; });
+    stage_vec(lds + VSH + G::vw1t, HB, tid, nthr, [&](int f) { return f < H ? kAcc * P[G::oW1 + f * (D + 1)] : 0.f; });
+    stage_vec(lds + VSH + G::vb2, HB, tid, nthr, [&](int f) { return f < H ? kAcc * P[G::ob2 + f] : 0.f; });
+    stage_vec(lds + VSH + G::vb3, DB, tid, nthr, [&](int f) { return f < D ? kAcc * P[G::ob3 + f] : 0.f; });
     stage_vec(lds + VSH + G::vdr, DB, tid, nthr, [&](int f) {
         return (f < D && (k_drift == DRIFT_DIAG || k_drift == DRIFT_DWELL)) ? a.drift[f] : 0.f; });
     stage_vec(lds + VSH + G::vrun, DB, tid, nthr, [&](int f) {
@@ -859,7 +949,7 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
     const float dt = a.dt, sqdt = a.sqdt;
 
     const float store_cxi = SPEC ? 1.f : ((k_store == 3) ? 0.f : 1.f);     // image in the xi slot: c_xi xi + c_z Z
-    const float store_cz = SPEC ? 0.f : ((k_store == 3) ? 1.f : (k_store == 2 ? -a.sqdt : (k_adaptive ? 0.f : a.sqdt)));
+    const float store_cz = kAccInv * (SPEC ? 0.f : ((k_store == 3) ? 1.f : (k_store == 2 ? -a.sqdt : (k_adaptive ? 0.f : a.sqdt))));
     // FAST instances always keep the path (the launcher sends store_path = 0 to the general instance): without the
     // wave-uniform branch the stores share a scheduling region with the products instead of standing as bursts of 28 - 32
     const bool do_store = FAST ? true : (k_store != 0);
@@ -927,12 +1017,12 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
                     split_panel8<DB>(X, xh, xl);
                     gemm_Txs<HB, KSD, DB, 2>(h1, lds + oW1, xh, xl, X[DB - 1], lane, [&](int u) __attribute__((always_inline)) { x_store(u, NU1 + NU2); });
 #pragma unroll
-                    for (int b = 0; b < DB; ++b) Tn[b] = X[b];
+                    for (int b = 0; b < DB; ++b) Tn[b] = f32x4{0.f, 0.f, 0.f, 0.f};             // 2048 (dt A) X; X joins it in the update below
                     gemm_Txs<DB, KSD, DB, 2>(Tn, ldsA, xh, xl, X[DB - 1], lane, [&](int u) __attribute__((always_inline)) { x_store(NU1 + u, NU1 + NU2); });
                     if constexpr (NU1 + NU2 == 0) x_store(0, 1);
                 } else {
                     constexpr int NU1 = (DB / 2) * HB;
-                    gemm_Tx<HB, KSD, DB, 2>(h1, lds + oW1, X, lane, [&](int u) __attribute__((always_inline)) { x_store(u, NU1); });
+                    gemm_Tx<HB, KSD, DB, 2, true>(h1, lds + oW1, X, lane, [&](int u) __attribute__((always_inline)) { x_store(u, NU1); });
                     if constexpr (NU1 == 0) x_store(0, 1);
                 }
             }
@@ -940,7 +1030,7 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
             else gemm_T<HB, KSD, DB>(h1, lds + oW1, X, lane);
             PSP_STAMP(fs1);
 #pragma unroll
-            for (int m = 0; m < HB; ++m) h1[m] = tanh4(h1[m]);
+            for (int m = 0; m < HB; ++m) h1[m] = tanh4<X3>(h1[m]);
             PSP_STAMP(fs2);
             f32x4 h2[HB];
 #pragma unroll
@@ -991,13 +1081,13 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
                 }
             };
             if constexpr (X3) {
-                gemm_Tx<HB, KSH, HB, 2>(h2, lds + oW2, h1, lane, [&](int u) __attribute__((always_inline)) { h_store(h1, G::pH1, u, NUH2); philox_portion(u); });
+                gemm_Tx<HB, KSH, HB, 2, true>(h2, lds + oW2, h1, lane, [&](int u) __attribute__((always_inline)) { h_store(h1, G::pH1, u, NUH2); philox_portion(u); });
                 if constexpr (NUH2 == 0) h_store(h1, G::pH1, 0, 1);
             }
             else if constexpr (BF16) gemm_Tb<HB, HB>(h2, lds + oW2, h1, lane);
             else gemm_T<HB, KSH, HB>(h2, lds + oW2, h1, lane);
 #pragma unroll
-            for (int m = 0; m < HB; ++m) h2[m] = tanh4(h2[m]);
+            for (int m = 0; m < HB; ++m) h2[m] = tanh4<X3>(h2[m]);
             if (!X3 && do_store) {
 #pragma unroll
                 for (int ks = 0; ks < 4 * HB; ++ks) {
@@ -1009,7 +1099,7 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
 #pragma unroll
             for (int m = 0; m < DB; ++m) Z[m] = vb3[m * 4];
             if constexpr (X3) {
-                gemm_Tx<DB, KSH, HB, 2>(Z, lds + oW3, h2, lane, [&](int u) __attribute__((always_inline)) { h_store(h2, G::pH2, u, NUH3); philox_portion(NUH2 + u); });
+                gemm_Tx<DB, KSH, HB, 2, true>(Z, lds + oW3, h2, lane, [&](int u) __attribute__((always_inline)) { h_store(h2, G::pH2, u, NUH3); philox_portion(NUH2 + u); });
                 if constexpr (NUH3 == 0) h_store(h2, G::pH2, 0, 1);
             }
             else if constexpr (BF16) gemm_Tb<DB, HB>(Z, lds + oW3, h2, lane);
@@ -1017,6 +1107,8 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
             PSP_STAMP(fs3);
 
             // ---- Brownian increment xi_{n+1} and the two row sums |Z|^2, Z.xi (solver.py:477-478)
+            // (X3: Z holds 2048 Z.  The row sums are formed of it and rescaled once per lane; the stored image, the u_L2 term
+            // and the increment v take the 2^-11 in a coefficient they have anyway.)
             float S = 0.f, Pz = 0.f, UL = 0.f;
 #pragma unroll
             for (int b = 0; b < DB; ++b) {
@@ -1059,22 +1151,27 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int f = 16 * b + 4 * r + q;
-                        const float e = (f < D) ? Z[b][r] + ur[f < D ? f : D - 1] : 0.f;
+                        const float e = (f < D) ? (X3 ? fmaf(Z[b][r], kSplitInv, ur[f < D ? f : D - 1]) : Z[b][r] + ur[f < D ? f : D - 1]) : 0.f;
                         UL = fmaf(e, e, UL);
                     }
                 }
                 // v = c dt + xi sqrt(dt), c = -Z (adaptive) or 0  (solver.py:451-456,471-472)
-                Z[b] = k_adaptive ? (sqdt * xi - dt * Z[b]) : (sqdt * xi);
+                if constexpr (X3) Z[b] = k_adaptive ? (sqdt * xi - (dt * kSplitInv) * Z[b]) : (sqdt * xi);
+                else Z[b] = k_adaptive ? (sqdt * xi - dt * Z[b]) : (sqdt * xi);
             }
             ULsum = fmaf(UL, dt, ULsum);
             S = qsum(S);
             Pz = qsum(Pz);
+            if constexpr (X3) { S *= kSplitInv * kSplitInv; Pz *= kSplitInv; }
             PSP_STAMP(fs4);
 
             // ---- X_{n+1} = X + b(X) dt + sigma v      (solver.py:471-472)
             if (!early_drift) {
 #pragma unroll
                 for (int b = 0; b < DB; ++b) Tn[b] = X[b];
+            } else {
+#pragma unroll
+                for (int b = 0; b < DB; ++b) Tn[b] = X[b] + kSplitInv * Tn[b];        // X + (dt A) X of the first layer's pass
             }
             if (k_drift == DRIFT_DENSE) {
                 if constexpr (!X3) gemm_T<DB, KSD, DB>(Tn, ldsA, X, lane);     // + (dt A) X
@@ -1086,7 +1183,14 @@ __global__ __launch_bounds__(512) void hjb_fwd_kernel(const HjbArgs a) {
                 for (int b = 0; b < DB; ++b) Tn[b] -= dt * (4.0f * vdr[b * 4] * (X[b] * (X[b] * X[b] - 1.0f)));
             }
             if (k_sigma == SIGMA_DENSE) {
-                if constexpr (X3) gemm_Tx<DB, KSD, DB>(Tn, ldsB, Z, lane);
+                if constexpr (X3) {
+                    f32x4 Bv[DB];
+#pragma unroll
+                    for (int b = 0; b < DB; ++b) Bv[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    gemm_Tx<DB, KSD, DB, 2, true>(Bv, ldsB, Z, lane);
+#pragma unroll
+                    for (int b = 0; b < DB; ++b) Tn[b] = Tn[b] + kSplitInv * Bv[b];
+                }
                 else gemm_T<DB, KSD, DB>(Tn, ldsB, Z, lane);     // + B v
             } else if (k_sigma == SIGMA_SCALE) {
 #pragma unroll
