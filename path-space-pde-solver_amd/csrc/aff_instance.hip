@@ -6,24 +6,15 @@ namespace psp {
 namespace {
 template <int DB>
 hipError_t launch_fwd(const AffArgs& a, int grid, int threads, int lds_bytes, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&aff_fwd_kernel<DB>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((aff_fwd_kernel<DB>), dim3(grid), dim3(threads), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<aff_fwd_kernel<DB>>(dim3(grid), dim3(threads), lds_bytes, stream, a);
 }
 template <int DB>
 hipError_t launch_adj(const AffArgs& a, int grid, int threads, int lds_bytes, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&aff_adj_kernel<DB>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((aff_adj_kernel<DB>), dim3(grid), dim3(threads), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<aff_adj_kernel<DB>>(dim3(grid), dim3(threads), lds_bytes, stream, a);
 }
 template <int DB>
 hipError_t launch_bwd(const AffArgs& a, int grid, hipStream_t stream) {
-    hipLaunchKernelGGL((aff_bwd_kernel<DB>), dim3(grid), dim3(kAffBwdThreads), 0, stream, a);
-    return hipGetLastError();
+    return launch<aff_bwd_kernel<DB>>(dim3(grid), dim3(kAffBwdThreads), 0, stream, a);
 }
 template <int DB>
 AffInstance make_instance() { return AffInstance{&launch_fwd<DB>, &launch_adj<DB>, &launch_bwd<DB>}; }

@@ -1295,77 +1295,44 @@ template <int D, int H>
 struct GenLaunch {
     using G = GGeo<D, H>;
     static int fwd_lds() { return G::fwd_lds_floats() * 4; }
+    static int fwd_x3_lds() { return G::fwd_x3_lds_floats() * 4; }
     static int bwd2_lds() { return (G::gEx + 2 * 4 * G::EXT * 256) * 4; }
-    static hipError_t bwd2(const GenArgs& a, int grid, hipStream_t s) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gen_bwd2_kernel<D, H>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bwd2_lds());
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((gen_bwd2_kernel<D, H>), dim3(grid), dim3(512), bwd2_lds(), s, a);
-        return hipGetLastError();
+    static int bwd2_x3_lds() { return (G::gW2hr + SplitGeo<G::KSH, G::HB>::floats(G::HB) + 2 * 4 * G::EXT * 256) * 4; }
+    template <bool BF16, bool X3>
+    static hipError_t bwd2_as(const GenArgs& a, int grid, hipStream_t s) {
+        return launch_lds<gen_bwd2_kernel<D, H, BF16, X3>>(dim3(grid), dim3(512), X3 ? bwd2_x3_lds() : bwd2_lds(), s, a);
     }
-    static hipError_t bwd2_bf16(const GenArgs& a, int grid, hipStream_t s) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gen_bwd2_kernel<D, H, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bwd2_lds());
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((gen_bwd2_kernel<D, H, true>), dim3(grid), dim3(512), bwd2_lds(), s, a);
-        return hipGetLastError();
-    }
-    template <bool BF16, bool PHILOX>
+    template <bool BF16, bool PHILOX, bool X3, int SPECK = -1>
     static hipError_t fwd_as(const GenArgs& a, int grid, int block, hipStream_t s) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gen_fwd_kernel<D, H, BF16, PHILOX>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, fwd_lds());
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((gen_fwd_kernel<D, H, BF16, PHILOX>), dim3(grid), dim3(block), fwd_lds(), s, a);
-        return hipGetLastError();
-    }
-    static hipError_t fwd(const GenArgs& a, int grid, int block, hipStream_t s) {
-        return a.noise_mode == NOISE_PHILOX ? fwd_as<false, true>(a, grid, block, s) : fwd_as<false, false>(a, grid, block, s);
+        return launch_lds<gen_fwd_kernel<D, H, BF16, PHILOX, X3, SPECK>>(dim3(grid), dim3(block), X3 ? fwd_x3_lds() : fwd_lds(), s, a);
     }
     // specialised problem kinds (gen_fwd_kernel SPECK): unbounded, non-adaptive, path store on, no per-step value output
+    static constexpr int kSpecDwell = DRIFT_DWELL | (GH_QUAD << 4), kSpecAllenCahn = DRIFT_ZERO | (GH_ALLEN_CAHN << 4);
     static int spec_kind(const GenArgs& a) {
         if (!spec_enabled() || a.noise_mode != NOISE_PHILOX || a.domain_kind != DOM_NONE || a.adaptive || a.store_path != 1 || a.Vsteps != nullptr) return -1;
-        if (a.drift_kind == DRIFT_DWELL && a.h_kind == GH_QUAD) return DRIFT_DWELL | (GH_QUAD << 4);
-        if (a.drift_kind == DRIFT_ZERO && a.h_kind == GH_ALLEN_CAHN) return DRIFT_ZERO | (GH_ALLEN_CAHN << 4);
+        if (a.drift_kind == DRIFT_DWELL && a.h_kind == GH_QUAD) return kSpecDwell;
+        if (a.drift_kind == DRIFT_ZERO && a.h_kind == GH_ALLEN_CAHN) return kSpecAllenCahn;
         return -1;
     }
-    template <bool BF16, bool X3, int SPECK>
-    static hipError_t fwd_spec(const GenArgs& a, int grid, int block, hipStream_t s) {
-        const int bytes = X3 ? G::fwd_x3_lds_floats() * 4 : fwd_lds();
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gen_fwd_kernel<D, H, BF16, true, X3, SPECK>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((gen_fwd_kernel<D, H, BF16, true, X3, SPECK>), dim3(grid), dim3(block), bytes, s, a);
-        return hipGetLastError();
+    // the specialised kinds are built for the bf16 and the split-product forward only
+    template <bool BF16, bool X3>
+    static hipError_t fwd_mode(const GenArgs& a, int grid, int block, hipStream_t s) {
+        if constexpr (BF16 || X3) {
+            const int sk = spec_kind(a);
+            if (sk == kSpecDwell) return fwd_as<BF16, true, X3, kSpecDwell>(a, grid, block, s);
+            if (sk == kSpecAllenCahn) return fwd_as<BF16, true, X3, kSpecAllenCahn>(a, grid, block, s);
+        }
+        return a.noise_mode == NOISE_PHILOX ? fwd_as<BF16, true, X3>(a, grid, block, s) : fwd_as<BF16, false, X3>(a, grid, block, s);
     }
-    static hipError_t fwd_bf16(const GenArgs& a, int grid, int block, hipStream_t s) {
-        const int sk = spec_kind(a);
-        if (sk == (DRIFT_DWELL | (GH_QUAD << 4))) return fwd_spec<true, false, DRIFT_DWELL | (GH_QUAD << 4)>(a, grid, block, s);
-        if (sk == (DRIFT_ZERO | (GH_ALLEN_CAHN << 4))) return fwd_spec<true, false, DRIFT_ZERO | (GH_ALLEN_CAHN << 4)>(a, grid, block, s);
-        return a.noise_mode == NOISE_PHILOX ? fwd_as<true, true>(a, grid, block, s) : fwd_as<true, false>(a, grid, block, s);
-    }
-    static int bwd2_x3_lds() { return (G::gW2hr + SplitGeo<G::KSH, G::HB>::floats(G::HB) + 2 * 4 * G::EXT * 256) * 4; }
+    // the table's entries: plain members in the table's order, which is the order of the kernels in the code object
+    static hipError_t fwd(const GenArgs& a, int grid, int block, hipStream_t s) { return fwd_mode<false, false>(a, grid, block, s); }
+    static hipError_t bwd2(const GenArgs& a, int grid, hipStream_t s) { return bwd2_as<false, false>(a, grid, s); }
+    static hipError_t fwd_bf16(const GenArgs& a, int grid, int block, hipStream_t s) { return fwd_mode<true, false>(a, grid, block, s); }
+    static hipError_t bwd2_bf16(const GenArgs& a, int grid, hipStream_t s) { return bwd2_as<true, false>(a, grid, s); }
+    static hipError_t fwd_x3(const GenArgs& a, int grid, int block, hipStream_t s) { return fwd_mode<false, true>(a, grid, block, s); }
     static hipError_t bwd2_x3(const GenArgs& a, int grid, hipStream_t s) {
         if (bwd2_x3_lds() > 160 * 1024) return bwd2(a, grid, s);       // (split table does not fit: the fp32-MFMA kernel, same results)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gen_bwd2_kernel<D, H, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bwd2_x3_lds());
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((gen_bwd2_kernel<D, H, false, true>), dim3(grid), dim3(512), bwd2_x3_lds(), s, a);
-        return hipGetLastError();
-    }
-    static int fwd_x3_lds() { return G::fwd_x3_lds_floats() * 4; }
-    template <bool PHILOX>
-    static hipError_t fwd_x3_as(const GenArgs& a, int grid, int block, hipStream_t s) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gen_fwd_kernel<D, H, false, PHILOX, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, fwd_x3_lds());
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((gen_fwd_kernel<D, H, false, PHILOX, true>), dim3(grid), dim3(block), fwd_x3_lds(), s, a);
-        return hipGetLastError();
-    }
-    static hipError_t fwd_x3(const GenArgs& a, int grid, int block, hipStream_t s) {
-        const int sk = spec_kind(a);
-        if (sk == (DRIFT_DWELL | (GH_QUAD << 4))) return fwd_spec<false, true, DRIFT_DWELL | (GH_QUAD << 4)>(a, grid, block, s);
-        if (sk == (DRIFT_ZERO | (GH_ALLEN_CAHN << 4))) return fwd_spec<false, true, DRIFT_ZERO | (GH_ALLEN_CAHN << 4)>(a, grid, block, s);
-        return a.noise_mode == NOISE_PHILOX ? fwd_x3_as<true>(a, grid, block, s) : fwd_x3_as<false>(a, grid, block, s);
+        return bwd2_as<false, true>(a, grid, s);
     }
     static GenInstance instance() {
         return GenInstance{D, H, G::P, G::PB, G::PB16, &fwd_lds, &fwd, &bwd2_lds, &bwd2, &fwd_bf16, &bwd2_bf16,

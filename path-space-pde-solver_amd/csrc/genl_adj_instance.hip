@@ -8,16 +8,12 @@
 namespace psp {
 
 template <int NW> static hipError_t genl_adj_launch_nw(const GenlAdjArgs& a, int ntile16, int lds_bytes, hipStream_t st) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_adj_kernel<NW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((genl_adj_kernel<NW>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
-    return hipGetLastError();
+    return launch_lds<genl_adj_kernel<NW>>(dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
 }
 
 hipError_t genl_adj_launch(const GenlAdjArgs& a, int nw, int ntile16, int lds_bytes, hipStream_t st) {
     if (a.a.driftA) {
-        hipLaunchKernelGGL(genl_adj_tables_kernel, dim3(8), dim3(256), 0, st, a);
-        hipError_t e = hipGetLastError();
+        const hipError_t e = launch<genl_adj_tables_kernel>(dim3(8), dim3(256), 0, st, a);
         if (e != hipSuccess) return e;
     }
     return nw == 1 ? genl_adj_launch_nw<1>(a, ntile16, lds_bytes, st)

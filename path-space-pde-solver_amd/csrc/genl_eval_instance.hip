@@ -9,20 +9,14 @@ namespace psp {
 namespace {
 template <int NW>
 hipError_t launch_one(const GenlEvalArgs& a, int grid, int lds_bytes, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_eval_kernel<NW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((genl_eval_kernel<NW>), dim3(grid), dim3(64 * NW), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<genl_eval_kernel<NW>>(dim3(grid), dim3(64 * NW), lds_bytes, stream, a);
 }
 }  // namespace
 
 hipError_t genl_eval_launch(const GenlEvalArgs& a, int nw, int grid, int lds_bytes, hipStream_t stream) {
     hipError_t e = nw == 1 ? launch_one<1>(a, grid, lds_bytes, stream) : launch_one<8>(a, grid, lds_bytes, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(genl_eval_reduce_kernel, dim3(1), dim3(64 * kEvalStats), 0, stream, a.partial, grid,
-                       a.log_out, a.slot_dev, a.slot, a.log_slots);
-    return hipGetLastError();
+    return launch<genl_eval_reduce_kernel>(dim3(1), dim3(64 * kEvalStats), 0, stream, a.partial, grid, a.log_out, a.slot_dev, a.slot, a.log_slots);
 }
 
 }  // namespace psp

@@ -1084,10 +1084,7 @@ __global__ __launch_bounds__(64 * NW) void genl_bwd_kernel(const GenlArgs ga_) {
 
 // host side: launches (the dynamic LDS size exceeds the 64 KiB default)
 template <int NW, bool DENSE = false, bool LQ = false, bool LOGU = false, bool EIG = false> inline hipError_t genl_launch_fwd(const typename GenlFwdArgsOf<LOGU, EIG>::type& a, int ntile16, int lds_bytes, hipStream_t st) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_fwd_kernel<NW, DENSE, LQ, LOGU, EIG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((genl_fwd_kernel<NW, DENSE, LQ, LOGU, EIG>), dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
-    return hipGetLastError();
+    return launch_lds<genl_fwd_kernel<NW, DENSE, LQ, LOGU, EIG>>(dim3(ntile16), dim3(64 * NW), lds_bytes, st, a);
 }
 // the linear-quadratic instances <NW, true, true> are compiled in a unit of their own (genl_lq_instance.hip), so that the unit
 // of the other instances holds the kernels it held; nw = 1, 4 or 8
@@ -1099,10 +1096,7 @@ hipError_t genl_ul2_launch_stage(const GenlLogArgs& a, hipStream_t st);
 // the eigenvalue instances <NW, false, false, false, true>: a unit of their own (genl_eig_instance.hip)
 hipError_t genl_eig_launch_fwd(const GenlEigFwdArgs& a, int nw, int ntile16, int lds_bytes, hipStream_t st);
 template <int NW, int MS = GenlGeo<NW>::MAXSLOT> inline hipError_t genl_launch_bwd(const GenlArgs& a, int grid, int groups, int lds_bytes, hipStream_t st) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genl_bwd_kernel<NW, MS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((genl_bwd_kernel<NW, MS>), dim3(grid, groups), dim3(64 * NW), lds_bytes, st, a);
-    return hipGetLastError();
+    return launch_lds<genl_bwd_kernel<NW, MS>>(dim3(grid, groups), dim3(64 * NW), lds_bytes, st, a);
 }
 
 }  // namespace psp

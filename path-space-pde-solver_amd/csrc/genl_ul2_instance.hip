@@ -29,8 +29,7 @@ __global__ __launch_bounds__(256) void genl_ul2_stage_kernel(const GenlLogArgs l
 }
 
 hipError_t genl_ul2_launch_stage(const GenlLogArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(genl_ul2_stage_kernel, dim3(128), dim3(256), 0, st, a);
-    return hipGetLastError();
+    return launch<genl_ul2_stage_kernel>(dim3(128), dim3(256), 0, st, a);
 }
 
 hipError_t genl_ul2_launch_fwd(const GenlLogArgs& a, int nw, int ntile16, int lds_bytes, hipStream_t st) {

@@ -10,6 +10,7 @@
 // microseconds of latency, not a 700-fma chain per thread on one CU.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "launch.h"
 
 namespace psp {
 
@@ -57,8 +58,7 @@ __global__ __launch_bounds__(kBasisThreads) void hjb_basis_w1_kernel(const float
 template <bool TRANSPOSE>
 inline hipError_t launch_basis_w1(const float* src, float* dst, const float* B, int d, int H, long long n, hipStream_t s) {
     const int grid = (H + kBasisRows - 1) / kBasisRows;
-    hipLaunchKernelGGL((hjb_basis_w1_kernel<TRANSPOSE>), dim3(grid), dim3(kBasisThreads), basis_lds_bytes(d), s, src, dst, B, d, H, n);
-    return hipGetLastError();
+    return launch<hjb_basis_w1_kernel<TRANSPOSE>>(dim3(grid), dim3(kBasisThreads), basis_lds_bytes(d), s, src, dst, B, d, H, n);
 }
 
 }  // namespace psp

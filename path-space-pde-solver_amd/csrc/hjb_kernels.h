@@ -19,6 +19,7 @@
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "launch.h"
 
 namespace psp {
 
@@ -1747,11 +1748,7 @@ struct HjbLaunch {
     template <int MODE, int FAST>
     static hipError_t fwd_as(const HjbArgs& a, int grid, int block, hipStream_t s) {
         const int bytes = MODE == 2 ? fwd_x3_lds(a.drift_kind, a.sigma_kind) : fwd_lds(a.drift_kind, a.sigma_kind);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjb_fwd_kernel<D, H, MODE, FAST>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjb_fwd_kernel<D, H, MODE, FAST>), dim3(grid), dim3(block), bytes, s, a);
-        return hipGetLastError();
+        return launch_lds<hjb_fwd_kernel<D, H, MODE, FAST>>(dim3(grid), dim3(block), bytes, s, a);
     }
     // FAST (no vector-memory load in the time loop): Philox noise, no u_L2 log, no time-feature table -- every training launch
     static bool fast(const HjbArgs& a) { return a.noise_mode == NOISE_PHILOX && a.uref == nullptr && a.tfeat == nullptr && a.store_path != 0; }
@@ -1773,12 +1770,7 @@ struct HjbLaunch {
     }
     static int bwd2_lds() { return G::bwd2_lds_floats() * 4; }
     static hipError_t bwd2(const HjbArgs& a, int grid, hipStream_t s) {
-        const int bytes = bwd2_lds();
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjb_bwd2_kernel<D, H>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjb_bwd2_kernel<D, H>), dim3(grid), dim3(512), bytes, s, a);
-        return hipGetLastError();
+        return launch_lds<hjb_bwd2_kernel<D, H>>(dim3(grid), dim3(512), bwd2_lds(), s, a);
     }
     static HjbInstance instance() {
         return HjbInstance{D, H, G::P, &fwd_lds, &fwd, G::PB, &bwd2_lds, &bwd2};

@@ -222,11 +222,7 @@ struct HjbaLaunch {
     template <bool X3>
     static hipError_t adj_as(const HjbArgs& a, int grid, int block, hipStream_t s) {
         const int bytes = (X3 ? G::fwd_x3_lds_floats(a.drift_kind, a.sigma_kind) : G::fwd_lds_floats(a.drift_kind, a.sigma_kind)) * 4;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjb_adj_kernel<D, H, X3>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjb_adj_kernel<D, H, X3>), dim3(grid), dim3(block), bytes, s, a);
-        return hipGetLastError();
+        return launch_lds<hjb_adj_kernel<D, H, X3>>(dim3(grid), dim3(block), bytes, s, a);
     }
     static hipError_t adj(const HjbArgs& a, int grid, int block, hipStream_t s) { return adj_as<false>(a, grid, block, s); }
     static hipError_t adj_x3(const HjbArgs& a, int grid, int block, hipStream_t s) { return adj_as<true>(a, grid, block, s); }

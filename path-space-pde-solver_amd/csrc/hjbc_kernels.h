@@ -619,12 +619,7 @@ struct HjbcLaunch {
     static int lds_bytes(int nt) { return (nt == 4 ? GeoC<D, H, 4>::lds_floats : GeoC<D, H, 2>::lds_floats) * 4; }
     template <int NT>
     static hipError_t fwd_nt(const HjbArgs& a, int grid, hipStream_t s) {
-        const int bytes = GeoC<D, H, NT>::lds_floats * 4;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbc_fwd_kernel<D, H, NT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbc_fwd_kernel<D, H, NT>), dim3(grid), dim3(512), bytes, s, a);
-        return hipGetLastError();
+        return launch_lds<hjbc_fwd_kernel<D, H, NT>>(dim3(grid), dim3(512), GeoC<D, H, NT>::lds_floats * 4, s, a);
     }
     // grid = ceil(ntile16 / nt) workgroups of 512 threads; the x3 tables of hjbw_tables_kernel(.., 3)
     static hipError_t fwd(const HjbArgs& a, int grid, int nt, hipStream_t s) {

@@ -1461,141 +1461,71 @@ struct DnetInstance {
 template <int D, int H>
 struct DnetLaunch {
     using W = DGeo<D, H>;
-    static hipError_t adj(const DnetArgs& a, int grid, hipStream_t s) {
-        hipLaunchKernelGGL((hjbd_tables_kernel<D, H>), dim3(512), dim3(256), 0, s, a, 1);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        const int bytes = W::lds_floats * 4;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_adj_kernel<D, H>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbd_adj_kernel<D, H>), dim3(grid), dim3(256), bytes, s, a);
-        return hipGetLastError();
-    }
-    static hipError_t adj_x3(const DnetArgs& a, int grid, hipStream_t s) {
-        hipLaunchKernelGGL((hjbd_tables_kernel<D, H>), dim3(512), dim3(256), 0, s, a, 3);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        const int bytes = W::lds_floats_x3 * 4;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_adj_kernel<D, H, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbd_adj_kernel<D, H, true>), dim3(grid), dim3(256), bytes, s, a);
-        return hipGetLastError();
-    }
-    template <bool X3, int LOGU>
-    static hipError_t fwd_launch_k(const DnetArgs& a, int grid, int bytes, hipStream_t s) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_fwd_kernel<D, H, X3, false, LOGU>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbd_fwd_kernel<D, H, X3, false, LOGU>), dim3(grid), dim3(256), bytes, s, a);
-        return hipGetLastError();
+    static hipError_t tables(const DnetArgs& a, int mode, hipStream_t s) {   // 0 / 2: forward (fp32 / split), 1 / 3: adjoint, 4: u_L2 gains
+        return launch<hjbd_tables_kernel<D, H>>(dim3(512), dim3(256), 0, s, a, mode);
     }
     template <bool X3>
-    static hipError_t fwd_launch_log(const DnetArgs& a, int grid, int bytes, hipStream_t s) {      // u_L2 log on: its kind's instance
-        if (a.ul2_kind == 1) return fwd_launch_k<X3, 2>(a, grid, bytes, s);
-        if (a.ul2_kind == 2) return fwd_launch_k<X3, 3>(a, grid, bytes, s);
-        return fwd_launch_k<X3, 1>(a, grid, bytes, s);
+    static constexpr int kLdsBytes = (X3 ? W::lds_floats_x3 : W::lds_floats) * 4;
+    template <bool X3>
+    static hipError_t adj_as(const DnetArgs& a, int grid, hipStream_t s) {
+        const hipError_t e = tables(a, X3 ? 3 : 1, s);
+        return e != hipSuccess ? e : launch_lds<hjbd_adj_kernel<D, H, X3>>(dim3(grid), dim3(256), kLdsBytes<X3>, s, a);
     }
-    static hipError_t ul2_stage(const DnetArgs& a, hipStream_t s) {
-        hipLaunchKernelGGL((hjbd_tables_kernel<D, H>), dim3(512), dim3(256), 0, s, a, 4);
-        return hipGetLastError();
+    template <bool X3, bool SPEC, int LOGU>
+    static hipError_t fwd_as(const DnetArgs& a, int grid, hipStream_t s) {
+        return launch_lds<hjbd_fwd_kernel<D, H, X3, SPEC, LOGU>>(dim3(grid), dim3(256), kLdsBytes<X3>, s, a);
     }
+    template <bool X3>
+    static hipError_t fwd_log(const DnetArgs& a, int grid, hipStream_t s) {      // u_L2 log on: its kind's instance
+        if (a.ul2_kind == 1) return fwd_as<X3, false, 2>(a, grid, s);
+        if (a.ul2_kind == 2) return fwd_as<X3, false, 3>(a, grid, s);
+        return fwd_as<X3, false, 1>(a, grid, s);
+    }
+    static hipError_t ul2_stage(const DnetArgs& a, hipStream_t s) { return tables(a, 4, s); }
     static hipError_t fwd(const DnetArgs& a, int grid, hipStream_t s) {
-        hipLaunchKernelGGL((hjbd_tables_kernel<D, H>), dim3(512), dim3(256), 0, s, a, 0);
-        hipError_t e = hipGetLastError();
+        const hipError_t e = tables(a, 0, s);
         if (e != hipSuccess) return e;
-        const int bytes = W::lds_floats * 4;
-        if (a.h.uref != nullptr) return fwd_launch_log<false>(a, grid, bytes, s);            // u_L2 log on
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_fwd_kernel<D, H>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbd_fwd_kernel<D, H>), dim3(grid), dim3(256), bytes, s, a);
-        return hipGetLastError();
+        if (a.h.uref != nullptr) return fwd_log<false>(a, grid, s);                          // u_L2 log on
+        return fwd_as<false, false, 0>(a, grid, s);
     }
     static hipError_t fwd_x3(const DnetArgs& a, int grid, hipStream_t s) {
-        hipLaunchKernelGGL((hjbd_tables_kernel<D, H>), dim3(512), dim3(256), 0, s, a, 2);
-        hipError_t e = hipGetLastError();
+        const hipError_t e = tables(a, 2, s);
         if (e != hipSuccess) return e;
-        const int bytes = W::lds_floats_x3 * 4;
         const HjbArgs& h = a.h;
         if (spec_enabled() && h.noise_mode == NOISE_PHILOX && h.drift_kind == DRIFT_DENSE && h.sigma_kind == SIGMA_DENSE && h.adaptive && h.runcost_kind == RUN_ZERO &&
-            h.loss_kind != LOSS_RELENT && h.uref == nullptr && h.tfeat == nullptr) {            // the LLGC training launch: SPEC
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_fwd_kernel<D, H, true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((hjbd_fwd_kernel<D, H, true, true>), dim3(grid), dim3(256), bytes, s, a);
-            return hipGetLastError();
-        }
-        if (h.uref != nullptr) return fwd_launch_log<true>(a, grid, bytes, s);               // u_L2 log on
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_fwd_kernel<D, H, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbd_fwd_kernel<D, H, true>), dim3(grid), dim3(256), bytes, s, a);
-        return hipGetLastError();
+            h.loss_kind != LOSS_RELENT && h.uref == nullptr && h.tfeat == nullptr)               // the LLGC training launch: SPEC
+            return fwd_as<true, true, 0>(a, grid, s);
+        if (h.uref != nullptr) return fwd_log<true>(a, grid, s);                             // u_L2 log on
+        return fwd_as<true, false, 0>(a, grid, s);
     }
     static constexpr int NALL = W::DB + 2 * W::HB;
     static constexpr int kTiles0 = cdiv(NALL, 4) * NALL;                                      // accumulator tiles per wave, one launch
     static constexpr int kTiles1 = cdiv(NALL, 4) * W::DB, kTiles2 = cdiv(W::DB + W::HB, 4) * 2 * W::HB;   // ... split by columns
     static constexpr int kMaxTiles = 48;                  // beyond this the 512-entry register file spills heavily
     static constexpr int kPasses = kTiles0 <= kMaxTiles ? 1 : ((kTiles1 <= kMaxTiles && kTiles2 <= kMaxTiles) ? 2 : 0);
-    template <int PASS>
+    template <int PASS, bool X3, bool SQ>
     static hipError_t bwd_pass(const DnetArgs& a, int grid, hipStream_t s) {
-        const int bytes = W::bwd_lds_floats * 4;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_bwd_kernel<D, H, PASS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbd_bwd_kernel<D, H, PASS>), dim3(grid), dim3(256), bytes, s, a);
-        return hipGetLastError();
+        return launch_lds<hjbd_bwd_kernel<D, H, PASS, X3, SQ>>(dim3(grid), dim3(256), W::bwd_lds_floats * 4, s, a);
     }
-    static hipError_t bwd(const DnetArgs& a, int grid, hipStream_t s) {
+    // the weight-gradient outer products: fp32, X3 = split products (detached adaptive runs), SQ = squared (second moment of the
+    // per-trajectory gradients, fp32)
+    template <bool X3, bool SQ>
+    static hipError_t bwd_as(const DnetArgs& a, int grid, hipStream_t s) {
         if constexpr (kPasses == 1) {
-            return bwd_pass<0>(a, grid, s);
+            return bwd_pass<0, X3, SQ>(a, grid, s);
         } else if constexpr (kPasses == 2) {
-            hipError_t e = bwd_pass<1>(a, grid, s);
-            return e != hipSuccess ? e : bwd_pass<2>(a, grid, s);
+            const hipError_t e = bwd_pass<1, X3, SQ>(a, grid, s);
+            return e != hipSuccess ? e : bwd_pass<2, X3, SQ>(a, grid, s);
         } else {
             return hipErrorNotSupported;
         }
     }
-    template <int PASS>
-    static hipError_t bwd_pass_x3(const DnetArgs& a, int grid, hipStream_t s) {
-        const int bytes = W::bwd_lds_floats * 4;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_bwd_kernel<D, H, PASS, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbd_bwd_kernel<D, H, PASS, true>), dim3(grid), dim3(256), bytes, s, a);
-        return hipGetLastError();
-    }
-    static hipError_t bwd_x3(const DnetArgs& a, int grid, hipStream_t s) {       // split-product outer products (detached adaptive runs)
-        if constexpr (kPasses == 1) {
-            return bwd_pass_x3<0>(a, grid, s);
-        } else if constexpr (kPasses == 2) {
-            hipError_t e = bwd_pass_x3<1>(a, grid, s);
-            return e != hipSuccess ? e : bwd_pass_x3<2>(a, grid, s);
-        } else {
-            return hipErrorNotSupported;
-        }
-    }
-    template <int PASS>
-    static hipError_t bwd_pass_sq(const DnetArgs& a, int grid, hipStream_t s) {
-        const int bytes = W::bwd_lds_floats * 4;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbd_bwd_kernel<D, H, PASS, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbd_bwd_kernel<D, H, PASS, false, true>), dim3(grid), dim3(256), bytes, s, a);
-        return hipGetLastError();
-    }
-    static hipError_t bwd_sq(const DnetArgs& a, int grid, hipStream_t s) {       // second moment of the per-trajectory gradients
-        if constexpr (kPasses == 1) {
-            return bwd_pass_sq<0>(a, grid, s);
-        } else if constexpr (kPasses == 2) {
-            hipError_t e = bwd_pass_sq<1>(a, grid, s);
-            return e != hipSuccess ? e : bwd_pass_sq<2>(a, grid, s);
-        } else {
-            return hipErrorNotSupported;
-        }
-    }
+    // the table's entries: plain members in the table's order, which is the order of the kernels in the code object
+    static hipError_t bwd(const DnetArgs& a, int grid, hipStream_t s) { return bwd_as<false, false>(a, grid, s); }
+    static hipError_t adj(const DnetArgs& a, int grid, hipStream_t s) { return adj_as<false>(a, grid, s); }
+    static hipError_t adj_x3(const DnetArgs& a, int grid, hipStream_t s) { return adj_as<true>(a, grid, s); }
+    static hipError_t bwd_x3(const DnetArgs& a, int grid, hipStream_t s) { return bwd_as<true, false>(a, grid, s); }
+    static hipError_t bwd_sq(const DnetArgs& a, int grid, hipStream_t s) { return bwd_as<false, true>(a, grid, s); }
     static DnetInstance instance() {
         // (set / shared table sizes: the larger of the fp32 and the split layouts -- the caller allocates one region for both)
         return DnetInstance{D, H, W::lds_floats * 4, W::set_floats > W::set_floats_x3 ? W::set_floats : W::set_floats_x3, W::vec_floats,

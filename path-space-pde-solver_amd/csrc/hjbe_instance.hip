@@ -6,11 +6,7 @@ namespace psp {
 namespace {
 template <int DB, int CTRL>
 hipError_t launch_one(const IsArgs& a, int grid, int lds_bytes, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbe_rollout_kernel<DB, CTRL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((hjbe_rollout_kernel<DB, CTRL>), dim3(grid), dim3(kIsThreads), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<hjbe_rollout_kernel<DB, CTRL>>(dim3(grid), dim3(kIsThreads), lds_bytes, stream, a);
 }
 
 template <int DB>

@@ -751,21 +751,11 @@ struct HjbqLaunch {
     static int lds_bytes() { return GeoQ<D, H>::fits ? GeoQ<D, H>::lds_floats * 4 : (1 << 30); }
     template <int FAST>
     static hipError_t fwd_as(const HjbArgs& a, int grid, hipStream_t s) {
-        const int bytes = lds_bytes();
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbq_fwd_kernel<D, H, FAST>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbq_fwd_kernel<D, H, FAST>), dim3(grid), dim3(GeoQ<D, H>::NT), bytes, s, a);
-        return hipGetLastError();
+        return launch_lds<hjbq_fwd_kernel<D, H, FAST>>(dim3(grid), dim3(GeoQ<D, H>::NT), lds_bytes(), s, a);
     }
     static hipError_t adj(const HjbArgs& a, int grid, hipStream_t s) {
         if constexpr (GeoQ<D, H>::fits) {
-            const int bytes = lds_bytes();
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbq_adj_kernel<D, H>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((hjbq_adj_kernel<D, H>), dim3(grid), dim3(512), bytes, s, a);
-            return hipGetLastError();
+            return launch_lds<hjbq_adj_kernel<D, H>>(dim3(grid), dim3(512), lds_bytes(), s, a);
         } else {
             return hipErrorInvalidValue;
         }

@@ -428,12 +428,7 @@ struct HjbsLaunch {
     static int lds_bytes() { return GeoS<D, H>::lds_floats * 4; }
     template <int FAST>
     static hipError_t fwd_as(const HjbArgs& a, int grid, hipStream_t s) {
-        const int bytes = lds_bytes();
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbs_fwd_kernel<D, H, FAST>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbs_fwd_kernel<D, H, FAST>), dim3(grid), dim3(64 * GeoS<D, H>::W), bytes, s, a);
-        return hipGetLastError();
+        return launch_lds<hjbs_fwd_kernel<D, H, FAST>>(dim3(grid), dim3(64 * GeoS<D, H>::W), lds_bytes(), s, a);
     }
     static hipError_t fwd(const HjbArgs& a, int grid, hipStream_t s) {
         const bool fast = a.noise_mode == NOISE_PHILOX && a.uref == nullptr && a.tfeat == nullptr;

@@ -1975,74 +1975,37 @@ struct HjbwLaunch {
         return ((D <= 256) && (GeoB2<D, H>::lds_floats * 4 <= 160 * 1024) && (G::HB == 4)) ? GeoB2<D, H>::lds_floats * 4 : W::bwd_lds_floats * 4;
     }
     static hipError_t tables(const HjbArgs& a, int backward, hipStream_t s) {
-        hipLaunchKernelGGL((hjbw_tables_kernel<D, H>), dim3(256), dim3(256), 0, s, a, backward);
-        return hipGetLastError();
+        return launch<hjbw_tables_kernel<D, H>>(dim3(256), dim3(256), 0, s, a, backward);
+    }
+    template <bool LOGU, bool PHILOX, bool X3>
+    static hipError_t fwd_as(const HjbArgs& a, int grid, int block, hipStream_t s) {
+        const hipError_t e = tables(a, X3 ? 3 : 0, s);
+        if (e != hipSuccess) return e;
+        return launch_lds<hjbw_fwd_kernel<D, H, LOGU, PHILOX, X3>>(dim3(grid), dim3(block), (X3 ? W::fwd_x3_lds_floats : W::fwd_lds_floats) * 4, s, a);
     }
     static hipError_t fwd(const HjbArgs& a, int grid, int block, hipStream_t s) {
-        hipError_t e = tables(a, 0, s);
-        if (e != hipSuccess) return e;
-        const int bytes = W::fwd_lds_floats * 4;
-        if (a.uref) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_fwd_kernel<D, H, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((hjbw_fwd_kernel<D, H, true>), dim3(grid), dim3(block), bytes, s, a);
-            return hipGetLastError();
-        }
-        if (a.noise_mode == NOISE_PHILOX && a.tfeat == nullptr) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_fwd_kernel<D, H, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((hjbw_fwd_kernel<D, H, false, true>), dim3(grid), dim3(block), bytes, s, a);
-            return hipGetLastError();
-        }
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_fwd_kernel<D, H, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbw_fwd_kernel<D, H, false>), dim3(grid), dim3(block), bytes, s, a);
-        return hipGetLastError();
+        if (a.uref) return fwd_as<true, false, false>(a, grid, block, s);
+        if (a.noise_mode == NOISE_PHILOX && a.tfeat == nullptr) return fwd_as<false, true, false>(a, grid, block, s);
+        return fwd_as<false, false, false>(a, grid, block, s);
     }
     // split-product forward (training launches and supplied-noise runs; the u_L2-logging instance stays fp32)
     static int fwd_x3_lds(int, int) { return W::fwd_x3_lds_floats * 4; }
     static hipError_t fwd_x3(const HjbArgs& a, int grid, int block, hipStream_t s) {
         if (a.uref) return fwd(a, grid, block, s);
-        hipError_t e = tables(a, 3, s);
-        if (e != hipSuccess) return e;
-        const int bytes = W::fwd_x3_lds_floats * 4;
         // (a SPEC instance -- hjbw_fwd_kernel's last template argument -- measured SLOWER here: the larger scheduling regions cost the
         //  d = 500 kernel 158 spilled registers, 16.4 -> 18.6 ms, and leave d = 200 unchanged, 3.52 vs 3.56 ms; it is not instantiated)
-        if (a.noise_mode == NOISE_PHILOX && a.tfeat == nullptr) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_fwd_kernel<D, H, false, true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((hjbw_fwd_kernel<D, H, false, true, true>), dim3(grid), dim3(block), bytes, s, a);
-            return hipGetLastError();
-        }
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_fwd_kernel<D, H, false, false, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbw_fwd_kernel<D, H, false, false, true>), dim3(grid), dim3(block), bytes, s, a);
-        return hipGetLastError();
+        if (a.noise_mode == NOISE_PHILOX && a.tfeat == nullptr) return fwd_as<false, true, true>(a, grid, block, s);
+        return fwd_as<false, false, true>(a, grid, block, s);
     }
     // d <= 256: the role-specialised kernel (8 waves, W3^T staged in LDS from the parameters: no table pass), if its LDS fits
     static constexpr bool kRoles = (D <= 256) && (GeoB2<D, H>::lds_floats * 4 <= 160 * 1024) && (G::HB == 4);
     static hipError_t bwd2(const HjbArgs& a, int grid, hipStream_t s) {
         if constexpr (kRoles) {
-            const int bytes = GeoB2<D, H>::lds_floats * 4;
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_bwd2_kernel<D, H>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((hjbw_bwd2_kernel<D, H>), dim3(grid), dim3(512), bytes, s, a);
-            return hipGetLastError();
+            return launch_lds<hjbw_bwd2_kernel<D, H>>(dim3(grid), dim3(512), GeoB2<D, H>::lds_floats * 4, s, a);
         }
-        hipError_t e = tables(a, 1, s);
+        const hipError_t e = tables(a, 1, s);
         if (e != hipSuccess) return e;
-        const int bytes = W::bwd_lds_floats * 4;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_bwd_kernel<D, H>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbw_bwd_kernel<D, H>), dim3(grid), dim3(256), bytes, s, a);
-        return hipGetLastError();
+        return launch_lds<hjbw_bwd_kernel<D, H>>(dim3(grid), dim3(256), W::bwd_lds_floats * 4, s, a);
     }
     // split-product backward for the instances that run hjbw_bwd_kernel (d > 256: one wave per SIMD)
     static hipError_t bwd2_x3(const HjbArgs& a, int grid, hipStream_t s) {
@@ -2052,40 +2015,21 @@ struct HjbwLaunch {
         if constexpr (kRoles || D <= 256) {
             return bwd2(a, grid, s);
         } else {
-            hipError_t e = tables(a, 5, s);
+            const hipError_t e = tables(a, 5, s);
             if (e != hipSuccess) return e;
-            const int bytes = BwdX3Lds<D, H>::floats * 4;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_bwd_x3_kernel<D, H>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((hjbw_bwd_x3_kernel<D, H>), dim3(grid), dim3(256), bytes, s, a);
-            return hipGetLastError();
+            return launch_lds<hjbw_bwd_x3_kernel<D, H>>(dim3(grid), dim3(256), BwdX3Lds<D, H>::floats * 4, s, a);
         }
     }
-    static hipError_t adj(const HjbArgs& a, int grid, int block, hipStream_t s) {
-        hipError_t e = tables(a, 2, s);
+    template <bool X3>
+    static hipError_t adj_as(const HjbArgs& a, int grid, int block, hipStream_t s) {
+        const hipError_t e = tables(a, X3 ? 4 : 2, s);
         if (e != hipSuccess) return e;
-        const int bytes = W::fwd_lds_floats * 4;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_adj_kernel<D, H>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbw_adj_kernel<D, H>), dim3(grid), dim3(block), bytes, s, a);
-        return hipGetLastError();
-    }
-    static hipError_t adj_x3(const HjbArgs& a, int grid, int block, hipStream_t s) {
-        hipError_t e = tables(a, 4, s);
-        if (e != hipSuccess) return e;
-        const int bytes = W::fwd_x3_lds_floats * 4;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_adj_kernel<D, H, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjbw_adj_kernel<D, H, true>), dim3(grid), dim3(block), bytes, s, a);
-        return hipGetLastError();
+        return launch_lds<hjbw_adj_kernel<D, H, X3>>(dim3(grid), dim3(block), (X3 ? W::fwd_x3_lds_floats : W::fwd_lds_floats) * 4, s, a);
     }
     static HjbInstance instance() {
         HjbInstance r{D, H, G::P, &fwd_lds, &fwd, G::PB, &bwd2_lds, &bwd2};
-        r.launch_adj = &adj;
-        r.launch_adj_x3 = &adj_x3;
+        r.launch_adj = &adj_as<false>;
+        r.launch_adj_x3 = &adj_as<true>;
         r.launch_bwd2_x3 = &bwd2_x3;
         r.wide = 1;
         r.bwd2_one_per_cu = kRoles ? 1 : 0;

@@ -375,12 +375,7 @@ struct HjbwxLaunch {
     static constexpr bool kOk = (D <= 256) && (Geo<D, H>::HB == 4) && (BX::lds_floats * 4 <= 160 * 1024);
     static hipError_t bwd(const HjbArgs& a, int grid, hipStream_t s) {
         if constexpr (kOk) {
-            const int bytes = BX::lds_floats * 4;
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjbw_bwd2x_kernel<D, H>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((hjbw_bwd2x_kernel<D, H>), dim3(grid), dim3(512), bytes, s, a);
-            return hipGetLastError();
+            return launch_lds<hjbw_bwd2x_kernel<D, H>>(dim3(grid), dim3(512), BX::lds_floats * 4, s, a);
         }
         return hipErrorNotSupported;
     }

@@ -672,20 +672,12 @@ template <int D, int H>
 struct HjbxLaunch {
     using X = GeoX<D, H>;
     static int lds_bytes() { return X::lds_floats() * 4; }
+    template <bool PATH4>
+    static hipError_t bwd_as(const HjbArgs& a, int grid, hipStream_t s) {
+        return launch_lds<hjb_bwd3_kernel<D, H, PATH4>>(dim3(grid), dim3(512), lds_bytes(), s, a);
+    }
     static hipError_t bwd(const HjbArgs& a, int grid, hipStream_t s) {
-        const int bytes = lds_bytes();
-        if (a.store_path == 4) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjb_bwd3_kernel<D, H, true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((hjb_bwd3_kernel<D, H, true>), dim3(grid), dim3(512), bytes, s, a);
-            return hipGetLastError();
-        }
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hjb_bwd3_kernel<D, H, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hjb_bwd3_kernel<D, H, false>), dim3(grid), dim3(512), bytes, s, a);
-        return hipGetLastError();
+        return a.store_path == 4 ? bwd_as<true>(a, grid, s) : bwd_as<false>(a, grid, s);
     }
 };
 

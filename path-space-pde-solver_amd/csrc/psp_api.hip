@@ -9,6 +9,7 @@
 #include <rccl/rccl.h>   // types only: the entry points are bound with dlsym at first use (psp_comm_*)
 
 #include "../../include/psp.h"
+#include "launch.h"
 #include "hjb_kernels.h"
 #include "hjb_basis_kernels.h"
 #include "gen_kernels.h"
@@ -68,6 +69,7 @@ int fail_hip(hipError_t e, const char* where) {
     snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
     return -10;
 }
+int hip_rc(hipError_t e, const char* where) { return e == hipSuccess ? 0 : fail_hip(e, where); }   // how a launching entry point ends
 
 // one (d, H) -> instance table per kernel family (the .def files list what build.py compiled)
 template <class Inst> struct Entry { int d, H; Inst (*fn)(); };
@@ -117,9 +119,7 @@ bool find_instance(int d, int H, psp::HjbInstance* out) {
 // launch one of the small kernels below and report a refused launch as "<kernel> launch: <HIP error>" (0, or the code of fail_hip)
 template <auto Kernel, class... Args>
 int launch_checked(const char* what, dim3 grid, dim3 block, size_t lds_bytes, void* stream, Args... args) {
-    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, (hipStream_t)stream, args...);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip(e, what);
+    return hip_rc(psp::launch<Kernel>(grid, block, lds_bytes, (hipStream_t)stream, args...), what);
 }
 #define PSP_LAUNCH(kernel, ...) launch_checked<kernel>(#kernel " launch", __VA_ARGS__)
 using psp::genl_tables_kernel;     // (so that its message reads "genl_tables_kernel launch" like the others)
@@ -310,6 +310,14 @@ int check_gh_par(int32_t h_kind, const float* h_par, int32_t d) {
     return 0;
 }
 
+// the stopping domain of a psp_gen_config (psp_gen_* and, through its base, psp_genl_*)
+int check_gen_domain(const psp_gen_config& c) {
+    if (c.domain_kind == PSP_DOM_SPHERE && !(c.dom_a > 0.f)) return fail(-1, "sphere radius must be positive");
+    if (c.domain_kind == PSP_DOM_BOX && !(c.dom_a < c.dom_b)) return fail(-1, "box bounds must satisfy X_l < X_r");
+    if (c.domain_kind == PSP_DOM_ANNULUS && !(c.dom_a >= 0.f && c.dom_a < c.dom_b)) return fail(-1, "annulus radii must satisfy 0 <= r_1 < r_2");
+    return 0;
+}
+
 int make_gen_plan(const psp_gen_config* c, GenPlan* p) {
     if (!c) return fail(-1, "null config");
     if (c->d <= 0 || c->H <= 0 || c->K_local <= 0 || c->N <= 0) return fail(-1, "non-positive d/H/K/N");
@@ -322,9 +330,7 @@ int make_gen_plan(const psp_gen_config* c, GenPlan* p) {
         c->domain_kind < 0 || c->domain_kind > PSP_DOM_ANNULUS)        // (_SIN_FULL and _SINNORM2 read sum_i x_i: psp_genl_* only)
         return fail(-1, "config enum out of range");
     if (int rc = check_gh_par(c->h_kind, c->h_par, (c->d_real > 0 && c->d_real < c->d) ? c->d_real : c->d)) return rc;
-    if (c->domain_kind == PSP_DOM_SPHERE && !(c->dom_a > 0.f)) return fail(-1, "sphere radius must be positive");
-    if (c->domain_kind == PSP_DOM_BOX && !(c->dom_a < c->dom_b)) return fail(-1, "box bounds must satisfy X_l < X_r");
-    if (c->domain_kind == PSP_DOM_ANNULUS && !(c->dom_a >= 0.f && c->dom_a < c->dom_b)) return fail(-1, "annulus radii must satisfy 0 <= r_1 < r_2");
+    if (int rc = check_gen_domain(*c)) return rc;
     if (c->drift_kind != PSP_DRIFT_ZERO && !c->drift) return fail(-1, "drift vector missing (double-well kappa / diagonal of A)");
     if ((c->v_steps_out == nullptr) != (c->y_steps_out == nullptr)) return fail(-1, "v_steps_out and y_steps_out go together");
     if (p->inst.fwd_lds_bytes() > kMaxLds)
@@ -346,18 +352,23 @@ int make_gen_plan(const psp_gen_config* c, GenPlan* p) {
     return 0;
 }
 
+// the problem of a psp_gen_config as the psp_gen_* and the psp_genl_* kernels read it; the other fields are each caller's own
+void fill_gen_problem(const psp_gen_config& c, int ntile16, psp::GenArgs* a) {
+    a->drift = c.drift; a->k_offset = c.k_offset; a->K_local = c.K_local; a->N = c.N; a->ntile16 = ntile16;
+    a->dt = c.dt; a->sqdt = c.sqrt_dt; a->T = c.T; a->sigma_scale = c.sigma_scale;
+    a->drift_kind = c.drift_kind; a->h_kind = c.h_kind; a->adaptive = c.adaptive;
+    a->noise_mode = c.noise_mode; a->store_path = c.store_path;
+    a->domain_kind = c.domain_kind; a->dom_a = c.dom_a; a->dom_b = c.dom_b;
+    for (int i = 0; i < 4; ++i) a->h_par[i] = c.h_par[i];
+    a->dwell_form = c.dwell_form ? 1 : 0;
+}
+
 void fill_gen_args(const psp_gen_config* c, const GenPlan& p, psp::GenArgs* a) {
     memset(a, 0, sizeof(*a));
-    a->drift = c->drift; a->k_offset = c->k_offset; a->K_local = c->K_local; a->N = c->N; a->ntile16 = p.ntile16;
-    a->dt = c->dt; a->sqdt = c->sqrt_dt; a->T = c->T; a->sigma_scale = c->sigma_scale;
-    a->drift_kind = c->drift_kind; a->h_kind = c->h_kind; a->adaptive = c->adaptive;
-    a->noise_mode = c->noise_mode; a->store_path = c->store_path;
-    a->domain_kind = c->domain_kind; a->dom_a = c->dom_a; a->dom_b = c->dom_b;
+    fill_gen_problem(*c, p.ntile16, a);
     a->d_real = (c->d_real > 0 && c->d_real < c->d) ? c->d_real : c->d;
-    for (int i = 0; i < 4; ++i) a->h_par[i] = c->h_par[i];
     a->Vsteps = c->v_steps_out; a->Ysteps = c->y_steps_out; a->per_sample = c->per_sample_weights ? 1 : 0;
     a->path16 = (c->mlp_dtype == PSP_MLP_BF16) ? 1 : 0;       // both kernels on bf16 MFMA: bf16-pair path block
-    a->dwell_form = c->dwell_form ? 1 : 0;
 }
 
 // ---- small kernels -------------------------------------------------------------------
@@ -675,8 +686,7 @@ int psp_is_rollout(const psp_is_config* c, const float* xi, uint64_t seed, uint3
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.iter = iter;
     const long long grid = ((long long)c->K_local + psp::kIsThreads - 1) / psp::kIsThreads;
     hipError_t e = psp::is_rollout_launch(a, (int)grid, lds_bytes, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "hjbe_rollout_kernel launch");
-    return 0;
+    return hip_rc(e, "hjbe_rollout_kernel launch");
 }
 
 // ---- DenseNet control (hjbd_kernels.h): time_approx='outer' and DenseNet(d+1 -> d) controls ---------------------
@@ -754,6 +764,21 @@ int make_dnet_plan(const psp_dnet_config* c, DnetPlan* p) {
     p->bwd_ok = (p->inst.bwd_lds_bytes <= kMaxLds && p->inst.bwd_passes > 0) ? 1 : 0;   // else: too many accumulator tiles per wave
     return 0;
 }
+// the net's own shape, as every psp_dnet_* launch passes it
+void fill_dnet_shape(const psp_dnet_config* c, psp::DnetArgs* a) {
+    a->d_real = c->d_real; a->h_real = c->H_real; a->time_input = c->time_input ? 1 : 0; a->per_step = c->per_step ? 1 : 0;
+}
+// the arguments of the weight-gradient outer products (psp_dnet_rollout_bwd and psp_dnet_rollout_bwd_sq)
+psp::DnetArgs dnet_bwd_args(const psp_dnet_config* c, const DnetPlan& p, const float* params, const float* images, const float* w,
+                            float* partial) {
+    const psp_hjb_config* b = &c->base;
+    psp::DnetArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h.params = params; a.h.K_local = b->K_local; a.h.N = b->N; a.h.ntile16 = p.ntile16; a.h.sqdt = b->sqrt_dt; a.h.dt = b->dt;
+    a.pimg = const_cast<float*>(images); a.wts = w; a.partial = partial; a.slices = p.slices;
+    fill_dnet_shape(c, &a);
+    return a;
+}
 }  // namespace
 
 extern "C" int psp_dnet_instance_count(void) { return table_count(kDnetTable); }
@@ -792,19 +817,14 @@ extern "C" int psp_dnet_rollout_bwd(const psp_dnet_config* cfg, const float* par
     if (!p.bwd_ok) return fail(-3, "the hand-written DenseNet-control backward does not cover this instance (accumulator tiles)");
     if (!params || !images || !w || !partial) return fail(-1, "null buffer passed to psp_dnet_rollout_bwd");
     const psp_hjb_config* b = &cfg->base;
-    psp::DnetArgs a;
-    memset(&a, 0, sizeof(a));
-    a.h.params = params; a.h.K_local = b->K_local; a.h.N = b->N; a.h.ntile16 = p.ntile16; a.h.sqdt = b->sqrt_dt; a.h.dt = b->dt;
-    a.pimg = const_cast<float*>(images); a.wts = w; a.partial = partial; a.slices = p.slices;
-    a.d_real = cfg->d_real; a.h_real = cfg->H_real; a.time_input = cfg->time_input ? 1 : 0; a.per_step = cfg->per_step ? 1 : 0;
+    psp::DnetArgs a = dnet_bwd_args(cfg, p, params, images, w, partial);
     // split-product outer products where the stored image is the Brownian increment itself (detached adaptive run: the power-of-two
     // scale of the weight-carrying tiles then needs nothing but the weights); guarded by the fp32 kernel like the other split kernels
     const bool x3 = b->mlp_dtype == PSP_MLP_F16X3 && b->adaptive && b->store_path == 1 && p.inst.launch_bwd_x3;
     auto fp32 = [&]() { return p.inst.launch_bwd(a, p.bwd_grid, (hipStream_t)stream); };
     const hipError_t e = !x3 ? fp32() : launch_either(b->range_flag, a.h.cond, a.h.cond_want,
                                                       [&]() { return p.inst.launch_bwd_x3(a, p.bwd_grid, (hipStream_t)stream); }, fp32);
-    if (e != hipSuccess) return fail_hip(e, "hjbd_bwd_kernel launch");
-    return 0;
+    return hip_rc(e, "hjbd_bwd_kernel launch");
 }
 
 extern "C" int psp_dnet_rollout_bwd_sq(const psp_dnet_config* cfg, const float* params, const float* images, const float* w,
@@ -815,16 +835,9 @@ extern "C" int psp_dnet_rollout_bwd_sq(const psp_dnet_config* cfg, const float* 
     if (!p.bwd_ok || !p.inst.launch_bwd_sq)
         return fail(-3, "the hand-written DenseNet-control backward does not cover this instance (accumulator tiles)");
     if (!params || !images || !w || !partial) return fail(-1, "null buffer passed to psp_dnet_rollout_bwd_sq");
-    const psp_hjb_config* b = &cfg->base;
-    psp::DnetArgs a;
-    memset(&a, 0, sizeof(a));
-    a.h.params = params; a.h.K_local = b->K_local; a.h.N = b->N; a.h.ntile16 = p.ntile16; a.h.sqdt = b->sqrt_dt; a.h.dt = b->dt;
-    a.pimg = const_cast<float*>(images); a.wts = w; a.partial = partial; a.slices = p.slices;
-    a.d_real = cfg->d_real; a.h_real = cfg->H_real; a.time_input = cfg->time_input ? 1 : 0; a.per_step = cfg->per_step ? 1 : 0;
     // always the fp32 MFMAs, never predicated on the range flag: squares of ~1/K-scaled tiles have no place on the f16 pipe
-    const hipError_t e = p.inst.launch_bwd_sq(a, p.bwd_grid, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "hjbd_bwd_kernel (squared outer products) launch");
-    return 0;
+    const psp::DnetArgs a = dnet_bwd_args(cfg, p, params, images, w, partial);
+    return hip_rc(p.inst.launch_bwd_sq(a, p.bwd_grid, (hipStream_t)stream), "hjbd_bwd_kernel (squared outer products) launch");
 }
 
 // ---- gradient-variance diagnostic: slices -> moments -> sqrt(var) / mean, one workgroup per time step -----------------------
@@ -934,14 +947,13 @@ extern "C" int psp_dnet_adjoint_sweep(const psp_dnet_config* cfg, const float* p
     fill_problem(b, p.ntile16, &h);
     h.params = params; h.XN = const_cast<float*>(XN); h.adj_mu = mu; h.adj_nu = nu; h.adj_wT = wT;
     a.tbl = tables; a.pimg = images;
-    a.d_real = cfg->d_real; a.h_real = cfg->H_real; a.time_input = cfg->time_input ? 1 : 0; a.per_step = cfg->per_step ? 1 : 0;
+    fill_dnet_shape(cfg, &a);
     a.coord_split = b->coord_split;
     const bool x3 = b->mlp_dtype == PSP_MLP_F16X3 && p.inst.launch_adj_x3 && p.inst.lds_bytes_x3 <= kMaxLds;
     auto fp32 = [&]() { return p.inst.launch_adj(a, p.grid, (hipStream_t)stream); };
     const hipError_t e = !x3 ? fp32() : launch_either(b->range_flag, h.cond, h.cond_want,           // range guard: both sweeps, predicated
                                                       [&]() { return p.inst.launch_adj_x3(a, p.grid, (hipStream_t)stream); }, fp32);
-    if (e != hipSuccess) return fail_hip(e, "hjbd_adj_kernel launch");
-    return 0;
+    return hip_rc(e, "hjbd_adj_kernel launch");
 }
 
 extern "C" int psp_dnet_ul2_stage(const psp_dnet_config* cfg, float* tables, void* stream) {
@@ -955,8 +967,7 @@ extern "C" int psp_dnet_ul2_stage(const psp_dnet_config* cfg, float* tables, voi
     a.h.N = cfg->base.N; a.h.uref = cfg->ul2_tables;
     a.tbl = tables; a.ul2_gofs = p.ul2_gofs;
     hipError_t e = p.inst.launch_ul2_stage(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "hjbd_tables_kernel (gain tables) launch");
-    return 0;
+    return hip_rc(e, "hjbd_tables_kernel (gain tables) launch");
 }
 
 extern "C" int psp_dnet_rollout_fwd(const psp_dnet_config* cfg, const float* params, const float* x0, int32_t x0_stride,
@@ -985,7 +996,7 @@ extern "C" int psp_dnet_rollout_fwd(const psp_dnet_config* cfg, const float* par
     a.tbl = tables; a.px = px; a.pxi = pxi;
     if ((cfg->r1_out == nullptr) != (cfg->r2_out == nullptr)) return fail(-1, "r1_out and r2_out go together");
     a.pr1 = cfg->r1_out; a.pr2 = cfg->r2_out; a.pimg = cfg->images_out;
-    a.d_real = cfg->d_real; a.h_real = cfg->H_real; a.time_input = cfg->time_input ? 1 : 0; a.per_step = cfg->per_step ? 1 : 0;
+    fill_dnet_shape(cfg, &a);
     a.coord_split = b->coord_split;
     if (p.ul2) {                               // u_L2 log: h.uref = the kind's reference data (non-null selects the LOGU kernels)
         h.uref = cfg->ul2_kind == PSP_UL2_TABLE ? b->u_ref : cfg->ul2_tables;
@@ -1003,8 +1014,7 @@ extern "C" int psp_dnet_rollout_fwd(const psp_dnet_config* cfg, const float* par
                            [&]() { return PSP_LAUNCH(range_flag_partials_kernel, dim3(1), dim3(256), 0, stream, fwd_partial, 2 * p.grid, b->range_flag); },
                            fp32);
     const hipError_t e = fp32();
-    if (e != hipSuccess) return fail_hip(e, "hjbd_fwd_kernel launch");
-    return 0;
+    return hip_rc(e, "hjbd_fwd_kernel launch");
 }
 
 // ---- linear / affine / constant controls (aff_kernels.h): time_approx='outer' with a list of Linear / Affine / Constant ---------
@@ -1109,7 +1119,7 @@ int psp_aff_rollout_fwd(const psp_aff_config* cfg, const float* maps, const floa
     a.D = D_out; a.XN = XN_out; a.Yout = Y_out; a.fwd_partial = fwd_partial; a.path = path;
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.iter = iter;
     const hipError_t e = p.inst.launch_fwd(a, p.grid, p.threads, p.lds_fwd, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail_hip(e, "aff_fwd_kernel launch");
+    return hip_rc(e, "aff_fwd_kernel launch");
 }
 
 int psp_aff_terminal_reduce(const psp_aff_config* cfg, const double* fwd_partial, double* sums_out, void* stream) {
@@ -1136,7 +1146,7 @@ int psp_aff_adjoint_sweep(const psp_aff_config* cfg, const float* maps, float* p
     aff_fill(cfg, p, &a);
     a.M = maps; a.path = path; a.XN = const_cast<float*>(XN); a.mu = mu; a.nu = nu; a.wT = wT;
     const hipError_t e = p.inst.launch_adj(a, p.grid, p.threads, p.lds_adj, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail_hip(e, "aff_adj_kernel launch");
+    return hip_rc(e, "aff_adj_kernel launch");
 }
 
 int psp_aff_rollout_bwd(const psp_aff_config* cfg, const float* path, const float* w, float* partial, void* stream) {
@@ -1149,7 +1159,7 @@ int psp_aff_rollout_bwd(const psp_aff_config* cfg, const float* path, const floa
     aff_fill(cfg, p, &a);
     a.path = const_cast<float*>(path); a.w = w; a.partial = partial; a.has_matrix = cfg->has_matrix ? 1 : 0;
     const hipError_t e = p.inst.launch_bwd(a, p.bwd_grid, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail_hip(e, "aff_bwd_kernel launch");
+    return hip_rc(e, "aff_bwd_kernel launch");
 }
 
 int psp_debug_set_stamp_buffer(unsigned long long* buf, int64_t n_entries) {
@@ -1242,8 +1252,7 @@ int psp_hjb_rollout_fwd(const psp_hjb_config* cfg, const float* params, const fl
             : p.fwd_split ? p.inst.launch_fwd_split(a, p.fwd_grid, (hipStream_t)stream)
                           : p.inst.launch_fwd(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream);
     }
-    if (e != hipSuccess) return fail_hip(e, "hjb_fwd_kernel launch");
-    return 0;
+    return hip_rc(e, "hjb_fwd_kernel launch");
 }
 
 int psp_hjb_rollout_eval(const psp_hjb_config* cfg, const float* params, const float* x0, int32_t x0_stride,
@@ -1267,8 +1276,7 @@ int psp_hjb_rollout_eval(const psp_hjb_config* cfg, const float* params, const f
     hipError_t e = p.fwd_quad ? p.inst.launch_fwd_quad(a, p.fwd_grid, (hipStream_t)stream)
                    : p.fwd_split ? p.inst.launch_fwd_split(a, p.fwd_grid, (hipStream_t)stream)
                                  : p.inst.launch_fwd(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "hjb_fwd_kernel (eval) launch");
-    return 0;
+    return hip_rc(e, "hjb_fwd_kernel (eval) launch");
 }
 
 int psp_hjb_terminal_reduce(const psp_hjb_config* cfg, const double* fwd_partial, double* sums_out, void* stream) {
@@ -1388,8 +1396,7 @@ int psp_hjb_adjoint_sweep(const psp_hjb_config* cfg, const float* params, float*
     a.tables = reinterpret_cast<float*>(fwd_partial + 2 * (size_t)p.fwd_grid);
     if (p.fwd_quad && p.inst.launch_adj_quad) {           // smallest K: four trajectories per workgroup (hjbq_adj_kernel)
         hipError_t eq = p.inst.launch_adj_quad(a, 4 * p.ntile16, (hipStream_t)stream);
-        if (eq != hipSuccess) return fail_hip(eq, "hjbq_adj_kernel launch");
-        return 0;
+        return hip_rc(eq, "hjbq_adj_kernel launch");
     }
     // one wave per 16-trajectory tile, like the forward kernels (the recursion is sequential in time)
     const int fw = tile_waves(p.ntile16, p.inst.wide);
@@ -1398,8 +1405,7 @@ int psp_hjb_adjoint_sweep(const psp_hjb_config* cfg, const float* params, float*
     auto fp32 = [&]() { return p.inst.launch_adj(a, grid, fw * 64, (hipStream_t)stream); };
     const hipError_t e = !adj_x3 ? fp32() : launch_either(cfg->range_flag, a.cond, a.cond_want,    // range guard: both sweeps, predicated
                                                           [&]() { return p.inst.launch_adj_x3(a, grid, fw * 64, (hipStream_t)stream); }, fp32);
-    if (e != hipSuccess) return fail_hip(e, "hjb_adj_kernel launch");
-    return 0;
+    return hip_rc(e, "hjb_adj_kernel launch");
 }
 
 int psp_gen_supported(int32_t d, int32_t H) {
@@ -1457,8 +1463,7 @@ int psp_gen_rollout_fwd(const psp_gen_config* cfg, const float* params, const fl
                            fp32);
     }
     const hipError_t e = cfg->mlp_dtype != PSP_MLP_FP32 ? p.inst.launch_fwd_bf16(a, p.fwd_grid, p.fwd_waves * 64, (hipStream_t)stream) : fp32();
-    if (e != hipSuccess) return fail_hip(e, "gen_fwd_kernel launch");
-    return 0;
+    return hip_rc(e, "gen_fwd_kernel launch");
 }
 
 int psp_gen_rollout_bwd(const psp_gen_config* cfg, const float* params, const float* path, const float* ahat,
@@ -1560,9 +1565,7 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs*
     if (int rc = check_gh_par(b.h_kind, b.h_par, b.d)) return rc;
     if (c->sigma_kind == PSP_GENL_SIGMA_DENSE && !c->sigma) return fail(-1, "sigma matrix missing");
     if (c->activation < 0 || c->activation > PSP_ACT_TANH) return fail(-1, "value net: unknown activation");
-    if (b.domain_kind == PSP_DOM_SPHERE && !(b.dom_a > 0.f)) return fail(-1, "sphere radius must be positive");
-    if (b.domain_kind == PSP_DOM_BOX && !(b.dom_a < b.dom_b)) return fail(-1, "box bounds must satisfy X_l < X_r");
-    if (b.domain_kind == PSP_DOM_ANNULUS && !(b.dom_a >= 0.f && b.dom_a < b.dom_b)) return fail(-1, "annulus radii must satisfy 0 <= r_1 < r_2");
+    if (int rc = check_gen_domain(b)) return rc;
     if (b.drift_kind != PSP_DRIFT_ZERO && !b.drift) return fail(-1, "drift vector missing (double-well kappa / diagonal of A)");
     psp::GenlArgs& a = p->a;
     memset(&a, 0, sizeof(a));
@@ -1658,48 +1661,14 @@ int make_genl_plan(const psp_genl_config* c, GenlPlan* p, const psp_genl_coeffs*
     long long grid = per_cu * cus;
     if (grid > nblk) grid = nblk;
     p->bwd_grid = (int)grid;
-    // the GenArgs part: as fill_gen_args
-    psp::GenArgs& g = a.g;
-    g.drift = b.drift; g.k_offset = b.k_offset; g.K_local = b.K_local; g.N = b.N; g.ntile16 = p->ntile16;
-    g.dt = b.dt; g.sqdt = b.sqrt_dt; g.T = b.T; g.sigma_scale = b.sigma_scale;
-    g.drift_kind = b.drift_kind; g.h_kind = b.h_kind; g.adaptive = b.adaptive;
-    g.noise_mode = b.noise_mode; g.store_path = b.store_path;
-    g.domain_kind = b.domain_kind; g.dom_a = b.dom_a; g.dom_b = b.dom_b; g.d_real = b.d;
-    for (int i = 0; i < 4; ++i) g.h_par[i] = b.h_par[i];
-    g.dwell_form = b.dwell_form ? 1 : 0;
+    fill_gen_problem(b, p->ntile16, &a.g);
+    a.g.d_real = b.d;                                      // (every coordinate is real here)
     return 0;
 }
 // the step counts of the tiles live behind the (N + 1) x 16 ceil(K/16) coefficients of `ahat`
 int* genl_nexec(const psp_genl_config* cfg, const GenlPlan& p, const float* ahat) {
     return reinterpret_cast<int*>(const_cast<float*>(ahat)) + (size_t)(cfg->base.N + 1) * p.ntile16 * 16;
 }
-}  // namespace
-
-int psp_genl_query(const psp_genl_config* cfg, psp_genl_sizes* out) { return psp_genl_query_lq(cfg, nullptr, out); }
-
-int psp_genl_query_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, psp_genl_sizes* out) {
-    return psp_genl_query_ul2(cfg, coeffs, nullptr, out);
-}
-
-namespace {
-int genl_sizes_of(const psp_genl_config* cfg, const GenlPlan& p, psp_genl_sizes* out);
-}
-
-int psp_genl_query_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, psp_genl_sizes* out) {
-    GenlPlan p;
-    int rc = make_genl_plan(cfg, &p, coeffs, ul2);
-    if (rc) return rc;
-    return genl_sizes_of(cfg, p, out);
-}
-
-int psp_genl_query_eig(const psp_genl_config* cfg, const psp_genl_eig* eig, psp_genl_sizes* out) {
-    GenlPlan p;
-    int rc = make_genl_plan(cfg, &p, nullptr, nullptr, eig);
-    if (rc) return rc;
-    return genl_sizes_of(cfg, p, out);
-}
-
-namespace {
 int genl_sizes_of(const psp_genl_config* cfg, const GenlPlan& p, psp_genl_sizes* out) {
     if (!out) return fail(-1, "null output");
     memset(out, 0, sizeof(*out));
@@ -1717,6 +1686,26 @@ int genl_sizes_of(const psp_genl_config* cfg, const GenlPlan& p, psp_genl_sizes*
     return 0;
 }
 }  // namespace
+
+int psp_genl_query(const psp_genl_config* cfg, psp_genl_sizes* out) { return psp_genl_query_lq(cfg, nullptr, out); }
+
+int psp_genl_query_lq(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, psp_genl_sizes* out) {
+    return psp_genl_query_ul2(cfg, coeffs, nullptr, out);
+}
+
+int psp_genl_query_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, psp_genl_sizes* out) {
+    GenlPlan p;
+    int rc = make_genl_plan(cfg, &p, coeffs, ul2);
+    if (rc) return rc;
+    return genl_sizes_of(cfg, p, out);
+}
+
+int psp_genl_query_eig(const psp_genl_config* cfg, const psp_genl_eig* eig, psp_genl_sizes* out) {
+    GenlPlan p;
+    int rc = make_genl_plan(cfg, &p, nullptr, nullptr, eig);
+    if (rc) return rc;
+    return genl_sizes_of(cfg, p, out);
+}
 
 int psp_genl_rollout_fwd(const psp_genl_config* cfg, const float* params, const float* x0, const float* t0,
                                     const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path, float* ahat,
@@ -1740,28 +1729,7 @@ int psp_genl_ul2_stage(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs
     p.a.tables = tables; p.a.tables_w = tables;
     const psp::GenlLogArgs la = {p.a, p.u};
     hipError_t e = psp::genl_ul2_launch_stage(la, (hipStream_t)stream);          // (genl_ul2_instance.hip)
-    if (e != hipSuccess) return fail_hip(e, "genl_ul2_stage_kernel launch");
-    return 0;
-}
-
-namespace {
-int genl_rollout_fwd_any(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, const psp_genl_eig* eig,
-                         const float* params, const float* x0, const float* t0, const float* xi, uint64_t seed, uint32_t iter,
-                         float* tables, float* path, float* ahat, float* VN, float* YN, float* XN, float* tN,
-                         unsigned long long* kcount, void* stream);
-}
-
-int psp_genl_rollout_fwd_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, const float* params,
-                             const float* x0, const float* t0, const float* xi, uint64_t seed, uint32_t iter, float* tables,
-                             float* path, float* ahat, float* VN, float* YN, float* XN, float* tN, unsigned long long* kcount,
-                             void* stream) {
-    return genl_rollout_fwd_any(cfg, coeffs, ul2, nullptr, params, x0, t0, xi, seed, iter, tables, path, ahat, VN, YN, XN, tN, kcount, stream);
-}
-
-int psp_genl_rollout_fwd_eig(const psp_genl_config* cfg, const psp_genl_eig* eig, const float* params, const float* x0, const float* t0,
-                             const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path, float* ahat, float* VN,
-                             float* YN, float* XN, float* tN, unsigned long long* kcount, void* stream) {
-    return genl_rollout_fwd_any(cfg, nullptr, nullptr, eig, params, x0, t0, xi, seed, iter, tables, path, ahat, VN, YN, XN, tN, kcount, stream);
+    return hip_rc(e, "genl_ul2_stage_kernel launch");
 }
 
 namespace {
@@ -1803,10 +1771,22 @@ int genl_rollout_fwd_any(const psp_genl_config* cfg, const psp_genl_coeffs* coef
     else
     e = p.nw_fwd == 1 ? psp::genl_launch_fwd<1>(p.a, p.ntile16, p.fwd_lds, st)
         : p.nw_fwd == 4 ? psp::genl_launch_fwd<4>(p.a, p.ntile16, p.fwd_lds, st) : psp::genl_launch_fwd<8>(p.a, p.ntile16, p.fwd_lds, st);
-    if (e != hipSuccess) return fail_hip(e, "genl_fwd_kernel launch");
-    return 0;
+    return hip_rc(e, "genl_fwd_kernel launch");
 }
 }  // namespace
+
+int psp_genl_rollout_fwd_ul2(const psp_genl_config* cfg, const psp_genl_coeffs* coeffs, const psp_genl_ul2* ul2, const float* params,
+                             const float* x0, const float* t0, const float* xi, uint64_t seed, uint32_t iter, float* tables,
+                             float* path, float* ahat, float* VN, float* YN, float* XN, float* tN, unsigned long long* kcount,
+                             void* stream) {
+    return genl_rollout_fwd_any(cfg, coeffs, ul2, nullptr, params, x0, t0, xi, seed, iter, tables, path, ahat, VN, YN, XN, tN, kcount, stream);
+}
+
+int psp_genl_rollout_fwd_eig(const psp_genl_config* cfg, const psp_genl_eig* eig, const float* params, const float* x0, const float* t0,
+                             const float* xi, uint64_t seed, uint32_t iter, float* tables, float* path, float* ahat, float* VN,
+                             float* YN, float* XN, float* tN, unsigned long long* kcount, void* stream) {
+    return genl_rollout_fwd_any(cfg, nullptr, nullptr, eig, params, x0, t0, xi, seed, iter, tables, path, ahat, VN, YN, XN, tN, kcount, stream);
+}
 
 int psp_genl_rollout_bwd(const psp_genl_config* cfg_in, const float* params, const float* tables, const float* path,
                          const float* ahat, const float* wY, const float* wV, float* grad_partial, float* grad_out, void* stream) {
@@ -1900,8 +1880,7 @@ int psp_genl_adjoint_sweep(const psp_genl_config* cfg, const psp_genl_coeffs* co
     aa.coef_out = ahat; aa.wt_out = ws;
     aa.tAT = adj->drift_t_offset;
     hipError_t e = psp::genl_adj_launch(aa, p.nw_fwd, p.ntile16, lds, (hipStream_t)stream);       // (genl_adj_instance.hip)
-    if (e != hipSuccess) return fail_hip(e, "genl_adj_kernel launch");
-    return 0;
+    return hip_rc(e, "genl_adj_kernel launch");
 }
 
 // ---- the K_test_log diagnostic on the device (genl_eval_kernels.h) ----------------------------------------------------------
@@ -1995,8 +1974,7 @@ int psp_genl_test_error(const psp_genl_eval_config* cfg, const float* params, co
     hipStream_t st = (hipStream_t)stream;
     if (const int rct = PSP_LAUNCH(genl_tables_kernel, dim3(128), dim3(256), 0, st, ea.n)) return rct;
     const hipError_t err = psp::genl_eval_launch(ea, e.nw, e.grid, e.lds, st);
-    if (err != hipSuccess) return fail_hip(err, "genl_eval_kernel launch");
-    return 0;
+    return hip_rc(err, "genl_eval_kernel launch");
 }
 
 // ---- collectives: RCCL on the caller's stream, bound lazily so that the library loads without librccl ---------------
@@ -2108,15 +2086,13 @@ int psp_hjb_basis_params(const float* params, float* params_out, const float* B,
     if (rc) return rc;
     if (n_params < (int64_t)H * (d + 1)) return fail(-1, "psp_hjb_basis_params: n_params is smaller than W1");
     hipError_t e = psp::launch_basis_w1<false>(params, params_out, B, d, H, (long long)n_params, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "hjb_basis_w1_kernel launch");
-    return 0;
+    return hip_rc(e, "hjb_basis_w1_kernel launch");
 }
 int psp_hjb_basis_grad(float* grad, const float* B, int32_t d, int32_t H, void* stream) {
     int rc = basis_check(grad, grad, B, d, H, "psp_hjb_basis_grad");
     if (rc) return rc;
     hipError_t e = psp::launch_basis_w1<true>(grad, grad, B, d, H, (long long)H * (d + 1), (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "hjb_basis_w1_kernel launch");
-    return 0;
+    return hip_rc(e, "hjb_basis_w1_kernel launch");
 }
 
 int psp_philox_normal_fill(float* out, int32_t N, int32_t K_local, int32_t d, int64_t k_offset,
@@ -2254,8 +2230,7 @@ int psp_pinn_residual(const psp_pinn_config* cfg, const float* params, const flo
     pinn_scratch(&p, scratch);
     p.a.params = params; p.a.x = x; p.a.t = t; p.a.R = R_out;
     const hipError_t e = psp::pinn_launch_forward(p.a, p.lds_fwd, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "pinn_forward_kernel launch");
-    return 0;
+    return hip_rc(e, "pinn_forward_kernel launch");
 }
 
 int psp_pinn_backward(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, const float* scratch,
@@ -2293,8 +2268,7 @@ int psp_pinn_pairs_residual(const psp_pinn_config* cfg, const float* params, con
     pinn_scratch(&p, scratch);
     p.a.params = params; p.a.x = x; p.a.t = t; p.a.R = A_out;
     const hipError_t e = psp::pinn_launch_forward(p.a, p.lds_fwd, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "pinn_forward_kernel launch");
-    return 0;
+    return hip_rc(e, "pinn_forward_kernel launch");
 }
 
 int psp_pinn_pairs_reduce(const psp_pinn_config* cfg, const float* x, const float* t, const float* scratch, const float* A,
@@ -2314,8 +2288,7 @@ int psp_pinn_pairs_reduce(const psp_pinn_config* cfg, const float* x, const floa
     a.x = x; a.t = t; a.V = p.a.V; a.A = A;
     a.rho = rho_out; a.nu = nu_out; a.work = static_cast<double*>(pair_work); a.loss = loss_out;
     const hipError_t e = psp::pinn_launch_pairs(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "pinn_pair_kernel launch");
-    return 0;
+    return hip_rc(e, "pinn_pair_kernel launch");
 }
 
 int psp_pinn_pairs_backward(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, const float* scratch,

@@ -17,16 +17,16 @@ def _deps(unit):
 
 
 def test_gen_instance_lists_its_headers():
-    assert {"csrc/gen_kernels.h", "csrc/gh_kinds.h", "csrc/hjb_kernels.h"} <= _deps("gen_instance.hip")
+    assert {"csrc/gen_kernels.h", "csrc/gh_kinds.h", "csrc/hjb_kernels.h", "csrc/launch.h"} <= _deps("gen_instance.hip")
 
 
 def test_the_api_unit_lists_the_instance_lists_and_the_header():
     deps = _deps("psp_api.hip")
     assert {"csrc/instances.def", "csrc/gen_instances.def", "csrc/wide_instances.def", "csrc/dense_instances.def",
-            "../include/psp.h"} <= deps
+            "../include/psp.h", "csrc/launch.h"} <= deps
 
 
 def test_pinn_instance_lists_its_headers():
     deps = _deps("pinn_instance.hip")
-    assert {"csrc/pinn_kernels.h", "csrc/gh_kinds.h"} <= deps
+    assert {"csrc/pinn_kernels.h", "csrc/gh_kinds.h", "csrc/launch.h"} <= deps
     assert "csrc/hjb_kernels.h" not in deps                          # the PINN kernels do without the rollouts' MFMA machinery
