@@ -69,7 +69,9 @@ extern "C" {
                          *        PSP_GH_AFFINE_EXP / _SINE_SOURCE / _SINNORM2 (the exit-time and box problems),
                          *        psp_gen_config.dwell_form (the former `reserved`), PSP_VTRUE_LOGQ / _SINPROD / _SINSUM / _SINR2;
                          *        PSP_DRIFT_WELL_DIAG / _RADIAL_WELL, PSP_TERM_QUAD_LINEAR / _RADIAL_QUAD and psp_hjb_config.coord_split
-                         *        (the former `reserved`) -- psp_dnet_* only */
+                         *        (the former `reserved`) -- psp_dnet_* only;
+                         *        psp_loss_stats_state_bytes / psp_loss_stats_accumulate / psp_loss_stats_finish -- the loss
+                         *        estimators' statistics over chunks of (Y_N, D) in double (no struct: the state is a buffer) */
 
 /* drift b(x): reference problems.py:36-37,154-155 (dense), :311-315 (double well) */
 enum { PSP_DRIFT_ZERO = 0, PSP_DRIFT_DENSE = 1, PSP_DRIFT_DIAG = 2, PSP_DRIFT_DOUBLE_WELL = 3 };
@@ -1126,6 +1128,32 @@ int psp_pinn_pairs_reduce(const psp_pinn_config* cfg, const float* x, const floa
  * psp_pinn_backward. */
 int psp_pinn_pairs_backward(const psp_pinn_config* cfg, const float* params, const float* x, const float* t, const float* scratch,
                             const float* rbar, const float* vadd, float* grad_partial, float* grad_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Statistics of the loss estimators (appended in 0.4.0, no version bump; csrc/lstat_kernels.h): what
+ * utilities.loss_relative_errors reduces the chunks of a forward-only rollout with (the reference's notebook
+ * `Compare relative errors of losses.ipynb`).  Per trajectory, from fp32 Y = Y_N and D = Y_N - g(X_N), in double
+ * (g = Y - D is exact there, exp is the double-precision one):
+ *     terminal exp(-g)     cross_entropy Y exp(-g)     cross_entropy_detach Y exp(-g + Y)
+ *     cross_entropy_detach_selection: the same, only samples with |v| < 100 (NaN and inf are not selected)
+ *     moment D^2           log_variance: D up to its fourth central moment
+ * `state` is a DEVICE buffer of psp_loss_stats_state_bytes() bytes, 8-byte aligned, ZEROED by the caller before the first
+ * chunk.  It holds mergeable moments (count, mean, M2; for D also M3, M4) and the per-workgroup partials of a call; no struct
+ * describes it.  psp_loss_stats_accumulate adds n trajectories in three launches: per-workgroup sums, per-workgroup power sums
+ * about the chunk's means, and one workgroup that sums the partials in index order and merges the chunk into the state.
+ * Every sum has a fixed order that depends on n alone (no atomics): equal sequences of calls give equal bits; another split
+ * of the same samples differs by rounding only.  Non-finite samples are not filtered: they make what they enter NaN.
+ * psp_loss_stats_finish writes 20 doubles (DEVICE):
+ *     out[3 e + 0 .. 2] = mean, unbiased variance, sqrt(variance) / |mean|  for e = 0 terminal, 1 cross_entropy,
+ *                         2 cross_entropy_detach, 3 cross_entropy_detach_selection, 5 moment;
+ *     out[12 .. 14]     = log_variance: var(D) unbiased, mean((D - mean D)^4) - var(D)^2, and their relative error;
+ *     out[18] = samples selected by e = 3,  out[19] = samples in all.
+ * A variance over one sample is NaN (0 / 0), as torch.var gives.
+ * -1: a null pointer or n < 0 (nothing is launched); n = 0 is a no-op.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t psp_loss_stats_state_bytes(void);
+int psp_loss_stats_accumulate(const float* Y, const float* D, int64_t n, double* state, void* stream);
+int psp_loss_stats_finish(const double* state, double* out, void* stream);
 
 /* Diagnostics: device buffer that receives per-wave phase cycle sums (8 u64 per wave of the
  * backward kernel).  Returns 1 if the library was built with -DPSP_STAMPS (diagnostic build,

@@ -26,7 +26,7 @@ from .plan_native import PlanUnsupported  # noqa: F401
 from . import native  # noqa: F401
 from . import native_shapes  # noqa: F401
 from . import plan_native, plan_dense_native, plan_general_native, plan_value_native, plan_pinn_native  # noqa: F401
-from .utilities import do_importance_sampling_me  # noqa: F401
+from .utilities import do_importance_sampling_me, loss_relative_errors  # noqa: F401
 
 __all__ = ['Solver', 'GeneralSolver', 'EllipticSolver', 'ExponentialOnSphere', 'ExponentialOnBallNonlinear',
            'ExponentialOnBallNonlinearSin', 'ExponentialOnBallNonlinearSinHessian', 'ExponentialOnSphereNonlinearParabolic', 'QuadraticOnBox', 'Committor', 'LLGC', 'LQGC', 'DoubleWell', 'DoubleWell_multidim', 'DoubleWell_OU', 'DoubleWell_multidim_2', 'DoubleWell_multidim_3', 'LLGC_general_f', 'DoubleWell_multidim_for_general_solver',

@@ -100,7 +100,8 @@ def _build(force, jobs, verbose, only):
              ("genl_ul2_instance.hip", "genl_ul2_inst.o", NOSLP),   # psp_genl_rollout_fwd_ul2 (two shapes, three variants), gain staging
              ("genl_eig_instance.hip", "genl_eig_inst.o", NOSLP),   # psp_genl_rollout_fwd_eig: three waves-per-tile variants
              ("genl_adj_instance.hip", "genl_adj_inst.o", NOSLP),   # psp_genl_adjoint_sweep: three waves-per-tile variants
-             ("pinn_instance.hip", "pinn_inst.o", NOSLP)]           # psp_pinn_*: residual, per-sample finish, adjoint
+             ("pinn_instance.hip", "pinn_inst.o", NOSLP),           # psp_pinn_*: residual, per-sample finish, adjoint
+             ("lstat_instance.hip", "lstat_inst.o", NOSLP)]         # psp_loss_stats_*: the loss estimators' statistics in double
     per_shape = [("hjbd_instance.hip", "dnet_inst", "dense_instances.def", NOSLP, 1 << 30),
                  ("hjb_instance.hip", "inst", "instances.def", NOSLP, 1 << 30),
                  ("hjbw_instance.hip", "wide_inst", "wide_instances.def", CLASSIC, 1 << 30),

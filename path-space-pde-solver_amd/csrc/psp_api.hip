@@ -21,6 +21,7 @@
 #include "hjbe_kernels.h"
 #include "aff_kernels.h"
 #include "pinn_kernels.h"
+#include "lstat_kernels.h"
 
 // The kernels keep the header's enums numerically (device code does not include the C header): every such numbering, tied here.
 #define PSP_SAME(a, b) static_assert(int(a) == int(b), #a " != " #b)
@@ -2303,6 +2304,23 @@ int psp_pinn_pairs_backward(const psp_pinn_config* cfg, const float* params, con
     const hipError_t e = psp::pinn_launch_backward(p.a, p.lds_bwd, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "pinn_backward_kernel launch");
     return PSP_LAUNCH(reduce_grad_kernel, dim3((p.a.P + 31) / 32), dim3(256), 0, stream, grad_partial, p.a.G, p.a.P, grad_out);
+}
+
+// ---- statistics of the loss estimators over chunks of (Y_N, D) (csrc/lstat_kernels.h) ------------------------------------------
+int64_t psp_loss_stats_state_bytes(void) { return (int64_t)psp::kLstatStateDoubles * 8; }
+
+int psp_loss_stats_accumulate(const float* Y, const float* D, int64_t n, double* state, void* stream) {
+    if (!Y || !D || !state) return fail(-1, "null buffer passed to psp_loss_stats_accumulate");
+    if (n < 0) return fail(-1, "psp_loss_stats_accumulate: n must not be negative");
+    if (n == 0) return 0;
+    psp::LstatArgs a;
+    a.Y = Y; a.D = D; a.n = n; a.state = state; a.G = psp::lstat_grid(n);
+    return hip_rc(psp::lstat_launch_accumulate(a, (hipStream_t)stream), "lstat kernels launch");
+}
+
+int psp_loss_stats_finish(const double* state, double* out, void* stream) {
+    if (!state || !out) return fail(-1, "null buffer passed to psp_loss_stats_finish");
+    return hip_rc(psp::lstat_launch_finish(state, out, (hipStream_t)stream), "lstat_finish_kernel launch");
 }
 
 }  // extern "C"

@@ -250,6 +250,9 @@ SIGNATURES = {
     "psp_pinn_pairs_residual": (C.c_int, [C.POINTER(PinnConfig), _P, _P, _P, _P, _P, _P]),
     "psp_pinn_pairs_reduce": (C.c_int, [C.POINTER(PinnConfig), _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
     "psp_pinn_pairs_backward": (C.c_int, [C.POINTER(PinnConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psp_loss_stats_state_bytes": (C.c_int64, []),
+    "psp_loss_stats_accumulate": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "psp_loss_stats_finish": (C.c_int, [_P, _P, _P]),
     "psp_genl_query": (C.c_int, [C.POINTER(GenlConfig), C.POINTER(GenlSizes)]),
     "psp_genl_rollout_fwd": (C.c_int, [C.POINTER(GenlConfig), _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P]),

@@ -8,6 +8,10 @@ same controlled Euler-Maruyama rollout as the training step, forward only, at ``
 
 Native plan: psp_hjb_rollout_eval (include/psp.h) on the solver's control net whenever the solver is
 native-eligible; composite torch plan otherwise.  Plotting helpers of the reference are out of scope.
+
+``loss_relative_errors`` is not in the reference's utilities.py: it is the cell of its notebook `Compare relative errors of
+losses.ipynb` (a forward-only rollout of a bare net at K = 5e7 and the statistics of five loss estimators) as a function, in
+chunks on the forward kernels with the statistics reduced on the device in double (psp_loss_stats_*, csrc/lstat_kernels.h).
 """
 import ctypes as C
 
@@ -604,3 +608,395 @@ def compute_test_error_native(model, problem, K, modus='elliptic', seed=None, it
         dumps['keep'] = dumps['keep'].bool()
         return l2, mae, mre, dumps
     return l2, mae, mre
+
+
+# ---- relative errors of the loss estimators (reference `Compare relative errors of losses.ipynb`, third cell) --------------------
+LRE_TILE = 16                                  # the forward kernels' trajectory tile: chunks are whole tiles
+LRE_NATIVE_CHUNK = 1 << 20                     # default chunk of the native plan: two 4 MiB buffers
+LRE_TORCH_CHUNK = 1 << 16                      # ... of the composite plan, which holds (chunk, d) tensors per step
+LRE_MAX_SAMPLES = 1 << 24                      # return_samples keeps two K-sized fp32 buffers
+LRE_REFERENCE_NOISE_LIMIT = 1 << 28            # noise='reference' holds K * N * d floats on the host (1 GiB)
+LRE_PHILOX_FILL_FLOATS = 1 << 27               # the composite plan's materialised Philox stream per chunk on a GPU
+LRE_KEYS = ('terminal', 'cross_entropy', 'cross_entropy_detach', 'cross_entropy_detach_selection', 'log_variance', 'moment')
+LRE_SELECT = 100.0
+
+
+def lre_chunk(K, chunk, default):
+    """The chunk the rollout runs in: `chunk` (None: `default`) rounded up to whole tiles, at most K rounded up."""
+    c = int(default if chunk is None else chunk)
+    if c < 1:
+        raise ValueError('chunk must be positive')
+    up = lambda v: -(-int(v) // LRE_TILE) * LRE_TILE
+    return min(up(c), up(K))
+
+
+def _lre_merge(a, b):
+    """(n, mean, M2, M3, M4) of two sample sets -> of their union (Chan et al. / Pebay), numpy float64 scalars."""
+    na, ma, M2a, M3a, M4a = a
+    nb, mb, M2b, M3b, M4b = b
+    if nb == 0:
+        return a
+    if na == 0:
+        return b
+    n = na + nb
+    dl = mb - ma
+    mean = ma + dl * (nb / n) if np.isfinite(dl) else (na * ma + nb * mb) / n      # an infinite mean stays infinite
+    return (n, mean, M2a + M2b + dl * dl * (na * nb / n),
+            M3a + M3b + dl ** 3 * (na * nb * (na - nb) / (n * n)) + 3.0 * dl * (na * M2b - nb * M2a) / n,
+            M4a + M4b + dl ** 4 * (na * nb * (na * na - na * nb + nb * nb) / (n ** 3))
+            + 6.0 * dl * dl * (na * na * M2b + nb * nb * M2a) / (n * n) + 4.0 * dl * (na * M3b - nb * M3a) / n)
+
+
+class _HostLossStats:
+    """The statistics of psp_loss_stats_* in float64 torch on the host: the composite plan where there is no GPU."""
+
+    def __init__(self):
+        zero = tuple(np.float64(0.0) for _ in range(5))
+        self.acc = [zero] * 6                    # terminal, CE, CE detached, its selection, moment, D
+
+    @staticmethod
+    def _moments(v):
+        n = v.numel()
+        if n == 0:
+            return tuple(np.float64(0.0) for _ in range(5))
+        m = v.mean()
+        c = v - m
+        e = c.sum() / n
+        c = c - (e if torch.isfinite(e) else 0.0)
+        e = e if torch.isfinite(e) else torch.zeros(())
+        c2 = c * c
+        return tuple(np.float64(x) for x in (n, (m + e).item(), c2.sum().item(), (c2 * c).sum().item(), (c2 * c2).sum().item()))
+
+    def accumulate(self, Y, D):
+        y, d = Y.detach().cpu().double(), D.detach().cpu().double()
+        g = y - d
+        ced = y * torch.exp(-g + y)
+        samples = (torch.exp(-g), y * torch.exp(-g), ced, ced[ced.abs() < LRE_SELECT], d * d, d)
+        with np.errstate(all='ignore'):
+            self.acc = [_lre_merge(a, self._moments(v)) for a, v in zip(self.acc, samples)]
+
+    def finish(self):
+        out = np.full(20, np.nan)
+        with np.errstate(all='ignore'):
+            for slot, a in zip((0, 1, 2, 3, 5), self.acc[:5]):
+                mean = a[1] if a[0] > 0 else np.float64(np.nan)
+                var = a[2] / (a[0] - 1.0)
+                out[3 * slot:3 * slot + 3] = mean, var, np.sqrt(var) / abs(mean)
+            n, _, M2, _, M4 = self.acc[5]
+            var = M2 / (n - 1.0)
+            vv = M4 / n - var * var
+            out[12:15] = var, vv, np.sqrt(vv) / abs(var)
+            out[18], out[19] = self.acc[3][0], n
+        return out
+
+
+class _DeviceLossStats:
+    """psp_loss_stats_accumulate / psp_loss_stats_finish (csrc/lstat_kernels.h) on a device-resident state."""
+
+    def __init__(self, dev):
+        self.lib, self.dev = nat.load(), dev
+        self.state = torch.zeros(self.lib.psp_loss_stats_state_bytes() // 8, dtype=torch.float64, device=dev)
+
+    def accumulate(self, Y, D):
+        nat.check(self.lib.psp_loss_stats_accumulate(nat.ptr(Y), nat.ptr(D), Y.numel(), nat.ptr(self.state),
+                                                     nat.stream_ptr(self.dev)), 'psp_loss_stats_accumulate')
+
+    def finish(self):
+        out = torch.empty(20, dtype=torch.float64, device=self.dev)
+        nat.check(self.lib.psp_loss_stats_finish(nat.ptr(self.state), nat.ptr(out), nat.stream_ptr(self.dev)),
+                  'psp_loss_stats_finish')
+        return out.cpu().numpy()                 # the one read-back of the call
+
+
+def _lre_control(control, N):
+    """(z_n, time_approx) of a bare net, a list of per-step nets or a Solver."""
+    if hasattr(control, 'z_n') and hasattr(control, 'time_approx'):
+        if getattr(control, 'approx_method', 'control') != 'control':
+            raise ValueError("a Solver's control is read from z_n: approx_method must be 'control'")
+        z, ta = control.z_n, control.time_approx
+    elif isinstance(control, (list, tuple, torch.nn.ModuleList)):
+        z, ta = list(control), 'outer'
+    elif callable(control):
+        z, ta = control, 'inner'
+    else:
+        raise TypeError('control must be a net of (t, x), a list of per-step nets of x or a Solver')
+    if ta == 'outer':
+        z = list(z)
+        if len(z) != N:
+            raise ValueError('a per-step control needs one net per time step: N = floor(T / delta_t) = %d, got %d' % (N, len(z)))
+    return z, ta
+
+
+def _lre_plan(problem, view):
+    """(kernel family 'dnet' / 'hjb', None) or (None, the reason for the composite plan)."""
+    try:
+        from .function_space import DenseNet, MySequential
+    except ImportError:
+        from function_space import DenseNet, MySequential
+    if view.backend == 'torch':
+        return None, "backend='torch' requested"
+    first = view.z_n[0] if view.time_approx == 'outer' else view.z_n
+    if not isinstance(first, (DenseNet, MySequential)) or (isinstance(first, MySequential) and view.time_approx != 'inner'):
+        return None, ('the control is a user net (the forward kernels take a DenseNet(d + 1 -> d), a list of N DenseNet(d -> d) or '
+                      'a MySequential(d + 1 -> d))')
+    if getattr(problem, 'native_spec', None) is None or problem.native_spec() is None:
+        return None, (getattr(problem, 'native_plan_reason', None)
+                      or 'the problem has no native_spec() (coefficients outside the native catalogue)')
+    if isinstance(first, DenseNet):
+        nets = view.z_n if view.time_approx == 'outer' else [view.z_n]
+        if any(n.activation != 'relu2' or n.output_relu for n in nets):
+            return None, 'the DenseNet-control kernels take the relu(.)**2 net without an output ReLU'
+        why = _dense_reason(problem, view)
+        return ('dnet', None) if why is None else (None, why)
+    why = _native_reason(problem, view, 'approx', False)
+    return ('hjb', None) if why is None else (None, why)
+
+
+def _lre_base(b, problem, pad, keep, K, N, delta_t, adaptive, philox, dev):
+    """The psp_hjb_config fields both kernel families share for a forward-only chunked rollout."""
+    try:
+        from .plan_common import pad_coeff
+    except ImportError:
+        from plan_common import pad_coeff
+    spec = problem.native_spec()
+
+    def dev_f32(t):
+        t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        keep.append(t)
+        return t
+
+    b.N, b.K_global = N, K
+    b.dt = float(torch.tensor(delta_t, dtype=torch.float32).item())
+    b.sqrt_dt = float(torch.sqrt(torch.tensor(delta_t, dtype=torch.float32)).item())
+    b.drift_kind, b.sigma_kind, b.sigma_scale = spec['drift'][0], spec['sigma'][0], float(spec['sigma'][2])
+    b.runcost_kind, b.term_kind = spec['runcost'][0], spec['term'][0]
+    b.coord_split = int(spec.get('split', 0))
+    b.adaptive, b.loss_kind, b.store_path = (1 if adaptive else 0), nat.LOSS_LOG_VARIANCE, 0
+    b.noise_mode = nat.NOISE_PHILOX if philox else nat.NOISE_SUPPLIED
+    b.drift = nat.ptr(dev_f32(pad_coeff(pad, spec['drift'][1]))) if spec['drift'][1] is not None else None
+    b.sigma = nat.ptr(dev_f32(pad.drift_or_sigma(spec['sigma'][1]))) if spec['sigma'][1] is not None else None
+    b.runcost = nat.ptr(dev_f32(pad.vec(spec['runcost'][1]))) if spec['runcost'][1] is not None else None
+    b.term = nat.ptr(dev_f32(pad_coeff(pad, spec['term'][1])))
+    return dev_f32(pad.vec(torch.as_tensor(problem.X_0, dtype=torch.float32).reshape(-1).to(dev)))
+
+
+def _lre_chunks(K, chunk):
+    return [(k0, min(chunk, K - k0)) for k0 in range(0, K, chunk)]
+
+
+def _lre_xi_chunk(xi_all, k0, kc, pad, dev):
+    """The kernels' (N + 1, kc, d_pad) layout of the host draws (N, K, d): slice n + 1 drives step n."""
+    N, _, d = xi_all.shape
+    xi = torch.zeros(N + 1, kc, pad.dp, dtype=torch.float32, device=dev)
+    xi[1:, :, :d] = xi_all[:, k0:k0 + kc].to(dev)
+    return xi
+
+
+def _lre_native(family, problem, view, K, N, delta_t, chunk, philox, seed, xi_all, sink):
+    """K trajectories in chunks on psp_dnet_rollout_fwd / psp_hjb_rollout_fwd, forward only (store_path = 0): k_offset is the
+    chunk's first global trajectory and (seed, iter = 0) is the same for every chunk, so a trajectory's Philox noise does not
+    depend on the chunking.  `sink(Y, D)` takes the two chunk buffers on the stream; nothing is read back here."""
+    try:
+        from .plan_dense_native import _instance_for
+        from .plan_native import chunk_scratch_sizes
+    except ImportError:
+        from plan_dense_native import _instance_for
+        from plan_native import chunk_scratch_sizes
+    dev, lib, d = view.device, nat.load(), problem.d
+    keep = []
+    chunks = _lre_chunks(K, chunk)
+    sizes_k = sorted({kc for _, kc in chunks})
+    seed64 = int(seed or 0) & 0xFFFFFFFFFFFFFFFF          # (unused under supplied noise, where seed may be None)
+    Yb = torch.empty(chunk, dtype=torch.float32, device=dev)
+    Db = torch.empty(chunk, dtype=torch.float32, device=dev)
+    stream = nat.stream_ptr(dev)
+    if family == 'dnet':
+        outer = view.time_approx == 'outer'
+        nets = view.z_n if outer else [view.z_n]
+        H = nets[0].nn_dims[1]
+        d_pad, H_pad = _instance_for(d, H)
+        pad = shapes.ParamPad(d, H, d_pad, H_pad, dev)
+        cfg = nat.DnetConfig()
+        b = cfg.base
+        b.d, b.H = d_pad, H_pad
+        x0 = _lre_base(b, problem, pad, keep, K, N, delta_t, view.adaptive_forward_process, philox, dev)
+        cfg.d_real, cfg.H_real = d, H
+        cfg.time_input, cfg.per_step = (0 if outer else 1), (1 if outer else 0)
+        flat = torch.cat([p.detach().reshape(-1) for net in nets for p in net.W]).to(device=dev, dtype=torch.float32).contiguous()
+        sizes = nat.DnetSizes()
+        b.K_local = sizes_k[-1]
+        nat.check(lib.psp_dnet_query(C.byref(cfg), C.byref(sizes)), 'psp_dnet_query')
+        part = torch.empty(sizes.fwd_partial_bytes // 8, dtype=torch.float64, device=dev)
+        tables = torch.empty(sizes.table_bytes // 4, dtype=torch.float32, device=dev)
+        for k0, kc in chunks:
+            b.K_local, b.k_offset = kc, k0
+            xi = None if philox else _lre_xi_chunk(xi_all, k0, kc, pad, dev)
+            nat.check(lib.psp_dnet_rollout_fwd(C.byref(cfg), nat.ptr(flat), nat.ptr(x0), 0, None, nat.ptr(xi), seed64, 0, None,
+                                               None, None, nat.ptr(Db), None, None, nat.ptr(Yb), nat.ptr(part), nat.ptr(tables),
+                                               stream), 'psp_dnet_rollout_fwd')
+            sink(Yb[:kc], Db[:kc])
+        return
+    net = view.z_n
+    H = net.native_shape()[1]
+    cfg = nat.HjbConfig()
+    cfg.K_local = sizes_k[-1]
+    pad0 = shapes.ParamPad(d, H, d, H, dev)                           # (the coefficient kinds first: choose() reads them)
+    _lre_base(cfg, problem, pad0, [], K, N, delta_t, view.adaptive_forward_process, philox, dev)
+    chosen, why = shapes.choose(cfg, d, H)
+    if chosen is None:
+        raise NotImplementedError('native loss_relative_errors unavailable: ' + why)
+    d_pad, H_pad = chosen[0], chosen[1]
+    pad = shapes.ParamPad(d, H, d_pad, H_pad, dev)
+    x0 = _lre_base(cfg, problem, pad, keep, K, N, delta_t, view.adaptive_forward_process, philox, dev)
+    sizes = chunk_scratch_sizes(cfg, sizes_k)
+    flat = torch.cat([p.detach().reshape(-1) for p in net.flat_layout()]).to(device=dev, dtype=torch.float32).contiguous()
+    flat = pad.scatter_params(flat, pad.new_padded_params() if not pad.identity else None)
+    part = torch.empty(max(sizes.fwd_partial_bytes // 8, 2), dtype=torch.float64, device=dev)
+    for k0, kc in chunks:
+        cfg.K_local, cfg.k_offset = kc, k0
+        xi = None if philox else _lre_xi_chunk(xi_all, k0, kc, pad, dev)
+        nat.check(lib.psp_hjb_rollout_fwd(C.byref(cfg), nat.ptr(flat), nat.ptr(x0), 0, None, nat.ptr(xi), seed64, 0, None,
+                                          nat.ptr(Db), None, nat.ptr(Yb), nat.ptr(part), stream), 'psp_hjb_rollout_fwd')
+        sink(Yb[:kc], Db[:kc])
+
+
+def _lre_torch(problem, view, K, N, delta_t, chunk, philox, seed, xi_all, sink):
+    """The notebook's loop in fp32 torch on view.device, chunk by chunk.  Noise: the host draws (`xi_all`), or under 'philox' the
+    kernels' own stream materialised by psp_philox_normal_fill on a GPU -- the same noise as the native plan -- and a
+    torch.Generator seeded with `seed` where there is none (that stream depends on the chunking)."""
+    dev, d = view.device, problem.d
+    dt = torch.tensor(delta_t).to(dev)
+    sq = torch.sqrt(dt).to(dev)
+    X_0 = torch.as_tensor(problem.X_0, dtype=torch.float32).to(dev)
+    outer = view.time_approx == 'outer'
+    on_gpu = dev.type == 'cuda'
+    gen = None
+    if philox and on_gpu:
+        chunk = min(chunk, max(LRE_TILE, LRE_PHILOX_FILL_FLOATS // ((N + 1) * d) // LRE_TILE * LRE_TILE))
+    elif philox:
+        gen = torch.Generator().manual_seed(int(seed))
+    for k0, kc in _lre_chunks(K, chunk):
+        if philox and on_gpu:
+            fill = torch.empty(N + 1, kc, d, dtype=torch.float32, device=dev)
+            nat.check(nat.load().psp_philox_normal_fill(nat.ptr(fill), N, kc, d, k0, int(seed) & 0xFFFFFFFFFFFFFFFF, 0,
+                                                        nat.stream_ptr(dev)), 'psp_philox_normal_fill')
+        X = X_0.repeat(kc, 1)
+        Y = torch.zeros(kc).to(dev)
+        with torch.no_grad():
+            for n in range(N):
+                if not philox:
+                    xi = xi_all[n, k0:k0 + kc].to(dev)
+                else:
+                    xi = fill[n + 1] if on_gpu else torch.randn(kc, d, generator=gen)
+                if outer:
+                    Z = view.z_n[n](X)
+                else:
+                    Z = view.z_n(torch.cat([torch.ones([kc, 1]).to(dev) * n * dt, X], 1))
+                c = -Z.t() if view.adaptive_forward_process else torch.zeros(d, 1).to(dev)
+                sig = problem.sigma(X)
+                X = (X + (problem.b(X) + torch.mm(sig, c).t()) * dt + torch.mm(sig, xi.t()).t() * sq)
+                Y = (Y + (-problem.h(dt * n, X, Y, Z) + torch.sum(Z * c.t(), 1)) * dt + torch.sum(Z * xi, 1) * sq)
+            D = Y - problem.g(X)
+        sink(Y.contiguous(), D.contiguous())
+
+
+def loss_relative_errors(problem, control, K, delta_t=0.005, adaptive_forward_process=False, noise='philox', seed=0, device=None,
+                         backend='auto', chunk=None, return_samples=False):
+    """Relative errors of the loss estimators over K forward-only trajectories of one control: the third cell of the reference's
+    `experiments/HJB-log-variance-loss/Compare relative errors of losses.ipynb` (K = 5e7, N = 200, d <= 15 there).
+
+    ``control``: a bare DenseNet(d + 1 -> d) (the notebook's net; the time input is column 0), a bare MySequential(d + 1 -> d),
+    a list of N DenseNet(d -> d), or a Solver (its ``z_n`` and ``time_approx`` are used); any other callable of [t, x] (or list of
+    callables of x) runs on the composite plan.  Per step n < N = floor(T / delta_t), from X_0 = problem.X_0 and Y_0 = 0:
+        Z = control(t_n, X_n) with the time feature ones * n * delta_t in fp32;   c = -Z if adaptive_forward_process else 0
+        X_{n+1} = X_n + (b(X_n) + sigma c) dt + sigma xi sqrt(dt)
+        Y      += (-h(t_n, X_{n+1}, Y, Z) + Z . c) dt + Z . xi sqrt(dt)         (-h = |Z|^2 / 2 + f in this project's sign)
+    With D = Y_N - g(X_N) the result holds, per estimator, the tuple (mean, variance, relative_error) of the samples
+        'terminal' exp(-g)     'cross_entropy' Y exp(-g)     'cross_entropy_detach' Y exp(-g + Y)
+        'cross_entropy_detach_selection' the same over the samples with |v| < 100, with their count as a fourth entry
+        'moment' D^2           'log_variance': mean = var(D), variance = mean((D - mean D)^4) - var(D)^2
+    relative_error = sqrt(variance) / |mean|; variances are unbiased as torch.var's.  (For the selection the notebook records
+    sqrt(variance) and |mean| themselves.)  Also 'K', 'N', 'plan' ('native' or 'torch') and 'plan_reason'; with
+    ``return_samples`` (K <= 2**24) the per-trajectory fp32 'Y' and 'D'.
+
+    DELIBERATE DIFFERENCE FROM THE NOTEBOOK: every sum is formed in float64 (psp_loss_stats_* on a GPU; g = Y - D, the
+    exponentials and the moments in double), where the notebook reduces fp32 tensors with torch.  Non-finite samples are not
+    filtered: they make what they enter NaN.
+
+    Plans.  backend='auto' on a GPU runs the K trajectories in chunks on the forward kernels (psp_dnet_rollout_fwd for DenseNets,
+    psp_hjb_rollout_fwd for a MySequential; store_path = 0) when the problem has a ``native_spec()``; each chunk is reduced on
+    the device and only the final statistics are read back.  Everything else -- no GPU, a user net, a problem outside the
+    catalogue, backend='torch' -- runs the same update in fp32 torch with the same chunking and says why in 'plan_reason';
+    backend='native' raises instead.  ``chunk`` (default 2**20 native, 2**16 composite) is rounded up to the kernels' tile of 16
+    trajectories.
+    noise='philox': the kernels' counter-based stream keyed by (seed, global trajectory index): a trajectory's noise does not
+    depend on the chunking (the DenseNet kernel's samples are then bit-identical; psp_hjb_rollout_fwd picks among three forward
+    variants by chunk size, which agree to summation order).  noise='reference': the notebook's draws, randn(K, d) per step from the CPU generator after
+    torch.manual_seed(seed) (seed=None: the generator continues from where it stands, as in the notebook after the net was
+    built); they are held on the host, so K * N * d is limited to 2**28."""
+    from types import SimpleNamespace
+    if backend not in ('auto', 'native', 'torch'):
+        raise ValueError("backend must be 'auto', 'native' or 'torch'")
+    if noise not in ('philox', 'reference'):
+        raise ValueError("noise must be 'philox' or 'reference'")
+    K = int(K)
+    if K < 1:
+        raise ValueError('K must be positive')
+    if not delta_t > 0:
+        raise ValueError('delta_t must be positive')
+    N = int(np.floor(problem.T / delta_t))
+    if N < 1:
+        raise ValueError('delta_t = %g leaves no time step in T = %g' % (delta_t, problem.T))
+    if return_samples and K > LRE_MAX_SAMPLES:
+        raise ValueError('return_samples keeps two K-sized buffers and is limited to K <= 2**24 = %d (K = %d)' % (LRE_MAX_SAMPLES, K))
+    d = problem.d
+    philox = noise == 'philox'
+    if philox and seed is None:
+        raise ValueError("noise='philox' needs an integer seed")
+    if not philox and K * N * d > LRE_REFERENCE_NOISE_LIMIT:
+        raise ValueError("noise='reference' holds the K * N * d = %d draws on the host; the limit is 2**28 = %d -- use "
+                         "noise='philox'" % (K * N * d, LRE_REFERENCE_NOISE_LIMIT))
+    z, ta = _lre_control(control, N)
+    if device is None:
+        device = getattr(control, 'device', None) or getattr(problem, 'device', None) or 'cpu'
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    view = SimpleNamespace(device=dev, approx_method='control', loss_method='log-variance', time_approx=ta, z_n=z, d=d,
+                           adaptive_forward_process=bool(adaptive_forward_process), detach_forward=True, burgers_drift=False,
+                           log_gradient=False, metastability_logs=None, u_l2_error_flag=False, compute_gradient_variance=0,
+                           IS_variance_K=0, problem=problem, N=N, delta_t_np=delta_t, backend=backend, K=K, seed=seed)
+    family, reason = _lre_plan(problem, view)
+    if family is None and backend == 'native':
+        raise NotImplementedError('native loss_relative_errors unavailable: ' + reason)
+    chunk = lre_chunk(K, chunk, LRE_NATIVE_CHUNK if family is not None else LRE_TORCH_CHUNK)
+    xi_all = None
+    if not philox:
+        if seed is not None:
+            torch.manual_seed(int(seed))
+        xi_all = torch.empty(N, K, d)
+        for n in range(N):
+            xi_all[n] = torch.randn(K, d)
+    stats = _DeviceLossStats(dev) if dev.type == 'cuda' else _HostLossStats()
+    samples = [torch.empty(K, dtype=torch.float32, device=dev) for _ in range(2)] if return_samples else None
+    filled = [0]
+
+    def sink(Y, D):
+        stats.accumulate(Y, D)
+        if samples is not None:
+            samples[0][filled[0]:filled[0] + Y.numel()].copy_(Y)
+            samples[1][filled[0]:filled[0] + D.numel()].copy_(D)
+        filled[0] += Y.numel()
+
+    run = _lre_torch if family is None else (lambda *a: _lre_native(family, *a))
+    run(problem, view, K, N, delta_t, chunk, philox, seed, xi_all, sink)
+    res = stats.finish()
+    assert filled[0] == K and int(res[19]) == K, (filled[0], res[19], K)
+    out = {}
+    for i, key in enumerate(LRE_KEYS):
+        out[key] = tuple(float(v) for v in res[3 * i:3 * i + 3])
+    out['cross_entropy_detach_selection'] += (int(res[18]),)
+    out.update(K=K, N=N, chunk=chunk, plan='torch' if family is None else 'native', plan_reason=reason)
+    if samples is not None:
+        out['Y'], out['D'] = samples
+    return out
