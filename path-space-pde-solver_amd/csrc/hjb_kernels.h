@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "launch.h"
+#include "block_index.h"
 
 namespace psp {
 
@@ -1379,20 +1380,19 @@ __global__ __launch_bounds__(512) void hjb_bwd2_kernel(const HjbArgs a) {
         // software pipeline over this wave's blocks: xi and the trajectory weight of the NEXT round are requested at
         // the top of an iteration (a whole iteration of lead), h2 of the current block right after G is formed
         // (consumed after the GEMM)
-        auto own_block = [&](int it2) __attribute__((always_inline)) {
-            const long long b0 = ((long long)blockIdx.x + (long long)it2 * gridDim.x) * 4 + sub;
-            return b0 < nblk ? b0 : -1LL;
-        };
+        // this wave's block of the current round and of the next (block_index.h: no division in the round loop); a slot outside
+        // the store rests on the stand-in block nblk - 1, with weight zero
+        BlockCursor cur = BlockCursor::start(blockIdx.x, (uint32_t)sub, gridDim.x, (uint32_t)a.ntile16, (uint32_t)a.N);
+        BlockCursor nxt = cur;
+        nxt.advance();
         f32x4 xin[DB];
         float dkn;
         {
-            const long long b0 = own_block(0);
-            const long long blk = b0 >= 0 ? b0 : nblk - 1;
-            const float* pb = a.path + (size_t)blk * (size_t)G::PB + lane;
-            const int k0 = (int)(blk % a.ntile16) * 16 + j;
+            const float* pb = a.path + (size_t)cur.blk * (size_t)G::PB + lane;
+            const int k0 = (int)cur.t16 * 16 + j;
             dkn = a.D[k0 < a.K_local ? k0 : 0];
             if (regen) {
-                regen_xi<D, DB>(xin, (uint32_t)(a.k_offset + k0), (uint32_t)(blk / a.ntile16), q, iter_now, a.seed_lo, a.seed_hi);
+                regen_xi<D, DB>(xin, (uint32_t)(a.k_offset + k0), cur.n, q, iter_now, a.seed_lo, a.seed_hi);
             } else {
 #pragma unroll
                 for (int b = 0; b < DB; ++b)
@@ -1404,13 +1404,9 @@ __global__ __launch_bounds__(512) void hjb_bwd2_kernel(const HjbArgs a) {
             PSP_STAMP(tp0);
             if (it < R) {
                 // ---------------------------------------------------------- produce round r into bufs[it & 1]
-                const long long blk0 = own_block(it);
-                const bool bvalid = blk0 >= 0;
-                const long long blk = bvalid ? blk0 : nblk - 1;
-                const int t16 = (int)(blk % a.ntile16);
-                const int k = t16 * 16 + j;
-                const bool kvalid = bvalid && k < a.K_local;
-                const float* pb = a.path + (size_t)blk * (size_t)G::PB + lane;
+                const int k = (int)cur.t16 * 16 + j;
+                const bool kvalid = cur.valid && k < a.K_local;
+                const float* pb = a.path + (size_t)cur.blk * (size_t)G::PB + lane;
                 float* ex = bufs + ((it & 1) * 4 + sub) * EXB + lane;
                 // LOSS_WEIGHTS: the caller supplies w_k = dLoss/dY_k directly in the D argument
                 const float dk = dkn;
@@ -1427,13 +1423,11 @@ __global__ __launch_bounds__(512) void hjb_bwd2_kernel(const HjbArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) h2[m][r] = pb[G::pH2 + (4 * m + r) * 64];
                 {
-                    const long long n0 = own_block(it + 1);
-                    const long long nblk1 = n0 >= 0 ? n0 : nblk - 1;
-                    const float* pn = a.path + (size_t)nblk1 * (size_t)G::PB + lane;
-                    const int k1 = (int)(nblk1 % a.ntile16) * 16 + j;
+                    const float* pn = a.path + (size_t)nxt.blk * (size_t)G::PB + lane;
+                    const int k1 = (int)nxt.t16 * 16 + j;
                     dkn = a.D[k1 < a.K_local ? k1 : 0];
                     if (regen) {
-                        regen_xi<D, DB>(xin, (uint32_t)(a.k_offset + k1), (uint32_t)(nblk1 / a.ntile16), q, iter_now, a.seed_lo, a.seed_hi);
+                        regen_xi<D, DB>(xin, (uint32_t)(a.k_offset + k1), nxt.n, q, iter_now, a.seed_lo, a.seed_hi);
                     } else {
 #pragma unroll
                         for (int b = 0; b < DB; ++b)
@@ -1457,6 +1451,8 @@ __global__ __launch_bounds__(512) void hjb_bwd2_kernel(const HjbArgs a) {
                 for (int ks = 0; ks < 4 * HB; ++ks) ex[oDZ2 + ks * 64] = dz2[ks >> 2][ks & 3];
                 PSP_STAMP(tp4);
                 PSP_ACC(3, tp4, tp2);                 // dz2 store
+                cur = nxt;                                // block it + 1 of this round is block it of the next
+                nxt.advance();
             }
             PSP_STAMP(tp5);
             __syncthreads();                              // swap the exchange buffers (pairs with the consumer loop)

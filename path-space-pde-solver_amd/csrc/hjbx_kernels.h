@@ -242,23 +242,21 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
         for (int b = 0; b < DB; ++b) sG[b] = zero4;
 #pragma unroll
         for (int m = 0; m < HB; ++m) { sZ2[m] = zero4; sZ1[m] = zero4; sT1[m] = zero4; }
-        auto own_block = [&](int it2) __attribute__((always_inline)) {
-            const long long b0 = ((long long)blockIdx.x + (long long)it2 * gridDim.x) * 4 + sub;
-            return b0 < nblk ? b0 : -1LL;
-        };
-        auto path_of = [&](int it2) __attribute__((always_inline)) {
-            const long long b0 = own_block(it2);
-            return a.path + (size_t)(b0 >= 0 ? b0 : nblk - 1) * (size_t)G::PB + lane;
+        // this wave's block of the current round and of the next (block_index.h: no division, nothing 64-bit in the round loop
+        // but the path offset); a slot outside the store rests on the stand-in block nblk - 1, with weight zero
+        BlockCursor cur = BlockCursor::start(blockIdx.x, (uint32_t)sub, gridDim.x, (uint32_t)a.ntile16, (uint32_t)a.N);
+        BlockCursor nxt = cur;
+        nxt.advance();
+        auto path_of = [&](const BlockCursor& c) __attribute__((always_inline)) {
+            return a.path + (size_t)c.blk * (size_t)G::PB + lane;
         };
         // (the register budget -- 256, with 76 registers of bias sums -- has no room for a second set of landing registers, and a
         // spilled register's reload would wait behind every load in flight)
         f32x4 xin[DB], h2n[HB], h1n[HB];
         float dkn;
         {
-            const long long b0 = own_block(0);
-            const long long blk = b0 >= 0 ? b0 : nblk - 1;
-            const float* pb = path_of(0);
-            const int k0 = (int)(blk % a.ntile16) * 16 + j;
+            const float* pb = path_of(cur);
+            const int k0 = (int)cur.t16 * 16 + j;
             dkn = a.D[k0 < a.K_local ? k0 : 0];
             // Stored xi (REGEN = false): h2 of the current block is requested at the top of its round (used behind the first
             // product); h1 (used behind the second product) and the xi image and weight of the NEXT round behind the first product,
@@ -291,9 +289,8 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
         }
         float gs, ginv;
         {
-            const long long b0 = own_block(0);
-            const int k0 = (int)((b0 >= 0 ? b0 : nblk - 1) % a.ntile16) * 16 + j;
-            const bool kv = b0 >= 0 && k0 < a.K_local;
+            const int k0 = (int)cur.t16 * 16 + j;
+            const bool kv = cur.valid && k0 < a.K_local;
             float am = 0.f;
 #pragma unroll
             for (int b = 0; b < DB; ++b)
@@ -316,17 +313,13 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
         for (int it = 0; it <= R; ++it) {
             PSP_STAMP(tp0);
             if (it < R) {
-                const long long blk0 = own_block(it);
-                const bool bvalid = blk0 >= 0;
-                const long long blk = bvalid ? blk0 : nblk - 1;
-                const int t16 = (int)(blk % a.ntile16);
-                const int k = t16 * 16 + j;
-                const bool kvalid = bvalid && k < a.K_local;
-                const float tn = (float)(blk / a.ntile16) * dt;
+                const int k = (int)cur.t16 * 16 + j;
+                const bool kvalid = cur.valid && k < a.K_local;
+                const float tn = (float)cur.n * dt;
                 // exchange image of this round's pair (header comment): every tile, part and panel is an immediate offset from here
                 _Float16* exw = exh + ((it & 1) * 2 + (sub >> 1)) * PAIRH;
-                const float* pn = path_of(it + 1);
-                const float* pc = path_of(it);
+                const float* pn = path_of(nxt);
+                const float* pc = path_of(cur);
                 const float dkc = dkn;
                 if constexpr (!regen) {
 #pragma unroll
@@ -338,7 +331,7 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
                 const float wk = kvalid ? (a.loss_kind == LOSS_WEIGHTS ? dkc : coef * (dkc - meanD)) : 0.f;
                 f32x4 Gt[DB];
                 if constexpr (regen) {
-                    const uint32_t kg = (uint32_t)(a.k_offset + k), nstep = (uint32_t)(blk / a.ntile16);
+                    const uint32_t kg = (uint32_t)(a.k_offset + k), nstep = cur.n;
                     // (q through an opaque copy: the first Philox round of the call index 4 b + q is loop-invariant, and seven
                     // hoisted products per lane were spilled and reloaded every round -- behind every path load in flight)
                     const int qo = opaque_i(q);
@@ -395,9 +388,7 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
                     for (int m = 0; m < HB; ++m)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) h1n[m][r] = pc[G::pH1 + (4 * m + r) * 64];
-                    const long long n0 = own_block(it + 1);
-                    const long long nb1 = n0 >= 0 ? n0 : nblk - 1;
-                    const int k1 = (int)(nb1 % a.ntile16) * 16 + j;
+                    const int k1 = (int)nxt.t16 * 16 + j;
                     dkn = a.D[k1 < a.K_local ? k1 : 0];
 #pragma unroll
                     for (int b = 0; b < DB; ++b)
@@ -424,9 +415,7 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
                 }
                 if constexpr (regen) {
                     __builtin_amdgcn_sched_barrier(0);
-                    const long long n0 = own_block(it + 1);
-                    const long long nb1 = n0 >= 0 ? n0 : nblk - 1;
-                    const int k1 = (int)(nb1 % a.ntile16) * 16 + j;
+                    const int k1 = (int)nxt.t16 * 16 + j;
                     dkn = a.D[k1 < a.K_local ? k1 : 0];
 #pragma unroll
                     for (int m = 0; m < HB; ++m)
@@ -435,6 +424,8 @@ __global__ __launch_bounds__(512) void hjb_bwd3_kernel(const HjbArgs a) {
                 }
                 split_panel<HB>(dz1, Zh, Zl);
                 put_panel<HB, 0>(exw + X::hZ1, exw + X::hZ1l, pfull, 0, Zh, Zl);
+                cur = nxt;                                // block it + 1 of this round is block it of the next
+                nxt.advance();
             }
             PSP_STAMP(tp4);
             PSP_ACC(3, tp4, tp0);                     // whole produce phase
