@@ -51,6 +51,7 @@ extern "C" {
                          *        DenseNet-control forward for reference controls that depend on x (PSP_UL2_LINEAR / PSP_UL2_GRID);
                          *        psp_is_config / psp_is_rollout / psp_is_query / psp_abi_struct_sizes3 -- the reference-control and
                          *        uncontrolled importance-sampling rollout (PSP_ISC_*);
+                         *        psp_isw_sizes / psp_isw_query / psp_isw_rollout -- the same rollout for wide states, d <= PSP_ISW_MAX_D;
                          *        psp_genl_config.sigma_kind / sigma -- a dense constant diffusion matrix in the run-time-shaped
                          *        value-net kernels (PSP_GENL_SIGMA_*), and PSP_GH_EXPBALL_SIN_FULL;
                          *        psp_hjb_basis_params / psp_hjb_basis_grad -- the per-iteration transforms of a rollout in the
@@ -880,7 +881,8 @@ int psp_aff_rollout_bwd(const psp_aff_config* cfg, const float* path, const floa
 enum { PSP_ISC_NONE = 0, PSP_ISC_TABLE = 1, PSP_ISC_LINEAR = 2, PSP_ISC_GRID = 3 };
 
 typedef struct psp_is_config {
-    int32_t d;            /* state dimension, 1 <= d <= 64 (the compiled buckets 1, 4, 16, 32, 64)                          */
+    int32_t d;            /* state dimension: psp_is_rollout 1 <= d <= 64 (the compiled buckets 1, 4, 16, 32, 64);
+                           * psp_isw_rollout 1 <= d <= PSP_ISW_MAX_D (blocks of 16 features, buckets of 4, 8, 12, 16 blocks)  */
     int32_t K_local;      /* trajectories of this call                                                                        */
     int32_t N;            /* time steps, ceil(T / delta_t) (utilities.py:299)                                                 */
     int32_t control_kind; /* PSP_ISC_*                                                                                        */
@@ -915,6 +917,35 @@ int psp_is_rollout(const psp_is_config* cfg, const float* xi, uint64_t seed, uin
 int psp_is_query(const psp_is_config* cfg, int32_t* lds_bytes);
 /* sizeof(psp_is_config) (added in 0.4.0). */
 int psp_abi_struct_sizes3(int32_t out[1]);
+
+/* ------------------------------------------------------------------------------------------------
+ * The same rollout for wide states (appended in 0.4.0, no version bump; csrc/hjbew_kernels.h): the recursion, the kinds and the
+ * psp_is_config above, for 1 <= d <= PSP_ISW_MAX_D (d <= 64 included, so that the two kernels can be held against each other).
+ * One wave owns a tile of 16 trajectories with the state in the accumulator layout of v_mfma_f32_16x16x4_f32; the dense
+ * products A X, B (u dt + xi sqrt(dt)) and M_n X are fp32 MFMAs on tables a small kernel of the same call tiles into `tables`.
+ * The elementwise kinds round the state update op by op as psp_is_rollout does (X_N is bit-equal between the two there); the
+ * sums over features are reduced in another fixed order, so logw agrees to fp32 rounding, not bit for bit.  Equal arguments
+ * give equal bits.  d = 512 does not fit one wave's registers without scratch, hence PSP_ISW_MAX_D = 256.
+ * With P = 64 ceil(d / 64) padded features,
+ *   table_bytes = 4 (5 P + [drift DENSE] P^2 + [sigma DENSE] P^2 + (TABLE: N P | LINEAR: N P^2 | else 0)).
+ * ------------------------------------------------------------------------------------------------ */
+#define PSP_ISW_MAX_D 256
+
+typedef struct psp_isw_sizes {
+    int32_t struct_bytes; /* in: sizeof(psp_isw_sizes), checked by psp_isw_query                                              */
+    int32_t lds_bytes;    /* the workgroup's LDS: the GRID kind's rows of one step, else 0                                    */
+    int64_t table_bytes;  /* caller-owned scratch psp_isw_rollout writes before it reads (the formula above)                  */
+    int32_t workgroups;   /* ceil(ceil(K_local / 16) / 4): four 16-trajectory tiles, one per wave                             */
+    int32_t max_d;        /* PSP_ISW_MAX_D of the library                                                                     */
+} psp_isw_sizes;
+
+/* Every check psp_isw_rollout makes of the config, without a launch (no GPU needed).  -1 invalid argument (a wrong
+ * struct_bytes, a kind out of range, K_global < k_offset + K_local, a pointer the kind needs missing), -2 d outside
+ * 1 .. PSP_ISW_MAX_D, -3 GRID rows that do not fit the LDS; psp_last_error() names the reason. */
+int psp_isw_query(const psp_is_config* cfg, psp_isw_sizes* sizes);
+/* As psp_is_rollout; tables: table_bytes of scratch on the device (16-byte aligned), rewritten by every call. */
+int psp_isw_rollout(const psp_is_config* cfg, const float* xi, uint64_t seed, uint32_t iter, float* tables, float* logw_out,
+                    float* XN_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Rollout in the sigma basis (appended in 0.4.0, no version bump).  For a constant invertible sigma = B a caller may hand the

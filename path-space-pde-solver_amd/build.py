@@ -94,6 +94,7 @@ def _build(force, jobs, verbose, only):
     # (source, object, defines and flags); what a unit depends on is read from its #include lines (unit_deps)
     tasks = [("psp_api.hip", "psp_api.o", NOSLP),
              ("hjbe_instance.hip", "hjbe_inst.o", NOSLP),           # psp_is_rollout: every d bucket and control kind in one unit
+             ("hjbew_instance.hip", "hjbew_inst.o", NOSLP),         # psp_isw_rollout: every block bucket and control kind, table kernel
              ("aff_instance.hip", "aff_inst.o", NOSLP),             # psp_aff_*: the three d buckets in one unit
              ("genl_eval_instance.hip", "genl_eval_inst.o", NOSLP),     # psp_genl_test_error: both waves-per-tile instances
              ("genl_lq_instance.hip", "genl_lq_inst.o", NOSLP),     # psp_genl_rollout_fwd_lq: three waves-per-tile variants

@@ -36,6 +36,7 @@ LOSS_LOG_VARIANCE, LOSS_MOMENT, LOSS_WEIGHTS, LOSS_REL_ENTROPY = 0, 1, 2, 3
 UL2_TABLE, UL2_LINEAR, UL2_GRID = 0, 1, 2
 ISC_NONE, ISC_TABLE, ISC_LINEAR, ISC_GRID = 0, 1, 2, 3
 IS_MAX_D = 64                     # native range of psp_is_rollout (include/psp.h)
+ISW_MAX_D = 256                   # native range of psp_isw_rollout (include/psp.h PSP_ISW_MAX_D)
 GENL_MAX_HIDDEN_LAYERS, GENL_MAX_WIDTH, GENL_MAX_INPUT = 4, 128, 112      # the run-time-shaped value-net kernels (csrc/genl_kernels.h)
 NOISE_SUPPLIED, NOISE_PHILOX = 0, 1
 GH_ZERO, GH_QUAD, GH_ALLEN_CAHN, GH_EXPBALL_LIN, GH_EXPBALL_SQ, GH_EXPBALL_SIN, GH_EXPBALL_SIN_FULL = 0, 1, 2, 3, 4, 5, 6
@@ -122,6 +123,16 @@ class IsConfig(C.Structure):
                 ("u_ref", C.c_void_p), ("u_group", C.c_void_p), ("u_row", C.c_void_p),
                 ("u_ntables", C.c_int32), ("u_nrows", C.c_int32), ("u_ncols", C.c_int32),
                 ("u_xb", C.c_float), ("u_dx", C.c_float), ("u_xhi", C.c_float)]
+
+
+class IswSizes(C.Structure):
+    """psp_isw_sizes; ``struct_bytes`` is set here and checked by the library."""
+    _fields_ = [("struct_bytes", C.c_int32), ("lds_bytes", C.c_int32), ("table_bytes", C.c_int64), ("workgroups", C.c_int32),
+                ("max_d", C.c_int32)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_bytes = C.sizeof(IswSizes)
 
 
 class AffConfig(C.Structure):
@@ -238,6 +249,8 @@ SIGNATURES = {
     "psp_abi_struct_sizes3": (C.c_int, [C.POINTER(C.c_int32 * 1)]),
     "psp_is_rollout": (C.c_int, [C.POINTER(IsConfig), _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
     "psp_is_query": (C.c_int, [C.POINTER(IsConfig), C.POINTER(C.c_int32)]),
+    "psp_isw_query": (C.c_int, [C.POINTER(IsConfig), C.POINTER(IswSizes)]),
+    "psp_isw_rollout": (C.c_int, [C.POINTER(IsConfig), _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P]),
     "psp_abi_struct_sizes4": (C.c_int, [C.POINTER(C.c_int32 * 2)]),
     "psp_genl_eval_query": (C.c_int, [C.POINTER(GenlEvalConfig), C.POINTER(GenlEvalSizes)]),
     "psp_genl_test_error": (C.c_int, [C.POINTER(GenlEvalConfig), _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, C.c_int32, _P,

@@ -68,7 +68,7 @@ class Solver:
                  log_gradient=False, burgers_drift=False, verbose=True,
                  device=None, backend='auto', noise='reference', widths=(30, 30), mlp_dtype='auto',
                  path_budget_bytes=None, path_chunks=None, chunk_mode='auto', use_graph='auto', range_guard=True,
-                 path_noise='auto', state_basis='auto', value_state_path='torch'):
+                 path_noise='auto', state_basis='auto', value_state_path='torch', IS_wide_states='torch'):
         self.problem, self.name = problem, name
         self.date = date.today().strftime('%Y-%m-%d')
         self.d, self.T = problem.d, problem.T
@@ -112,6 +112,11 @@ class Solver:
         if value_state_path not in ('torch', 'native'):
             raise ValueError("value_state_path must be 'torch' or 'native'")
         self.value_state_path = value_state_path
+        # the in-loop importance-sampling log above d = 64 (utilities.do_importance_sampling_me wide_states): 'torch' (default) keeps
+        # the composite evaluation of a Linear / Constant list there, 'native' runs it on psp_isw_rollout.  No plan reads it.
+        if IS_wide_states not in ('torch', 'native'):
+            raise ValueError("IS_wide_states must be 'torch' or 'native'")
+        self.IS_wide_states = IS_wide_states
         # native plan: HBM budget of the path store kept for the backward pass (None: a third of the HBM); a larger store is
         # processed in K-chunks (plan_native.py).  path_chunks forces a chunk count; chunk_mode 'auto' | 'two_gradient' | 'recompute'
         self.path_budget_bytes, self.path_chunks, self.chunk_mode = path_budget_bytes, path_chunks, chunk_mode
@@ -440,7 +445,8 @@ class Solver:
                 y0_hist[l:l + 1].copy_(self.y_0.Y_0.detach())       # Y_0 before the update (solver.py:374)
             plan.iteration(l, losses, ul2)
             if self.IS_variance_K > 0 and l % self.IS_variance_iter == 0:        # solver.py:521-528
-                self.IS_rel_log.append(do_importance_sampling_me(self.problem, self, self.IS_variance_K)[2])
+                self.IS_rel_log.append(do_importance_sampling_me(self.problem, self, self.IS_variance_K,
+                                                                 wide_states=self.IS_wide_states)[2])
             # early stopping reads the u_L2 log every iteration once l > early_stopping_time (solver.py:550-554)
             watch = ul2 is not None and self.early_stopping_time is not None and l > self.early_stopping_time
             if (self.verbose and l % self.print_every == 0) or l == self.L - 1 or watch:
@@ -541,7 +547,8 @@ class Solver:
                 self.particles_close_to_target.append(
                     torch.mean((torch.sqrt(torch.sum((X - target) ** 2, 1)) < epsilon).float()))
             if self.IS_variance_K > 0 and l % self.IS_variance_iter == 0:        # solver.py:521-528
-                self.IS_rel_log.append(do_importance_sampling_me(self.problem, self, self.IS_variance_K)[2])
+                self.IS_rel_log.append(do_importance_sampling_me(self.problem, self, self.IS_variance_K,
+                                                                 wide_states=self.IS_wide_states)[2])
             self.times.append(time.time() - t_0)
             if self.verbose and l % self.print_every == 0:
                 msg = ('%d - loss: %.4e - u L2: %.4e - time/iter: %.2fs'

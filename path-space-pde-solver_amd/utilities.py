@@ -215,7 +215,7 @@ def _is_dense_native(problem, model, K, delta_t, logw_only=False):
     return _stats(D - 2.0 * Fint)
 
 
-def _affine_is_reason(problem, model):
+def _affine_is_reason(problem, model, wide=False):
     """None if the learned control is a Linear or Constant list that psp_is_rollout evaluates as u = -Z_n (PSP_ISC_LINEAR /
     PSP_ISC_TABLE; plan_affine_native.is_control_tables), else the reason."""
     try:
@@ -231,7 +231,7 @@ def _affine_is_reason(problem, model):
         return 'the learned control is not a list of Linear or of Constant modules (Affine keeps the composite evaluation)'
     if len(model.z_n) != model.N:
         return 'z_n does not hold one module per time step'
-    return _coeff_reason(problem, model)
+    return _coeff_reason(problem, model, wide)
 
 
 def _is_affine_native(problem, model, K, delta_t, logw_only=False):
@@ -280,20 +280,27 @@ def _is_composite(problem, model, K, delta_t):
 
 
 def do_importance_sampling_me(problem, model, K, control='approx', simulate_naive=False, verbose=False,
-                              delta_t=0.01, on_cpu=False, cross_statistics=None):
+                              delta_t=0.01, on_cpu=False, cross_statistics=None, wide_states='torch'):
     """Reference utilities.py:287-359.  Returns (mean_IS, variance_IS, rel_error_IS), preceded by the naive estimator's three
     numbers when ``simulate_naive``.  ``control='true'`` (with model.u_l2_error_flag) evaluates IS under problem.u_true;
-    ``cross_statistics`` adds the counts of final states above it to the verbose lines.  ``on_cpu`` is not built."""
+    ``cross_statistics`` adds the counts of final states above it to the verbose lines.  ``on_cpu`` is not built.
+    ``wide_states``: where the naive rollout, the ``control='true'`` rollout and a Linear / Constant list run above d = 64 --
+    'torch' (default) on the composite plan, 'native' on psp_isw_rollout (csrc/hjbew_kernels.h, d <= native.ISW_MAX_D);
+    d <= 64 runs on psp_is_rollout under either value."""
     if on_cpu:
         raise NotImplementedError('on_cpu is not built')
+    if wide_states not in ('torch', 'native'):
+        raise ValueError("wide_states must be 'torch' or 'native'")
+    wide = wide_states == 'native'
     if simulate_naive or cross_statistics is not None or (control != 'approx' and model.u_l2_error_flag):
-        return _is_estimators(problem, model, K, control, simulate_naive, verbose, delta_t, cross_statistics)
+        return _is_estimators(problem, model, K, control, simulate_naive, verbose, delta_t, cross_statistics, wide)
     reason = _native_reason(problem, model, control, simulate_naive)
     if reason is None:
         out = _is_native(problem, model, K, delta_t)
     elif _dense_reason(problem, model) is None:
         out = _is_dense_native(problem, model, K, delta_t)
-    elif _affine_is_reason(problem, model) is None:
+    elif _affine_is_reason(problem, model, wide) is None and (
+            problem.d <= nat.IS_MAX_D or getattr(model, 'backend', 'auto') == 'native' or _affine_wide_ok(problem, model, K, delta_t)):
         out = _is_affine_native(problem, model, K, delta_t)
     else:
         if getattr(model, 'backend', 'auto') == 'native':
@@ -321,7 +328,7 @@ def _true_control_reason(problem, model, N, delta_t):
     return None                                      # (the LDS budget is psp_is_query's to judge: _is_estimators)
 
 
-def _coeff_reason(problem, model):
+def _coeff_reason(problem, model, wide=False):
     try:
         from .problems import coefficients_overridden
     except ImportError:
@@ -335,7 +342,7 @@ def _coeff_reason(problem, model):
     over = coefficients_overridden(problem)
     if over is not None:
         return 'problem.%s is not the catalogue implementation' % over
-    if problem.d > nat.IS_MAX_D:
+    if problem.d > nat.IS_MAX_D and not wide:          # (wide: psp_isw_query judges d, with its own message)
         return 'd = %d is outside the native range d <= %d of psp_is_rollout' % (problem.d, nat.IS_MAX_D)
     if model.device.type != 'cuda':
         return 'the model is not on a GPU'
@@ -399,20 +406,45 @@ def _is_config(problem, model, K, delta_t, kind, philox):
 
 
 def _is_query(cfg):
-    """None if psp_is_rollout accepts the config (the LDS budget included), else its reason."""
+    """None if the rollout accepts the config (the LDS budget included), else its reason: psp_is_rollout up to d = 64,
+    psp_isw_rollout above (a config of that size gets here under wide_states='native' only: _coeff_reason)."""
     lib = nat.load()
+    if cfg.d > nat.IS_MAX_D:
+        if lib.psp_isw_query(C.byref(cfg), C.byref(nat.IswSizes())) != 0:
+            return nat.last_error()
+        return None
     if lib.psp_is_query(C.byref(cfg), None) != 0:
         return nat.last_error()
     return None
 
 
+def _affine_wide_ok(problem, model, K, delta_t):
+    """backend='auto' above d = 64: whether psp_isw_query takes the Linear / Constant list's config (else the composite plan)."""
+    try:
+        from .plan_affine_native import is_control_tables
+    except ImportError:
+        from plan_affine_native import is_control_tables
+    kind, table = is_control_tables(model, int(np.ceil(problem.T / delta_t)), delta_t)
+    cfg, keep = _is_config(problem, model, K, delta_t, nat.ISC_NONE, False)
+    cfg.control_kind, cfg.u_ref = kind, nat.ptr(table)
+    return _is_query(cfg) is None
+
+
 def _is_rollout(problem, model, K, cfg, xi, iter_, want_XN):
-    """One psp_is_rollout call: (log-weights (K), X_N (K, d) or None) on the model's device."""
+    """One psp_is_rollout call (d <= 64) or psp_isw_rollout call (above): (log-weights (K), X_N (K, d) or None) on the model's
+    device."""
     dev = model.device
     lib = nat.load()
     d = problem.d
     logw = torch.empty(K, dtype=torch.float32, device=dev)
     XN = torch.empty(K, d, dtype=torch.float32, device=dev) if want_XN else None
+    if cfg.d > nat.IS_MAX_D:
+        sizes = nat.IswSizes()
+        nat.check(lib.psp_isw_query(C.byref(cfg), C.byref(sizes)), 'psp_isw_query')
+        tables = torch.empty(max(1, sizes.table_bytes // 4), dtype=torch.float32, device=dev)
+        nat.check(lib.psp_isw_rollout(C.byref(cfg), nat.ptr(xi), (int(model.seed) + 7919) & 0xFFFFFFFFFFFFFFFF, iter_, nat.ptr(tables),
+                                      nat.ptr(logw), nat.ptr(XN), nat.stream_ptr(dev)), 'psp_isw_rollout')
+        return logw, XN
     nat.check(lib.psp_is_rollout(C.byref(cfg), nat.ptr(xi), (int(model.seed) + 7919) & 0xFFFFFFFFFFFFFFFF, iter_, nat.ptr(logw),
                                  nat.ptr(XN), nat.stream_ptr(dev)), 'psp_is_rollout')
     return logw, XN
@@ -469,10 +501,10 @@ def _learned_kernel(problem, model, control):
     return reason
 
 
-def _full_reason(problem, model, K, control, simulate_naive, delta_t, cross):
+def _full_reason(problem, model, K, control, simulate_naive, delta_t, cross, wide=False):
     """None if _is_estimators runs natively (psp_is_rollout, next to today's evaluation kernel for a learned control), else the
     reason."""
-    why = _coeff_reason(problem, model)
+    why = _coeff_reason(problem, model, wide)
     if why is not None:
         return why
     if control != 'approx' and model.u_l2_error_flag:
@@ -483,13 +515,13 @@ def _full_reason(problem, model, K, control, simulate_naive, delta_t, cross):
     return kernel if isinstance(kernel, str) else None
 
 
-def _is_estimators(problem, model, K, control, simulate_naive, verbose, delta_t, cross):
+def _is_estimators(problem, model, K, control, simulate_naive, verbose, delta_t, cross, wide=False):
     """simulate_naive / control='true' / cross_statistics: fully native or fully composite (utilities.py:296-359)."""
     try:
         from .plan_dense_native import ul2_kind
     except ImportError:
         from plan_dense_native import ul2_kind
-    reason = _full_reason(problem, model, K, control, simulate_naive, delta_t, cross)
+    reason = _full_reason(problem, model, K, control, simulate_naive, delta_t, cross, wide)
     true_control = control != 'approx' and model.u_l2_error_flag
     philox = getattr(model, 'noise', 'reference') == 'philox'
     cfgs = {}
