@@ -2,8 +2,16 @@
 
     python path-space-pde-solver_amd/build.py [--force] [-j N]
 
-One translation unit per (d, H) line of csrc/instances.def plus csrc/psp_api.hip, linked
-into csrc/libpsp_hip.so next to the sources so the library travels with the tree.
+Three kinds of translation unit under csrc/, linked into csrc/libpsp_hip.so next to the sources so that the
+library travels with the tree:
+
+* the C ABI layer (include/psp.h): api_common.hip and one api_<family>.hip per kernel family, over api_common.h;
+* one instance unit per kernel family whose kernels are shaped at run time (hjbe_, hjbew_, aff_, genl_*_, pinn_,
+  lstat_instance.hip);
+* one instance unit per (d, H) line of a .def list for the families compiled per shape (instances.def,
+  wide_instances.def, dense_instances.def, gen_instances.def).
+
+A unit is recompiled when one of the files it is made of changes (unit_deps: its #include "..." lines, followed).
 hipcc cross-compiles without a GPU.
 """
 import argparse
@@ -70,21 +78,21 @@ def _compile(src, obj, defs, force):
     return obj, True
 
 
-def build(force=False, jobs=None, verbose=True, extra_flags=(), lib_path=None, obj_dir=None, only=None):
-    """extra_flags / lib_path / obj_dir / only=[(d,H)..] are for diagnostic variants (e.g.
-    -DPSP_STAMPS into csrc/libpsp_hip_stamps.so); the default call builds the shipped library."""
+def build(force=False, jobs=None, verbose=True, extra_flags=(), lib_path=None, obj_dir=None):
+    """extra_flags / lib_path / obj_dir are for diagnostic variants (e.g. -DPSP_STAMPS into
+    csrc/libpsp_hip_stamps.so); the default call builds the shipped library."""
     global FLAGS, OBJ, LIB
     saved = (FLAGS, OBJ, LIB)
     FLAGS = FLAGS + list(extra_flags)
     OBJ = obj_dir or OBJ
     LIB = lib_path or LIB
     try:
-        return _build(force, jobs, verbose, only)
+        return _build(force, jobs, verbose)
     finally:
         FLAGS, OBJ, LIB = saved
 
 
-def _build(force, jobs, verbose, only):
+def _build(force, jobs, verbose):
     os.makedirs(OBJ, exist_ok=True)
     # The split of an fp32 operand into its f16 pair (hjb_kernels.h split8) costs two instructions per value only when the SLP
     # vectoriser leaves its two fmas alone: every translation unit but the wide family's is compiled with it off (measured, same
@@ -92,7 +100,14 @@ def _build(force, jobs, verbose, only):
     # the round-3 form).
     NOSLP, CLASSIC = ["-fno-slp-vectorize"], ["-DPSP_SPLIT_CLASSIC=1"]
     # (source, object, defines and flags); what a unit depends on is read from its #include lines (unit_deps)
-    tasks = [("psp_api.hip", "psp_api.o", NOSLP),
+    tasks = [("api_common.hip", "api_common.o", NOSLP),             # error buffer, shared checks and small kernels, Adam, RCCL, psp_loss_stats_*
+             ("api_hjb.hip", "api_hjb.o", NOSLP),                   # psp_hjb_*: planner, narrow and wide tables, fused tail, basis, control eval
+             ("api_gen.hip", "api_gen.o", NOSLP),                   # psp_gen_*: planner, table, the range guard's two kernels
+             ("api_dnet.hip", "api_dnet.o", NOSLP),                 # psp_dnet_*, psp_gradvar_finish: planner, table, gradvar kernels
+             ("api_aff.hip", "api_aff.o", NOSLP),                   # psp_aff_*: planner and bucket table
+             ("api_genl.hip", "api_genl.o", NOSLP),                 # psp_genl_*: planner, genl_tables_kernel, plain genl_fwd / genl_bwd instances
+             ("api_is.hip", "api_is.o", NOSLP),                     # psp_is_*, psp_isw_*: the checks and the argument fill of both rollouts
+             ("api_pinn.hip", "api_pinn.o", NOSLP),                 # psp_pinn_*, psp_pinn_pairs_*: planner
              ("hjbe_instance.hip", "hjbe_inst.o", NOSLP),           # psp_is_rollout: every d bucket and control kind in one unit
              ("hjbew_instance.hip", "hjbew_inst.o", NOSLP),         # psp_isw_rollout: every block bucket and control kind, table kernel
              ("aff_instance.hip", "aff_inst.o", NOSLP),             # psp_aff_*: the three d buckets in one unit

@@ -1,5 +1,5 @@
 // The adjoint sweep of the state path for the value-function ansatz (genl_adj_kernels.h: genl_adj_kernel, one, four and eight waves
-// per 16-trajectory tile, and the kernel that builds the table of (dt A)^T).  A unit of its own: psp_api.hip, genl_lq_instance.hip
+// per 16-trajectory tile, and the kernel that builds the table of (dt A)^T).  A unit of its own: api_genl.hip, genl_lq_instance.hip
 // and genl_ul2_instance.hip keep the kernels they had.
 #define PSP_GENL_DEVICE_HELPERS_ONLY
 #define PSP_GENL_ADJ_KERNELS

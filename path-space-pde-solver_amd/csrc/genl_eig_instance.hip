@@ -1,7 +1,7 @@
 // The eigenvalue instances of the run-time-shaped forward kernel (genl_kernels.h: genl_fwd_kernel<NW, false, false, false, true> --
 // sigma = s I, a trained lambda read from device memory, the gate of an output ReLU, the per-trajectory S_k and the h / drift kinds
 // of the Fokker-Planck and nonlinear Schroedinger eigenvalue problems), one, four and eight waves per 16-trajectory tile.  A unit
-// of their own: psp_api.hip and the other instance units keep the kernels they had.
+// of their own: api_genl.hip and the other instance units keep the kernels they had.
 #define PSP_GENL_DEVICE_HELPERS_ONLY
 #include "genl_kernels.h"
 

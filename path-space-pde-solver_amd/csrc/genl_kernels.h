@@ -198,7 +198,7 @@ __device__ __forceinline__ int genl_w_index(AP a, int i, int rf, int u) {
 }
 
 // A-operand tables + staged vectors from the flat parameters (registration order W_1, b_1, .., W_out, b_out)
-// (an ordinary kernel: defined in the one translation unit that launches it, psp_api.hip; a unit that includes this header for
+// (an ordinary kernel: defined in the one translation unit that launches it, api_genl.hip; a unit that includes this header for
 //  its device helpers alone defines PSP_GENL_DEVICE_HELPERS_ONLY)
 #ifndef PSP_GENL_DEVICE_HELPERS_ONLY
 __global__ __launch_bounds__(256) void genl_tables_kernel(const GenlArgs a) {

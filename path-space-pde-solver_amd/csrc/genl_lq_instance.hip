@@ -1,6 +1,6 @@
 // The linear-quadratic instances of the run-time-shaped forward kernel (genl_kernels.h: genl_fwd_kernel<NW, true, true> -- Z = B grad_x V,
 // the drift product (dt A) X, the running cost at the moved state), one, four and eight waves per 16-trajectory tile.
-// A unit of their own: psp_api.hip keeps the set of kernels it had.  genl_tables_kernel stays where it is launched.
+// A unit of their own: api_genl.hip keeps the set of kernels the API unit had.  genl_tables_kernel stays where it is launched.
 #define PSP_GENL_DEVICE_HELPERS_ONLY
 #include "genl_kernels.h"
 

@@ -1,7 +1,7 @@
 // The u_L2-log instances of the run-time-shaped forward kernel (genl_kernels.h: genl_fwd_kernel<NW, false, false, true> -- sigma = s I,
 // element-wise drift: the double wells, diagonal LLGC -- and genl_fwd_kernel<NW, true, true, true> -- the linear-quadratic
 // coefficients: dense LLGC, LQGC), one, four and eight waves per 16-trajectory tile, and the kernel that stages the gains of a
-// reference control linear in x.  A unit of their own: psp_api.hip and genl_lq_instance.hip keep the kernels they had.
+// reference control linear in x.  A unit of their own: api_genl.hip and genl_lq_instance.hip keep the kernels they had.
 #define PSP_GENL_DEVICE_HELPERS_ONLY
 #include "genl_kernels.h"
 

@@ -1,4 +1,4 @@
-// gh_kinds.h -- the h kinds of the value-net kernels (PSP_GH_* of include/psp.h; psp_api.hip asserts the numbering) and the
+// gh_kinds.h -- the h kinds of the value-net kernels (PSP_GH_* of include/psp.h; api_gen.hip asserts the numbering) and the
 // arithmetic of the kinds that more than one kernel family evaluates: the rollout kernels (gen_kernels.h, genl_kernels.h) and the
 // PINN finish kernel (pinn_kernels.h).  Nothing here needs the MFMA machinery of hjb_kernels.h.
 #pragma once

@@ -48,7 +48,7 @@ constexpr int kPinnZS = 132;           // row stride of a layer's pre-activation
 constexpr int kPinnThreads = 256;      // four waves
 constexpr int kPinnMaxWg = 256;        // partial gradients of the backward kernel
 
-// (DRIFT_* live in hjb_kernels.h with the MFMA machinery this header does without: psp_api.hip asserts that the two agree)
+// (DRIFT_* live in hjb_kernels.h with the MFMA machinery this header does without: api_pinn.hip ties these to PSP_DRIFT_*, api_hjb.hip those)
 enum { PINN_DRIFT_ZERO = 0, PINN_DRIFT_DIAG = 2, PINN_DRIFT_DWELL = 3 };                      // PSP_DRIFT_*
 enum { PINN_ACT_RELU2 = 0, PINN_ACT_TANH2 = 1, PINN_ACT_TANH = 2 };                           // PSP_ACT_*
 

@@ -5,7 +5,7 @@ Each draw is one GeneralSolver / EllipticSolver case with a value net the templa
 hidden layers of widths in {1 .. 128}, relu^2 / tanh^2 / tanh in the dense-concat layout or DenseNet_tanh's nn.Linear layout,
 input widths 1 .. 112 across the 16-column block edges, ragged batches, horizons past which tiles leave the time loop at
 different steps, unbounded / sphere (Dirichlet, Neumann) / box / corner / ball / annulus domains, diffusion and BSDE losses.
-make_genl_plan (csrc/psp_api.hip) picks the waves per tile of the forward (1, 4 or 8) and the backward instance
+make_genl_plan (csrc/api_genl.hip) picks the waves per tile of the forward (1, 4 or 8) and the backward instance
 (genl_bwd_kernel<1>, <8, 3> for at most 24 hidden blocks, <8, 4> above); PSP_GENL_NW forces the choice, and every run asserts
 the geometry it asked for, so a later change of the heuristic cannot drop coverage silently.  Every run is compared with the
 oracle: loss <= 5e-5 relative on the first iteration and <= 1e-4 after, the first iteration's gradient <= 5e-4 max|g|, K_log

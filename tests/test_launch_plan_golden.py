@@ -8,7 +8,7 @@ both noise modes, store_path 1 / 2 / 4, range_flag null and set -- and tests/gol
 library answered when the table was recorded: every field of the sizes struct, or the return code and psp_last_error().
 Dimensions a family's plan ignores are swept at one K only, and equal answers are stored once (`rows` indexes `answers`).
 
-Host refactors of psp_api.hip must leave this table as it is.  A deliberate change of a selection rule re-records it:
+Host refactors of the C ABI layer (csrc/api_*.hip, where each family's planner lives) must leave this table as it is.  A deliberate change of a selection rule re-records it:
 
     python tests/test_launch_plan_golden.py --record
 """

@@ -166,6 +166,6 @@ def test_the_statistics_unit_is_built_from_its_own_headers():
     spec.loader.exec_module(build)
     deps = {os.path.relpath(p, pkg).replace(os.sep, "/") for p in build.unit_deps(os.path.join(pkg, "csrc", "lstat_instance.hip"))}
     assert deps == {"csrc/lstat_instance.hip", "csrc/lstat_kernels.h", "csrc/launch.h"}     # no MFMA machinery, no C header
-    api = {os.path.relpath(p, pkg).replace(os.sep, "/") for p in build.unit_deps(os.path.join(pkg, "csrc", "psp_api.hip"))}
+    api = {os.path.relpath(p, pkg).replace(os.sep, "/") for p in build.unit_deps(os.path.join(pkg, "csrc", "api_common.hip"))}   # psp_loss_stats_*
     assert "csrc/lstat_kernels.h" in api
     assert "lstat_instance.hip" in open(os.path.join(pkg, "build.py")).read()
